@@ -1,6 +1,6 @@
 """Benchmark of the hot path: HRNet-W32 256x192 top-down inference (BASELINE.json metric / configs[2]).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
         N > 1: one rank per GPU over RCCL.  Either the driver launches the ranks itself (torch.distributed.run: RANK /
         WORLD_SIZE in the environment), or - when no WORLD_SIZE is set - this process starts them as children through
         torch.distributed.run BEFORE it makes any GPU call and exits with their status.
@@ -10,7 +10,12 @@ resident in HBM: HRNet-W32 backbone + HRNetHead (direct fp32-MFMA conv plan) + T
 (arg-max + +-0.25 shift + back-projection).  Crops shard over ranks with no data-path collective
 (weak scaling); value = images all ranks processed / max-over-ranks wall time.
 
-Prints ONE JSON line (rank 0) with the contract fields plus
+A plain run sets up, warms up, times K steps and prints ONE JSON line (rank 0) with the contract fields (metric, value,
+unit, higher_is_better, dtype, ms_per_step = milliseconds of one timed step) and the workload's config.
+  --dump-outputs DIR  after the timed steps, what the last timed step handed its caller (rank 0: key points `preds`, boxes
+                 `boxes`, heat-maps `heatmap` unless the flip test ran) as DIR/<name>.npy in float32, at most 64 MB in all.
+                 Weights and inputs are seeded: the same arguments give the same inputs in every run.
+  --full       everything else the benchmark measures, added to the same line:
   roofline     - the dominant kernel (the conv instantiation with the largest share of step time):
                  algorithmic FLOP per launch / its average launch duration, measured live with HIP
                  events on the launch stream; peak = fp32 matrix-core rate of MI355X_MICROARCH.md.
@@ -21,6 +26,9 @@ Prints ONE JSON line (rank 0) with the contract fields plus
   extra_workloads (N=1, after the headline's timed region) - short legs, each in a child process with its own timed region and
                  roofline: HRNet-W32 under amp O2, BASELINE configs[4] (W48 384x288 UDP/DARK + flip test, fp16), configs[1]
                  (SimpleBaseline-R50), and the configs[3] training step in fp32 and in the reference's amp-O2 recipe.
+  hbm_ops      - the decode / loss / target kernels against the HBM roofline (N=1 headline only).
+  extra_workloads.config3_train_ampO2_dp (N>1) - the data-parallel training leg on every rank, after the headline.
+  --no-roofline / --no-cpu-baseline / --no-extra leave single parts of --full out; --layers and --extra need --full.
 """
 import argparse
 import json
@@ -899,7 +907,7 @@ EXTRA_LEGS = {
 
 
 def run_extra_legs(selected=None, timeout_s=240):
-    """Each leg = this script in a fresh child process (own timed region, own roofline), started AFTER the headline's timed
+    """Each leg = this script in a fresh child process under --full (own timed region, own roofline), started AFTER the headline's timed
     region; a leg that fails or exceeds its limit is reported as such and never takes the headline line down."""
     out = {}
     env = dict(os.environ)
@@ -911,7 +919,7 @@ def run_extra_legs(selected=None, timeout_s=240):
         log(f"extra leg {name}: {' '.join(leg_args)}")
         try:
             # the leg's progress lines go straight to this process's stderr (a silent parent looks hung to the GPU box's watchdog)
-            proc = subprocess.run([sys.executable, os.path.abspath(__file__), "--gpus", "1", "--leg", *leg_args], env=env,
+            proc = subprocess.run([sys.executable, os.path.abspath(__file__), "--gpus", "1", "--leg", "--full", *leg_args], env=env,
                                   stdout=subprocess.PIPE, stderr=None, text=True, timeout=timeout_s)
             line = next((ln for ln in reversed(proc.stdout.splitlines()) if ln.startswith("{")), None)
             if proc.returncode != 0 or line is None:
@@ -1039,6 +1047,30 @@ def loader_bench(args, mp, dev):
         "roofline": None, "cpu_baseline": None}))
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """`--dump-outputs DIR`: every array as DIR/<name>.npy in float32.  Should the set exceed 64 MB (a large --batch), the
+    largest arrays keep a fixed, seeded sample of their leading (crop) axis; the crops kept go beside them as
+    <name>_rows.npy (float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    for name in sorted(host, key=lambda k: -host[k].nbytes):
+        a = host[name]
+        if total <= DUMP_BUDGET_BYTES:
+            break
+        keep = max(1, int(a.shape[0] * (DUMP_BUDGET_BYTES - (total - a.nbytes)) / a.nbytes))
+        rows = np.sort(np.random.RandomState(0).choice(a.shape[0], keep, replace=False))
+        host[name] = a[rows]
+        np.save(os.path.join(out_dir, f"{name}_rows.npy"), rows.astype(np.float64))
+        total -= a.nbytes - host[name].nbytes
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+    log(f"outputs of the last timed step -> {out_dir}: " + ", ".join(f"{k} {list(a.shape)}" for k, a in host.items()))
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` without a launcher: start the N ranks through torch.distributed.run as ONE child process tree.
     Nothing in this process has touched the GPU yet (importing torch does not), so no GPU-initialised process is replaced."""
@@ -1054,7 +1086,8 @@ def spawn_ranks(n):
     return subprocess.call(cmd, env=env)
 
 
-def main():
+def parse_args(argv=None):
+    """The command line; a run without --full switches the roofline, CPU baseline and extra legs off."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -1072,8 +1105,24 @@ def main():
     ap.add_argument("--leg", action="store_true", help="this process IS an extra leg: no CPU baseline, no further legs")
     ap.add_argument("--sweep", default="", help="comma-separated per-GPU batch sizes: time each (its own plan) and report them all")
     ap.add_argument("--hbm-ops", action="store_true", help="print only the hbm_ops block (decode / loss / target kernels against the HBM roofline)")
-    args = ap.parse_args()
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step returned (preds, boxes, heatmap) to DIR/<name>.npy in float32")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: roofline, hbm_ops, cpu_baseline, extra legs, the DP leg")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        if args.layers or args.extra:
+            ap.error("--layers and --extra belong to the --full measurements: add --full")
+        args.no_roofline = args.no_cpu_baseline = args.no_extra = True
+    if args.dump_outputs and (args.hbm_ops or args.sweep or args.workload not in WORKLOADS):
+        ap.error("--dump-outputs covers the inference workloads (not --sweep / --hbm-ops / training / loader)")
+    return args
 
+
+def main():
+    args = parse_args()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(spawn_ranks(args.gpus))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -1157,7 +1206,7 @@ def main():
     log("timing")
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        out = step()
     sync_all()
     elapsed = time.perf_counter() - t0
     if dist is not None:
@@ -1166,6 +1215,11 @@ def main():
         elapsed = float(t.item())
 
     log(f"timed region done: {elapsed / args.steps * 1e3:.2f} ms/step")
+    if args.dump_outputs and rank == 0:
+        # eval_net -> ((preds, boxes), heatmap); the flip test -> (preds, boxes).  The heat-map is the plan's output buffer:
+        # written out before anything else (the --full roofline) replays the plan.
+        (preds, boxes), heatmap = out if multi_run is None else (out, None)
+        dump_outputs(args.dump_outputs, {"preds": preds, "boxes": boxes, **({"heatmap": heatmap} if heatmap is not None else {})})
     result = None
     if rank == 0:
         plan = net.get_plan((n_plan, 3, ih, iw), dev)
@@ -1188,7 +1242,7 @@ def main():
             result["roofline"] = roofline_report(plan, layers_csv=args.layers, workload=args.workload)
             log("roofline done")
         headline = world == 1 and args.workload == "hrnet_w32" and args.amp == "O0" and not args.leg
-        if headline:
+        if headline and args.full:
             result["hbm_ops"] = hbm_ops_report(mp, dev)
         if headline and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(net.state_dict(), mp, dev)

@@ -226,7 +226,7 @@ def test_two_rank_nccl_hrnet_w32_step(tmp_path):
 
 
 def test_bench_two_rank_rehearsal_on_one_gpu_reports_the_dp_leg():
-    """`bench.py --gpus 2` as the driver launches it (bench.py spawns its ranks through torch.distributed.run), rehearsed on ONE GPU:
+    """`bench.py --gpus 2 --full` as the driver launches it (bench.py spawns its ranks through torch.distributed.run), rehearsed on ONE GPU:
     MINDPOSE_BENCH_SHARED_GPU_REHEARSAL=1 puts both ranks on device 0 with gloo for the barrier / MAX / gradient exchange.  Not a
     measurement - the first real multi-GPU run must not fail on plumbing: the line parses, names two ranks and carries the
     data-parallel training leg with its exchange figures (segmented backward, buckets released between the segments)."""
@@ -239,7 +239,7 @@ def test_bench_two_rank_rehearsal_on_one_gpu_reports_the_dp_leg():
         env.pop(k, None)
     # a child process tree of its own: nothing here has to be exec'ed from this (GPU-initialised) process
     proc = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-roofline",
-                           "--no-cpu-baseline"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
+                           "--no-cpu-baseline", "--full"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert proc.returncode == 0, proc.stderr[-2000:]
     line = json.loads([ln for ln in proc.stdout.splitlines() if ln.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["steps"] == 2 and line["scaling"] == "weak" and line["value"] > 0

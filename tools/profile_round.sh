@@ -10,7 +10,7 @@ mkdir -p $out
 export TMPDIR=/tmp
 export MINDPOSE_TUNE_CACHE=$out/${tag}_tune.json
 # 1. the bench line itself (also fills the tuner cache that the profiled runs replay)
-python3 bench.py "$@" > $out/${tag}_bench.json 2> $out/${tag}_bench.err
+python3 bench.py --full "$@" > $out/${tag}_bench.json 2> $out/${tag}_bench.err
 tail -c 600 $out/${tag}_bench.json; echo
 # 2. per-kernel times.  bench.py's roofline section times every launch alone on one stream (HIP events around
 #    mp_plan_run_range); the matching rocprof summary therefore comes from a single-lane replay (MINDPOSE_PLAN_LANES=0).
@@ -18,7 +18,7 @@ tail -c 600 $out/${tag}_bench.json; echo
 #    stretches) is kept next to it.
 cd /tmp
 export MINDPOSE_PLAN_LANES=0
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/${tag}_prof -o ${tag} -- python3 $root/bench.py "$@" --steps 5 --warmup 2 --no-cpu-baseline > $out/${tag}_bench_under_rocprof.json 2> $out/${tag}_rocprof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/${tag}_prof -o ${tag} -- python3 $root/bench.py --full "$@" --steps 5 --warmup 2 --no-cpu-baseline > $out/${tag}_bench_under_rocprof.json 2> $out/${tag}_rocprof.err
 f=$(find $out/${tag}_prof -name "*kernel_stats.csv" | head -1)
 cp "$f" $out/${tag}_kernel_stats.csv
 head -8 $out/${tag}_kernel_stats.csv

@@ -10,20 +10,20 @@ out=gpurun_out
 mkdir -p $out
 if [ "$part" = "1" ]; then
     tag=${2:-r03_h}  # r03_h: mid-round; r03_l: end of round (captured multi-lane plan replay)
-    python3 bench.py > $out/${tag}_bench_full.json 2> $out/${tag}_bench_full.err
+    python3 bench.py --full > $out/${tag}_bench_full.json 2> $out/${tag}_bench_full.err
     tail -c 300 $out/${tag}_bench_full.json; echo
     bash tools/profile_round.sh $tag --no-extra 2>&1 | tail -12
 elif [ "$part" = "4" ]; then
     bash tools/profile_round.sh ${2:-r03_m_o2} --amp O2 --no-extra 2>&1 | tail -8
 elif [ "$part" = "3" ]; then
     bash tools/profile_train.sh r03_j_train_o2 --amp O2 --batch 128 --steps 10 --warmup 3 --leg --no-roofline 2>&1 | tail -8
-    MINDPOSE_BENCH_TRAIN_SHAPES=$out/r03_j_train_o2_shapes.csv MINDPOSE_TUNE_CACHE=$out/r03_j_train_o2_tune.json python3 bench.py --workload hrnet_w32_train --amp O2 --batch 128 --steps 20 --warmup 5 --leg > $out/r03_j_train_o2_bench.json 2> $out/r03_j.err
+    MINDPOSE_BENCH_TRAIN_SHAPES=$out/r03_j_train_o2_shapes.csv MINDPOSE_TUNE_CACHE=$out/r03_j_train_o2_tune.json python3 bench.py --full --workload hrnet_w32_train --amp O2 --batch 128 --steps 20 --warmup 5 --leg > $out/r03_j_train_o2_bench.json 2> $out/r03_j.err
     tail -c 300 $out/r03_j_train_o2_bench.json; echo
     MINDPOSE_BN_FUSE=0 python3 bench.py --workload hrnet_w32_train --amp O2 --batch 128 --steps 20 --warmup 5 --leg --no-roofline > $out/r03_j_train_o2_percell_bench.json 2> $out/r03_j2.err
     tail -c 300 $out/r03_j_train_o2_percell_bench.json; echo
 else
     bash tools/profile_train.sh r03_d_train_o2 --amp O2 --batch 128 --steps 10 --warmup 3 --leg --no-roofline 2>&1 | tail -8
-    MINDPOSE_TUNE_CACHE=$out/r03_d_train_o2_tune.json python3 bench.py --workload hrnet_w32_train --amp O2 --batch 128 --steps 20 --warmup 5 --leg > $out/r03_d_train_o2_bench.json 2> $out/r03_d.err
+    MINDPOSE_TUNE_CACHE=$out/r03_d_train_o2_tune.json python3 bench.py --full --workload hrnet_w32_train --amp O2 --batch 128 --steps 20 --warmup 5 --leg > $out/r03_d_train_o2_bench.json 2> $out/r03_d.err
     tail -c 300 $out/r03_d_train_o2_bench.json; echo
     MINDPOSE_BN_FUSE=0 python3 bench.py --workload hrnet_w32_train --amp O2 --batch 128 --steps 20 --warmup 5 --leg --no-roofline > $out/r03_d_train_o2_percell_bench.json 2> $out/r03_d2.err
     tail -c 300 $out/r03_d_train_o2_percell_bench.json; echo

@@ -8,7 +8,7 @@ out=gpurun_out
 mkdir -p $out
 if [ "$part" = "1" ]; then
     # the bench line as the driver runs it (headline + cpu_baseline + extra_workloads)
-    python3 bench.py > $out/r02_h_bench_full.json 2> $out/r02_h_bench_full.err
+    python3 bench.py --full > $out/r02_h_bench_full.json 2> $out/r02_h_bench_full.err
     tail -c 300 $out/r02_h_bench_full.json; echo
     # rocprofv3 / PMC evidence; --no-extra: a profiled process must not start child processes (the profiler's preload has already
     # initialised the GPU when the program starts)
@@ -17,9 +17,9 @@ if [ "$part" = "1" ]; then
 else
     bash tools/profile_round.sh r02_l_sb --workload simplebaseline_r50 --leg 2>&1 | tail -12
     bash tools/profile_train.sh r02_j_train_o2 --amp O2 --batch 128 --steps 5 --warmup 2 --leg 2>&1 | tail -14
-    MINDPOSE_TUNE_CACHE=$out/r02_j_train_o2_tune.json python3 bench.py --workload hrnet_w32_train --amp O2 --batch 128 --steps 10 --warmup 3 --leg > $out/r02_j_train_o2_bench.json 2> $out/r02_j.err
+    MINDPOSE_TUNE_CACHE=$out/r02_j_train_o2_tune.json python3 bench.py --full --workload hrnet_w32_train --amp O2 --batch 128 --steps 10 --warmup 3 --leg > $out/r02_j_train_o2_bench.json 2> $out/r02_j.err
     tail -c 300 $out/r02_j_train_o2_bench.json; echo
     bash tools/profile_train.sh r02_k_train_f32 --batch 128 --steps 5 --warmup 2 --leg 2>&1 | tail -14
-    MINDPOSE_TUNE_CACHE=$out/r02_k_train_f32_tune.json python3 bench.py --workload hrnet_w32_train --batch 128 --steps 10 --warmup 3 --leg > $out/r02_k_train_f32_bench.json 2> $out/r02_k.err
+    MINDPOSE_TUNE_CACHE=$out/r02_k_train_f32_tune.json python3 bench.py --full --workload hrnet_w32_train --batch 128 --steps 10 --warmup 3 --leg > $out/r02_k_train_f32_bench.json 2> $out/r02_k.err
     tail -c 300 $out/r02_k_train_f32_bench.json; echo
 fi
