@@ -478,6 +478,21 @@ int mp_plan_add_fuse_sum_f16(mp_plan* plan, const void* base_dev, const void* t1
                              const void* t3_dev, int s3, void* out_dev, int n, int c, int h, int w, int relu);
 /* to_c8 != 0: NCHW fp32 -> c8 fp16, else c8 fp16 -> NCHW fp32 */
 int mp_plan_add_layout_f16(mp_plan* plan, int to_c8, const void* x_dev, void* out_dev, int n, int c, int h, int w);
+/* Channel concatenation ops.concat((a, b), 1) of the HigherHRNet head (mindpose/models/heads/higher_hrnet_head.py:217-229):
+ * out[n] = [a[n] (ca channels), b[n] (cb channels)].  c8 = 0: fp32 NCHW; c8 != 0: channel-blocked fp16, ca a multiple of 8 (a block
+ * copy per image; the pad channels of b's last block - zero - become out's).  mp_plan_add_concat records it as a plan entry. */
+int mp_concat_channels(const void* a_dev, int ca, const void* b_dev, int cb, void* out_dev, int n, int h, int w, int c8,
+                       mp_stream_t stream);
+int mp_plan_add_concat(mp_plan* plan, const void* a_dev, int ca, const void* b_dev, int cb, void* out_dev, int n, int h, int w,
+                       int c8);
+/* Column band of an activation: out[r][0, w_out) = in[r][start, start + w_out) for rows = n*c*h (fp32 NCHW) or n*ceil(c/8)*h
+ * (c8 != 0: channel-blocked fp16, one 16-byte block per pixel).  The plan splits a convolution that no kernel serves at its full
+ * width (the 512 / 832-pixel images of the bottom-up recipe, hrnet.py:377-385) into output-column bands: each band's input columns
+ * are copied out with this entry and the band's conv writes its columns through mp_conv_desc.out_off_x. */
+int mp_col_slice(const void* in_dev, void* out_dev, int rows, int w_in, int start, int w_out, int c8, mp_stream_t stream);
+int mp_plan_add_col_slice(mp_plan* plan, const void* in_dev, void* out_dev, int rows, int w_in, int start, int w_out, int c8);
+/* 1 when mp_conv2d_fwd_variant(desc, variant, ...) would accept this (shape, variant) - -1 = the library heuristic; host-only. */
+int mp_conv_supported(const mp_conv_desc* desc, int variant);
 
 /* ---- loader side: the crop that feeds the network -----------------------------------------------------
  * cv2.warpAffine(image, trans, (out_w, out_h), flags=cv2.INTER_LINEAR) of TopDownAffine._affine / _udp_affine
@@ -500,6 +515,35 @@ int mp_warp_affine(const uint8_t* src_dev, const long long* src_offsets_dev, con
 /* Horizontal flip of an NCHW fp32 batch, out[n,c,y,x] = in[n,c,y,W-1-x]: the input of the flip test's second run
  * (mindpose/engine/inferencer/topdown_inferencer.py:168-170), one pass; in and out must not overlap. */
 int mp_flip_width(const float* in_dev, float* out_dev, int n, int c, int h, int w, mp_stream_t stream);
+
+/* ---- bottom-up (associative-embedding) decoder, BottomUpHeatMapAEDecoder -------------------------------------------------
+ * Replaces mindpose/models/decoders/bottom_up_decoder.py:81-203 (the ~10 MindSpore ops of decode()) with two launches.
+ * stages[0 .. num_stages-1]: the model outputs in the reference's order, stages[num_stages-1] the full-resolution one (its h, w
+ * are the map size H, W); every stage's first k channels are heat maps, channels k.. of a stage with has_tags are its tags
+ * (k of them with tag_per_joint, else 1).  L = the number of stages with tags (1..4).  fp32 NCHW, contiguous.
+ *
+ * mp_bottomup_parse_nms_topk (bottom_up_decoder.py:102-138 _parse_heatmaps / _aggregate_heatmap, :173-178 _nms, the per-tile
+ *   half of :140-171 top_k): heatmap_raw [n,k,H,W] = mean of the stages resized to H x W (ResizeBilinear without half-pixel
+ *   centres), 0 where the nearest-resized mask [n,mask_h,mask_w] (uint8) is 0; tagging [n,k_tag,H,W,L] = the resized tags;
+ *   nms_kernel 3 / 5 / 7 = the max-pool NMS, 1 = none; the top max_num (value, flat index) of every 16 x 64 tile into the
+ *   workspace (mp_bottomup_workspace_bytes).  max_num 1..64, else MP_ERR_UNSUPPORTED.
+ * mp_bottomup_gather (bottom_up_decoder.py:140-171 _get_max_preds, :180-203 _shift_coordinate): merges the workspace into the
+ *   global top max_num per (image, joint), values descending and equal values in ascending flat index (ops.top_k), and writes
+ *   val_k [n,k,M], ind_k [n,k,M,2] (x, y) fp32 and tag_k [n,k,M,L] gathered from tagging; shift_coordinate adds 0.25 * sign of
+ *   the heatmap_raw central difference, entry m taking the offset of the m-th smallest selected flat index (the reference's
+ *   masked_select order).  Same stream as the first launch, same workspace. */
+typedef struct mp_bottomup_stage {
+    const float* data_dev; /* [n, c, h, w] */
+    int32_t c, h, w;
+    int32_t has_tags;
+} mp_bottomup_stage;
+size_t mp_bottomup_workspace_bytes(int n, int k, int h, int w, int max_num);
+int mp_bottomup_parse_nms_topk(const mp_bottomup_stage* stages_host, int num_stages, const uint8_t* mask_dev, int mask_h, int mask_w,
+                               int n, int k, int tag_per_joint, int nms_kernel, int max_num, float* heatmap_raw_dev,
+                               float* tagging_dev, void* workspace_dev, size_t workspace_bytes, mp_stream_t stream);
+int mp_bottomup_gather(const float* heatmap_raw_dev, const float* tagging_dev, const void* workspace_dev, size_t workspace_bytes,
+                       int n, int k, int h, int w, int tag_per_joint, int num_tags, int max_num, int shift_coordinate,
+                       float* val_k_dev, float* ind_k_dev, float* tag_k_dev, mp_stream_t stream);
 
 /* fp16 (amp O2) training passes over channel-blocked fp16 activations; same contracts as mp_bn_train_fwd / _bwd and
  * mp_fuse_upsample_sum_bwd (statistics, gamma / beta gradients and the workspace stay fp32 / fp64; mp_bn_workspace_bytes) */

@@ -35,6 +35,12 @@ class ConvStats(ctypes.Structure):
                 ("pre_out", ctypes.c_void_p), ("pre_relu", ctypes.c_int)]
 
 
+class BottomUpStage(ctypes.Structure):
+    """``mp_bottomup_stage`` of include/mindpose_hip.h (one model output handed to the bottom-up decoder)."""
+    _fields_ = [("data", ctypes.c_void_p), ("c", ctypes.c_int32), ("h", ctypes.c_int32), ("w", ctypes.c_int32),
+                ("has_tags", ctypes.c_int32)]
+
+
 class MindposeHipError(RuntimeError):
     pass
 
@@ -170,6 +176,15 @@ _PROTOTYPES = {
     "mp_plan_add_conv_f16": (c_int, [ctypes.c_void_p, ctypes.POINTER(ConvDesc), c_int] + [c_f32p] * 7),
     "mp_plan_add_fuse_sum_f16": (c_int, [ctypes.c_void_p, c_f32p, c_f32p, c_int, c_f32p, c_int, c_f32p, c_int, c_f32p] + [c_int] * 5),
     "mp_plan_add_layout_f16": (c_int, [ctypes.c_void_p, c_int, c_f32p, c_f32p] + [c_int] * 4),
+    "mp_concat_channels": (c_int, [c_f32p, c_int, c_f32p, c_int, c_f32p] + [c_int] * 4 + [ctypes.c_void_p]),
+    "mp_plan_add_concat": (c_int, [ctypes.c_void_p, c_f32p, c_int, c_f32p, c_int, c_f32p] + [c_int] * 4),
+    "mp_col_slice": (c_int, [c_f32p, c_f32p] + [c_int] * 5 + [ctypes.c_void_p]),
+    "mp_plan_add_col_slice": (c_int, [ctypes.c_void_p, c_f32p, c_f32p] + [c_int] * 5),
+    "mp_conv_supported": (c_int, [ctypes.POINTER(ConvDesc), c_int]),
+    "mp_bottomup_workspace_bytes": (c_size_t, [c_int] * 5),
+    "mp_bottomup_parse_nms_topk": (c_int, [ctypes.POINTER(BottomUpStage), c_int, c_f32p] + [c_int] * 7 + [c_f32p, c_f32p, c_f32p, c_size_t,
+                                                                                                     ctypes.c_void_p]),
+    "mp_bottomup_gather": (c_int, [c_f32p, c_f32p, c_f32p, c_size_t] + [c_int] * 8 + [c_f32p, c_f32p, c_f32p, ctypes.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)

@@ -1,0 +1,388 @@
+// Bottom-up (associative-embedding) decoder of HigherHRNet on gfx950, plus the channel concatenation of its head and the column-band
+// copy with which the plan runs convolutions too wide for their kernels (the 512 / 832-pixel images of the bottom-up recipe).
+//
+// Replaces bottom_up_decoder.py:81-203 of the reference (about ten MindSpore ops, each a full pass over the maps) with two launches:
+//
+//   bu_parse_kernel  one workgroup per (16 x 64 output tile, joint, image).  It builds the stage mean of the tile plus an NMS halo
+//                    in LDS (every stage resized to H x W, masked), writes heatmap_raw and the resized tags of the tile, applies the
+//                    max-pool NMS from LDS and sorts the tile's 1024 (value, flat index) keys; the first max_num keys go to a slab
+//                    in the workspace.  No atomics: the slab and everything after it is deterministic.
+//   bu_gather_kernel one workgroup per (joint, image) merges the slab into the global top max_num (chunks of 4096 keys, the
+//                    running top max_num kept at the front of each chunk), then writes val_k, ind_k (with the +-0.25 shift) and
+//                    tag_k gathered from the tagging map the first kernel wrote.
+//
+// Semantics restated from MindSpore behaviour [MS-knowledge]:
+//   - ops.ResizeBilinear((H, W)) = align_corners=False, half_pixel_centers=False: src = dst * (in / out), x0 = floor(src),
+//     x1 = min(x0 + 1, in - 1), fp32 lerp.  NOT torch's F.interpolate(align_corners=False), which uses half-pixel centres.
+//   - stage mean: base = stage[-1]; base += resize(stage[i]) for i in order; base /= num_stages (a true division; skipped for
+//     one stage).
+//   - ops.ResizeNearestNeighbor of the mask: src = floor(dst * in / out); masked_fill(~mask, 0) before the NMS; heatmap_raw is the
+//     masked map before the NMS.
+//   - nn.MaxPool2d(k, stride 1, pad_mode="same") of the NMS pads with -inf; a pixel is kept when the window maximum equals it,
+//     else it becomes 0.
+//   - ops.top_k: values in descending order, equal values in ascending flat index (a key (ordered value, ~index) sorted
+//     descending gives exactly that order; -0.0 is folded into +0.0 so that it ties with the zeros).
+//   - shift_coordinate quirk: masked_select returns the max_num selected pixels in FLAT-INDEX order, but the offsets are added
+//     to ind_k, which is in VALUE order: entry m gets sign(diff) * 0.25 of the m-th smallest selected flat index.
+//
+// fp contraction is OFF in this file: the resize / mean arithmetic restates MindSpore's fp32 expressions and is compared
+// bit-for-bit with a CPU restatement on dyadic inputs.
+#include "common.h"
+
+#include <math.h>
+
+#pragma clang fp contract(off)
+
+namespace mp {
+
+constexpr int kBuTileH = 16;
+constexpr int kBuTileW = 64;  // one wavefront per tile row: 256 B coalesced reads and writes
+constexpr int kBuTilePix = kBuTileH * kBuTileW;
+constexpr int kBuThreads = 256;
+constexpr int kBuMaxStages = 4;
+constexpr int kBuMaxRadius = 3;  // nms_kernel <= 7
+constexpr int kBuHaloPix = (kBuTileH + 2 * kBuMaxRadius) * (kBuTileW + 2 * kBuMaxRadius);
+constexpr int kBuMaxM = 64;
+constexpr int kBuMergeKeys = 4096;
+constexpr int kBuMergeThreads = 512;
+constexpr int kBuMaxTags = 4;
+
+struct BuStage {
+    const float* data;  // [N, C, Hs, Ws]
+    int c, h, w;
+    int tag_slot;       // position on the last axis of tagging, -1 = no tags in this stage
+    float sy, sx;       // in / out
+};
+
+struct BuParseParams {
+    BuStage st[kBuMaxStages];
+    int ns;                       // st[ns - 1] is the full-resolution stage
+    const uint8_t* mask;          // [N, MH, MW]
+    int mh, mw;
+    float msy, msx;
+    int n, k, h, w, ktag, tag_per_joint, num_tags, r, m, tiles_x, tiles;
+    float* raw;                   // [N, K, H, W]
+    float* tagging;               // [N, KTAG, H, W, L]
+    unsigned long long* slab;     // [N, K, tiles, M]
+};
+
+__device__ __forceinline__ unsigned ordered_bits(float v) {
+    unsigned u = __float_as_uint(v);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+__device__ __forceinline__ float unordered_float(unsigned o) {
+    return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
+}
+
+__device__ __forceinline__ unsigned long long topk_key(float v, int flat) {
+    if (v == 0.0f) v = 0.0f;  // -0.0 ties with +0.0, as in a value comparison
+    return ((unsigned long long)ordered_bits(v) << 32) | (unsigned long long)(0xffffffffu - (unsigned)flat);
+}
+
+// ResizeBilinear sample (align_corners=False, half_pixel_centers=False) of one plane at output pixel (y, x)
+__device__ __forceinline__ float resize_bilinear(const float* __restrict__ plane, int ih, int iw, float sy, float sx, int y, int x) {
+    const float fy = (float)y * sy, fx = (float)x * sx;
+    const int y0 = min((int)floorf(fy), ih - 1), x0 = min((int)floorf(fx), iw - 1);
+    const int y1 = min(y0 + 1, ih - 1), x1 = min(x0 + 1, iw - 1);
+    const float dy = fy - (float)y0, dx = fx - (float)x0;
+    const float a = plane[(size_t)y0 * iw + x0], b = plane[(size_t)y0 * iw + x1];
+    const float c = plane[(size_t)y1 * iw + x0], d = plane[(size_t)y1 * iw + x1];
+    const float top = a + (b - a) * dx;
+    const float bot = c + (d - c) * dx;
+    return top + (bot - top) * dy;
+}
+
+// masked stage mean at (n, k, y, x), inside the map
+__device__ __forceinline__ float aggregate(const BuParseParams& p, int n, int k, int y, int x) {
+    const BuStage& full = p.st[p.ns - 1];
+    float v = full.data[(((size_t)n * full.c + k) * p.h + y) * p.w + x];
+    for (int i = 0; i < p.ns - 1; ++i) {
+        const BuStage& s = p.st[i];
+        v = v + resize_bilinear(s.data + ((size_t)n * s.c + k) * s.h * s.w, s.h, s.w, s.sy, s.sx, y, x);
+    }
+    if (p.ns > 1) v = v / (float)p.ns;
+    const int my = min((int)floorf((float)y * p.msy), p.mh - 1), mx = min((int)floorf((float)x * p.msx), p.mw - 1);
+    return p.mask[((size_t)n * p.mh + my) * p.mw + mx] ? v : 0.0f;
+}
+
+// descending bitonic sort of P keys in LDS by NT threads (P a power of two, P / 2 a multiple of NT)
+template <int P, int NT>
+__device__ __forceinline__ void bitonic_sort_desc(unsigned long long* s) {
+    for (int kk = 2; kk <= P; kk <<= 1) {
+        for (int j = kk >> 1; j > 0; j >>= 1) {
+#pragma unroll
+            for (int q = 0; q < P / 2 / NT; ++q) {
+                const int t = (int)threadIdx.x + q * NT;
+                const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
+                const int l = i + j;
+                const unsigned long long a = s[i], b = s[l];
+                const bool desc = (i & kk) == 0;
+                if (desc ? (a < b) : (a > b)) {
+                    s[i] = b;
+                    s[l] = a;
+                }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+__global__ __launch_bounds__(kBuThreads) void bu_parse_kernel(BuParseParams p) {
+    __shared__ float halo[kBuHaloPix];
+    __shared__ unsigned long long keys[kBuTilePix];
+    const int tile = blockIdx.x, k = blockIdx.y, n = blockIdx.z;
+    const int ty0 = (tile / p.tiles_x) * kBuTileH, tx0 = (tile % p.tiles_x) * kBuTileW;
+    const int r = p.r, hw = kBuTileW + 2 * r, hh = kBuTileH + 2 * r;
+
+    for (int i = threadIdx.x; i < hh * hw; i += kBuThreads) {
+        const int y = ty0 + i / hw - r, x = tx0 + i % hw - r;
+        halo[i] = (y >= 0 && y < p.h && x >= 0 && x < p.w) ? aggregate(p, n, k, y, x) : -INFINITY;
+    }
+    __syncthreads();
+
+    // tags of this tile: joint k writes tag channel k (tag_per_joint) or joint 0 writes the single channel
+    const bool tags_here = p.tag_per_joint || k == 0;
+    const int kt = p.tag_per_joint ? k : 0;
+    const size_t plane = (size_t)p.h * p.w;
+#pragma unroll
+    for (int q = 0; q < kBuTilePix / kBuThreads; ++q) {
+        const int pix = (int)threadIdx.x + q * kBuThreads;
+        const int ly = pix / kBuTileW, lx = pix % kBuTileW;
+        const int y = ty0 + ly, x = tx0 + lx;
+        unsigned long long key = 0;  // below every real key: pixels outside the map never win
+        if (y < p.h && x < p.w) {
+            const int flat = y * p.w + x;
+            const float v = halo[(ly + r) * hw + lx + r];
+            p.raw[((size_t)n * p.k + k) * plane + flat] = v;
+            float mx = v;
+            for (int dy = -r; dy <= r; ++dy)
+                for (int dx = -r; dx <= r; ++dx) mx = fmaxf(mx, halo[(ly + r + dy) * hw + lx + r + dx]);
+            key = topk_key(mx == v ? v : 0.0f, flat);
+            if (tags_here) {
+                for (int i = 0; i < p.ns; ++i) {
+                    const BuStage& s = p.st[i];
+                    if (s.tag_slot < 0) continue;
+                    const float t = resize_bilinear(s.data + ((size_t)n * s.c + p.k + kt) * s.h * s.w, s.h, s.w, s.sy, s.sx, y, x);
+                    p.tagging[(((size_t)n * p.ktag + kt) * plane + flat) * p.num_tags + s.tag_slot] = t;
+                }
+            }
+        }
+        keys[pix] = key;
+    }
+    __syncthreads();
+    bitonic_sort_desc<kBuTilePix, kBuThreads>(keys);
+    unsigned long long* out = p.slab + (((size_t)n * p.k + k) * p.tiles + tile) * p.m;
+    for (int i = threadIdx.x; i < p.m; i += kBuThreads) out[i] = keys[i];
+}
+
+struct BuGatherParams {
+    const float* raw;
+    const float* tagging;
+    const unsigned long long* slab;
+    int n, k, h, w, ktag, tag_per_joint, num_tags, m, tiles, shift;
+    float* val_k;  // [N, K, M]
+    float* ind_k;  // [N, K, M, 2]
+    float* tag_k;  // [N, K, M, L]
+};
+
+__global__ __launch_bounds__(kBuMergeThreads) void bu_gather_kernel(BuGatherParams p) {
+    __shared__ unsigned long long keys[kBuMergeKeys];
+    __shared__ int by_index[kBuMaxM];
+    const int k = blockIdx.x, n = blockIdx.y;
+    const unsigned long long* src = p.slab + ((size_t)n * p.k + k) * p.tiles * p.m;
+    const int total = p.tiles * p.m;
+    // running top-M in keys[0, M); every pass fills the rest of the buffer with the next slab keys and sorts
+    for (int pos = 0, front = 0; pos < total; front = p.m) {
+        const int cnt = min(total - pos, kBuMergeKeys - front);
+        for (int i = threadIdx.x; i < kBuMergeKeys - front; i += kBuMergeThreads) keys[front + i] = i < cnt ? src[pos + i] : 0ull;
+        __syncthreads();
+        bitonic_sort_desc<kBuMergeKeys, kBuMergeThreads>(keys);
+        pos += cnt;
+    }
+
+    const int t = threadIdx.x;
+    const size_t nk = (size_t)n * p.k + k;
+    int flat = 0;
+    if (t < p.m) {
+        const unsigned long long key = keys[t];
+        flat = (int)(0xffffffffu - (unsigned)(key & 0xffffffffull));
+        p.val_k[nk * p.m + t] = unordered_float((unsigned)(key >> 32));
+        const int kt = p.tag_per_joint ? k : 0;
+        const float* tg = p.tagging + (((size_t)n * p.ktag + kt) * p.h * p.w + flat) * p.num_tags;
+        for (int l = 0; l < p.num_tags; ++l) p.tag_k[(nk * p.m + t) * p.num_tags + l] = tg[l];
+        // rank of this pixel among the selected ones in flat-index order (indices are distinct)
+        int rank = 0;
+        for (int j = 0; j < p.m; ++j) rank += (int)(0xffffffffu - (unsigned)(keys[j] & 0xffffffffull)) < flat;
+        by_index[rank] = flat;
+    }
+    __syncthreads();
+    if (t < p.m) {
+        float x = (float)(flat % p.w), y = (float)(flat / p.w);
+        if (p.shift) {
+            // value-order entry t takes the offset of the t-th smallest selected flat index (the reference's masked_select order)
+            const int f = by_index[t];
+            const int fx = f % p.w, fy = f / p.w;
+            const float* plane = p.raw + nk * p.h * p.w;
+            const float dx = (fx >= 1 && fx <= p.w - 2) ? plane[f + 1] - plane[f - 1] : 0.0f;
+            const float dy = (fy >= 1 && fy <= p.h - 2) ? plane[f + p.w] - plane[f - p.w] : 0.0f;
+            x = x + (float)((dx > 0.0f) - (dx < 0.0f)) * 0.25f;
+            y = y + (float)((dy > 0.0f) - (dy < 0.0f)) * 0.25f;
+        }
+        p.ind_k[(nk * p.m + t) * 2 + 0] = x;
+        p.ind_k[(nk * p.m + t) * 2 + 1] = y;
+    }
+}
+
+// out[n] = a[n] followed by b[n], in 16-byte words when every size and pointer allows it, else in 4-byte words
+template <typename T>
+__global__ __launch_bounds__(256) void concat_kernel(const T* __restrict__ a, size_t aw, const T* __restrict__ b, size_t bw,
+                                                     T* __restrict__ out, size_t total) {
+    const size_t per = aw + bw;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const size_t img = i / per, o = i - img * per;
+        out[i] = o < aw ? a[img * aw + o] : b[img * bw + (o - aw)];
+    }
+}
+
+// out[r][0, w_out) = in[r][start, start + w_out) for every row r: a column band of an activation (one T = one pixel: a float of fp32
+// NCHW or the 16-byte channel block of the c8 layout)
+template <typename T>
+__global__ __launch_bounds__(256) void col_slice_kernel(const T* __restrict__ in, int w_in, int start, T* __restrict__ out, int w_out,
+                                                        size_t total) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const size_t row = i / (unsigned)w_out, col = i - row * (unsigned)w_out;
+        out[i] = in[row * (unsigned)w_in + start + col];
+    }
+}
+
+static int bu_tiles_x(int w) { return (w + kBuTileW - 1) / kBuTileW; }
+static int bu_tiles(int h, int w) { return bu_tiles_x(w) * ((h + kBuTileH - 1) / kBuTileH); }
+
+}  // namespace mp
+
+using namespace mp;
+
+extern "C" {
+
+size_t mp_bottomup_workspace_bytes(int n, int k, int h, int w, int max_num) {
+    if (n <= 0 || k <= 0 || h <= 0 || w <= 0 || max_num <= 0) return 0;
+    return (size_t)n * k * bu_tiles(h, w) * max_num * sizeof(unsigned long long);
+}
+
+int mp_bottomup_parse_nms_topk(const mp_bottomup_stage* stages, int num_stages, const uint8_t* mask_dev, int mask_h, int mask_w,
+                               int n, int k, int tag_per_joint, int nms_kernel, int max_num, float* heatmap_raw_dev,
+                               float* tagging_dev, void* workspace_dev, size_t workspace_bytes, mp_stream_t stream) {
+    if (!stages || !mask_dev || !heatmap_raw_dev || !tagging_dev) return MP_ERR_NULL;
+    if (num_stages < 1 || num_stages > kBuMaxStages || n <= 0 || k <= 0 || mask_h <= 0 || mask_w <= 0) return MP_ERR_SHAPE;
+    if (nms_kernel != 1 && nms_kernel != 3 && nms_kernel != 5 && nms_kernel != 7) return MP_ERR_UNSUPPORTED;
+    if (max_num < 1 || max_num > kBuMaxM) return MP_ERR_UNSUPPORTED;
+    BuParseParams p{};
+    const mp_bottomup_stage& full = stages[num_stages - 1];
+    p.h = full.h;
+    p.w = full.w;
+    if (p.h <= 0 || p.w <= 0 || (size_t)p.h * p.w > 0x7fffffffu || max_num > p.h * p.w) return MP_ERR_SHAPE;
+    p.ktag = tag_per_joint ? k : 1;
+    int slot = 0;
+    for (int i = 0; i < num_stages; ++i) {
+        const mp_bottomup_stage& s = stages[i];
+        if (!s.data_dev) return MP_ERR_NULL;
+        if (s.h <= 0 || s.w <= 0 || s.c < k) return MP_ERR_SHAPE;
+        if (s.has_tags && s.c - k != p.ktag) return MP_ERR_SHAPE;
+        p.st[i] = BuStage{s.data_dev, s.c, s.h, s.w, s.has_tags ? slot : -1, (float)s.h / (float)p.h, (float)s.w / (float)p.w};
+        slot += s.has_tags ? 1 : 0;
+    }
+    if (slot == 0 || slot > kBuMaxTags) return MP_ERR_UNSUPPORTED;
+    const size_t need = mp_bottomup_workspace_bytes(n, k, p.h, p.w, max_num);
+    if (!workspace_dev || workspace_bytes < need) return MP_ERR_WORKSPACE;
+    p.ns = num_stages;
+    p.mask = mask_dev;
+    p.mh = mask_h;
+    p.mw = mask_w;
+    p.msy = (float)mask_h / (float)p.h;
+    p.msx = (float)mask_w / (float)p.w;
+    p.n = n;
+    p.k = k;
+    p.tag_per_joint = tag_per_joint ? 1 : 0;
+    p.num_tags = slot;
+    p.r = nms_kernel / 2;
+    p.m = max_num;
+    p.tiles_x = bu_tiles_x(p.w);
+    p.tiles = bu_tiles(p.h, p.w);
+    p.raw = heatmap_raw_dev;
+    p.tagging = tagging_dev;
+    p.slab = reinterpret_cast<unsigned long long*>(workspace_dev);
+    if (n > 65535 || k > 65535) return MP_ERR_SHAPE;
+    hipLaunchKernelGGL(bu_parse_kernel, dim3((unsigned)p.tiles, (unsigned)k, (unsigned)n), dim3(kBuThreads), 0, as_stream(stream), p);
+    return check_launch();
+}
+
+int mp_bottomup_gather(const float* heatmap_raw_dev, const float* tagging_dev, const void* workspace_dev, size_t workspace_bytes,
+                       int n, int k, int h, int w, int tag_per_joint, int num_tags, int max_num, int shift_coordinate,
+                       float* val_k_dev, float* ind_k_dev, float* tag_k_dev, mp_stream_t stream) {
+    if (!heatmap_raw_dev || !tagging_dev || !val_k_dev || !ind_k_dev || !tag_k_dev) return MP_ERR_NULL;
+    if (n <= 0 || k <= 0 || h <= 0 || w <= 0 || (size_t)h * w > 0x7fffffffu) return MP_ERR_SHAPE;
+    if (max_num < 1 || max_num > kBuMaxM || num_tags < 1 || num_tags > kBuMaxTags) return MP_ERR_UNSUPPORTED;
+    if (max_num > h * w || n > 65535 || k > 65535) return MP_ERR_SHAPE;
+    const size_t need = mp_bottomup_workspace_bytes(n, k, h, w, max_num);
+    if (!workspace_dev || workspace_bytes < need) return MP_ERR_WORKSPACE;
+    BuGatherParams p{};
+    p.raw = heatmap_raw_dev;
+    p.tagging = tagging_dev;
+    p.slab = reinterpret_cast<const unsigned long long*>(workspace_dev);
+    p.n = n;
+    p.k = k;
+    p.h = h;
+    p.w = w;
+    p.ktag = tag_per_joint ? k : 1;
+    p.tag_per_joint = tag_per_joint ? 1 : 0;
+    p.num_tags = num_tags;
+    p.m = max_num;
+    p.tiles = bu_tiles(h, w);
+    p.shift = shift_coordinate ? 1 : 0;
+    p.val_k = val_k_dev;
+    p.ind_k = ind_k_dev;
+    p.tag_k = tag_k_dev;
+    hipLaunchKernelGGL(bu_gather_kernel, dim3((unsigned)k, (unsigned)n), dim3(kBuMergeThreads), 0, as_stream(stream), p);
+    return check_launch();
+}
+
+int mp_concat_channels(const void* a_dev, int ca, const void* b_dev, int cb, void* out_dev, int n, int h, int w, int c8,
+                       mp_stream_t stream) {
+    if (!a_dev || !b_dev || !out_dev) return MP_ERR_NULL;
+    if (n <= 0 || ca <= 0 || cb <= 0 || h <= 0 || w <= 0) return MP_ERR_SHAPE;
+    if (c8 && ca % 8 != 0) return MP_ERR_UNSUPPORTED;  // the second part must start on an 8-channel block
+    const size_t hw = (size_t)h * w;
+    // bytes per image of each part: fp32 NCHW planes, or whole [H][W][8] fp16 blocks (the pad channels of b's last block are zero)
+    const size_t ab = c8 ? (size_t)(ca / 8) * hw * 16 : (size_t)ca * hw * 4;
+    const size_t bb = c8 ? (size_t)((cb + 7) / 8) * hw * 16 : (size_t)cb * hw * 4;
+    const bool wide = ab % 16 == 0 && bb % 16 == 0 && ((uintptr_t)a_dev | (uintptr_t)b_dev | (uintptr_t)out_dev) % 16 == 0;
+    const size_t unit = wide ? 16 : 4;
+    const size_t total = (size_t)n * (ab + bb) / unit;
+    size_t blocks = (total + 255) / 256;
+    if (blocks > 16384) blocks = 16384;
+    if (wide)
+        hipLaunchKernelGGL(concat_kernel<uint4>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), (const uint4*)a_dev, ab / 16,
+                           (const uint4*)b_dev, bb / 16, (uint4*)out_dev, total);
+    else
+        hipLaunchKernelGGL(concat_kernel<uint32_t>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), (const uint32_t*)a_dev,
+                           ab / 4, (const uint32_t*)b_dev, bb / 4, (uint32_t*)out_dev, total);
+    return check_launch();
+}
+
+int mp_col_slice(const void* in_dev, void* out_dev, int rows, int w_in, int start, int w_out, int c8, mp_stream_t stream) {
+    if (!in_dev || !out_dev) return MP_ERR_NULL;
+    if (rows <= 0 || w_in <= 0 || w_out <= 0 || start < 0 || start + w_out > w_in) return MP_ERR_SHAPE;
+    const size_t total = (size_t)rows * w_out;
+    size_t blocks = (total + 255) / 256;
+    if (blocks > 16384) blocks = 16384;
+    if (c8)
+        hipLaunchKernelGGL(col_slice_kernel<uint4>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), (const uint4*)in_dev, w_in,
+                           start, (uint4*)out_dev, w_out, total);
+    else
+        hipLaunchKernelGGL(col_slice_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), (const float*)in_dev, w_in,
+                           start, (float*)out_dev, w_out, total);
+    return check_launch();
+}
+
+}  // extern "C"

@@ -358,7 +358,8 @@ struct mp_plan {
         int kind;  // 0 conv, 1 maxpool, 2 fuse-sum; fp16 layout: 3 conv, 4 fuse-sum, 5 NCHW fp32 -> c8, 6 c8 -> NCHW fp32;
                    // 7 = all-lane barrier (no launch), 8 = fused fp16 BasicBlock, 9 = fp32 Winograd conv,
                    // 10 = fp16 expand + reduce 1x1 chain (stage 1), 11 = fp16 first conv from the fp32 image, 12 = fp32 first conv (streaming form),
-                   // 13 = fp32 expand + reduce 1x1 chain (stage 1)
+                   // 13 = fp32 expand + reduce 1x1 chain (stage 1), 14 = channel concatenation (s[0] / s[1] channels, relu = c8 layout),
+                   // 15 = column band copy (n rows, c = input width, h = first column, w = band width, relu = c8 layout)
         int lane;  // execution lane: 0 = the caller's stream, 1..3 = the plan's own side streams
         ConvLaunch conv;
         ConvF16Launch conv16;
@@ -414,6 +415,8 @@ static int run_entry(const mp_plan::Entry& e, mp_stream_t stream) {
         case 11: return stemf16_launch(e.stem16, as_stream(stream));
         case 12: return stemf32_launch(e.stem32, as_stream(stream));
         case 13: return pwchain32_launch(e.pwchain32, as_stream(stream));
+        case 14: return mp_concat_channels(e.x16, e.s[0], e.t16[0], e.s[1], e.out16, e.n, e.h, e.w, e.relu, stream);
+        case 15: return mp_col_slice(e.x16, e.out16, e.n, e.c, e.h, e.w, e.relu, stream);
         default: return MP_ERR_UNSUPPORTED;
     }
 }
@@ -768,6 +771,38 @@ int mp_plan_add_layout_f16(mp_plan* plan, int to_c8, const void* x, void* out, i
     e.lane = plan->cur_lane;
     plan->entries.push_back(e);
     return MP_OK;
+}
+
+int mp_plan_add_concat(mp_plan* plan, const void* a, int ca, const void* b, int cb, void* out, int n, int h, int w, int c8) {
+    if (!plan || !a || !b || !out) return MP_ERR_NULL;
+    if (n <= 0 || ca <= 0 || cb <= 0 || h <= 0 || w <= 0) return MP_ERR_SHAPE;
+    if (c8 && ca % 8 != 0) return MP_ERR_UNSUPPORTED;
+    mp_plan::Entry e{};
+    e.kind = 14;
+    e.x16 = a; e.t16[0] = b; e.out16 = out;
+    e.s[0] = ca; e.s[1] = cb; e.relu = c8 ? 1 : 0;
+    e.n = n; e.c = ca + cb; e.h = h; e.w = w;
+    e.lane = plan->cur_lane;
+    plan->entries.push_back(e);
+    return MP_OK;
+}
+
+int mp_plan_add_col_slice(mp_plan* plan, const void* in, void* out, int rows, int w_in, int start, int w_out, int c8) {
+    if (!plan || !in || !out) return MP_ERR_NULL;
+    if (rows <= 0 || w_in <= 0 || w_out <= 0 || start < 0 || start + w_out > w_in) return MP_ERR_SHAPE;
+    mp_plan::Entry e{};
+    e.kind = 15;
+    e.x16 = in; e.out16 = out;
+    e.n = rows; e.c = w_in; e.h = start; e.w = w_out; e.relu = c8 ? 1 : 0;
+    e.lane = plan->cur_lane;
+    plan->entries.push_back(e);
+    return MP_OK;
+}
+
+int mp_conv_supported(const mp_conv_desc* desc, int variant) {
+    if (validate_desc(desc) != MP_OK) return 0;
+    ConvLaunch L{};
+    return choose_variant(*desc, L, variant) == MP_OK ? 1 : 0;
 }
 
 int mp_plan_size(const mp_plan* plan) { return plan ? (int)plan->entries.size() : MP_ERR_NULL; }

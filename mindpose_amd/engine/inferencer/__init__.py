@@ -1,3 +1,4 @@
+from .bottomup_inferencer import BottomUpHeatMapAEInferencer  # noqa: F401
 from .topdown_inferencer import TopDownHeatMapInferencer  # noqa: F401
 
-__all__ = ["TopDownHeatMapInferencer"]
+__all__ = ["BottomUpHeatMapAEInferencer", "TopDownHeatMapInferencer"]

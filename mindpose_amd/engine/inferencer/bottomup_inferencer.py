@@ -1,0 +1,115 @@
+"""Bottom-up (associative-embedding) inference engine (reference: mindpose/engine/inferencer/bottomup_inferencer.py:18-250).
+
+The network and the decoder run on the HIP path (``EvalNet(net, BottomUpHeatMapAEDecoder)``); the grouping
+(``match_by_tag``), the optional missing-joint refinement and the back-projection are host numpy, as in the reference.
+"""
+from functools import partial
+from typing import Any, Dict, Iterable, List, Optional, Tuple
+
+import numpy as np
+import torch
+
+from ...data.transform.utils import transform_keypoints
+from ...models import EvalNet
+from ...models.decoders import BottomUpHeatMapAEDecoder
+from ...register import register
+from ...utils.match import match_by_tag
+
+
+@register("inferencer", extra_name="bottomup_heatmap_ae")
+class BottomUpHeatMapAEInferencer:
+    """Runs the evaluation network over an iterable of batches and returns records ``{pred, score, image_path}``."""
+
+    def __init__(self, net: EvalNet, config: Optional[Dict[str, Any]] = None, progress_bar: bool = False,
+                 decoder: Optional[BottomUpHeatMapAEDecoder] = None) -> None:
+        self.net = net
+        self.config = config if config else dict()
+        self._inference_cfg = self.load_inference_cfg()
+        self.progress_bar = progress_bar
+        self.decoder = decoder
+        if self.decoder is None and self._inference_cfg["hflip_tta"]:
+            raise ValueError("Decoder must be provided for flip TTA")
+        if self._inference_cfg["hflip_tta"] and not self._inference_cfg["has_heatmap_output"]:
+            raise ValueError("flip TTA need heatmap output.")
+        if self._inference_cfg["hflip_tta"]:
+            raise NotImplementedError("bottom-up flip TTA (hflip_tta=True) is not implemented on the HIP path yet")
+
+    def load_inference_cfg(self) -> Dict[str, Any]:
+        """bottomup_inferencer.py:66-89."""
+        c = self.config
+        cfg = dict(has_heatmap_output=c["has_heatmap_output"], hflip_tta=c["hflip_tta"], joint_order=c["joint_order"],
+                   vis_thr=float(c["vis_thr"]), ignore_too_much=c["ignore_too_much"], use_rounded_norm=c["use_rounded_norm"],
+                   tag_thr=float(c["tag_thr"]), pixel_std=float(c["pixel_std"]), downsample_scale=c["downsample_scale"],
+                   refine_missing_joint=c["refine_missing_joint"])
+        flip_index = np.array(c["flip_pairs"])[:, ::-1].flatten()
+        cfg["flip_index"] = np.insert(flip_index, 0, 0)
+        return cfg
+
+    def __call__(self, dataset: Iterable[Dict[str, Any]]) -> List[Dict[str, Any]]:
+        return self.infer(dataset)
+
+    @torch.no_grad()
+    def infer(self, dataset: Iterable[Dict[str, Any]]) -> List[Dict[str, Any]]:
+        """``dataset`` yields dicts with ``image, mask`` (CUDA tensors) and ``center, scale, image_shape, image_file``;
+        returns one record ``{pred [P, K, 3 + L], score [P], image_path}`` per image (:91-187)."""
+        outputs = []
+        for data in dataset:
+            if self._inference_cfg["has_heatmap_output"]:
+                preds, _ = self.net(data["image"], data["mask"])
+            else:
+                preds = self.net(data["image"], data["mask"])
+            keypoints, scores = self._parse(*preds)
+            center, scale, image_shape = (np.asarray(data[k].cpu() if torch.is_tensor(data[k]) else data[k])
+                                          for k in ("center", "scale", "image_shape"))
+            keypoints = transform_keypoints(keypoints, center, scale, image_shape / self._inference_cfg["downsample_scale"],
+                                            pixel_std=self._inference_cfg["pixel_std"])
+            paths = data.get("image_file", [None] * len(keypoints))
+            for pred, score, path in zip(keypoints, scores, paths):
+                outputs.append(dict(pred=pred, score=score, image_path=path.tolist() if hasattr(path, "tolist") else path))
+        return outputs
+
+    def _parse(self, val_k, tag_k, ind_k, heatmap, tagging_heatmap) -> Tuple[List[np.ndarray], List[List[float]]]:
+        """Grouping, per-person score (mean joint value) and the optional missing-joint refinement (:120-150)."""
+        keypoints = self._match(val_k, tag_k, ind_k)
+        scores = [[person[:, 2].mean() for person in people] for people in keypoints]
+        if self._inference_cfg["refine_missing_joint"]:
+            heatmap = heatmap.cpu().numpy()
+            tagging_heatmap = tagging_heatmap.cpu().numpy()
+            for i in range(len(keypoints)):
+                for j in range(len(keypoints[i])):
+                    keypoints[i][j] = refine_missing_joint(heatmap[i], tagging_heatmap[i], keypoints[i][j])
+        return keypoints, scores
+
+    def _match(self, val_k, tag_k, ind_k) -> List[np.ndarray]:
+        cfg = self._inference_cfg
+        fn = partial(match_by_tag, joint_order=cfg["joint_order"], vis_thr=cfg["vis_thr"], tag_thr=cfg["tag_thr"],
+                     ignore_too_much=cfg["ignore_too_much"], use_rounded_norm=cfg["use_rounded_norm"])
+        return list(map(fn, val_k.cpu().numpy(), tag_k.cpu().numpy(), ind_k.cpu().numpy()))
+
+
+def refine_missing_joint(heatmap: np.ndarray, tagging_heatmap: np.ndarray, keypoints: np.ndarray) -> np.ndarray:
+    """Fill the joints of one person that grouping left empty (bottomup_inferencer.py:189-250).  heatmap [K, H, W],
+    tagging_heatmap [K, H, W, L], keypoints [K, 3 + L] (updated in place and returned): per joint, the pixel maximising
+    heat-map value minus the rounded L2 distance between its tag and the person's mean tag, at its centre (+0.5) shifted
+    0.25 towards the larger horizontal / vertical neighbour; taken only where the person has no value and the pixel's is > 0."""
+    k, h, w = heatmap.shape
+    located = keypoints[:, :2].astype(np.int32)
+    person_tags = [tagging_heatmap[j, located[j, 1], located[j, 0]] for j in range(k) if keypoints[j, 2] > 0]
+    mean_tag = np.mean(person_tags, axis=0)
+
+    dist = np.round(np.linalg.norm(tagging_heatmap - mean_tag[None, None, None, :], axis=3))
+    best = np.argmax((heatmap - dist).reshape(k, -1), axis=1)
+    ys_int, xs_int = np.unravel_index(best, (h, w))
+    xs = xs_int.astype(np.float32) + 0.5
+    ys = ys_int.astype(np.float32) + 0.5
+    for j in range(k):
+        x, y = xs_int[j], ys_int[j]
+        xs[j] += 0.25 if heatmap[j, y, min(x + 1, w - 1)] > heatmap[j, y, max(x - 1, 0)] else -0.25
+        ys[j] += 0.25 if heatmap[j, min(y + 1, h - 1), x] > heatmap[j, max(0, y - 1), x] else -0.25
+
+    vals = heatmap[np.arange(k), ys_int, xs_int]
+    found = np.stack((xs, ys, vals), axis=1)
+    for j in range(k):
+        if found[j, 2] > 0 and keypoints[j, 2] == 0:
+            keypoints[j, :3] = found[j]
+    return keypoints

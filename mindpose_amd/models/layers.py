@@ -547,9 +547,11 @@ class Plan:
     # -- ops ----------------------------------------------------------------------------------
     def conv(self, x: torch.Tensor, conv: Conv2d, bn: Optional[BatchNorm2d] = None, relu: bool = False,
              res1: Optional[torch.Tensor] = None, res2: Optional[torch.Tensor] = None,
-             out: Optional[torch.Tensor] = None, upsample: int = 1) -> torch.Tensor:
+             out: Optional[torch.Tensor] = None, upsample: int = 1, _band=None) -> torch.Tensor:
         """conv (+BN or bias) (+res1) (+res2) (+ReLU); ``upsample`` = nearest factor applied while storing
-        (``out`` / ``res*`` then live at the up-sampled resolution)."""
+        (``out`` / ``res*`` then live at the up-sampled resolution).  A layer no kernel serves at its full width is recorded as
+        output-column bands (`_conv_by_columns`); ``_band = (first output column, band width, left padding)`` is one of them, ``x``
+        then being the band's input columns and ``out`` the full-width output."""
         n, cin, h, w = x.shape
         k, s, pad = conv.kernel_size, conv.stride, conv.padding
         if cin != conv.in_channels:
@@ -557,7 +559,16 @@ class Plan:
         half = isinstance(x, ActC8)  # the kernel family follows the activation: fp32 NCHW tensors take the fp32 kernels
         ho = (h + 2 * pad - k) // s + 1
         wo = (w + 2 * pad - k) // s + 1
+        col0, pad_left = 0, pad
+        if _band is not None:
+            col0, wo, pad_left = _band
         oh, ow = ho * upsample, wo * upsample
+        if _band is not None:
+            ow = out.shape[3]
+        elif upsample == 1:
+            d = self._conv_desc(n, cin, h, w, conv.out_channels, k, s, pad, pad, ho, wo, ho, wo, 0, relu)
+            if not self._conv_served(d, half, int(res1 is not None) + int(res2 is not None)):
+                return self._conv_by_columns(x, conv, bn, relu, res1, res2, out)
         if out is None:
             out = self.alloc(n, conv.out_channels, oh, ow) if half else self.alloc_f32(n, conv.out_channels, oh, ow)
         if tuple(out.shape) != (n, conv.out_channels, oh, ow):
@@ -568,8 +579,8 @@ class Plan:
         packed = self._pack(conv.weight, conv.out_channels, cin, k, False, 0, 0, half)
         scale, shift = self._affine(conv.out_channels, bn, conv.bias, half)
         d = _lib.ConvDesc(n=n, cin=cin, h=h, w=w, cout=conv.out_channels, kh=k, kw=k, stride=s, pad_top=pad,
-                          pad_left=pad, conv_h=ho, conv_w=wo, out_h=oh, out_w=ow, out_mul=upsample, out_rep=upsample,
-                          out_off_y=0, out_off_x=0, relu=int(relu), flags=0)
+                          pad_left=pad_left, conv_h=ho, conv_w=wo, out_h=oh, out_w=ow, out_mul=upsample, out_rep=upsample,
+                          out_off_y=0, out_off_x=col0, relu=int(relu), flags=0)
         if half and upsample != 1:
             raise NotImplementedError("fp16 plans add up-sampled terms with fuse_sum, not through the conv epilogue")
         packed_u = None
@@ -589,6 +600,63 @@ class Plan:
                        _lib.ptr(res1), _lib.ptr(res2), _lib.ptr(out)), "mp_plan_add_conv")
         self.layer_info.append(dict(kind="conv_f16" if half else "conv", k=k, stride=s, cin=cin, cout=conv.out_channels,
                                     h=h, w=w, n=n, macs=n * ho * wo * conv.out_channels * cin * k * k))
+        return out
+
+    @staticmethod
+    def _conv_desc(n, cin, h, w, cout, k, s, pad_top, pad_left, ho, wo, out_h, out_w, col0, relu):
+        return _lib.ConvDesc(n=n, cin=cin, h=h, w=w, cout=cout, kh=k, kw=k, stride=s, pad_top=pad_top, pad_left=pad_left, conv_h=ho,
+                             conv_w=wo, out_h=out_h, out_w=out_w, out_mul=1, out_rep=1, out_off_y=0, out_off_x=col0, relu=int(relu),
+                             flags=0)
+
+    def _conv_served(self, d, half: bool, n_res: int) -> bool:
+        """Does any kernel form (the library heuristic, a tile variant the tuner could pick, the Winograd form) take this conv?"""
+        if half:
+            return any(self.lib.mp_f16_conv_supported(ctypes.byref(d), v, n_res, 0) == 1 for v in range(-1, F16_VARIANTS))
+        if any(self.lib.mp_conv_supported(ctypes.byref(d), v) == 1 for v in range(-1, F32_SMALL_WIDE + 1)):
+            return True
+        return winograd_enabled() and self.lib.mp_conv_winograd_supported(ctypes.byref(d)) == 0
+
+    def col_slice(self, x, start: int, width: int):
+        """Columns [start, start + width) of an activation of the plan's layout, as a new buffer (mp_plan_add_col_slice)."""
+        n, c, h, w = x.shape
+        half = isinstance(x, ActC8)
+        out = self.alloc(n, c, h, width) if half else self.alloc_f32(n, c, h, width)
+        rows = n * ((c + 7) // 8 if half else c) * h
+        _lib.check(self.lib.mp_plan_add_col_slice(self.handle, _lib.ptr(x), _lib.ptr(out), rows, w, start, width, int(half)),
+                   "mp_plan_add_col_slice")
+        self.layer_info.append(dict(kind="col_slice", n=n, c=c, h=h, w=width, macs=0))
+        return out
+
+    def _conv_by_columns(self, x, conv: Conv2d, bn, relu, res1, res2, out):
+        """A conv too wide for every kernel (the first convs of HRNet on 512 / 832-pixel images, the full-resolution layers of the
+        HigherHRNet head): the fewest equal output-column bands that every band's kernel takes.  Each band copies its input
+        columns (plus the kernel's reach) into a buffer of its own and writes its output columns in place (out_off_x); a band's
+        arithmetic is the full layer's, per output pixel."""
+        n, cin, h, w = x.shape
+        k, s, pad = conv.kernel_size, conv.stride, conv.padding
+        half = isinstance(x, ActC8)
+        ho, wo = (h + 2 * pad - k) // s + 1, (w + 2 * pad - k) // s + 1
+        n_res = int(res1 is not None) + int(res2 is not None)
+        for nb in range(2, 33):
+            width = -(-wo // nb)
+            bands = []
+            for c0 in range(0, wo, width):
+                cw = min(width, wo - c0)
+                first = c0 * s - pad  # input column of the band's first tap
+                start, pl = max(first, 0), max(-first, 0)
+                stop = min(w, (c0 + cw - 1) * s - pad + k)
+                d = self._conv_desc(n, cin, h, stop - start, conv.out_channels, k, s, pad, pl, ho, cw, ho, wo, c0, relu)
+                bands.append((c0, cw, start, stop - start, pl, d))
+            if all(self._conv_served(b[5], half, n_res) for b in bands):
+                break
+        else:
+            raise _lib.MindposeHipError(f"no kernel serves the conv {tuple(x.shape)} -> {conv.out_channels} channels (k {k}, stride {s}), "
+                                        "not even in output-column bands")
+        if out is None:
+            out = self.alloc(n, conv.out_channels, ho, wo) if half else self.alloc_f32(n, conv.out_channels, ho, wo)
+        for c0, cw, start, wb, pl, _ in bands:
+            xb = self.col_slice(x, start, wb)
+            self.conv(xb, conv, bn, relu, res1, res2, out, _band=(c0, cw, pl))
         return out
 
     def fuses_basic_block(self, x: torch.Tensor, conv1: Conv2d, conv2: Conv2d) -> bool:
@@ -796,6 +864,8 @@ class Plan:
 
         phases = [(py, px) for py in (0, 1) for px in (0, 1)]
         macs = n * h * w * cout * cin * 4
+        if not all(self._conv_served(desc(py, px), half, 0) for py, px in phases):
+            return self._deconv_by_columns(x, deconv, out, scale, shift, relu)
         if half:
             for py, px in phases:
                 packed = self._pack(deconv.weight, cout, cin, 2, True, py, px, True)
@@ -851,6 +921,41 @@ class Plan:
             self.layer_info.append(dict(kind="deconv_phase", k=2, stride=1, cin=cin, cout=cout, h=h, w=w, n=n, macs=macs))
         return out
 
+    def _deconv_by_columns(self, x, deconv: Conv2dTranspose, out, scale, shift, relu: bool):
+        """`deconv4x4s2` on a map too wide for every phase kernel (the HigherHRNet head on 832-pixel images): each 2x2 phase conv
+        in the fewest input-column bands every band's kernel takes (`_conv_by_columns`; phase px of band column j lands on output
+        column 2 j + px)."""
+        half = isinstance(x, ActC8)
+        n, cin, h, w = x.shape
+        cout = deconv.out_channels
+        for py, px in [(py, px) for py in (0, 1) for px in (0, 1)]:
+            packed = self._pack(deconv.weight, cout, cin, 2, True, py, px, half)
+            for nb in range(2, 33):
+                width = -(-w // nb)
+                bands = []
+                for c0 in range(0, w, width):
+                    cw = min(width, w - c0)
+                    first = c0 - (1 - px)
+                    start, pl = max(first, 0), max(-first, 0)
+                    stop = min(w, c0 + cw - 1 - (1 - px) + 2)
+                    d = _lib.ConvDesc(n=n, cin=cin, h=h, w=stop - start, cout=cout, kh=2, kw=2, stride=1, pad_top=1 - py, pad_left=pl,
+                                      conv_h=h, conv_w=cw, out_h=2 * h, out_w=2 * w, out_mul=2, out_rep=1, out_off_y=py,
+                                      out_off_x=2 * c0 + px, relu=int(relu), flags=0)
+                    bands.append((start, stop - start, d))
+                if all(self._conv_served(d, half, 0) for _, _, d in bands):
+                    break
+            else:
+                raise _lib.MindposeHipError(f"no kernel serves the transposed conv {tuple(x.shape)} -> {cout}, not even in bands")
+            for start, wb, d in bands:
+                xb = self.col_slice(x, start, wb)
+                v = tune_conv_variant(self.lib, d, xb, packed, scale, shift, None, None, out, half=half)
+                add = self.lib.mp_plan_add_conv_f16 if half else self.lib.mp_plan_add_conv_variant
+                _lib.check(add(self.handle, ctypes.byref(d), v, _lib.ptr(xb), _lib.ptr(packed), _lib.ptr(scale), _lib.ptr(shift), None,
+                               None, _lib.ptr(out)), "mp_plan_add_conv(deconv phase band)")
+                self.layer_info.append(dict(kind="deconv_phase_f16" if half else "deconv_phase", k=2, stride=1, cin=cin, cout=cout, h=h,
+                                            w=d.w, n=n, macs=n * h * d.conv_w * cout * cin * 4))
+        return out
+
     def fuse_sum(self, base: torch.Tensor, terms, out: torch.Tensor, relu: bool = True) -> torch.Tensor:
         """out = act(((base + up(t1)) + up(t2)) + up(t3)); ``terms`` = [(low-res tensor, integer scale), ...] (1-3)."""
         n, c, h, w = base.shape
@@ -866,6 +971,20 @@ class Plan:
         self.layer_info.append(dict(kind="fuse_sum", n=n, c=c, h=h, w=w, terms=len(terms), macs=0))
         return out
 
+    def concat(self, a, b):
+        """``ops.concat((a, b), 1)`` of two activations of the plan's layout into a new buffer (mp_plan_add_concat): fp32 NCHW, or
+        channel-blocked fp16 when ``a`` has a multiple of 8 channels (one block copy per image)."""
+        n, ca, h, w = a.shape
+        cb = b.shape[1]
+        half = isinstance(a, ActC8)
+        if half != isinstance(b, ActC8) or tuple(b.shape) != (n, cb, h, w):
+            raise ValueError(f"concat operands {tuple(a.shape)} / {tuple(b.shape)} do not match")
+        out = self.alloc(n, ca + cb, h, w) if half else self.alloc_f32(n, ca + cb, h, w)
+        _lib.check(self.lib.mp_plan_add_concat(self.handle, _lib.ptr(a), ca, _lib.ptr(b), cb, _lib.ptr(out), n, h, w, int(half)),
+                   "mp_plan_add_concat")
+        self.layer_info.append(dict(kind="concat", n=n, c=ca + cb, h=h, w=w, macs=0))
+        return out
+
     def maxpool3x3s2_same(self, x: torch.Tensor) -> torch.Tensor:
         if isinstance(x, ActC8):
             raise NotImplementedError("max-pool runs on fp32 NCHW activations (the ResNet stem stays fp32 under amp O2)")
@@ -879,10 +998,11 @@ class Plan:
 class PlannedModule(nn.Module):
     """Base of every module whose forward is a recorded HIP launch plan.
 
-    Sub-classes implement ``emit(plan, x) -> out`` (record launches, return the output buffer).
+    Sub-classes implement ``emit(plan, x) -> out`` (record launches, return the output buffer, or a list / tuple of them for a
+    multi-output network such as HigherHRNet).
     ``forward`` copies the batch into the plan's static input buffer (skipped when the caller already
-    wrote into ``input_buffer(shape)``), replays the plan and returns the plan's output buffer
-    (a view that the next call overwrites - clone it if it must outlive the next forward).
+    wrote into ``input_buffer(shape)``), replays the plan and returns the plan's output buffer - or the list of them
+    (views that the next call overwrites - clone them if they must outlive the next forward).
     """
 
     def __init__(self) -> None:
@@ -925,7 +1045,10 @@ class PlannedModule(nn.Module):
                 plan = Plan(device, half=half)
                 plan.input = plan.alloc_f32(*shape)
                 out = self.emit(plan, plan.input)  # backbones switch to the fp16 layout themselves (plan.enter)
-                plan.output = plan.from_c8(out) if isinstance(out, ActC8) else out
+                if isinstance(out, (list, tuple)):
+                    plan.output = [plan.from_c8(o) if isinstance(o, ActC8) else o for o in out]
+                else:
+                    plan.output = plan.from_c8(out) if isinstance(out, ActC8) else out
             self._plans[key] = plan
         return plan
 
