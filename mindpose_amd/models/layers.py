@@ -319,6 +319,43 @@ def tune_conv_variant(lib, d, x, packed, scale, shift, res1, res2, out, half: bo
     return _autotune(key, macs, F16_VARIANTS if half else F32_SMALL_WIDE + 1, launch)
 
 
+def conv_column_bands(n, cin, h, w, cout, k, s, pad, relu, nb):
+    """A conv layer [n, cin, h, w] -> cout channels (k x k, stride s, padding pad) as output-column bands of ceil(wo / nb) columns:
+    per band ``(start, width_in, ConvDesc)`` - the band reads input columns [start, start + width_in) as a tensor of its own and
+    writes output columns [out_off_x, out_off_x + conv_w) of the full [n, cout, ho, wo] output.  Only the first band keeps the left
+    padding; the last one is clipped at the input's right edge, where the kernel's bounds check supplies the layer's own zeros."""
+    ho, wo = (h + 2 * pad - k) // s + 1, (w + 2 * pad - k) // s + 1
+    width = -(-wo // nb)
+    bands = []
+    for c0 in range(0, wo, width):
+        cw = min(width, wo - c0)
+        first = c0 * s - pad  # input column of the band's first tap
+        start, pl = max(first, 0), max(-first, 0)
+        stop = min(w, (c0 + cw - 1) * s - pad + k)
+        d = _lib.ConvDesc(n=n, cin=cin, h=h, w=stop - start, cout=cout, kh=k, kw=k, stride=s, pad_top=pad, pad_left=pl, conv_h=ho,
+                          conv_w=cw, out_h=ho, out_w=wo, out_mul=1, out_rep=1, out_off_y=0, out_off_x=c0, relu=int(relu), flags=0)
+        bands.append((start, stop - start, d))
+    return bands
+
+
+def deconv_phase_column_bands(n, cin, h, w, cout, py, px, relu, nb):
+    """Phase (py, px) of Conv2dTranspose(k=4, s=2, p=1) on [n, cin, h, w] - a 2x2 stride-1 conv whose output pixel (y, j) lands on
+    (2 y + py, 2 j + px) - as input-column bands of ceil(w / nb) columns: per band ``(start, width_in, ConvDesc)`` as in
+    `conv_column_bands`; column j of the band that starts at c0 lands on output column 2 (c0 + j) + px."""
+    width = -(-w // nb)
+    bands = []
+    for c0 in range(0, w, width):
+        cw = min(width, w - c0)
+        first = c0 - (1 - px)
+        start, pl = max(first, 0), max(-first, 0)
+        stop = min(w, c0 + cw - 1 - (1 - px) + 2)
+        d = _lib.ConvDesc(n=n, cin=cin, h=h, w=stop - start, cout=cout, kh=2, kw=2, stride=1, pad_top=1 - py, pad_left=pl,
+                          conv_h=h, conv_w=cw, out_h=2 * h, out_w=2 * w, out_mul=2, out_rep=1, out_off_y=py,
+                          out_off_x=2 * c0 + px, relu=int(relu), flags=0)
+        bands.append((start, stop - start, d))
+    return bands
+
+
 class Plan:
     """A recorded forward: native ``mp_plan`` + the tensors it points into."""
 
@@ -609,12 +646,16 @@ class Plan:
                              flags=0)
 
     def _conv_served(self, d, half: bool, n_res: int) -> bool:
-        """Does any kernel form (the library heuristic, a tile variant the tuner could pick, the Winograd form) take this conv?"""
+        """Does any kernel form (the library heuristic, a tile variant the tuner could pick, the Winograd form) take this conv?
+        Forced variants count only where the tuner picks one: with ``MINDPOSE_AUTOTUNE=0``, or below its MAC threshold, the entry
+        is recorded with the heuristic, which then has to take the layer itself (else: column bands)."""
+        macs = d.n * d.conv_h * d.conv_w * d.cout * d.cin * d.kh * d.kw
+        tuned = os.environ.get("MINDPOSE_AUTOTUNE", "1") != "0" and macs >= _TUNE_MIN_MACS
         if half:
-            return any(self.lib.mp_f16_conv_supported(ctypes.byref(d), v, n_res, 0) == 1 for v in range(-1, F16_VARIANTS))
-        if any(self.lib.mp_conv_supported(ctypes.byref(d), v) == 1 for v in range(-1, F32_SMALL_WIDE + 1)):
+            return any(self.lib.mp_f16_conv_supported(ctypes.byref(d), v, n_res, 0) == 1 for v in range(-1, F16_VARIANTS if tuned else 0))
+        if any(self.lib.mp_conv_supported(ctypes.byref(d), v) == 1 for v in range(-1, F32_SMALL_WIDE + 1 if tuned else 0)):
             return True
-        return winograd_enabled() and self.lib.mp_conv_winograd_supported(ctypes.byref(d)) == 0
+        return tuned and winograd_enabled() and self.lib.mp_conv_winograd_supported(ctypes.byref(d)) == 0
 
     def col_slice(self, x, start: int, width: int):
         """Columns [start, start + width) of an activation of the plan's layout, as a new buffer (mp_plan_add_col_slice)."""
@@ -638,25 +679,17 @@ class Plan:
         ho, wo = (h + 2 * pad - k) // s + 1, (w + 2 * pad - k) // s + 1
         n_res = int(res1 is not None) + int(res2 is not None)
         for nb in range(2, 33):
-            width = -(-wo // nb)
-            bands = []
-            for c0 in range(0, wo, width):
-                cw = min(width, wo - c0)
-                first = c0 * s - pad  # input column of the band's first tap
-                start, pl = max(first, 0), max(-first, 0)
-                stop = min(w, (c0 + cw - 1) * s - pad + k)
-                d = self._conv_desc(n, cin, h, stop - start, conv.out_channels, k, s, pad, pl, ho, cw, ho, wo, c0, relu)
-                bands.append((c0, cw, start, stop - start, pl, d))
-            if all(self._conv_served(b[5], half, n_res) for b in bands):
+            bands = conv_column_bands(n, cin, h, w, conv.out_channels, k, s, pad, relu, nb)
+            if all(self._conv_served(d, half, n_res) for _, _, d in bands):
                 break
         else:
             raise _lib.MindposeHipError(f"no kernel serves the conv {tuple(x.shape)} -> {conv.out_channels} channels (k {k}, stride {s}), "
                                         "not even in output-column bands")
         if out is None:
             out = self.alloc(n, conv.out_channels, ho, wo) if half else self.alloc_f32(n, conv.out_channels, ho, wo)
-        for c0, cw, start, wb, pl, _ in bands:
+        for start, wb, d in bands:
             xb = self.col_slice(x, start, wb)
-            self.conv(xb, conv, bn, relu, res1, res2, out, _band=(c0, cw, pl))
+            self.conv(xb, conv, bn, relu, res1, res2, out, _band=(d.out_off_x, d.conv_w, d.pad_left))
         return out
 
     def fuses_basic_block(self, x: torch.Tensor, conv1: Conv2d, conv2: Conv2d) -> bool:
@@ -931,17 +964,7 @@ class Plan:
         for py, px in [(py, px) for py in (0, 1) for px in (0, 1)]:
             packed = self._pack(deconv.weight, cout, cin, 2, True, py, px, half)
             for nb in range(2, 33):
-                width = -(-w // nb)
-                bands = []
-                for c0 in range(0, w, width):
-                    cw = min(width, w - c0)
-                    first = c0 - (1 - px)
-                    start, pl = max(first, 0), max(-first, 0)
-                    stop = min(w, c0 + cw - 1 - (1 - px) + 2)
-                    d = _lib.ConvDesc(n=n, cin=cin, h=h, w=stop - start, cout=cout, kh=2, kw=2, stride=1, pad_top=1 - py, pad_left=pl,
-                                      conv_h=h, conv_w=cw, out_h=2 * h, out_w=2 * w, out_mul=2, out_rep=1, out_off_y=py,
-                                      out_off_x=2 * c0 + px, relu=int(relu), flags=0)
-                    bands.append((start, stop - start, d))
+                bands = deconv_phase_column_bands(n, cin, h, w, cout, py, px, relu, nb)
                 if all(self._conv_served(d, half, 0) for _, _, d in bands):
                     break
             else:

@@ -197,6 +197,151 @@ def test_decoder_refuses_max_num_above_64():
         mp.create_decoder("bottomup_heatmap_ae", max_num=65)
 
 
+# ---- the decoder's edges: ragged tiles, stage layouts, tag stages, NMS sizes, top-k limits, mask ratios ------------------------------
+def _sized_outputs(n, sizes, with_ae, tag_per_joint, gen):
+    ktag = K if tag_per_joint else 1
+    return [_dyadic((n, K + (ktag if ae else 0), h, w), gen) for (h, w), ae in zip(sizes, with_ae)]
+
+
+def _ratio_mask(n, size, gen, blank=None):
+    """mask of any size with a per-image zero border on the right / bottom; image ``blank`` all false"""
+    h, w = size
+    m = torch.zeros(n, h, w, dtype=torch.bool)
+    for i in range(n):
+        m[i, : h - (h // 8) * (i % 3), : w - w // 6 - (w // 10) * (i % 2)] = True
+    if blank is not None:
+        m[blank] = False
+    return m
+
+
+EDGE_CASES = {
+    # n, stage sizes (last = the map), with_ae_loss, nms_kernel, tag_per_joint, shift, max_num, mask size, all-false image
+    "40x24_ragged_tile_rows": (2, [(20, 12), (40, 24)], [True, False], 3, True, True, 30, (80, 48), None),
+    "50x70_two_tile_columns": (1, [(25, 35), (50, 70)], [True, False], 5, True, False, 30, (50, 70), None),   # mask at 1x
+    "416x256_transposed": (1, [(208, 128), (416, 256)], [True, False], 3, True, True, 30, (832, 512), None),
+    "three_stages_4_2_1": (2, [(10, 6), (20, 12), (40, 24)], [True, False, False], 3, True, True, 20, (120, 72), None),  # mask at 3x
+    "two_tag_stages_nms7": (2, [(20, 12), (40, 24)], [True, True], 7, True, True, 30, (80, 48), None),
+    "two_tag_stages_one_tag_map_no_nms": (2, [(25, 35), (50, 70)], [True, True], 1, False, True, 30, (100, 140), None),
+    "mask_ratio_2p5_by_2p375_blank_image": (3, [(20, 12), (40, 24)], [True, False], 3, True, False, 30, (100, 57), 1),
+    "n_times_k_204": (12, [(20, 12), (40, 24)], [True, False], 5, True, True, 30, (80, 48), 7),
+}
+
+
+@pytest.mark.parametrize("name", list(EDGE_CASES))
+def test_decoder_edges_bit_equal_on_dyadic_inputs(name):
+    """Map heights that are not a multiple of the 16-row tile, widths below and just above the 64-column tile, the transposed
+    recipe shape, three stages, two tag-carrying stages (num_tags = 2), NMS windows 1 and 7, masks at 1x / 3x / a non-integer
+    ratio of the map, an all-false mask for one image, a few hundred (image, joint) workgroups.  Every resize scale here is a
+    power of two, so the lerp products are exact and the outputs are bit-equal to the CPU restatement."""
+    n, sizes, with_ae, nms_kernel, tag_per_joint, shift, max_num, mask_size, blank = EDGE_CASES[name]
+    gen = torch.Generator().manual_seed(len(name) + n)
+    outs = _sized_outputs(n, sizes, with_ae, tag_per_joint, gen)
+    mask = _ratio_mask(n, mask_size, gen, blank)
+    dec = mp.create_decoder("bottomup_heatmap_ae", num_joints=K, num_stages=len(sizes), with_ae_loss=with_ae, use_nms=True,
+                            nms_kernel=nms_kernel, max_num=max_num, tag_per_joint=tag_per_joint, shift_coordinate=shift)
+    got = dec([o.to(DEV) for o in outs], mask.to(DEV))
+    torch.cuda.synchronize()
+    ref = oracle_decode(outs, mask, len(sizes), with_ae, True, nms_kernel, max_num, tag_per_joint, shift)
+    assert ref[4].shape[-1] == sum(with_ae) and ref[1].shape[-1] == sum(with_ae)
+    if blank is not None:
+        assert (ref[3][blank] == 0).all() and (ref[0][blank] == 0).all()  # the blank image really decodes to zeros
+        assert torch.equal(ref[2][blank, :, :, 0] + ref[2][blank, :, :, 1] * sizes[-1][1],
+                           torch.arange(max_num).float().expand(K, -1))    # ... returned in flat-index order
+    for nm, g, r in zip(("val_k", "tag_k", "ind_k", "heatmap_raw", "tagging"), got, ref):
+        assert tuple(g.shape) == tuple(r.shape), nm
+        assert torch.equal(g.cpu(), r), f"{nm} differs"
+
+
+def test_decoder_lower_stage_that_does_not_divide_the_map():
+    """A 13 x 11 stage under a 40 x 24 map: the resize scales 13/40 and 11/24 are not dyadic, so the source coordinates and the
+    lerp products round.  The kernel is built with fp contraction off and restates the oracle's fp32 expressions operation by
+    operation, so every rounding is the same and bit equality holds here too."""
+    gen = torch.Generator().manual_seed(21)
+    sizes, with_ae = [(13, 11), (40, 24)], [True, False]
+    outs = _sized_outputs(2, sizes, with_ae, True, gen)
+    mask = _ratio_mask(2, (80, 48), gen)
+    dec = mp.create_decoder("bottomup_heatmap_ae", use_nms=True, nms_kernel=3, max_num=30)
+    got = [t.cpu() for t in dec([o.to(DEV) for o in outs], mask.to(DEV))]
+    ref = oracle_decode(outs, mask, 2, with_ae, True, 3, 30, True, False)
+    frac = ref[3] * 1024.0
+    assert (frac != frac.round()).any()  # the resized term really left the dyadic grid of the inputs
+    for nm, g, r in zip(("val_k", "tag_k", "ind_k", "heatmap_raw", "tagging"), got, ref):
+        assert torch.equal(g, r), f"{nm} differs"
+
+
+@pytest.mark.parametrize("shift", [False, True])
+def test_decoder_returns_every_pixel_when_max_num_is_the_map(shift):
+    """max_num == h * w on an 8 x 8 map: every pixel comes back - the NMS survivors in value order, then the zeros (suppressed and
+    masked pixels) in ascending flat index."""
+    gen = torch.Generator().manual_seed(9)
+    outs = _sized_outputs(2, [(8, 8)], [True], True, gen)
+    mask = _ratio_mask(2, (16, 16), gen)
+    dec = mp.create_decoder("bottomup_heatmap_ae", num_stages=1, with_ae_loss=[True], use_nms=True, nms_kernel=3, max_num=64,
+                            shift_coordinate=shift)
+    got = [t.cpu() for t in dec([o.to(DEV) for o in outs], mask.to(DEV))]
+    ref = oracle_decode(outs, mask, 1, [True], True, 3, 64, True, shift)
+    assert (ref[0][..., -1] <= 0).all() and (ref[0][..., 0] > 0).all() and (ref[0] == 0).any()  # a real mix of peaks and zeros
+    if not shift:
+        idx = (ref[2][..., 0] + ref[2][..., 1] * 8).long()
+        assert torch.equal(idx.sort(dim=2).values, torch.arange(64).expand(2, K, -1))           # every pixel exactly once
+    for g, r in zip(got, ref):
+        assert torch.equal(g, r)
+
+
+def test_decoder_multi_pass_merge_with_a_zero_tail():
+    """112 tiles x max_num 64 = 7168 keys per (image, joint): the merge runs over two chunks of 4096, and with only seven positive
+    peaks the global top-64 is completed by zeros from the FIRST tiles, in flat-index order."""
+    gen = torch.Generator().manual_seed(6)
+    size = (256, 416)
+    assert (size[0] // 16) * -(-size[1] // 64) * 64 > 4096
+    outs = [-o.abs() for o in _outputs(2, size, [True, False], True, 2, gen)]
+    for j in range(7):
+        outs[-1][:, :K, 250 - 30 * j, 400 - 50 * j] = 2.0 * (j + 1)   # above the lower stage's term; the last tiles: past the first chunk
+    mask = _mask(2, size, gen)
+    mask[:, 400:, :] = True
+    mask[:, :, 700:] = True
+    dec = mp.create_decoder("bottomup_heatmap_ae", use_nms=True, nms_kernel=3, max_num=64, shift_coordinate=True)
+    got = [t.cpu() for t in dec([o.to(DEV) for o in outs], mask.to(DEV))]
+    ref = oracle_decode(outs, mask, 2, [True, False], True, 3, 64, True, True)
+    assert (ref[0][..., 7:] == 0).all() and (ref[0][..., :7] > 0).all()  # seven peaks, then the tail really is zeros
+    for g, r in zip(got, ref):
+        assert torch.equal(g, r)
+
+
+def test_decoder_error_paths_through_the_c_abi():
+    from mindpose_amd import _lib
+    lib = _lib.load()
+    n, h, w, m = 1, 16, 16, 8
+    stage = torch.zeros(n, 2 * K, h, w, device=DEV)
+    mask = torch.ones(n, h, w, dtype=torch.uint8, device=DEV)
+    raw, tagging = torch.empty(n, K, h, w, device=DEV), torch.empty(n, K, h, w, 4, device=DEV)
+    ws_bytes = lib.mp_bottomup_workspace_bytes(n, K, h, w, m)
+    assert ws_bytes == n * K * 1 * m * 8
+    ws = torch.empty(ws_bytes // 8 + 64, device=DEV, dtype=torch.int64)
+    val, ind, tag = torch.empty(n, K, 64, device=DEV), torch.empty(n, K, 64, 2, device=DEV), torch.empty(n, K, 64, 4, device=DEV)
+
+    def parse(stages=1, nms=3, max_num=m, bytes_=ws_bytes, ws_ptr=True):
+        descs = (_lib.BottomUpStage * stages)(*[_lib.BottomUpStage(data=stage.data_ptr(), c=2 * K, h=h, w=w, has_tags=1)] * stages)
+        return lib.mp_bottomup_parse_nms_topk(descs, stages, _lib.ptr(mask), h, w, n, K, 1, nms, max_num, _lib.ptr(raw), _lib.ptr(tagging),
+                                              _lib.ptr(ws) if ws_ptr else None, bytes_, _lib.stream())
+
+    def gather(max_num=m, bytes_=ws_bytes, num_tags=1, hh=h, ww=w):
+        return lib.mp_bottomup_gather(_lib.ptr(raw), _lib.ptr(tagging), _lib.ptr(ws), bytes_, n, K, hh, ww, 1, num_tags, max_num, 0,
+                                      _lib.ptr(val), _lib.ptr(ind), _lib.ptr(tag), _lib.stream())
+
+    assert parse() == 0 and gather() == 0
+    assert parse(bytes_=ws_bytes - 8) == -5 and gather(bytes_=ws_bytes - 8) == -5   # MP_ERR_WORKSPACE: too small
+    assert parse(ws_ptr=False) == -5                                                 # ... or missing
+    assert parse(nms=9) == -3 and parse(nms=2) == -3 and parse(nms=0) == -3          # MP_ERR_UNSUPPORTED
+    assert parse(max_num=65, bytes_=ws_bytes * 16) == -3 and parse(max_num=0) == -3
+    assert gather(max_num=65, bytes_=ws_bytes * 16) == -3
+    assert gather(max_num=5, hh=2, ww=2) == -2                                       # max_num > h * w: MP_ERR_SHAPE
+    assert parse(stages=5) == -2                                                     # more stages than the kernel carries
+    assert parse(stages=4) == 0                                                      # four tag stages are the limit ...
+    assert gather(num_tags=5) == -3                                                  # ... five are refused
+    torch.cuda.synchronize()
+
+
 # ---- network ---------------------------------------------------------------------------------------------------------------------
 def _head_forward(params, x, amp=False):
     """higher_hrnet_head.py:217-229 restated: final_layers[0], concat, Conv2dTranspose(4, 2, 1) + BN + ReLU, 4 BasicBlocks,
@@ -236,7 +381,8 @@ def _net(amp_level="O0"):
 
 
 # the eval sizes of the bottom-up recipe (configs/higher_hrnet/higher_hrnet_w32_ascend.yaml: 512 x 512, up to 832 x 512)
-@pytest.mark.parametrize("n,h,w", [(2, 512, 512), (1, 512, 832)])
+# ... and an in-between size whose column bands are ragged (176 / 352 / 704-column layers)
+@pytest.mark.parametrize("n,h,w", [(2, 512, 512), (1, 512, 832), (1, 576, 704)])
 def test_higher_hrnet_fp32_vs_oracle(n, h, w):
     net = _net()
     x = torch.randn(n, 3, h, w, generator=torch.Generator().manual_seed(11))
@@ -251,7 +397,7 @@ def test_higher_hrnet_fp32_vs_oracle(n, h, w):
         _check(g, r, 1e-3)
 
 
-@pytest.mark.parametrize("n,h,w", [(1, 512, 512), (1, 512, 832)])
+@pytest.mark.parametrize("n,h,w", [(1, 512, 512), (1, 512, 832), (1, 576, 704)])
 def test_higher_hrnet_amp_o2_vs_amp_oracle(n, h, w):
     net = _net("O2")
     x = torch.randn(n, 3, h, w, generator=torch.Generator().manual_seed(12))
