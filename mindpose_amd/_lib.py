@@ -14,6 +14,15 @@ LIB_PATH = os.environ.get("MINDPOSE_HIP_LIB", os.path.join(_HERE, "csrc", "libmi
 MP_REFINE_NONE, MP_REFINE_SHIFT, MP_REFINE_DARK = 0, 1, 2
 MP_CONV_SHARES_CUS = 1  # mp_conv_desc.flags: the launch runs beside other kernels of a training step (include/mindpose_hip.h)
 MP_CONV_PHASES4 = 2     # mp_conv_desc.flags (fp16 family): the four 2x2 phase convs of a stride-2 3x3 data gradient as one launch
+MP_ERR_UNSUPPORTED = -3  # return code: this kernel form / variant does not serve the shape (include/mindpose_hip.h)
+
+
+def env_on(name: str, default: bool = True) -> bool:
+    """An on / off switch of the environment, read when called (tests and the A/B tools flip these inside a running process):
+    a switch that defaults to on is off only for ``"0"``, one that defaults to off is on only for ``"1"``."""
+    value = os.environ.get(name)
+    return value != "0" if default else value == "1"
+
 
 c_f32p = ctypes.c_void_p  # device pointers travel as integers
 c_int = ctypes.c_int

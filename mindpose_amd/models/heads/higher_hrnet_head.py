@@ -14,7 +14,8 @@ import torch.nn as nn
 
 from ...register import register
 from ..backbones.hrnet import BasicBlock
-from ..layers import ActC8, BatchNorm2d, Conv2d, Conv2dTranspose, Plan
+from ..act_c8 import ActC8
+from ..layers import BatchNorm2d, Conv2d, Conv2dTranspose, Plan
 from .head import Head
 
 

@@ -3,19 +3,21 @@
 The modules only OWN parameters (named exactly like the reference's MindSpore cells so a mindpose
 checkpoint maps 1:1); all arithmetic happens in ``libmindpose_hip.so``.  A network forward is
 recorded once per input shape into a native launch plan (``mp_plan_*``) and replayed by one C call.
+Which tile variant / kernel form a recorded conv runs is the tuner's choice (tuner.py).
 """
 import ctypes
-import os
 from typing import Dict, List, Optional, Tuple
 
 import torch
 import torch.nn as nn
 
 from .. import _lib
+from .act_c8 import ActC8
+from .tuner import (BLOCK_ROWS, F16_VARIANTS, F32_SMALL_WIDE, F32_WINOGRAD, _autotune, autotune_on, tune_conv_variant, tuned,
+                    winograd_enabled)
+from .tuner import _TUNE_MIN_MACS  # noqa: F401 - not used here: tests/test_gpu_bands.py restates `Plan._conv_served` from this module's names
 
 BN_EPS = 1e-5  # mindspore.nn.BatchNorm2d default eps
-F16_VARIANTS = 48  # csrc/conv_f16.h F_COUNT: tile shapes the fp16 autotuner times per launch shape
-F16_WS_BASE = 37   # csrc/conv_f16.h F_WS_BASE: first weight-stationary persistent shape (conv_f16_ws.hip)
 
 
 class Conv2d(nn.Module):
@@ -60,263 +62,26 @@ class BatchNorm2d(nn.Module):
         return scale.contiguous(), shift.contiguous()
 
 
-_TUNE_CACHE: Dict[Tuple, int] = {}
-_TUNE_FILE_LOADED = False
+
+def conv_desc(n, cin, h, w, cout, k, stride, pad_top, pad_left, conv_h, conv_w, out_h, out_w, out_mul=1, out_rep=1, off_y=0, off_x=0,
+              relu=False, flags=0):
+    """``mp_conv_desc``: a k x k conv of [n, cin, h, w] computing conv_h x conv_w pixels per image, pixel (y, x) stored at
+    (out_mul y + off_y, out_mul x + off_x) of the [n, cout, out_h, out_w] output as an out_rep x out_rep block."""
+    return _lib.ConvDesc(n=n, cin=cin, h=h, w=w, cout=cout, kh=k, kw=k, stride=stride, pad_top=pad_top, pad_left=pad_left,
+                         conv_h=conv_h, conv_w=conv_w, out_h=out_h, out_w=out_w, out_mul=out_mul, out_rep=out_rep, out_off_y=off_y,
+                         out_off_x=off_x, relu=int(relu), flags=flags)
 
 
-def _tune_file() -> Optional[str]:
-    """MINDPOSE_TUNE_CACHE=<path>: persist the autotuner's choices (JSON, keyed by launch shape) so that a later process
-    - a profiling run, a production worker - replays them without timing trial launches."""
-    return os.environ.get("MINDPOSE_TUNE_CACHE") or None
-
-
-_BUILD_ID = None
-
-
-def _tune_stamp() -> str:
-    """Variant indices only mean something for one BUILD of the kernels: the stamp carries the library's version string and a
-    digest of the shared object itself (a rebuilt kernel invalidates the persisted choices without a hand-bumped version)."""
-    global _BUILD_ID
-    if _BUILD_ID is None:
-        import hashlib
-        h = hashlib.sha1()
-        try:
-            with open(_lib.LIB_PATH, "rb") as f:
-                for block in iter(lambda: f.read(1 << 20), b""):
-                    h.update(block)
-            _BUILD_ID = h.hexdigest()[:16]
-        except OSError:
-            _BUILD_ID = "unknown"
-    return f"{_lib.load().mp_version().decode()}|{_BUILD_ID}"
-
-
-def _tune_load() -> None:
-    global _TUNE_FILE_LOADED
-    path = _tune_file()
-    if _TUNE_FILE_LOADED or not path:
-        return
-    _TUNE_FILE_LOADED = True
-    try:
-        import json
-        with open(path) as f:
-            doc = json.load(f)
-        if doc.get("stamp") != _tune_stamp():  # written by another library version: variant indices may have moved
-            return
-        for k, v in doc.get("choices", {}).items():
-            _TUNE_CACHE.setdefault(k, int(v))
-    except (OSError, ValueError, AttributeError):
-        pass
-
-
-def _dist_rank_world():
-    try:
-        import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized():
-            return dist.get_rank(), dist.get_world_size()
-    except Exception:
-        pass
-    return 0, 1
-
-
-def share_tuner_choices(group=None) -> int:
-    """THE collective of the tuner, at a point the CALLER chooses: rank 0's whole choice table is broadcast once
-    (``broadcast_object_list``) and every other rank adopts it, so that the ranks of one job run the same numeric form of every
-    layer (the fp32 candidates differ numerically: Winograd vs direct, one GEMM launch vs four phase convs).  Every rank of
-    ``group`` must call it, at the same point of its program - e.g. right after rank 0's warm-up (`tune_on_rank0_first`).  The
-    tuner itself never communicates: a plan that only one rank builds (EvalCallback's rank-0 evaluation, a no-grad probe) can
-    therefore never strand or cross-match a collective.  Returns the number of choices adopted (0 on rank 0 / one rank)."""
-    if _dist_rank_world()[1] == 1:
-        return 0
-    import torch.distributed as dist
-    rank, world = dist.get_rank(group), dist.get_world_size(group)  # ranks OF THE GROUP: a sub-group without global rank 0 has its own sender
-    if world <= 1:
-        return 0
-    box = [{k: v for k, v in _TUNE_CACHE.items() if isinstance(k, str)} if rank == 0 else None]
-    dist.broadcast_object_list(box, src=dist.get_global_rank(group, 0) if group is not None else 0, group=group)
-    if rank == 0:
-        return 0
-    _TUNE_CACHE.update(box[0])
-    return len(box[0])
-
-
-def tune_on_rank0_first(build, group=None):
-    """``build()`` - anything that records plans / runs warm-up passes and contains NO collective - on rank 0 first (it tunes),
-    then `share_tuner_choices`, then on the other ranks (every shape is a cache hit: nothing is timed twice, all ranks run rank 0's
-    forms).  One rank: just ``build()``.  Rank 0 reaches the broadcast even when its ``build()`` raised (the exception is re-raised
-    behind it), so a failure on rank 0 cannot leave the other ranks waiting."""
-    if _dist_rank_world()[1] == 1:
-        return build()
-    import torch.distributed as dist
-    rank = dist.get_rank(group)
-    out, failure = None, None
-    if rank == 0:
-        try:
-            out = build()
-        except Exception as exc:  # noqa: BLE001 - re-raised below, after the collective every rank is waiting in
-            failure = exc
-    share_tuner_choices(group)
-    if failure is not None:
-        raise failure
-    return out if rank == 0 else build()
-
-
-def _tune_save() -> None:
-    """Whole-file replace through a temporary (a torn file would silently drop the cache); rank 0 is the only writer of a job."""
-    path = _tune_file()
-    if not path or _dist_rank_world()[0] != 0:
-        return
-    try:
-        import json
-        tmp = f"{path}.{os.getpid()}.tmp"
-        with open(tmp, "w") as f:
-            json.dump({"stamp": _tune_stamp(), "choices": {k: v for k, v in _TUNE_CACHE.items() if isinstance(k, str)}}, f)
-        os.replace(tmp, path)
-    except OSError:
-        pass
-
-
-class ActC8:
-    """fp16 activation in the channel-blocked layout of the fp16 matrix-core path: physical tensor
-    ``[N][ceil(C/8)][H][W][8]`` halfs (padding channels zero), ``shape`` = the logical NCHW shape."""
-
-    def __init__(self, n: int, c: int, h: int, w: int, device) -> None:
-        self.shape = torch.Size((n, c, h, w))
-        self.c8_tensor = torch.zeros(n, (c + 7) // 8, h, w, 8, device=device, dtype=torch.float16)
-        self.device = self.c8_tensor.device
-
-    def data_ptr(self) -> int:
-        return self.c8_tensor.data_ptr()
-
-    def to_nchw(self) -> torch.Tensor:
-        """fp32 NCHW copy (tests / debugging)."""
-        n, c, h, w = self.shape
-        return self.c8_tensor.permute(0, 1, 4, 2, 3).reshape(n, -1, h, w)[:, :c].float().contiguous()
-
-
-# launches below this many multiply-accumulates keep the library's heuristic (MINDPOSE_TUNE_MIN_MACS overrides).  Round 4 tuned from
-# 2^26 up - which left EVERY layer of a one-crop forward (28 M MACs per 32-channel conv at N = 1) on the heuristic: a top-down
-# pipeline serves a handful of crops per frame, and there the tile choice decides whether a launch covers 8 or 64 CUs
-_TUNE_MIN_MACS = int(os.environ.get("MINDPOSE_TUNE_MIN_MACS", str(1 << 22)))
-
-
-def _autotune(key, macs, n_variants, launch) -> int:
-    """Time ``launch(v)`` for every tile variant (HIP events, best of two groups of 5 launches; MP_ERR_UNSUPPORTED = variant not
-    available, any other error code raises) and cache the winner per launch shape; -1 = library heuristic when tuning is off (MINDPOSE_AUTOTUNE=0) or
-    pointless (tiny layers)."""
-    if os.environ.get("MINDPOSE_AUTOTUNE", "1") == "0":
-        return -1
-    _tune_load()
-    key = repr(key)
-    hit = _TUNE_CACHE.get(key)
-    if hit is not None:
-        return hit
-    best, best_t = -1, None
-    if macs >= _TUNE_MIN_MACS:  # a miss is timed on whichever rank meets it - no communication here (share_tuner_choices)
-        for v in range(n_variants):
-            rc = launch(v)
-            if rc == -3:  # MP_ERR_UNSUPPORTED: this variant does not serve the shape
-                continue
-            _lib.check(rc, f"tuner trial launch, variant {v}, {key}")  # any other code (a HIP error) must not silently drop a candidate
-            t = None
-            for _ in range(2):  # best of two groups of five: one group of three mis-ranked close candidates run to run (+-1.5 %)
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                for _ in range(5):
-                    launch(v)
-                e1.record()
-                e1.synchronize()
-                dt = e0.elapsed_time(e1)
-                t = dt if t is None or dt < t else t
-            if best_t is None or t < best_t:
-                best, best_t = v, t
-            log = os.environ.get("MINDPOSE_TUNE_LOG")  # per-candidate timings (ms per 5 launches), for kernel work
-            if log:
-                with open(log, "a") as fh:
-                    fh.write(f"{key}\t{v}\t{t:.4f}\n")
-    _TUNE_CACHE[key] = best
-    if macs >= _TUNE_MIN_MACS:
-        _tune_save()
-    return best
-
-
-BLOCK_ROWS = (0, 4, 2, 1)  # band heights the fused-BasicBlock tuner times (0 = the tallest that fits)
-F32_VARIANTS = 9   # direct MFMA tile variants 0..7 (csrc/conv_mfma.h ConvVariant) + 8 = the streaming 1x1 kernel (conv_pw_f32.hip)
-F32_WINOGRAD = 9   # the tuner's index of the Winograd F(2x2,3x3) form (csrc/conv_wino_f32.hip)
-F32_GEMM = 10      # the blocked-GEMM 1x1 kernel (csrc/conv_gemm_f32.hip; conv_api.hip kGemm)
-F32_SMALL = 11     # the K-split kernel for small problems - a handful of crops (csrc/conv_small_f32.hip; conv_api.hip kSmall)
-F32_SMALL_WIDE = 12  # ... with 48 / 64 pixels per workgroup (a few dozen crops: the weights of a workgroup serve more pixels)
-
-
-def winograd_enabled() -> bool:
-    """``MINDPOSE_WINOGRAD=0`` keeps every fp32 3x3 convolution on the direct kernel (bit-identical to round 1's results)."""
-    return os.environ.get("MINDPOSE_WINOGRAD", "1") != "0"
-
-
-def tune_conv_variant(lib, d, x, packed, scale, shift, res1, res2, out, half: bool = False, packed_u=None, stats=None) -> int:
-    """Pick the tile variant for one conv launch shape by timing the candidates on the layer's real buffers.  Results
-    are cached per shape, so a network's ~40 distinct shapes are tuned once per process.  ``packed_u`` (fp32 only): the
-    Winograd-transformed weights; the Winograd form then competes as index ``F32_WINOGRAD``.  ``stats`` (fp16 training):
-    ``dict(mode, z, y, relu)`` - the launch is the one with BatchNorm statistics in its epilogue (mp_f16_conv2d_fwd_stats: other
-    register budgets, two more tensor reads in mode 2), timed as such and cached under its own key; with ``pre = dict(scale, shift, y,
-    relu)`` the launch also applies the BatchNorm of the layer below on its operand (candidates: mp_f16_conv_pre_supported)."""
-    key = tuple(getattr(d, f) for f, _ in d._fields_) + (res1 is not None, res2 is not None, str(out.device), half)
-    if packed_u is not None:
-        key += ("wino",)
-    if stats is not None:
-        key += ("stats", int(stats["mode"]), int(bool(stats.get("relu"))))
-        if stats.get("pre") is not None:  # BatchNorm apply of the layer below on the operand: its own candidate set, its own key
-            key += ("pre",)
-    macs = d.n * d.conv_h * d.conv_w * d.cout * d.cin * d.kh * d.kw
-    stream = _lib.stream()
-    # in-place accumulation (out aliases res1) must not be disturbed by trial launches: tune into a scratch copy
-    alias = res1 is not None and res1.data_ptr() == out.data_ptr()
-    trial_out = out
-    if alias:
-        trial_out = torch.empty_like(out) if torch.is_tensor(out) else ActC8(*out.shape, out.device)
-    fn = lib.mp_f16_conv2d_fwd if half else lib.mp_conv2d_fwd_variant
-
-    stats_buf = {}
-    # a statistics build that leaves more than 512 partial slots per channel costs its consumer an extra fold launch (~5 us): such
-    # variants compete only when no variant of the shape stays within 512
-    slot_cap = [512]
-    with_pre = stats is not None and stats.get("pre") is not None
-    if stats is not None and not any(0 < lib.mp_f16_conv_stats_parts(ctypes.byref(d), v) <= 512 for v in range(F16_VARIANTS)
-                                     if not with_pre or lib.mp_f16_conv_pre_supported(ctypes.byref(d), v)):
-        slot_cap[0] = 1 << 30
-
-    no_small = os.environ.get("MINDPOSE_F32_SMALL", "1") == "0"  # before / after evidence: the candidate set without the small-problem kernel
-    no_ws = half and os.environ.get("MINDPOSE_F16_WS", "1") == "0"  # before / after evidence: the round-3 candidate set
-
-    def launch(v):
-        if no_ws and v >= F16_WS_BASE:  # (the round-4 weights-in-registers shapes 45.. included)
-            return -3
-        if stats is not None:
-            n_parts = lib.mp_f16_conv_stats_parts(ctypes.byref(d), v)
-            if n_parts <= 0 or n_parts > slot_cap[0]:
-                return -3
-            need = (d.cout + 7) // 8 * n_parts * 16
-            if stats_buf.get("n", 0) < need:
-                stats_buf["t"], stats_buf["n"] = torch.empty(need, device=out.device, dtype=torch.float32), need
-            st = _lib.ConvStats(mode=int(stats["mode"]), relu=int(bool(stats.get("relu"))), partials=stats_buf["t"].data_ptr(),
-                                partials_bytes=need * 4, z=_lib.ptr(stats.get("z")), y=_lib.ptr(stats.get("y")) if stats.get("relu") else None)
-            pre = stats.get("pre")
-            if pre is not None:
-                if not lib.mp_f16_conv_pre_supported(ctypes.byref(d), v):
-                    return -3
-                st.pre_scale, st.pre_shift, st.pre_out, st.pre_relu = _lib.ptr(pre["scale"]), _lib.ptr(pre["shift"]), _lib.ptr(pre["y"]), int(pre["relu"])
-            return lib.mp_f16_conv2d_fwd_stats(ctypes.byref(d), v, _lib.ptr(x), _lib.ptr(packed), _lib.ptr(scale), _lib.ptr(shift),
-                                               _lib.ptr(res1), _lib.ptr(trial_out), ctypes.byref(st), stream)
-        if not half and v in (F32_SMALL, F32_SMALL_WIDE) and no_small:
-            return -3
-        if not half and v == F32_WINOGRAD:
-            if packed_u is None:
-                return -3  # MP_ERR_UNSUPPORTED: no Winograd form of this layer
-            return lib.mp_conv2d_winograd_fwd(ctypes.byref(d), _lib.ptr(x), _lib.ptr(packed_u), _lib.ptr(scale), _lib.ptr(shift),
-                                              _lib.ptr(res1), _lib.ptr(res2), _lib.ptr(trial_out), stream)
-        return fn(ctypes.byref(d), v, _lib.ptr(x), _lib.ptr(packed), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(res1),
-                  _lib.ptr(res2), _lib.ptr(trial_out), stream)
-
-    return _autotune(key, macs, F16_VARIANTS if half else F32_SMALL_WIDE + 1, launch)
+def deconv_phase_desc(n, cin, h, w, cout, py, px, relu, c0=0, cw=None):
+    """Phase (py, px) of Conv2dTranspose(k=4, s=2, p=1) on [n, cin, h, w] - a 2x2 stride-1 conv whose output pixel (y, j) lands on
+    (2 y + py, 2 j + px) - for the columns j in [c0, c0 + cw) (default: all w of them): ``(start, width_in, ConvDesc)``, the conv
+    reading input columns [start, start + width_in) as a tensor of its own (all of them: start 0, width_in w)."""
+    cw = w - c0 if cw is None else cw
+    first = c0 - (1 - px)  # input column of the first tap
+    start, stop = max(first, 0), min(w, first + cw + 1)
+    d = conv_desc(n, cin, h, stop - start, cout, 2, 1, 1 - py, max(-first, 0), h, cw, 2 * h, 2 * w, out_mul=2, off_y=py,
+                  off_x=2 * c0 + px, relu=relu)
+    return start, stop - start, d
 
 
 def conv_column_bands(n, cin, h, w, cout, k, s, pad, relu, nb):
@@ -330,30 +95,21 @@ def conv_column_bands(n, cin, h, w, cout, k, s, pad, relu, nb):
     for c0 in range(0, wo, width):
         cw = min(width, wo - c0)
         first = c0 * s - pad  # input column of the band's first tap
-        start, pl = max(first, 0), max(-first, 0)
-        stop = min(w, (c0 + cw - 1) * s - pad + k)
-        d = _lib.ConvDesc(n=n, cin=cin, h=h, w=stop - start, cout=cout, kh=k, kw=k, stride=s, pad_top=pad, pad_left=pl, conv_h=ho,
-                          conv_w=cw, out_h=ho, out_w=wo, out_mul=1, out_rep=1, out_off_y=0, out_off_x=c0, relu=int(relu), flags=0)
-        bands.append((start, stop - start, d))
+        start, stop = max(first, 0), min(w, (c0 + cw - 1) * s - pad + k)
+        bands.append((start, stop - start, conv_desc(n, cin, h, stop - start, cout, k, s, pad, max(-first, 0), ho, cw, ho, wo,
+                                                     off_x=c0, relu=relu)))
     return bands
 
 
 def deconv_phase_column_bands(n, cin, h, w, cout, py, px, relu, nb):
-    """Phase (py, px) of Conv2dTranspose(k=4, s=2, p=1) on [n, cin, h, w] - a 2x2 stride-1 conv whose output pixel (y, j) lands on
-    (2 y + py, 2 j + px) - as input-column bands of ceil(w / nb) columns: per band ``(start, width_in, ConvDesc)`` as in
+    """`deconv_phase_desc` as input-column bands of ceil(w / nb) columns: per band ``(start, width_in, ConvDesc)`` as in
     `conv_column_bands`; column j of the band that starts at c0 lands on output column 2 (c0 + j) + px."""
     width = -(-w // nb)
-    bands = []
-    for c0 in range(0, w, width):
-        cw = min(width, w - c0)
-        first = c0 - (1 - px)
-        start, pl = max(first, 0), max(-first, 0)
-        stop = min(w, c0 + cw - 1 - (1 - px) + 2)
-        d = _lib.ConvDesc(n=n, cin=cin, h=h, w=stop - start, cout=cout, kh=2, kw=2, stride=1, pad_top=1 - py, pad_left=pl,
-                          conv_h=h, conv_w=cw, out_h=2 * h, out_w=2 * w, out_mul=2, out_rep=1, out_off_y=py,
-                          out_off_x=2 * c0 + px, relu=int(relu), flags=0)
-        bands.append((start, stop - start, d))
-    return bands
+    return [deconv_phase_desc(n, cin, h, w, cout, py, px, relu, c0, min(width, w - c0)) for c0 in range(0, w, width)]
+
+
+def _macs(d) -> int:
+    return d.n * d.conv_h * d.conv_w * d.cout * d.cin * d.kh * d.kw
 
 
 class Plan:
@@ -363,7 +119,7 @@ class Plan:
         self.lib = _lib.load()
         self.device = device
         self.half = half  # amp O2/O3: fp16 matrix-core kernels over channel-blocked fp16 activations
-        self.lanes = os.environ.get("MINDPOSE_PLAN_LANES", "1") != "0"
+        self.lanes = _lib.env_on("MINDPOSE_PLAN_LANES")
         self.handle = ctypes.c_void_p(self.lib.mp_plan_create())
         if not self.handle:
             raise _lib.MindposeHipError("mp_plan_create failed")
@@ -400,6 +156,13 @@ class Plan:
         t = torch.empty(shape, device=self.device, dtype=torch.float32)
         self.keep.append(t)
         return t
+
+    def _alloc_like(self, x, *shape: int):
+        """Activation buffer of ``x``'s kind (the kernel family follows the activation, not the plan: the fp32 stem of an fp16 plan)."""
+        return self.alloc(*shape) if isinstance(x, ActC8) else self.alloc_f32(*shape)
+
+    def _conv_info(self, kind: str, k: int, stride: int, cin: int, cout: int, h: int, w: int, n: int, macs: int) -> None:
+        self.layer_info.append(dict(kind=kind, k=k, stride=stride, cin=cin, cout=cout, h=h, w=w, n=n, macs=macs))
 
     def to_c8(self, x: torch.Tensor) -> "ActC8":
         """NCHW fp32 -> channel-blocked fp16 (first entry of an fp16 plan)."""
@@ -440,7 +203,7 @@ class Plan:
                 # two queues (tools/timeline.sh on the inference plan: 12 barriers per HRNet-W32 forward): O2 inference +10 %, fp32 +2 %.
                 # MINDPOSE_PLAN_GRAPH_LANES=0: keep replaying through the native call.
                 self._multi = True
-                if os.environ.get("MINDPOSE_PLAN_GRAPH_LANES", "1") == "0":
+                if not _lib.env_on("MINDPOSE_PLAN_GRAPH_LANES"):
                     self._graph_ok = False
 
     def barrier(self) -> None:
@@ -458,7 +221,7 @@ class Plan:
             return
         _lib.check(self.lib.mp_plan_run(self.handle, _lib.stream()), "mp_plan_run")
         self._runs += 1
-        if self._runs == 2 and self._graph_ok and os.environ.get("MINDPOSE_HIP_GRAPH", "1") != "0":
+        if self._runs == 2 and self._graph_ok and _lib.env_on("MINDPOSE_HIP_GRAPH"):
             self._capture()
 
     def _capture(self) -> None:
@@ -533,17 +296,12 @@ class Plan:
             return self._packed[key]
         w = weight.detach().to(self.device, torch.float32).contiguous()
         if half:
-            nbytes = self.lib.mp_f16_packed_weight_bytes(cout, cin, k, k)
-            packed = torch.empty(nbytes // 2, device=self.device, dtype=torch.float16)
-            _lib.check(self.lib.mp_f16_pack_weight(_lib.ptr(w), _lib.ptr(packed), cout, cin, k, k, int(transposed), py, px,
-                                                   _lib.stream()), "mp_f16_pack_weight")
-            self.keep += [w, packed]
-            self._packed[key] = packed
-            return packed
-        nbytes = self.lib.mp_conv_packed_weight_bytes(cout, cin, k, k)
-        packed = torch.empty(nbytes // 4, device=self.device, dtype=torch.float32)
-        _lib.check(self.lib.mp_conv_pack_weight(_lib.ptr(w), _lib.ptr(packed), cout, cin, k, k, int(transposed), py, px,
-                                                _lib.stream()), "mp_conv_pack_weight")
+            nbytes, pack, dtype = self.lib.mp_f16_packed_weight_bytes(cout, cin, k, k), self.lib.mp_f16_pack_weight, torch.float16
+        else:
+            nbytes, pack, dtype = self.lib.mp_conv_packed_weight_bytes(cout, cin, k, k), self.lib.mp_conv_pack_weight, torch.float32
+        packed = torch.empty(nbytes // (2 if half else 4), device=self.device, dtype=dtype)
+        _lib.check(pack(_lib.ptr(w), _lib.ptr(packed), cout, cin, k, k, int(transposed), py, px, _lib.stream()),
+                   "mp_f16_pack_weight" if half else "mp_conv_pack_weight")
         self.keep += [w, packed]
         self._packed[key] = packed
         return packed
@@ -584,84 +342,87 @@ class Plan:
     # -- ops ----------------------------------------------------------------------------------
     def conv(self, x: torch.Tensor, conv: Conv2d, bn: Optional[BatchNorm2d] = None, relu: bool = False,
              res1: Optional[torch.Tensor] = None, res2: Optional[torch.Tensor] = None,
-             out: Optional[torch.Tensor] = None, upsample: int = 1, _band=None) -> torch.Tensor:
+             out: Optional[torch.Tensor] = None, upsample: int = 1) -> torch.Tensor:
         """conv (+BN or bias) (+res1) (+res2) (+ReLU); ``upsample`` = nearest factor applied while storing
         (``out`` / ``res*`` then live at the up-sampled resolution).  A layer no kernel serves at its full width is recorded as
-        output-column bands (`_conv_by_columns`); ``_band = (first output column, band width, left padding)`` is one of them, ``x``
-        then being the band's input columns and ``out`` the full-width output."""
+        output-column bands (`_conv_by_columns`)."""
         n, cin, h, w = x.shape
-        k, s, pad = conv.kernel_size, conv.stride, conv.padding
+        k, s, pad, cout = conv.kernel_size, conv.stride, conv.padding, conv.out_channels
         if cin != conv.in_channels:
             raise ValueError(f"conv expects {conv.in_channels} input channels, got {cin}")
         half = isinstance(x, ActC8)  # the kernel family follows the activation: fp32 NCHW tensors take the fp32 kernels
-        ho = (h + 2 * pad - k) // s + 1
-        wo = (w + 2 * pad - k) // s + 1
-        col0, pad_left = 0, pad
-        if _band is not None:
-            col0, wo, pad_left = _band
-        oh, ow = ho * upsample, wo * upsample
-        if _band is not None:
-            ow = out.shape[3]
-        elif upsample == 1:
-            d = self._conv_desc(n, cin, h, w, conv.out_channels, k, s, pad, pad, ho, wo, ho, wo, 0, relu)
-            if not self._conv_served(d, half, int(res1 is not None) + int(res2 is not None)):
-                return self._conv_by_columns(x, conv, bn, relu, res1, res2, out)
-        if out is None:
-            out = self.alloc(n, conv.out_channels, oh, ow) if half else self.alloc_f32(n, conv.out_channels, oh, ow)
-        if tuple(out.shape) != (n, conv.out_channels, oh, ow):
-            raise ValueError(f"bad out shape {tuple(out.shape)}")
-        for r in (res1, res2):
-            if r is not None and tuple(r.shape) != tuple(out.shape):
-                raise ValueError(f"residual shape {tuple(r.shape)} != out shape {tuple(out.shape)}")
-        packed = self._pack(conv.weight, conv.out_channels, cin, k, False, 0, 0, half)
-        scale, shift = self._affine(conv.out_channels, bn, conv.bias, half)
-        d = _lib.ConvDesc(n=n, cin=cin, h=h, w=w, cout=conv.out_channels, kh=k, kw=k, stride=s, pad_top=pad,
-                          pad_left=pad_left, conv_h=ho, conv_w=wo, out_h=oh, out_w=ow, out_mul=upsample, out_rep=upsample,
-                          out_off_y=0, out_off_x=col0, relu=int(relu), flags=0)
         if half and upsample != 1:
             raise NotImplementedError("fp16 plans add up-sampled terms with fuse_sum, not through the conv epilogue")
-        packed_u = None
-        if (not half and winograd_enabled() and os.environ.get("MINDPOSE_AUTOTUNE", "1") != "0"
-                and self.lib.mp_conv_winograd_supported(ctypes.byref(d)) == 0):
-            packed_u = self._pack_winograd(conv.weight, conv.out_channels, cin)
-        variant = tune_conv_variant(self.lib, d, x, packed, scale, shift, res1, res2, out, half=half, packed_u=packed_u)
-        if not half and variant == F32_WINOGRAD:
-            _lib.check(self.lib.mp_plan_add_conv_winograd(self.handle, ctypes.byref(d), _lib.ptr(x), _lib.ptr(packed_u), _lib.ptr(scale),
-                                                          _lib.ptr(shift), _lib.ptr(res1), _lib.ptr(res2), _lib.ptr(out)),
-                       "mp_plan_add_conv_winograd")
-            self.layer_info.append(dict(kind="conv_winograd", k=k, stride=s, cin=cin, cout=conv.out_channels, h=h, w=w, n=n,
-                                        macs=n * ho * wo * conv.out_channels * cin * k * k))
-            return out
-        add = self.lib.mp_plan_add_conv_f16 if half else self.lib.mp_plan_add_conv_variant
-        _lib.check(add(self.handle, ctypes.byref(d), variant, _lib.ptr(x), _lib.ptr(packed), _lib.ptr(scale), _lib.ptr(shift),
-                       _lib.ptr(res1), _lib.ptr(res2), _lib.ptr(out)), "mp_plan_add_conv")
-        self.layer_info.append(dict(kind="conv_f16" if half else "conv", k=k, stride=s, cin=cin, cout=conv.out_channels,
-                                    h=h, w=w, n=n, macs=n * ho * wo * conv.out_channels * cin * k * k))
+        ho = (h + 2 * pad - k) // s + 1
+        wo = (w + 2 * pad - k) // s + 1
+        d = conv_desc(n, cin, h, w, cout, k, s, pad, pad, ho, wo, ho * upsample, wo * upsample, upsample, upsample, relu=relu)
+        if upsample == 1 and not self._conv_served(d, half, int(res1 is not None) + int(res2 is not None)):
+            return self._conv_by_columns(x, conv, bn, relu, res1, res2, out)
+        out = self._conv_out(x, d, res1, res2, out)
+        return self._record_conv(d, x, self._pack(conv.weight, cout, cin, k, False, 0, 0, half), *self._affine(cout, bn, conv.bias, half),
+                                 res1, res2, out, "conv_f16" if half else "conv", packed_u=self._winograd_weight(d, conv, half))
+
+    def _conv_out(self, x, d, res1, res2, out):
+        """The [n, cout, out_h, out_w] output of ``d``: the caller's ``out`` (checked, with the residuals), else a new buffer."""
+        shape = (d.n, d.cout, d.out_h, d.out_w)
+        if out is None:
+            out = self._alloc_like(x, *shape)
+        if tuple(out.shape) != shape:
+            raise ValueError(f"bad out shape {tuple(out.shape)}")
+        for r in (res1, res2):
+            if r is not None and tuple(r.shape) != shape:
+                raise ValueError(f"residual shape {tuple(r.shape)} != out shape {shape}")
         return out
 
-    @staticmethod
-    def _conv_desc(n, cin, h, w, cout, k, s, pad_top, pad_left, ho, wo, out_h, out_w, col0, relu):
-        return _lib.ConvDesc(n=n, cin=cin, h=h, w=w, cout=cout, kh=k, kw=k, stride=s, pad_top=pad_top, pad_left=pad_left, conv_h=ho,
-                             conv_w=wo, out_h=out_h, out_w=out_w, out_mul=1, out_rep=1, out_off_y=0, out_off_x=col0, relu=int(relu),
-                             flags=0)
+    def _winograd_weight(self, d, conv: Conv2d, half: bool):
+        """The Winograd form of ``conv``'s weight where it competes in the tuner for ``d`` (fp32, 3x3 stride 1), else None.  Asks
+        for the tuner's switch only, not `tuned(macs)`: a small layer's tuner key carries the form too (its pick is then -1)."""
+        if half or not (winograd_enabled() and autotune_on()) or self.lib.mp_conv_winograd_supported(ctypes.byref(d)) != 0:
+            return None
+        return self._pack_winograd(conv.weight, conv.out_channels, conv.in_channels)
+
+    def _record_conv(self, d, x, packed, scale, shift, res1, res2, out, kind: str, packed_u=None, variant: Optional[int] = None):
+        """THE place where a conv becomes a plan entry: the tuner picks the variant of ``d`` on the operand buffers (unless the
+        caller already holds the pick), the entry is added in that form - ``packed_u``: the Winograd weight (fp32), which then
+        competes - and its `layer_info` record follows (what ``d`` describes: a band reports the band).  Returns ``out``."""
+        half = isinstance(x, ActC8)
+        if variant is None:
+            variant = tune_conv_variant(self.lib, d, x, packed, scale, shift, res1, res2, out, half=half, packed_u=packed_u)
+        operands = [_lib.ptr(t) for t in (scale, shift, res1, res2, out)]
+        if not half and variant == F32_WINOGRAD:
+            kind = "conv_winograd"
+            _lib.check(self.lib.mp_plan_add_conv_winograd(self.handle, ctypes.byref(d), _lib.ptr(x), _lib.ptr(packed_u), *operands),
+                       "mp_plan_add_conv_winograd")
+        else:
+            add = self.lib.mp_plan_add_conv_f16 if half else self.lib.mp_plan_add_conv_variant
+            _lib.check(add(self.handle, ctypes.byref(d), variant, _lib.ptr(x), _lib.ptr(packed), *operands), f"mp_plan_add_conv ({kind})")
+        self._conv_info(kind, d.kh, d.stride, d.cin, d.cout, d.h, d.w, d.n, _macs(d))
+        return out
 
     def _conv_served(self, d, half: bool, n_res: int) -> bool:
         """Does any kernel form (the library heuristic, a tile variant the tuner could pick, the Winograd form) take this conv?
         Forced variants count only where the tuner picks one: with ``MINDPOSE_AUTOTUNE=0``, or below its MAC threshold, the entry
         is recorded with the heuristic, which then has to take the layer itself (else: column bands)."""
-        macs = d.n * d.conv_h * d.conv_w * d.cout * d.cin * d.kh * d.kw
-        tuned = os.environ.get("MINDPOSE_AUTOTUNE", "1") != "0" and macs >= _TUNE_MIN_MACS
+        picks = tuned(_macs(d))
         if half:
-            return any(self.lib.mp_f16_conv_supported(ctypes.byref(d), v, n_res, 0) == 1 for v in range(-1, F16_VARIANTS if tuned else 0))
-        if any(self.lib.mp_conv_supported(ctypes.byref(d), v) == 1 for v in range(-1, F32_SMALL_WIDE + 1 if tuned else 0)):
+            return any(self.lib.mp_f16_conv_supported(ctypes.byref(d), v, n_res, 0) == 1 for v in range(-1, F16_VARIANTS if picks else 0))
+        if any(self.lib.mp_conv_supported(ctypes.byref(d), v) == 1 for v in range(-1, F32_SMALL_WIDE + 1 if picks else 0)):
             return True
-        return tuned and winograd_enabled() and self.lib.mp_conv_winograd_supported(ctypes.byref(d)) == 0
+        return picks and winograd_enabled() and self.lib.mp_conv_winograd_supported(ctypes.byref(d)) == 0
+
+    def _fewest_bands(self, bands_of, half: bool, n_res: int, what: str):
+        """``bands_of(nb)`` for the smallest nb in 2..32 whose every band some kernel serves."""
+        for nb in range(2, 33):
+            bands = bands_of(nb)
+            if all(self._conv_served(d, half, n_res) for _, _, d in bands):
+                return bands
+        raise _lib.MindposeHipError(f"no kernel serves the {what}, not even in column bands")
 
     def col_slice(self, x, start: int, width: int):
         """Columns [start, start + width) of an activation of the plan's layout, as a new buffer (mp_plan_add_col_slice)."""
         n, c, h, w = x.shape
         half = isinstance(x, ActC8)
-        out = self.alloc(n, c, h, width) if half else self.alloc_f32(n, c, h, width)
+        out = self._alloc_like(x, n, c, h, width)
         rows = n * ((c + 7) // 8 if half else c) * h
         _lib.check(self.lib.mp_plan_add_col_slice(self.handle, _lib.ptr(x), _lib.ptr(out), rows, w, start, width, int(half)),
                    "mp_plan_add_col_slice")
@@ -674,35 +435,30 @@ class Plan:
         columns (plus the kernel's reach) into a buffer of its own and writes its output columns in place (out_off_x); a band's
         arithmetic is the full layer's, per output pixel."""
         n, cin, h, w = x.shape
-        k, s, pad = conv.kernel_size, conv.stride, conv.padding
+        k, s, pad, cout = conv.kernel_size, conv.stride, conv.padding, conv.out_channels
         half = isinstance(x, ActC8)
-        ho, wo = (h + 2 * pad - k) // s + 1, (w + 2 * pad - k) // s + 1
-        n_res = int(res1 is not None) + int(res2 is not None)
-        for nb in range(2, 33):
-            bands = conv_column_bands(n, cin, h, w, conv.out_channels, k, s, pad, relu, nb)
-            if all(self._conv_served(d, half, n_res) for _, _, d in bands):
-                break
-        else:
-            raise _lib.MindposeHipError(f"no kernel serves the conv {tuple(x.shape)} -> {conv.out_channels} channels (k {k}, stride {s}), "
-                                        "not even in output-column bands")
-        if out is None:
-            out = self.alloc(n, conv.out_channels, ho, wo) if half else self.alloc_f32(n, conv.out_channels, ho, wo)
+        bands = self._fewest_bands(lambda nb: conv_column_bands(n, cin, h, w, cout, k, s, pad, relu, nb), half,
+                                   int(res1 is not None) + int(res2 is not None),
+                                   f"conv {tuple(x.shape)} -> {cout} channels (k {k}, stride {s})")
+        out = self._conv_out(x, bands[0][2], res1, res2, out)
+        packed = self._pack(conv.weight, cout, cin, k, False, 0, 0, half)
+        scale, shift = self._affine(cout, bn, conv.bias, half)
         for start, wb, d in bands:
-            xb = self.col_slice(x, start, wb)
-            self.conv(xb, conv, bn, relu, res1, res2, out, _band=(d.out_off_x, d.conv_w, d.pad_left))
+            self._record_conv(d, self.col_slice(x, start, wb), packed, scale, shift, res1, res2, out, "conv_f16" if half else "conv",
+                              packed_u=self._winograd_weight(d, conv, half))
         return out
 
     def fuses_basic_block(self, x: torch.Tensor, conv1: Conv2d, conv2: Conv2d) -> bool:
         """The fused fp16 BasicBlock kernels cover the 32-channel branch (four 8-channel blocks) and, round 4, the 64-channel branch
         and 128-channel branches (3x3 stride 1 both convs; the library says whether the map fits a band: ``mp_f16_basicblock_supported``);
         ``MINDPOSE_FUSE_BLOCK=0`` keeps the two-launch path, ``MINDPOSE_FUSE_BLOCK64=0`` for the 64 / 128-channel blocks only."""
-        if not isinstance(x, ActC8) or os.environ.get("MINDPOSE_FUSE_BLOCK", "1") == "0":
+        if not isinstance(x, ActC8) or not _lib.env_on("MINDPOSE_FUSE_BLOCK"):
             return False
         n, c, h, w = x.shape
         if not all(cv.in_channels == c and cv.out_channels == c and cv.kernel_size == 3 and cv.stride == 1 and cv.padding == 1
                    and cv.bias is None for cv in (conv1, conv2)):
             return False
-        if c in (64, 128) and os.environ.get("MINDPOSE_FUSE_BLOCK64", "1") == "0":
+        if c in (64, 128) and not _lib.env_on("MINDPOSE_FUSE_BLOCK64"):
             return False
         return (24 < c <= 32 or c in (64, 128)) and self.lib.mp_f16_basicblock_supported(n, c, h, w) == 1
 
@@ -725,20 +481,16 @@ class Plan:
         _lib.check(self.lib.mp_plan_add_basicblock_f16(self.handle, _lib.ptr(x), _lib.ptr(p1), _lib.ptr(s1), _lib.ptr(b1),
                                                        _lib.ptr(p2), _lib.ptr(s2), _lib.ptr(b2), _lib.ptr(out), n, c, h, w, rows),
                    "mp_plan_add_basicblock_f16")
-        self.layer_info.append(dict(kind="basicblock_f16", k=3, stride=1, cin=c, cout=c, h=h, w=w, n=n,
-                                    macs=2 * n * h * w * c * c * 9))
+        self._conv_info("basicblock_f16", 3, 1, c, c, h, w, n, 2 * n * h * w * c * c * 9)
         return out
 
     def fuses_dual_pw(self, x: torch.Tensor, conv_a: Conv2d, conv_b: Conv2d) -> bool:
         """Two 1x1 convs on ONE 64-channel input as one launch (mp_f16_dual_pw_fwd): the down-sample conv (64 -> 256) and the reduce conv
         (64 -> 64) of stage 1's first Bottleneck.  fp16 plans, stride 1, no bias, pixel count a multiple of 64; switched with the chain
         launch (``MINDPOSE_FUSE_PWCHAIN``)."""
-        if not isinstance(x, ActC8) or os.environ.get("MINDPOSE_FUSE_PWCHAIN", "1") == "0":
+        if not isinstance(x, ActC8) or not _lib.env_on("MINDPOSE_FUSE_PWCHAIN"):
             return False
-        n, c, h, w = x.shape
-        ok = lambda cv, co: (cv.in_channels == 64 and cv.out_channels == co and cv.kernel_size == 1 and cv.stride == 1  # noqa: E731
-                             and cv.padding == 0 and cv.bias is None)
-        return c == 64 and ok(conv_a, 256) and ok(conv_b, 64) and (h * w) % 64 == 0 and n * 32 * h * w * 16 < 0x7FFFFFF0
+        return x.shape[1] == 64 and self._pw(conv_a, 64, 256) and self._pw(conv_b, 64, 64) and self._chain_fits(x, True)
 
     def dual_pw(self, x: torch.Tensor, conv_a: Conv2d, bn_a: BatchNorm2d, relu_a: bool, conv_b: Conv2d, bn_b: BatchNorm2d,
                 relu_b: bool) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -751,15 +503,14 @@ class Plan:
         _lib.check(self.lib.mp_plan_add_dual_pw_f16(self.handle, _lib.ptr(x), _lib.ptr(pa), _lib.ptr(sa), _lib.ptr(ba), int(relu_a), _lib.ptr(pb),
                                                     _lib.ptr(sb), _lib.ptr(bb), int(relu_b), _lib.ptr(ya), _lib.ptr(zb), n, c,
                                                     conv_a.out_channels, conv_b.out_channels, h, w), "mp_plan_add_dual_pw_f16")
-        self.layer_info.append(dict(kind="pwchain_f16", k=1, stride=1, cin=c, cout=conv_a.out_channels, h=h, w=w, n=n,
-                                    macs=n * h * w * c * (conv_a.out_channels + conv_b.out_channels)))
+        self._conv_info("pwchain_f16", 1, 1, c, conv_a.out_channels, h, w, n, n * h * w * c * (conv_a.out_channels + conv_b.out_channels))
         return ya, zb
 
     def fuses_stem(self, x: torch.Tensor, conv: Conv2d) -> bool:
         """Can the first conv run as the dedicated streaming kernel with (tap, channel) as its k axis?  fp16 plans: mp_f16_stem_conv_fwd
         reads the fp32 NCHW image itself (no layout pass, the 27 real k positions of a 3-channel 3x3 conv in ONE k-step); fp32 plans:
         mp_stem_conv_fwd (seven k-steps of 4).  ``MINDPOSE_FUSE_STEM=0`` keeps (layout pass +) the general conv."""
-        if isinstance(x, ActC8) or os.environ.get("MINDPOSE_FUSE_STEM", "1") == "0":
+        if isinstance(x, ActC8) or not _lib.env_on("MINDPOSE_FUSE_STEM"):
             return False
         n, c, h, w = x.shape
         lds = (6 if self.half else 12) * (w + 4) * 17 + 16  # the 17 staged rows of the three planes (fp16 / fp32)
@@ -773,18 +524,13 @@ class Plan:
         n, _, h, w = x.shape
         wt = conv.weight.detach().to(self.device, torch.float32).contiguous()
         self.keep.append(wt)
-        if not self.half:  # fp32 plans: the same (tap, channel) k axis on the fp32 matrix cores, NCHW in and out (mp_stem_conv_fwd)
-            out = self.alloc_f32(n, 64, h // 2, w // 2)
-            scale, shift = self._affine(64, bn, None, False)
-            _lib.check(self.lib.mp_plan_add_stem_conv(self.handle, _lib.ptr(x), _lib.ptr(wt), _lib.ptr(scale), _lib.ptr(shift), 1, _lib.ptr(out),
-                                                      n, h, w), "mp_plan_add_stem_conv")
-            self.layer_info.append(dict(kind="stem_f32", k=3, stride=2, cin=3, cout=64, h=h, w=w, n=n, macs=n * (h // 2) * (w // 2) * 64 * 27))
-            return out
+        # one argument list for both kernels; fp32 plans: the same (tap, channel) k axis on the fp32 matrix cores, NCHW in and out
         out = self.alloc(n, 64, h // 2, w // 2)
-        scale, shift = self._affine(64, bn, None, True)
-        _lib.check(self.lib.mp_plan_add_stem_conv_f16(self.handle, _lib.ptr(x), _lib.ptr(wt), _lib.ptr(scale), _lib.ptr(shift), 1, _lib.ptr(out),
-                                                      n, h, w), "mp_plan_add_stem_conv_f16")
-        self.layer_info.append(dict(kind="stem_f16", k=3, stride=2, cin=3, cout=64, h=h, w=w, n=n, macs=n * (h // 2) * (w // 2) * 64 * 27))
+        scale, shift = self._affine(64, bn, None, self.half)
+        add = self.lib.mp_plan_add_stem_conv_f16 if self.half else self.lib.mp_plan_add_stem_conv
+        _lib.check(add(self.handle, _lib.ptr(x), _lib.ptr(wt), _lib.ptr(scale), _lib.ptr(shift), 1, _lib.ptr(out), n, h, w),
+                   "mp_plan_add_stem_conv_f16" if self.half else "mp_plan_add_stem_conv")
+        self._conv_info("stem_f16" if self.half else "stem_f32", 3, 2, 3, 64, h, w, n, n * (h // 2) * (w // 2) * 64 * 27)
         return out
 
     def fuses_expand_reduce(self, mid: torch.Tensor, res: torch.Tensor, conv3: Conv2d, conv1_next: Conv2d) -> bool:
@@ -794,18 +540,24 @@ class Plan:
         without bias, maps whose pixel count is a multiple of 64.  ``MINDPOSE_FUSE_PWCHAIN=0`` (fp16) / ``MINDPOSE_FUSE_PWCHAIN32=0``
         (fp32) keep the two launches."""
         half = isinstance(mid, ActC8)
-        if half != isinstance(res, ActC8) or os.environ.get("MINDPOSE_FUSE_PWCHAIN" if half else "MINDPOSE_FUSE_PWCHAIN32", "1") == "0":
+        if half != isinstance(res, ActC8) or not _lib.env_on("MINDPOSE_FUSE_PWCHAIN" if half else "MINDPOSE_FUSE_PWCHAIN32"):
             return False
         n, cm, h, w = mid.shape
-        if not (cm == 64 and tuple(res.shape) == (n, 256, h, w) and self._pw(conv3, 64, 256) and self._pw(conv1_next, 256, 64)
-                and (h * w) % 64 == 0):
-            return False
-        return n * 32 * h * w * 16 < 0x7FFFFFF0 if half else n * 256 * h * w * 4 < 0x7FFFFFF0
+        return (cm == 64 and tuple(res.shape) == (n, 256, h, w) and self._pw(conv3, 64, 256) and self._pw(conv1_next, 256, 64)
+                and self._chain_fits(mid, half))
 
     @staticmethod
     def _pw(cv: Conv2d, ci: int, co: int) -> bool:
+        """A 1x1 stride-1 conv ci -> co without bias?"""
         return (cv.in_channels == ci and cv.out_channels == co and cv.kernel_size == 1 and cv.stride == 1 and cv.padding == 0
                 and cv.bias is None)
+
+    @staticmethod
+    def _chain_fits(x, half: bool) -> bool:
+        """Does the map of ``x`` fit the 64 -> 256 (-> 64) chain kernels: a multiple of 64 pixels, and the byte offsets of the
+        256-channel tensor - fp16: 32 channel blocks of 16 bytes a pixel, fp32: 256 planes of 4 bytes - within 31 bits?"""
+        n, _, h, w = x.shape
+        return (h * w) % 64 == 0 and (n * 32 * h * w * 16 if half else n * 256 * h * w * 4) < 0x7FFFFFF0
 
     def fuses_ds_expand_reduce(self, x0: torch.Tensor, ds_conv: Conv2d, conv3: Conv2d, conv1_next: Conv2d) -> bool:
         """Can the FIRST Bottleneck's down-sample conv (hrnet.py:74-81, 64 -> 256 on the block's input) be computed inside the expand +
@@ -813,24 +565,21 @@ class Plan:
         ``MINDPOSE_FUSE_PWCHAIN32_DS=0`` (fp32) / ``MINDPOSE_FUSE_PWCHAIN_DS=0`` (fp16: the dual 1x1 launch + the identity chain instead)
         keep the separate launch."""
         half = isinstance(x0, ActC8)
-        if half and (os.environ.get("MINDPOSE_FUSE_PWCHAIN", "1") == "0" or os.environ.get("MINDPOSE_FUSE_PWCHAIN_DS", "1") == "0"):
+        switch = "MINDPOSE_FUSE_PWCHAIN" if half else "MINDPOSE_FUSE_PWCHAIN32"
+        if not (_lib.env_on(switch) and _lib.env_on(switch + "_DS")):
             return False
-        if not half and (os.environ.get("MINDPOSE_FUSE_PWCHAIN32", "1") == "0" or os.environ.get("MINDPOSE_FUSE_PWCHAIN32_DS", "1") == "0"):
-            return False
-        n, c, h, w = x0.shape
-        if not (c == 64 and self._pw(ds_conv, 64, 256) and self._pw(conv3, 64, 256) and self._pw(conv1_next, 256, 64) and (h * w) % 64 == 0):
-            return False
-        return n * 32 * h * w * 16 < 0x7FFFFFF0 if half else n * 256 * h * w * 4 < 0x7FFFFFF0
+        return (x0.shape[1] == 64 and self._pw(ds_conv, 64, 256) and self._pw(conv3, 64, 256) and self._pw(conv1_next, 256, 64)
+                and self._chain_fits(x0, half))
 
     def fuses_expand_only(self, mid: torch.Tensor, res: torch.Tensor, conv3: Conv2d) -> bool:
         """fp32 plans: the LAST Bottleneck's expand conv + identity through the persistent weight-stationary kernel (no reduce conv
         follows).  ``MINDPOSE_FUSE_PWCHAIN32_LAST=0`` keeps the tuned general conv."""
-        if isinstance(mid, ActC8) or isinstance(res, ActC8) or os.environ.get("MINDPOSE_FUSE_PWCHAIN32", "1") == "0":
+        if isinstance(mid, ActC8) or isinstance(res, ActC8):
             return False
-        if os.environ.get("MINDPOSE_FUSE_PWCHAIN32_LAST", "1") == "0":
+        if not (_lib.env_on("MINDPOSE_FUSE_PWCHAIN32") and _lib.env_on("MINDPOSE_FUSE_PWCHAIN32_LAST")):
             return False
         n, cm, h, w = mid.shape
-        return cm == 64 and tuple(res.shape) == (n, 256, h, w) and self._pw(conv3, 64, 256) and (h * w) % 64 == 0 and n * 256 * h * w * 4 < 0x7FFFFFF0
+        return cm == 64 and tuple(res.shape) == (n, 256, h, w) and self._pw(conv3, 64, 256) and self._chain_fits(mid, False)
 
     def expand_reduce(self, mid: torch.Tensor, res: Optional[torch.Tensor], conv3: Conv2d, bn3: BatchNorm2d, conv1_next: Optional[Conv2d],
                       bn1_next: Optional[BatchNorm2d], ds=None):
@@ -841,44 +590,34 @@ class Plan:
         n, cm, h, w = mid.shape
         ce = conv3.out_channels
         cr = conv1_next.out_channels if conv1_next is not None else 0
-        macs = n * h * w * (cm * ce + ce * cr + (cm * ce if ds is not None else 0))
-        if not isinstance(mid, ActC8):
-            y = self.alloc_f32(n, ce, h, w)
-            z = self.alloc_f32(n, cr, h, w) if conv1_next is not None else None
-            p3 = self._pack(conv3.weight, ce, cm, 1, False, 0, 0)
-            s3, b3 = self._affine(ce, bn3, None)
-            p1 = s1 = b1 = pd = sd = bd = x0 = None
-            if conv1_next is not None:
-                p1 = self._pack(conv1_next.weight, cr, ce, 1, False, 0, 0)
-                s1, b1 = self._affine(cr, bn1_next, None)
-            if ds is not None:
-                x0, ds_conv, ds_bn = ds
-                pd = self._pack(ds_conv.weight, ce, cm, 1, False, 0, 0)
-                sd, bd = self._affine(ce, ds_bn, None)
-            _lib.check(self.lib.mp_plan_add_expand_reduce(self.handle, _lib.ptr(mid), _lib.ptr(res), _lib.ptr(x0), _lib.ptr(pd), _lib.ptr(sd),
-                                                          _lib.ptr(bd), _lib.ptr(p3), _lib.ptr(s3), _lib.ptr(b3), _lib.ptr(p1), _lib.ptr(s1), _lib.ptr(b1),
+        half = isinstance(mid, ActC8)
+        if half and conv1_next is None:
+            raise NotImplementedError("the expand conv alone is an fp32 form")
+        x0, ds_conv, ds_bn = ds if ds is not None else (None, None, None)
+
+        def operands(cv, bn, co, ci):  # (packed weight, scale, shift) pointers of one 1x1 conv of the chain; NULLs when it is absent
+            if cv is None:
+                return [None, None, None]
+            return [_lib.ptr(t) for t in (self._pack(cv.weight, co, ci, 1, False, 0, 0, half), *self._affine(co, bn, None, half))]
+
+        y = self._alloc_like(mid, n, ce, h, w)
+        z = self._alloc_like(mid, n, cr, h, w) if conv1_next is not None else None
+        expand, reduce, down = operands(conv3, bn3, ce, cm), operands(conv1_next, bn1_next, cr, ce), operands(ds_conv, ds_bn, ce, cm)
+        if not half:
+            _lib.check(self.lib.mp_plan_add_expand_reduce(self.handle, _lib.ptr(mid), _lib.ptr(res), _lib.ptr(x0), *down, *expand, *reduce,
                                                           _lib.ptr(y), _lib.ptr(z), n, cm, ce, cr if cr else 64, h, w),
                        "mp_plan_add_expand_reduce")
-            self.layer_info.append(dict(kind="pwchain_f32", k=1, stride=1, cin=cm, cout=ce, h=h, w=w, n=n, macs=macs))
-            return (y, z) if conv1_next is not None else y
-        y, z = self.alloc(n, ce, h, w), self.alloc(n, cr, h, w)
-        p3, p1 = self._pack(conv3.weight, ce, cm, 1, False, 0, 0, True), self._pack(conv1_next.weight, cr, ce, 1, False, 0, 0, True)
-        (s3, b3), (s1, b1) = self._affine(ce, bn3, None, True), self._affine(cr, bn1_next, None, True)
-        if ds is not None:
-            x0, ds_conv, ds_bn = ds
-            pd = self._pack(ds_conv.weight, ce, cm, 1, False, 0, 0, True)
-            sd, bd = self._affine(ce, ds_bn, None, True)
-            _lib.check(self.lib.mp_plan_add_ds_expand_reduce_f16(self.handle, _lib.ptr(mid), _lib.ptr(x0), _lib.ptr(pd), _lib.ptr(sd), _lib.ptr(bd),
-                                                                 _lib.ptr(p3), _lib.ptr(s3), _lib.ptr(b3), 1, _lib.ptr(p1), _lib.ptr(s1), _lib.ptr(b1), 1,
+        elif ds is not None:
+            _lib.check(self.lib.mp_plan_add_ds_expand_reduce_f16(self.handle, _lib.ptr(mid), _lib.ptr(x0), *down, *expand, 1, *reduce, 1,
                                                                  _lib.ptr(y), _lib.ptr(z), n, cm, ce, cr, h, w),
                        "mp_plan_add_ds_expand_reduce_f16")
-            self.layer_info.append(dict(kind="pwchain_f16", k=1, stride=1, cin=cm, cout=ce, h=h, w=w, n=n, macs=macs))
-            return y, z
-        _lib.check(self.lib.mp_plan_add_expand_reduce_f16(self.handle, _lib.ptr(mid), _lib.ptr(res), _lib.ptr(p3), _lib.ptr(s3), _lib.ptr(b3), 1,
-                                                          _lib.ptr(p1), _lib.ptr(s1), _lib.ptr(b1), 1, _lib.ptr(y), _lib.ptr(z), n, cm, ce, cr, h, w),
-                   "mp_plan_add_expand_reduce_f16")
-        self.layer_info.append(dict(kind="pwchain_f16", k=1, stride=1, cin=cm, cout=ce, h=h, w=w, n=n, macs=macs))
-        return y, z
+        else:
+            _lib.check(self.lib.mp_plan_add_expand_reduce_f16(self.handle, _lib.ptr(mid), _lib.ptr(res), *expand, 1, *reduce, 1,
+                                                              _lib.ptr(y), _lib.ptr(z), n, cm, ce, cr, h, w),
+                       "mp_plan_add_expand_reduce_f16")
+        self._conv_info("pwchain_f16" if half else "pwchain_f32", 1, 1, cm, ce, h, w, n,
+                        n * h * w * (cm * ce + ce * cr + (cm * ce if ds is not None else 0)))
+        return (y, z) if conv1_next is not None else y
 
     def deconv4x4s2(self, x: torch.Tensor, deconv: Conv2dTranspose, bn: BatchNorm2d, relu: bool = True) -> torch.Tensor:
         """Conv2dTranspose(k=4, s=2, p=1) + BN + ReLU as four 2x2 sub-pixel phase convolutions - four launches with a tuned form each,
@@ -887,27 +626,16 @@ class Plan:
         half = isinstance(x, ActC8)
         n, cin, h, w = x.shape
         cout = deconv.out_channels
-        out = self.alloc(n, cout, 2 * h, 2 * w) if half else self.alloc_f32(n, cout, 2 * h, 2 * w)
+        out = self._alloc_like(x, n, cout, 2 * h, 2 * w)
         scale, shift = self._affine(cout, bn, None, half)
-
-        def desc(py, px):
-            return _lib.ConvDesc(n=n, cin=cin, h=h, w=w, cout=cout, kh=2, kw=2, stride=1, pad_top=1 - py, pad_left=1 - px, conv_h=h,
-                                 conv_w=w, out_h=2 * h, out_w=2 * w, out_mul=2, out_rep=1, out_off_y=py, out_off_x=px, relu=int(relu),
-                                 flags=0)
-
         phases = [(py, px) for py in (0, 1) for px in (0, 1)]
-        macs = n * h * w * cout * cin * 4
-        if not all(self._conv_served(desc(py, px), half, 0) for py, px in phases):
+        descs = [deconv_phase_desc(n, cin, h, w, cout, py, px, relu)[2] for py, px in phases]
+        if not all(self._conv_served(d, half, 0) for d in descs):
             return self._deconv_by_columns(x, deconv, out, scale, shift, relu)
+        kind = "deconv_phase_f16" if half else "deconv_phase"
         if half:
-            for py, px in phases:
-                packed = self._pack(deconv.weight, cout, cin, 2, True, py, px, True)
-                d = desc(py, px)
-                v = tune_conv_variant(self.lib, d, x, packed, scale, shift, None, None, out, half=True)
-                _lib.check(self.lib.mp_plan_add_conv_f16(self.handle, ctypes.byref(d), v, _lib.ptr(x), _lib.ptr(packed),
-                                                         _lib.ptr(scale), _lib.ptr(shift), None, None, _lib.ptr(out)),
-                           "mp_plan_add_conv_f16(deconv phase)")
-                self.layer_info.append(dict(kind="deconv_phase_f16", k=2, stride=1, cin=cin, cout=cout, h=h, w=w, n=n, macs=macs))
+            for d, (py, px) in zip(descs, phases):
+                self._record_conv(d, x, self._pack(deconv.weight, cout, cin, 2, True, py, px, True), scale, shift, None, None, out, kind)
             return out
         # fp32: the four phase packings back to back in one buffer (the one-launch form reads them as slices)
         key = (id(deconv.weight), "deconv4")
@@ -923,10 +651,11 @@ class Plan:
         buf = self._packed[key]
         per = buf.numel() // 4
         slices = [buf[i * per:(i + 1) * per] for i in range(4)]
-        descs = [desc(py, px) for py, px in phases]
+        # the four picks come first: the one-launch form is timed against the four launches in THEIR tuned forms
         variants = [tune_conv_variant(self.lib, d, x, pk, scale, shift, None, None, out) for d, pk in zip(descs, slices)]
         fused = False
-        if os.environ.get("MINDPOSE_AUTOTUNE", "1") != "0" and self.lib.mp_deconv4x4s2_gemm_supported(ctypes.byref(descs[0])) == 0:
+        # the tuner's switch only, not `tuned(macs)`: below the threshold `_autotune` records its -1 under the key all the same
+        if autotune_on() and self.lib.mp_deconv4x4s2_gemm_supported(ctypes.byref(descs[0])) == 0:
             stream = _lib.stream()
 
             def launch(form):
@@ -940,18 +669,15 @@ class Plan:
                 return rc
 
             tkey = ("deconv4x4s2",) + tuple(getattr(descs[0], f) for f, _ in descs[0]._fields_) + (str(out.device),)
-            fused = _autotune(tkey, 4 * macs, 2, launch) == 1
+            fused = _autotune(tkey, 4 * _macs(descs[0]), 2, launch) == 1
         if fused:
             _lib.check(self.lib.mp_plan_add_deconv4x4s2_gemm(self.handle, ctypes.byref(descs[0]), _lib.ptr(x), _lib.ptr(buf),
                                                              _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(out)),
                        "mp_plan_add_deconv4x4s2_gemm")
-            self.layer_info.append(dict(kind="deconv_gemm", k=2, stride=1, cin=cin, cout=cout, h=h, w=w, n=n, macs=4 * macs))
+            self._conv_info("deconv_gemm", 2, 1, cin, cout, h, w, n, 4 * _macs(descs[0]))
             return out
         for d, pk, v in zip(descs, slices, variants):
-            _lib.check(self.lib.mp_plan_add_conv_variant(self.handle, ctypes.byref(d), v, _lib.ptr(x), _lib.ptr(pk),
-                                                         _lib.ptr(scale), _lib.ptr(shift), None, None, _lib.ptr(out)),
-                       "mp_plan_add_conv_variant(deconv phase)")
-            self.layer_info.append(dict(kind="deconv_phase", k=2, stride=1, cin=cin, cout=cout, h=h, w=w, n=n, macs=macs))
+            self._record_conv(d, x, pk, scale, shift, None, None, out, kind, variant=v)
         return out
 
     def _deconv_by_columns(self, x, deconv: Conv2dTranspose, out, scale, shift, relu: bool):
@@ -963,20 +689,11 @@ class Plan:
         cout = deconv.out_channels
         for py, px in [(py, px) for py in (0, 1) for px in (0, 1)]:
             packed = self._pack(deconv.weight, cout, cin, 2, True, py, px, half)
-            for nb in range(2, 33):
-                bands = deconv_phase_column_bands(n, cin, h, w, cout, py, px, relu, nb)
-                if all(self._conv_served(d, half, 0) for _, _, d in bands):
-                    break
-            else:
-                raise _lib.MindposeHipError(f"no kernel serves the transposed conv {tuple(x.shape)} -> {cout}, not even in bands")
+            bands = self._fewest_bands(lambda nb: deconv_phase_column_bands(n, cin, h, w, cout, py, px, relu, nb), half, 0,
+                                       f"transposed conv {tuple(x.shape)} -> {cout} channels (k 4, stride 2)")
             for start, wb, d in bands:
-                xb = self.col_slice(x, start, wb)
-                v = tune_conv_variant(self.lib, d, xb, packed, scale, shift, None, None, out, half=half)
-                add = self.lib.mp_plan_add_conv_f16 if half else self.lib.mp_plan_add_conv_variant
-                _lib.check(add(self.handle, ctypes.byref(d), v, _lib.ptr(xb), _lib.ptr(packed), _lib.ptr(scale), _lib.ptr(shift), None,
-                               None, _lib.ptr(out)), "mp_plan_add_conv(deconv phase band)")
-                self.layer_info.append(dict(kind="deconv_phase_f16" if half else "deconv_phase", k=2, stride=1, cin=cin, cout=cout, h=h,
-                                            w=d.w, n=n, macs=n * h * d.conv_w * cout * cin * 4))
+                self._record_conv(d, self.col_slice(x, start, wb), packed, scale, shift, None, None, out,
+                                  "deconv_phase_f16" if half else "deconv_phase")
         return out
 
     def fuse_sum(self, base: torch.Tensor, terms, out: torch.Tensor, relu: bool = True) -> torch.Tensor:
@@ -1121,7 +838,7 @@ class PlannedModule(nn.Module):
 def flip_pair_batched() -> bool:
     """``MINDPOSE_FLIP_BATCHED=0``: the flip test runs two forwards of N crops through one plan (rounds 1 - 3) instead of ONE
     forward of the 2N-crop batch [crops | mirrored crops]."""
-    return os.environ.get("MINDPOSE_FLIP_BATCHED", "1") != "0"
+    return _lib.env_on("MINDPOSE_FLIP_BATCHED")
 
 
 def auto_mixed_precision(network: nn.Module, amp_level: str = "O0") -> nn.Module:

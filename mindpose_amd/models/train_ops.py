@@ -14,7 +14,8 @@ import numpy as np
 import torch
 
 from .. import _lib
-from .layers import BN_EPS, F16_VARIANTS, F32_WINOGRAD, tune_conv_variant, winograd_enabled
+from .layers import BN_EPS, conv_desc
+from .tuner import F16_VARIANTS, F32_WINOGRAD, autotune_on, tune_conv_variant, winograd_enabled
 
 BN_MOMENTUM = 0.9  # mindspore.nn.BatchNorm2d(momentum=0.9): moving = 0.9*moving + 0.1*batch [MS-knowledge]
 
@@ -30,9 +31,8 @@ def _ones_zeros(c: int, device):
 
 def _desc(n, cin, h, w, cout, k, stride, pad_t, pad_l, conv_h, conv_w, out_h, out_w, out_mul=1, out_rep=1, off_y=0,
           off_x=0, flags=0):
-    return _lib.ConvDesc(n=n, cin=cin, h=h, w=w, cout=cout, kh=k, kw=k, stride=stride, pad_top=pad_t, pad_left=pad_l,
-                         conv_h=conv_h, conv_w=conv_w, out_h=out_h, out_w=out_w, out_mul=out_mul, out_rep=out_rep,
-                         out_off_y=off_y, out_off_x=off_x, relu=0, flags=_lib.MP_CONV_SHARES_CUS | flags)
+    return conv_desc(n, cin, h, w, cout, k, stride, pad_t, pad_l, conv_h, conv_w, out_h, out_w, out_mul, out_rep, off_y, off_x,
+                     flags=_lib.MP_CONV_SHARES_CUS | flags)
 
 
 def _conv_launch(lib, d, x, packed, scale, shift, out, what, packed_u=None, res1=None):
@@ -49,7 +49,7 @@ def _conv_launch(lib, d, x, packed, scale, shift, out, what, packed_u=None, res1
 
 def _pack_winograd(lib, d, w, cout, cin, mode, owner):
     """Winograd form of a 3x3 weight (mode 5: forward, 6: data gradient) when the descriptor is inside that form, else None."""
-    if not winograd_enabled() or os.environ.get("MINDPOSE_AUTOTUNE", "1") == "0" or lib.mp_conv_winograd_supported(ctypes.byref(d)) != 0:
+    if not winograd_enabled() or not autotune_on() or lib.mp_conv_winograd_supported(ctypes.byref(d)) != 0:
         return None
     return _cached_pack(lib, w, owner, False, cout, cin, 3, mode, 0, 0)
 
@@ -326,7 +326,7 @@ def _pack16(lib, w, cout, cin, k, mode, py=0, px=0, owner=None):
 
 def phases4_enabled() -> bool:
     """``MINDPOSE_DGRAD_PHASES4=0``: the stride-2 3x3 data gradient as four phase launches (A/B; the results are bit-identical)."""
-    return os.environ.get("MINDPOSE_DGRAD_PHASES4", "1") != "0"
+    return _lib.env_on("MINDPOSE_DGRAD_PHASES4")
 
 
 def _dgrad16_stride2(lib, w, owner, dz, dx, n, cin, cout, h, wd, ho, wo, ones, zeros, below=None):
@@ -545,7 +545,7 @@ class BatchNormAct16Fn(torch.autograd.Function):
     def backward(ctx, dy):
         lib = _lib.load()
         z, y, g, b, mean, invstd = ctx.saved_tensors
-        if ctx.relu and not ctx.has_res and os.environ.get("MINDPOSE_BN16_MASK_FROM_Z", "1") != "0":
+        if ctx.relu and not ctx.has_res and _lib.env_on("MINDPOSE_BN16_MASK_FROM_Z"):
             y = None  # no residual: the ReLU mask is re-derived from z (forward arithmetic), y is not read
         dy = dy.contiguous()
         n, _, h, w, _ = z.shape
@@ -920,7 +920,7 @@ class ResidualBlock32Fn(_ResidualBlockFn):
 
 
 def bn_fuse_enabled() -> bool:
-    return os.environ.get("MINDPOSE_BN_FUSE", "1") != "0"
+    return _lib.env_on("MINDPOSE_BN_FUSE")
 
 
 def _bn_fuse_parts() -> int:
@@ -980,7 +980,7 @@ def bn_pre_enabled() -> bool:
     26.6 ms) but the graph-replayed multi-lane step gets 0.8 % SLOWER (5.59 -> 5.55 k img/s, four interleaved pairs on two boxes) -
     the apply passes it removes are HBM-bound launches that were already hidden under the other lanes' convs, the time it adds sits
     in CU-filling conv launches."""
-    return os.environ.get("MINDPOSE_BN_PRE", "0") == "1"
+    return _lib.env_on("MINDPOSE_BN_PRE", default=False)
 
 
 _PRE_CAPABLE = {}
@@ -993,7 +993,7 @@ def _pre_capable(lib, d) -> bool:
     hit = _PRE_CAPABLE.get(key)
     if hit is None:
         macs = d.n * d.conv_h * d.conv_w * d.cout * d.cin * d.kh * d.kw
-        hit = (os.environ.get("MINDPOSE_AUTOTUNE", "1") != "0" and macs >= (1 << 26)
+        hit = (autotune_on() and macs >= (1 << 26)
                and any(lib.mp_f16_conv_pre_supported(ctypes.byref(d), v) for v in range(F16_VARIANTS)))
         _PRE_CAPABLE[key] = hit
     return hit
@@ -1144,7 +1144,7 @@ def flush_wgrad_jobs_early() -> None:
     stem backward (also bandwidth-bound, on ONE queue: two such streams together get more of the HBM than either alone).  The jobs
     and their groups are those the end-of-pass flush would have formed (no later layer has the shapes of stages 2 - 4): same bits.
     Only with the automatic end-of-pass flush on (a segmented capture carries its groups across the cuts itself)."""
-    if not _WGRAD_PENDING or not _WGRAD_AUTOFLUSH[0] or os.environ.get("MINDPOSE_WGRAD_EARLY_FLUSH", "1") == "0":
+    if not _WGRAD_PENDING or not _WGRAD_AUTOFLUSH[0] or not _lib.env_on("MINDPOSE_WGRAD_EARLY_FLUSH"):
         return
     dev = next(iter(_WGRAD_PENDING))[1]
     cur = torch.cuda.current_stream(dev)
@@ -1295,7 +1295,7 @@ def _chain16_bwd_steps(lib, groups, dy, out_link, in_link, needs_dx, res_is_inpu
                 dres = dy
         else:
             yy = y if (G["relu"] and G["res"]) else None  # no residual: the mask is re-derived from z, y is not read
-            if G["relu"] and not G["res"] and os.environ.get("MINDPOSE_BN16_MASK_FROM_Z", "1") == "0":
+            if G["relu"] and not G["res"] and not _lib.env_on("MINDPOSE_BN16_MASK_FROM_Z"):
                 yy = y
             job["yy"] = yy
             job["dr"] = torch.empty_like(z) if G["res"] else None
@@ -1429,7 +1429,7 @@ def residual_block(x, groups):
     if _is_c8(x) and bn_fuse_enabled() and first.stride == 1 and all(cv.bias is None for cv, _ in groups):
         return _chain16(x, groups, [True] * len(groups), residual=True)
     _claim(x)
-    if first.stride == 1 and all(cv.bias is None for cv, _ in groups) and os.environ.get("MINDPOSE_FUSE_RESIDUAL", "1") != "0":
+    if first.stride == 1 and all(cv.bias is None for cv, _ in groups) and _lib.env_on("MINDPOSE_FUSE_RESIDUAL"):
         meta = tuple((cv.stride, cv.padding, bn.moving_mean, bn.moving_variance) for cv, bn in groups)
         params = [t for cv, bn in groups for t in (cv.weight, bn.gamma, bn.beta)]
         return (ResidualBlock16Fn if _is_c8(x) else ResidualBlock32Fn).apply(x, meta, *params)
@@ -1553,7 +1553,7 @@ def grad_join(xs):
     """``xs`` routed through `GradJoinFn` (the BatchNorm links travel with the tensors); a list of one, CPU tensors or tensors without
     gradient pass through."""
     xs = list(xs)
-    if len(xs) < 2 or not all(x.is_cuda and x.requires_grad for x in xs) or os.environ.get("MINDPOSE_FAN_OUT_ONE_NODE", "1") == "0":
+    if len(xs) < 2 or not all(x.is_cuda and x.requires_grad for x in xs) or not _lib.env_on("MINDPOSE_FAN_OUT_ONE_NODE"):
         return xs
     outs = GradJoinFn.apply(*xs)
     for o, x in zip(outs, xs):
@@ -1569,11 +1569,11 @@ def fan_out_many(xs, ks):
     outs = [None] * len(xs)
     pick = []
     for j, (x, k) in enumerate(zip(xs, ks)):
-        if k <= 1 or not x.is_cuda or not x.requires_grad or (x.numel() * x.element_size()) % 16 or os.environ.get("MINDPOSE_FAN_OUT", "1") == "0":
+        if k <= 1 or not x.is_cuda or not x.requires_grad or (x.numel() * x.element_size()) % 16 or not _lib.env_on("MINDPOSE_FAN_OUT"):
             outs[j] = (x,) * k
         else:
             pick.append(j)
-    if len(pick) == 1 or os.environ.get("MINDPOSE_FAN_OUT_ONE_NODE", "1") == "0":
+    if len(pick) == 1 or not _lib.env_on("MINDPOSE_FAN_OUT_ONE_NODE"):
         for j in pick:
             outs[j] = fan_out(xs[j], ks[j])
     elif pick:
@@ -1587,7 +1587,7 @@ def fan_out_many(xs, ks):
 
 def fan_out(x, k: int):
     """``k`` handles on ``x`` whose gradients are summed by one kernel; needs 16-byte multiples (every activation here is)."""
-    if k <= 1 or not x.is_cuda or not x.requires_grad or (x.numel() * x.element_size()) % 16 or os.environ.get("MINDPOSE_FAN_OUT", "1") == "0":
+    if k <= 1 or not x.is_cuda or not x.requires_grad or (x.numel() * x.element_size()) % 16 or not _lib.env_on("MINDPOSE_FAN_OUT"):
         return (x,) * k  # the consumers of the k handles count themselves on x's BatchNorm link (the same tensor object)
     return FanOutFn.apply(x, k, _claim(x))
 

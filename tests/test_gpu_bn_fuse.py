@@ -18,7 +18,8 @@ if not torch.cuda.is_available():
     pytest.skip("needs an MI355X", allow_module_level=True)
 
 from mindpose_amd import _lib  # noqa: E402
-from mindpose_amd.models.layers import ActC8, F16_VARIANTS  # noqa: E402
+from mindpose_amd.models.act_c8 import ActC8  # noqa: E402
+from mindpose_amd.models.tuner import F16_VARIANTS  # noqa: E402
 from tests import f16_matrix as fm  # noqa: E402
 
 DEV = torch.device("cuda:0")

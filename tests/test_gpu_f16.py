@@ -21,7 +21,7 @@ if not torch.cuda.is_available():
 
 import mindpose_amd as mp  # noqa: E402
 from mindpose_amd import _lib  # noqa: E402
-from mindpose_amd.models.layers import ActC8  # noqa: E402
+from mindpose_amd.models.act_c8 import ActC8  # noqa: E402
 from oracle import nets as onets  # noqa: E402
 from tests import f16_matrix as fm  # noqa: E402
 from tests.f16_matrix import CONV_CASES, WREG_CASES, WREG_S2_CASES, WS_CASES  # noqa: E402

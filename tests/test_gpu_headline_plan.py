@@ -179,7 +179,7 @@ _CHILD = r"""
 import hashlib, json, sys, torch
 sys.path.insert(0, {root!r})
 import mindpose_amd as mp
-from mindpose_amd.models import layers
+from mindpose_amd.models import tuner
 dev = torch.device("cuda:0")
 net = mp.init_synthetic(mp.create_network("hrnet_w32", "hrnet_head"), seed=0).to(dev).eval()
 x = torch.randn(16, 3, 256, 192, generator=torch.Generator().manual_seed(7)).to(dev)
@@ -187,7 +187,7 @@ hm = net(x).cpu().contiguous()
 plan = net.get_plan(x.shape, dev)
 print(json.dumps(dict(sha=hashlib.sha256(hm.numpy().tobytes()).hexdigest(),
                       kinds=[e["kind"] for e in plan.layer_info],
-                      tuned=len([k for k in layers._TUNE_CACHE if isinstance(k, str)]))))
+                      tuned=len([k for k in tuner._TUNE_CACHE if isinstance(k, str)]))))
 """
 
 

@@ -15,7 +15,8 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 from mindpose_amd import _lib  # noqa: E402
-from mindpose_amd.models.layers import BatchNorm2d, Conv2d, Plan, F32_WINOGRAD  # noqa: E402
+from mindpose_amd.models.layers import BatchNorm2d, Conv2d, Plan  # noqa: E402
+from mindpose_amd.models.tuner import F32_WINOGRAD  # noqa: E402
 
 DEV = torch.device("cuda:0")
 

@@ -6,7 +6,7 @@ import torch
 
 sys.path.insert(0, ".")
 from mindpose_amd import _lib  # noqa: E402
-from mindpose_amd.models.layers import ActC8  # noqa: E402
+from mindpose_amd.models.act_c8 import ActC8  # noqa: E402
 
 lib = _lib.load()
 dev = torch.device("cuda:0")

@@ -7,7 +7,8 @@ import torch
 
 sys.path.insert(0, ".")
 from mindpose_amd import _lib  # noqa: E402
-from mindpose_amd.models.layers import ActC8, F16_VARIANTS  # noqa: E402
+from mindpose_amd.models.act_c8 import ActC8
+from mindpose_amd.models.tuner import F16_VARIANTS  # noqa: E402
 
 lib = _lib.load()
 dev = torch.device("cuda:0")

@@ -4,7 +4,7 @@ import ctypes, os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mindpose_amd import _lib
-from mindpose_amd.models.layers import ActC8
+from mindpose_amd.models.act_c8 import ActC8
 lib = _lib.load(); dev = torch.device("cuda:0")
 c, h, w = (int(v) for v in (sys.argv[1:4] if len(sys.argv) > 3 else (128, 16, 12)))
 variants = [int(v) for v in sys.argv[4].split(",")] if len(sys.argv) > 4 else [0, 1, 3, 5, 19]

@@ -6,7 +6,8 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench
 from mindpose_amd import _lib
-from mindpose_amd.models.layers import ActC8, F16_VARIANTS
+from mindpose_amd.models.act_c8 import ActC8
+from mindpose_amd.models.tuner import F16_VARIANTS
 lib = _lib.load(); dev = torch.device("cuda:0")
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 128
 for h, w in [(256, 192), (384, 288)]:

@@ -6,7 +6,7 @@ os.environ.setdefault("MINDPOSE_EXPERIMENT_KNOBS", "1")  # the MP_* knobs below 
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mindpose_amd import _lib
-from mindpose_amd.models.layers import ActC8
+from mindpose_amd.models.act_c8 import ActC8
 lib = _lib.load(); dev = torch.device("cuda:0")
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 128
 SHAPES = [(32, 32, 64, 48, 3, 1), (64, 64, 32, 24, 3, 1), (128, 128, 16, 12, 3, 1), (256, 256, 8, 6, 3, 1), (64, 256, 64, 48, 1, 1),

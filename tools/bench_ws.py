@@ -6,7 +6,8 @@ import ctypes, os, statistics, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mindpose_amd import _lib
-from mindpose_amd.models.layers import ActC8, F16_VARIANTS
+from mindpose_amd.models.act_c8 import ActC8
+from mindpose_amd.models.tuner import F16_VARIANTS
 lib = _lib.load(); dev = torch.device("cuda:0")
 which = sys.argv[1] if len(sys.argv) > 1 else "all"
 W32 = [(128, 32, 32, 64, 48), (128, 64, 64, 32, 24), (128, 128, 128, 16, 12)]

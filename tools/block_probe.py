@@ -6,7 +6,7 @@ import numpy as np
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mindpose_amd import _lib
-from mindpose_amd.models.layers import ActC8
+from mindpose_amd.models.act_c8 import ActC8
 lib = _lib.load(); dev = torch.device("cuda:0")
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 128
 c, h, w = 32, 64, 48

@@ -28,7 +28,7 @@ LEGS = {
 
 
 def parse_key(key, fields):
-    """repr(tuple) written by models/layers.py::tune_conv_variant -> dict, or None for keys of other tuners."""
+    """repr(tuple) written by models/tuner.py::tune_conv_variant -> dict, or None for keys of other tuners."""
     try:
         t = ast.literal_eval(key)
     except (ValueError, SyntaxError):

@@ -5,7 +5,7 @@ import ctypes, os, sys
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mindpose_amd import _lib
-from mindpose_amd.models.layers import ActC8
+from mindpose_amd.models.act_c8 import ActC8
 lib = _lib.load(); dev = torch.device("cuda:0")
 v, cin, cout, h, w, nn = [int(a) for a in sys.argv[1:7]]
 launches = int(sys.argv[7]) if len(sys.argv) > 7 else 20

@@ -7,7 +7,7 @@ import numpy as np
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from mindpose_amd import _lib
-from mindpose_amd.models.layers import ActC8
+from mindpose_amd.models.act_c8 import ActC8
 lib = _lib.load(); dev = torch.device("cuda:0")
 a = [int(v) for v in sys.argv[1:]]
 CASES = [tuple(a)] if len(a) == 6 else [(38, 48, 48, 96, 72, 64), (41, 96, 96, 48, 36, 64), (42, 96, 96, 48, 36, 64), (40, 64, 64, 32, 24, 128),
