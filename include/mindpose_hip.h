@@ -516,6 +516,18 @@ int mp_warp_affine(const uint8_t* src_dev, const long long* src_offsets_dev, con
  * (mindpose/engine/inferencer/topdown_inferencer.py:168-170), one pass; in and out must not overlap. */
 int mp_flip_width(const float* in_dev, float* out_dev, int n, int c, int h, int w, mp_stream_t stream);
 
+/* Bottom-up evaluation input in one pass (mindpose/data/transform/bottomup_transform.py:143-208 BottomUpRescale, :601-645
+ * BottomUpPad, data_factory.py:129-133): cv2.resize(image, (tw, th), INTER_LINEAR) of uint8 HWC sources (packed as for
+ * mp_warp_affine: src + src_offsets[i], src_hw[i] = (h, w), both device arrays), zero pad on the right and bottom to
+ * (pad_h, pad_w) - applied to the uint8 image, so a padded pixel normalises to (0 - mean) / std -, Normalize and HWC2CHW.
+ * dst_wh_host [n, 2]: (tw, th) per image, a HOST array (it is checked here and travels in the kernel arguments; up to 32 images are
+ * one launch).  out [n, 3, pad_h, pad_w] fp32; mask [n, pad_h, pad_w] uint8, 1 where y < th && x < tw.  mean / stddev already
+ * multiplied by 255.  The interpolation restates OpenCV's 8-bit fixed-point linear resize [cv2-knowledge; parity with cv2 itself
+ * is unpinned].  MP_ERR_NULL / MP_ERR_SHAPE as mp_warp_affine; tw > pad_w or th > pad_h -> MP_ERR_SHAPE. */
+int mp_resize_pad_normalize(const uint8_t* src_dev, const long long* src_offsets_dev, const int* src_hw_dev, const int* dst_wh_host,
+                            float* out_dev, uint8_t* mask_dev, int n, int pad_h, int pad_w, const float mean[3],
+                            const float stddev[3], mp_stream_t stream);
+
 /* ---- bottom-up (associative-embedding) decoder, BottomUpHeatMapAEDecoder -------------------------------------------------
  * Replaces mindpose/models/decoders/bottom_up_decoder.py:81-203 (the ~10 MindSpore ops of decode()) with two launches.
  * stages[0 .. num_stages-1]: the model outputs in the reference's order, stages[num_stages-1] the full-resolution one (its h, w
@@ -544,6 +556,16 @@ int mp_bottomup_parse_nms_topk(const mp_bottomup_stage* stages_host, int num_sta
 int mp_bottomup_gather(const float* heatmap_raw_dev, const float* tagging_dev, const void* workspace_dev, size_t workspace_bytes,
                        int n, int k, int h, int w, int tag_per_joint, int num_tags, int max_num, int shift_coordinate,
                        float* val_k_dev, float* ind_k_dev, float* tag_k_dev, mp_stream_t stream);
+
+/* mp_bottomup_refine_missing (mindpose/engine/inferencer/bottomup_inferencer.py:189-250, refine_missing_joint): for every person p
+ * of a batch's person list (image person_image[p], mean tag mean_tag [P, L] formed by the caller) and every joint, the first
+ * arg-max in flat index over the joint's H x W map of  heatmap_raw - rint(sqrt(sum_l (tagging_l - mean_tag_l)^2))  in fp32 (tag
+ * channel 0 without tag_per_joint); found [P, k, 3] = (x + 0.5 +- 0.25, y + 0.5 +- 0.25, heat-map value) of that pixel, the shifts by
+ * the reference's two clamped neighbour comparisons.  One workgroup per (joint, person); num_persons 0 = no launch, MP_OK.  Inputs
+ * are assumed finite; a person_image outside [0, n) leaves its rows of found unwritten. */
+int mp_bottomup_refine_missing(const float* heatmap_raw_dev, const float* tagging_dev, const float* mean_tag_dev,
+                               const int* person_image_dev, int num_persons, int n, int k, int h, int w, int tag_per_joint,
+                               int num_tags, float* found_dev, mp_stream_t stream);
 
 /* fp16 (amp O2) training passes over channel-blocked fp16 activations; same contracts as mp_bn_train_fwd / _bwd and
  * mp_fuse_upsample_sum_bwd (statistics, gamma / beta gradients and the workspace stay fp32 / fp64; mp_bn_workspace_bytes) */

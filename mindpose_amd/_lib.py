@@ -194,6 +194,9 @@ _PROTOTYPES = {
     "mp_bottomup_parse_nms_topk": (c_int, [ctypes.POINTER(BottomUpStage), c_int, c_f32p] + [c_int] * 7 + [c_f32p, c_f32p, c_f32p, c_size_t,
                                                                                                      ctypes.c_void_p]),
     "mp_bottomup_gather": (c_int, [c_f32p, c_f32p, c_f32p, c_size_t] + [c_int] * 8 + [c_f32p, c_f32p, c_f32p, ctypes.c_void_p]),
+    "mp_bottomup_refine_missing": (c_int, [c_f32p] * 4 + [c_int] * 7 + [c_f32p, ctypes.c_void_p]),
+    "mp_resize_pad_normalize": (c_int, [c_f32p] * 3 + [ctypes.POINTER(ctypes.c_int)] + [c_f32p] * 2 + [c_int] * 3
+                                + [ctypes.POINTER(ctypes.c_float)] * 2 + [ctypes.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)

@@ -256,6 +256,76 @@ __global__ __launch_bounds__(256) void col_slice_kernel(const T* __restrict__ in
     }
 }
 
+// ---- refine_missing_joint on the device (bottomup_inferencer.py:189-250 of the reference).  One workgroup per (joint, person): over
+// the H * W pixels of the joint's map of the person's image, the first arg-max in flat index of
+//     heatmap_raw - rintf(sqrtf(sum_l (tag_l - mean_tag_l)^2))
+// in fp32, the squares summed in l order (numpy's norm along the last axis; np.round = round half to even = rintf), then the
+// winner's centre (+0.5) shifted +-0.25 by the two clamped neighbour comparisons and its heat-map value.  Every lane keeps the best
+// (value, index) of its pixels, a wave shuffle reduce and an LDS merge pick the workgroup's; ties go to the lowest flat index
+// (np.argmax).  Inputs are assumed finite.
+constexpr int kBuRefineThreads = 256;
+
+struct BuRefineParams {
+    const float* raw;       // [N, K, H, W]
+    const float* tagging;   // [N, KTAG, H, W, L]
+    const float* mean_tag;  // [P, L]
+    const int* person_img;  // [P]
+    int n, k, h, w, ktag, tag_per_joint, num_tags;
+    float* found;           // [P, K, 3]
+};
+
+__device__ __forceinline__ bool refine_better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
+
+template <int L>
+__global__ __launch_bounds__(kBuRefineThreads) void bu_refine_kernel(BuRefineParams p) {
+    __shared__ float wave_v[kBuRefineThreads / kWave];
+    __shared__ int wave_i[kBuRefineThreads / kWave];
+    const int k = blockIdx.x, person = blockIdx.y;
+    const int img = p.person_img[person];
+    if (img < 0 || img >= p.n) return;  // (uniform per workgroup) an index outside the batch reads nothing
+    const int hw = p.h * p.w;
+    const float* __restrict__ plane = p.raw + ((size_t)img * p.k + k) * hw;
+    const float* __restrict__ tags = p.tagging + ((size_t)img * p.ktag + (p.tag_per_joint ? k : 0)) * (size_t)hw * L;
+    float mean[L];
+#pragma unroll
+    for (int l = 0; l < L; ++l) mean[l] = p.mean_tag[(size_t)person * L + l];
+
+    float bv = -INFINITY;
+    int bi = 0x7fffffff;
+    for (int i = threadIdx.x; i < hw; i += kBuRefineThreads) {  // ascending per lane: '>' keeps the lane's first maximum
+        float sum = 0.0f;
+#pragma unroll
+        for (int l = 0; l < L; ++l) {
+            const float d = tags[(size_t)i * L + l] - mean[l];
+            sum = sum + d * d;
+        }
+        const float v = plane[i] - rintf(sqrtf(sum));
+        if (v > bv) { bv = v; bi = i; }
+    }
+    for (int off = kWave / 2; off > 0; off >>= 1) {
+        const float ov = __shfl_down(bv, off, kWave);
+        const int oi = __shfl_down(bi, off, kWave);
+        if (refine_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+    }
+    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+    if (lane == 0) { wave_v[wave] = bv; wave_i[wave] = bi; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int q = 1; q < kBuRefineThreads / kWave; ++q)
+            if (refine_better(wave_v[q], wave_i[q], bv, bi)) { bv = wave_v[q]; bi = wave_i[q]; }
+        if (bi >= hw) bi = 0;  // no finite value anywhere (outside the contract): stay inside the map
+        const int y = bi / p.w, x = bi - y * p.w;
+        float xs = (float)x + 0.5f, ys = (float)y + 0.5f;
+        const float* row = plane + (size_t)y * p.w;
+        xs += row[min(x + 1, p.w - 1)] > row[max(x - 1, 0)] ? 0.25f : -0.25f;
+        ys += plane[(size_t)min(y + 1, p.h - 1) * p.w + x] > plane[(size_t)max(y - 1, 0) * p.w + x] ? 0.25f : -0.25f;
+        float* out = p.found + ((size_t)person * p.k + k) * 3;
+        out[0] = xs;
+        out[1] = ys;
+        out[2] = plane[bi];
+    }
+}
+
 static int bu_tiles_x(int w) { return (w + kBuTileW - 1) / kBuTileW; }
 static int bu_tiles(int h, int w) { return bu_tiles_x(w) * ((h + kBuTileH - 1) / kBuTileH); }
 
@@ -344,6 +414,37 @@ int mp_bottomup_gather(const float* heatmap_raw_dev, const float* tagging_dev, c
     p.ind_k = ind_k_dev;
     p.tag_k = tag_k_dev;
     hipLaunchKernelGGL(bu_gather_kernel, dim3((unsigned)k, (unsigned)n), dim3(kBuMergeThreads), 0, as_stream(stream), p);
+    return check_launch();
+}
+
+int mp_bottomup_refine_missing(const float* heatmap_raw_dev, const float* tagging_dev, const float* mean_tag_dev,
+                               const int* person_image_dev, int num_persons, int n, int k, int h, int w, int tag_per_joint,
+                               int num_tags, float* found_dev, mp_stream_t stream) {
+    if (num_persons == 0) return MP_OK;  // nobody to refine: no launch
+    if (!heatmap_raw_dev || !tagging_dev || !mean_tag_dev || !person_image_dev || !found_dev) return MP_ERR_NULL;
+    if (num_persons < 0 || n <= 0 || k <= 0 || h <= 0 || w <= 0 || (size_t)h * w > 0x7fffffffu) return MP_ERR_SHAPE;
+    if (num_tags < 1 || num_tags > kBuMaxTags) return MP_ERR_UNSUPPORTED;
+    if (num_persons > 65535) return MP_ERR_SHAPE;
+    BuRefineParams p{};
+    p.raw = heatmap_raw_dev;
+    p.tagging = tagging_dev;
+    p.mean_tag = mean_tag_dev;
+    p.person_img = person_image_dev;
+    p.n = n;
+    p.k = k;
+    p.h = h;
+    p.w = w;
+    p.ktag = tag_per_joint ? k : 1;
+    p.tag_per_joint = tag_per_joint ? 1 : 0;
+    p.num_tags = num_tags;
+    p.found = found_dev;
+    const dim3 grid((unsigned)k, (unsigned)num_persons), block(kBuRefineThreads);
+    switch (num_tags) {
+        case 1: hipLaunchKernelGGL(bu_refine_kernel<1>, grid, block, 0, as_stream(stream), p); break;
+        case 2: hipLaunchKernelGGL(bu_refine_kernel<2>, grid, block, 0, as_stream(stream), p); break;
+        case 3: hipLaunchKernelGGL(bu_refine_kernel<3>, grid, block, 0, as_stream(stream), p); break;
+        default: hipLaunchKernelGGL(bu_refine_kernel<4>, grid, block, 0, as_stream(stream), p); break;
+    }
     return check_launch();
 }
 

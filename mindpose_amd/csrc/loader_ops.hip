@@ -143,3 +143,140 @@ extern "C" int mp_flip_width(const float* in, float* out, int n, int c, int h, i
     hipLaunchKernelGGL(mp::flip_width_kernel, dim3((unsigned)blocks), dim3(256), 0, mp::as_stream(stream), in, out, rows, w);
     return mp::check_launch();
 }
+
+// ---- bottom-up evaluation input: BottomUpRescale + BottomUpPad + Normalize + HWC2CHW in one pass (bottomup_transform.py:143-208,
+// :601-645, data_factory.py:129-133).  cv2.resize(image, (tw, th), INTER_LINEAR) on uint8 HWC, zero pad on the right and bottom to
+// (PH, PW), (v - mean) / std per channel, written as three fp32 planes; the mask (1 inside the resized image) leaves by the same launch.
+// The pad happens on the uint8 image, BEFORE Normalize: a padded pixel is (0 - mean) / std, not 0.
+//
+// The interpolation restates OpenCV's 8-bit fixed-point linear resize [cv2-knowledge, PARITY UNPINNED: cv2 is not installed here]:
+// scale = src / dst in double; f = (float)((d + 0.5) * scale - 0.5), s = floor(f), f -= s; s < 0 -> (0, 0), s >= src - 1 ->
+// (src - 1, 0); coefficients saturate_cast<short>((1 - f) * 2048), saturate_cast<short>(f * 2048) (INTER_RESIZE_COEF_BITS = 11);
+// horizontal pass int32 S[sx] * a0 + S[sx + 1] * a1; vertical pass (((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2,
+// saturated to 0..255.  Integer arithmetic after the coefficients: the result does not depend on the thread mapping.
+namespace mp {
+namespace {
+
+constexpr int kRpnMaxImages = 32;  // (tw, th) of every image of a launch travel in the kernel arguments
+
+struct RpnParams {
+    const uint8_t* src;
+    const long long* src_off;
+    const int* src_hw;
+    float* out;     // [n, 3, PH, PW]
+    uint8_t* mask;  // [n, PH, PW]
+    int ph, pw;
+    float m[3], s[3];
+    int twh[kRpnMaxImages][2];
+};
+
+// source index and the two 11-bit coefficients of destination coordinate d (either axis)
+__device__ __forceinline__ void resize_term(int d, double scale, int src_size, int& s, int& c0, int& c1) {
+    float f = (float)(((double)d + 0.5) * scale - 0.5);
+    s = (int)floorf(f);
+    f -= (float)s;
+    if (s < 0) { s = 0; f = 0.f; }
+    if (s >= src_size - 1) { s = src_size - 1; f = 0.f; }
+    const float a0 = rintf((1.f - f) * 2048.f), a1 = rintf(f * 2048.f);  // saturate_cast<short>: cvRound, then the short range
+    c0 = (int)fminf(fmaxf(a0, -32768.f), 32767.f);
+    c1 = (int)fminf(fmaxf(a1, -32768.f), 32767.f);
+}
+
+// VEC adjacent destination pixels of one row per thread: VEC = 4 writes each plane with one 16-byte store and the mask with one
+// 4-byte store (PW % 4 == 0), VEC = 1 is the scalar form for any other width
+template <int VEC>
+__global__ __launch_bounds__(256) void resize_pad_normalize_kernel(RpnParams p) {
+    const int n = blockIdx.z, y = blockIdx.y;
+    const int H = p.src_hw[2 * n], W = p.src_hw[2 * n + 1];
+    const int tw = p.twh[n][0], th = p.twh[n][1];
+    __shared__ int row[4];  // the per-row terms, once per row: sy, sy + 1 (clamped), b0, b1
+    if (threadIdx.x == 0 && y < th) {
+        int sy, b0, b1;
+        resize_term(y, (double)H / (double)th, H, sy, b0, b1);
+        row[0] = sy; row[1] = min(sy + 1, H - 1); row[2] = b0; row[3] = b1;
+    }
+    __syncthreads();
+    const uint8_t* __restrict__ img = p.src + p.src_off[n];
+    const size_t plane = (size_t)p.ph * p.pw;
+    float* __restrict__ o = p.out + (size_t)n * 3 * plane + (size_t)y * p.pw;
+    uint8_t* __restrict__ mk = p.mask + (size_t)n * plane + (size_t)y * p.pw;
+    const float pad0 = (0.f - p.m[0]) / p.s[0], pad1 = (0.f - p.m[1]) / p.s[1], pad2 = (0.f - p.m[2]) / p.s[2];
+    const double scale_x = (double)W / (double)tw;
+    const int groups = (p.pw + VEC - 1) / VEC;
+    for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += gridDim.x * blockDim.x) {
+        float v[3][VEC];
+        uint8_t in[VEC];
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            const int x = g * VEC + e;
+            in[e] = (y < th && x < tw) ? 1 : 0;
+            v[0][e] = pad0; v[1][e] = pad1; v[2][e] = pad2;
+            if (in[e]) {
+                int sx, a0, a1;
+                resize_term(x, scale_x, W, sx, a0, a1);
+                const int sx1 = min(sx + 1, W - 1);
+                const uint8_t* r0 = img + (size_t)row[0] * W * 3;
+                const uint8_t* r1 = img + (size_t)row[1] * W * 3;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const int h0 = r0[sx * 3 + c] * a0 + r0[sx1 * 3 + c] * a1;
+                    const int h1 = r1[sx * 3 + c] * a0 + r1[sx1 * 3 + c] * a1;
+                    int u = (((row[2] * (h0 >> 4)) >> 16) + ((row[3] * (h1 >> 4)) >> 16) + 2) >> 2;
+                    u = u < 0 ? 0 : (u > 255 ? 255 : u);
+                    v[c][e] = ((float)u - p.m[c]) / p.s[c];
+                }
+            }
+        }
+        if constexpr (VEC == 4) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+                *reinterpret_cast<float4*>(o + c * plane + (size_t)g * 4) = make_float4(v[c][0], v[c][1], v[c][2], v[c][3]);
+            *reinterpret_cast<uchar4*>(mk + (size_t)g * 4) = make_uchar4(in[0], in[1], in[2], in[3]);
+        } else {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) o[c * plane + g] = v[c][0];
+            mk[g] = in[0];
+        }
+    }
+}
+
+}  // namespace
+}  // namespace mp
+
+extern "C" int mp_resize_pad_normalize(const uint8_t* src, const long long* src_offsets, const int* src_hw, const int* dst_wh_host,
+                                       float* out, uint8_t* mask, int n, int pad_h, int pad_w, const float mean[3], const float stddev[3],
+                                       mp_stream_t stream) {
+    if (!src || !src_offsets || !src_hw || !dst_wh_host || !out || !mask || !mean || !stddev) return MP_ERR_NULL;
+    if (n <= 0 || pad_h <= 0 || pad_w <= 0 || pad_h > 65535) return MP_ERR_SHAPE;
+    if (stddev[0] == 0.f || stddev[1] == 0.f || stddev[2] == 0.f) return MP_ERR_SHAPE;
+    for (int i = 0; i < n; ++i) {
+        const int tw = dst_wh_host[2 * i], th = dst_wh_host[2 * i + 1];
+        if (tw <= 0 || th <= 0 || tw > pad_w || th > pad_h) return MP_ERR_SHAPE;
+    }
+    const size_t plane = (size_t)pad_h * pad_w;
+    // 16-byte stores need every row of every plane on a 16-byte boundary (and the mask rows on a 4-byte one)
+    const bool wide = pad_w % 4 == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)mask % 4 == 0;
+    const int groups = wide ? pad_w / 4 : pad_w;
+    int bx = (groups + 255) / 256;
+    if (bx > 64) bx = 64;
+    for (int i0 = 0; i0 < n; i0 += mp::kRpnMaxImages) {  // one launch for a batch of up to 32 images
+        const int cnt = n - i0 < mp::kRpnMaxImages ? n - i0 : mp::kRpnMaxImages;
+        mp::RpnParams p{};
+        p.src = src;
+        p.src_off = src_offsets + i0;
+        p.src_hw = src_hw + 2 * i0;
+        p.out = out + (size_t)i0 * 3 * plane;
+        p.mask = mask + (size_t)i0 * plane;
+        p.ph = pad_h;
+        p.pw = pad_w;
+        for (int c = 0; c < 3; ++c) { p.m[c] = mean[c]; p.s[c] = stddev[c]; }
+        for (int i = 0; i < cnt; ++i) { p.twh[i][0] = dst_wh_host[2 * (i0 + i)]; p.twh[i][1] = dst_wh_host[2 * (i0 + i) + 1]; }
+        if (wide)
+            hipLaunchKernelGGL(mp::resize_pad_normalize_kernel<4>, dim3(bx, pad_h, cnt), dim3(256), 0, mp::as_stream(stream), p);
+        else
+            hipLaunchKernelGGL(mp::resize_pad_normalize_kernel<1>, dim3(bx, pad_h, cnt), dim3(256), 0, mp::as_stream(stream), p);
+        const int rc = mp::check_launch();
+        if (rc != MP_OK) return rc;
+    }
+    return MP_OK;
+}

@@ -1,4 +1,5 @@
-"""``create_dataset`` / ``create_pipeline`` of the top-down path (reference: mindpose/data/data_factory.py:16-171), MI355X-first.
+"""``create_dataset`` / ``create_pipeline`` (reference: mindpose/data/data_factory.py:16-171), MI355X-first: the top-down path for
+training and evaluation, the bottom-up path for evaluation (`BottomUpPipeline`).
 
 The reference wraps the record loader into ``mindspore.dataset.GeneratorDataset`` (shuffle when training, ``num_shards`` /
 ``shard_id`` sharding) and maps, per SAMPLE in CPU worker processes: Decode -> the transform list -> Normalize -> HWC2CHW ->
@@ -29,9 +30,10 @@ import torch
 
 from ..register import entrypoint
 from .column_names import COLUMN_MAP, FINAL_COLUMN_MAP
-from .transform.topdown_transform import TopDownAffine, TopDownGenerateTarget
+from .transform.bottomup_transform import BottomUpPad, BottomUpRescale, BottomUpResize, launch_resize_pad_normalize
+from .transform.topdown_transform import TopDownAffine, TopDownGenerateTarget, launch_warp_affine
 
-__all__ = ["create_dataset", "create_pipeline", "ShardedDataset", "TopDownPipeline"]
+__all__ = ["create_dataset", "create_pipeline", "ShardedDataset", "TopDownPipeline", "BottomUpPipeline"]
 
 
 class ShardedDataset:
@@ -233,11 +235,11 @@ class _DecodeProcesses:
             self._finalizer()
 
 
-class TopDownPipeline:
-    """What ``create_pipeline`` returns: iterating yields batches - dicts with the final columns of ``column_names.py``;
-    ``image`` ([B, 3, H, W] fp32 normalised), ``target`` / ``target_weight``, ``center`` / ``scale`` / ``bbox_scores`` are CUDA
-    tensors, ``boxes`` / ``bbox_ids`` numpy, ``image_file`` a list (what ``TopDownHeatMapInferencer.infer`` and the training
-    step consume)."""
+class _BatchPipeline:
+    """What the pipelines share: grouping the dataset's samples into batches, the image codec (thread pool or worker processes,
+    one batch ahead), the upload of a batch's decoded images and the prefetch on a side stream.  A pipeline implements
+    ``_run_sample(state) -> state`` (the host part of the transform list for one sample) and
+    ``_finish(states, pool, codec, region) -> batch`` (the device part for a batch)."""
 
     def __init__(self, dataset: ShardedDataset, transforms: list, column_names: List[str], final_column_names: List[str],
                  batch_size: int, is_train: bool, normalize: bool, normalize_mean, normalize_std, hwc_to_chw: bool, num_workers: int,
@@ -272,90 +274,52 @@ class TopDownPipeline:
         for _ in range(num_epochs):
             yield from iter(self)
 
-    # -- one sample through the transform list (host part) -----------------------------------------------------------------------
     def _run_sample(self, state: Dict[str, Any]) -> Dict[str, Any]:
-        if not (isinstance(state["image"], np.ndarray) and state["image"].ndim == 3):  # not decoded ahead by the thread pool
-            state["image"] = _decode(state["image"])
-        for t in self.transforms:
-            if isinstance(t, TopDownAffine):  # matrix + key points now, pixels with the batch
-                trans = t.get_matrix(state["center"], state["scale"], state["rotation"])
-                state["_affine"], state["_trans"] = t, trans
-                if "keypoints" in state:
-                    state["keypoints"] = t.transform_keypoints(state["keypoints"], trans)
-            elif isinstance(t, TopDownGenerateTarget):  # key points now, heat maps with the batch
-                state["_target"] = t
-            else:
-                state.update(t.transform(state))
-        return state
+        raise NotImplementedError
 
     def _finish(self, states: List[Dict[str, Any]], pool=None, codec=None, region=None) -> Dict[str, Any]:
-        dev = self.device
-        out: Dict[str, Any] = {}
-        aff = states[0].get("_affine")
-        if aff is not None:
-            # ONE upload per batch: the decoded images packed into a pinned staging tensor (torch's caching host allocator hands the
-            # block out again only after this stream has passed the copy), one asynchronous copy, the kernel's sources = views of it.
-            # (Per-image pageable copies were 128 synchronous transfers of ~0.9 MB per batch.)
-            srcs, flips, sizes = [], [], []
-            for s in states:
-                im = s["image"]
-                flipped = im.strides[1] < 0  # topdown_horizontal_random_flip hands back a mirrored VIEW: the kernel mirrors while sampling
-                srcs.append(im[:, ::-1] if flipped else im)
-                flips.append(flipped)
-                sizes.append((im.size + 255) & ~255)  # 256-byte aligned slots
-            offsets = np.concatenate([[0], np.cumsum(sizes)[:-1]]).tolist()
-            if codec is not None:
-                # the decoded images sit in page-locked shared memory (`_DecodeProcesses`): one asynchronous DMA per image, slot -> device
-                packed = torch.empty(sum(sizes), dtype=torch.uint8, device=dev)
-                for i, im in enumerate(srcs):
-                    flat = torch.from_numpy(im.reshape(-1)) if im.flags["C_CONTIGUOUS"] else torch.from_numpy(np.ascontiguousarray(im).reshape(-1))
-                    packed[offsets[i]:offsets[i] + im.size].copy_(flat, non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record(torch.cuda.current_stream(dev))
-                codec.consumed(region, ev)
-            else:
-                stage = torch.empty(sum(sizes), dtype=torch.uint8, pin_memory=True)
-                host = stage.numpy()
+        raise NotImplementedError
 
-                def pack(i):
-                    np.copyto(host[offsets[i]:offsets[i] + srcs[i].size].reshape(srcs[i].shape), srcs[i])
-                if pool is not None:
-                    list(pool.map(pack, range(len(srcs))))  # ~118 MB per batch of 128 VGA images: the copies run on the pool's threads
-                else:
-                    for i in range(len(srcs)):
-                        pack(i)
-                packed = stage.to(dev, non_blocking=True)
-            images, off = [], 0
-            for im, size in zip(srcs, sizes):
-                images.append(packed[off:off + im.size].view(im.shape))
-                off += size
-            mats = np.stack([s["_trans"] for s in states])
-            fused = self.normalize and self.hwc_to_chw
-            crops = aff._launch(images, list(range(len(states))), mats, fused, None, self.mean, self.std, flips if any(flips) else None)
-            if not fused:  # rare combinations: the warped uint8 image, then the requested steps as tensor ops
-                crops = crops.float()
-                if self.normalize:
-                    crops = (crops - torch.tensor(self.mean, device=dev) * 255.0) / (torch.tensor(self.std, device=dev) * 255.0)
-                if self.hwc_to_chw:
-                    crops = crops.permute(0, 3, 1, 2).contiguous()
-            out["image"] = crops
+    def _upload_images(self, states: List[Dict[str, Any]], pool=None, codec=None, region=None):
+        """The decoded images of a batch on the device: (views [H, W, 3] uint8 of one packed buffer, the per-sample mirror flags)."""
+        dev = self.device
+        # ONE upload per batch: the decoded images packed into a pinned staging tensor (torch's caching host allocator hands the
+        # block out again only after this stream has passed the copy), one asynchronous copy, the kernel's sources = views of it.
+        # (Per-image pageable copies were 128 synchronous transfers of ~0.9 MB per batch.)
+        srcs, flips, sizes = [], [], []
+        for s in states:
+            im = s["image"]
+            flipped = im.strides[1] < 0  # topdown_horizontal_random_flip hands back a mirrored VIEW: the kernel mirrors while sampling
+            srcs.append(im[:, ::-1] if flipped else im)
+            flips.append(flipped)
+            sizes.append((im.size + 255) & ~255)  # 256-byte aligned slots
+        offsets = np.concatenate([[0], np.cumsum(sizes)[:-1]]).tolist()
+        if codec is not None:
+            # the decoded images sit in page-locked shared memory (`_DecodeProcesses`): one asynchronous DMA per image, slot -> device
+            packed = torch.empty(sum(sizes), dtype=torch.uint8, device=dev)
+            for i, im in enumerate(srcs):
+                flat = torch.from_numpy(im.reshape(-1)) if im.flags["C_CONTIGUOUS"] else torch.from_numpy(np.ascontiguousarray(im).reshape(-1))
+                packed[offsets[i]:offsets[i] + im.size].copy_(flat, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(dev))
+            codec.consumed(region, ev)
         else:
-            raise ValueError("the top-down pipeline needs `topdown_affine` in its transform list (fixed-size network input)")
-        tgt = states[0].get("_target")
-        if tgt is not None:
-            kp = torch.from_numpy(np.stack([np.asarray(s["keypoints"], dtype=np.float32) for s in states])).to(dev)
-            out["target"], out["target_weight"] = tgt.generate(kp)
-        for name in self.final_column_names:
-            if name in out:
-                continue
-            vals = [s[name] for s in states]
-            if name in ("center", "scale", "bbox_scores"):
-                out[name] = torch.from_numpy(np.stack([np.asarray(v, dtype=np.float32) for v in vals])).to(dev)
-            elif name == "image_file":
-                out[name] = [str(v) for v in vals]
+            stage = torch.empty(sum(sizes), dtype=torch.uint8, pin_memory=True)
+            host = stage.numpy()
+
+            def pack(i):
+                np.copyto(host[offsets[i]:offsets[i] + srcs[i].size].reshape(srcs[i].shape), srcs[i])
+            if pool is not None:
+                list(pool.map(pack, range(len(srcs))))  # ~118 MB per batch of 128 VGA images: the copies run on the pool's threads
             else:
-                out[name] = np.stack([np.asarray(v) for v in vals])
-        return {k: out[k] for k in self.final_column_names}
+                for i in range(len(srcs)):
+                    pack(i)
+            packed = stage.to(dev, non_blocking=True)
+        images, off = [], 0
+        for im, size in zip(srcs, sizes):
+            images.append(packed[off:off + im.size].view(im.shape))
+            off += size
+        return images, flips
 
     def __iter__(self) -> Iterator[Dict[str, Any]]:
         if self.prefetch > 0 and self.device.type == "cuda":
@@ -474,19 +438,154 @@ class TopDownPipeline:
         return self._finish([self._run_sample(dict(s)) for s in pending], pool, codec if region is not None else None, region)
 
 
+class TopDownPipeline(_BatchPipeline):
+    """What ``create_pipeline`` returns: iterating yields batches - dicts with the final columns of ``column_names.py``;
+    ``image`` ([B, 3, H, W] fp32 normalised), ``target`` / ``target_weight``, ``center`` / ``scale`` / ``bbox_scores`` are CUDA
+    tensors, ``boxes`` / ``bbox_ids`` numpy, ``image_file`` a list (what ``TopDownHeatMapInferencer.infer`` and the training
+    step consume)."""
+
+    # -- one sample through the transform list (host part) -----------------------------------------------------------------------
+    def _run_sample(self, state: Dict[str, Any]) -> Dict[str, Any]:
+        if not (isinstance(state["image"], np.ndarray) and state["image"].ndim == 3):  # not decoded ahead by the thread pool
+            state["image"] = _decode(state["image"])
+        for t in self.transforms:
+            if isinstance(t, TopDownAffine):  # matrix + key points now, pixels with the batch
+                trans = t.get_matrix(state["center"], state["scale"], state["rotation"])
+                state["_affine"], state["_trans"] = t, trans
+                if "keypoints" in state:
+                    state["keypoints"] = t.transform_keypoints(state["keypoints"], trans)
+            elif isinstance(t, TopDownGenerateTarget):  # key points now, heat maps with the batch
+                state["_target"] = t
+            else:
+                state.update(t.transform(state))
+        return state
+
+    def _finish(self, states: List[Dict[str, Any]], pool=None, codec=None, region=None) -> Dict[str, Any]:
+        dev = self.device
+        out: Dict[str, Any] = {}
+        aff = states[0].get("_affine")
+        if aff is not None:
+            images, flips = self._upload_images(states, pool, codec, region)
+            mats = np.stack([s["_trans"] for s in states])
+            fused = self.normalize and self.hwc_to_chw
+            crops = aff._launch(images, list(range(len(states))), mats, fused, None, self.mean, self.std, flips if any(flips) else None)
+            if not fused:  # rare combinations: the warped uint8 image, then the requested steps as tensor ops
+                crops = crops.float()
+                if self.normalize:
+                    crops = (crops - torch.tensor(self.mean, device=dev) * 255.0) / (torch.tensor(self.std, device=dev) * 255.0)
+                if self.hwc_to_chw:
+                    crops = crops.permute(0, 3, 1, 2).contiguous()
+            out["image"] = crops
+        else:
+            raise ValueError("the top-down pipeline needs `topdown_affine` in its transform list (fixed-size network input)")
+        tgt = states[0].get("_target")
+        if tgt is not None:
+            kp = torch.from_numpy(np.stack([np.asarray(s["keypoints"], dtype=np.float32) for s in states])).to(dev)
+            out["target"], out["target_weight"] = tgt.generate(kp)
+        for name in self.final_column_names:
+            if name in out:
+                continue
+            vals = [s[name] for s in states]
+            if name in ("center", "scale", "bbox_scores"):
+                out[name] = torch.from_numpy(np.stack([np.asarray(v, dtype=np.float32) for v in vals])).to(dev)
+            elif name == "image_file":
+                out[name] = [str(v) for v in vals]
+            else:
+                out[name] = np.stack([np.asarray(v) for v in vals])
+        return {k: out[k] for k in self.final_column_names}
+
+
+class BottomUpPipeline(_BatchPipeline):
+    """The evaluation pipeline of the bottom-up path: one image per batch (landscape and portrait images pad to different shapes),
+    ``image`` [1, 3, H, W] fp32 normalised and ``mask`` [1, H, W] uint8 CUDA tensors, ``center`` / ``scale`` / ``image_shape`` numpy,
+    ``image_file`` a list - what ``BottomUpHeatMapAEInferencer.infer`` consumes.
+
+    The pixel transforms are recognised in the list; per sample only their geometry runs on the host, the pixels of a batch are ONE
+    launch: ``bottomup_rescale`` + ``bottomup_pad`` -> ``mp_resize_pad_normalize`` (resize, pad, Normalize, HWC2CHW and the mask),
+    ``bottomup_resize`` -> ``mp_warp_affine`` with the transform's matrix and an all-ones mask.  Any other list (rescale without
+    pad, no Normalize ...) runs the transforms' host ``transform`` chain and finishes with tensor operations."""
+
+    def __init__(self, *args: Any, **kwargs: Any) -> None:
+        super().__init__(*args, **kwargs)
+        kinds = [type(t) for t in self.transforms]
+        fused = self.normalize and self.hwc_to_chw
+        if fused and kinds == [BottomUpRescale, BottomUpPad]:
+            self.mode = "rescale_pad"
+        elif fused and kinds == [BottomUpResize]:
+            self.mode = "resize"
+        else:
+            self.mode = "host"
+
+    def _run_sample(self, state: Dict[str, Any]) -> Dict[str, Any]:
+        if not (isinstance(state["image"], np.ndarray) and state["image"].ndim == 3):
+            state["image"] = _decode(state["image"])
+        height, width = state["image"].shape[:2]
+        if self.mode == "rescale_pad":  # geometry now, pixels with the batch
+            rescale, pad = self.transforms
+            state.update(rescale.geometry(width, height))
+            state["_padded"] = pad.padded_size(*state["image_shape"])
+        elif self.mode == "resize":
+            state.update(self.transforms[0].geometry(width, height))
+        else:
+            for t in self.transforms:
+                state.update(t.transform(state))
+        return state
+
+    def _finish(self, states: List[Dict[str, Any]], pool=None, codec=None, region=None) -> Dict[str, Any]:
+        dev = self.device
+        n = len(states)
+        out: Dict[str, Any] = {}
+        sizes = {tuple(s["_padded"]) if self.mode == "rescale_pad" else tuple(s["image_shape"]) if self.mode == "resize"
+                 else (s["image"].shape[1], s["image"].shape[0]) for s in states}
+        if len(sizes) != 1:
+            raise ValueError(f"the images of a bottom-up batch must share one network input size, got {sorted(sizes)}")
+        pw, ph = (int(v) for v in sizes.pop())
+        if self.mode == "rescale_pad":
+            images, _ = self._upload_images(states, pool, codec, region)
+            out["image"], out["mask"] = launch_resize_pad_normalize(images, [s["image_shape"] for s in states], (pw, ph), self.mean, self.std)
+        elif self.mode == "resize":
+            images, _ = self._upload_images(states, pool, codec, region)
+            mats = np.stack([s["_trans"] for s in states])
+            out["image"] = launch_warp_affine(images, list(range(n)), mats, (ph, pw), True, None, self.mean, self.std)
+            out["mask"] = torch.ones(n, ph, pw, dtype=torch.uint8, device=dev)
+        else:  # the host chain made the pixels: the requested steps as tensor ops
+            image = torch.from_numpy(np.stack([np.ascontiguousarray(s["image"]) for s in states])).to(dev).float()
+            if self.normalize:
+                image = (image - torch.tensor(self.mean, device=dev) * 255.0) / (torch.tensor(self.std, device=dev) * 255.0)
+            if self.hwc_to_chw:
+                image = image.permute(0, 3, 1, 2).contiguous()
+            out["image"] = image
+            masks = [np.asarray(s["mask"], dtype=np.uint8) if np.ndim(s["mask"]) == 2 else np.ones((ph, pw), np.uint8) for s in states]
+            out["mask"] = torch.from_numpy(np.stack(masks)).to(dev)
+        for name in self.final_column_names:
+            if name in out:
+                continue
+            vals = [s[name] for s in states]
+            out[name] = [str(v) for v in vals] if name == "image_file" else np.stack([np.asarray(v) for v in vals])
+        return {k: out[k] for k in self.final_column_names}
+
+
 def create_pipeline(dataset: ShardedDataset, transforms: List[Union[str, Dict[str, Any]]], method: str = "topdown", batch_size: int = 1,
                     is_train: bool = True, normalize: bool = True, normalize_mean: List[float] = [0.485, 0.456, 0.406],
                     normalize_std: List[float] = [0.229, 0.224, 0.255], hwc_to_chw: bool = True, num_workers: int = 1,
-                    config: Optional[Dict[str, Any]] = None, prefetch: Optional[int] = None) -> TopDownPipeline:
+                    config: Optional[Dict[str, Any]] = None, prefetch: Optional[int] = None) -> Union[TopDownPipeline, BottomUpPipeline]:
     """Signature of data_factory.py:71-151 (the reference's ``normalize_std`` really ends in 0.255: checkpoints were trained with it)
-    plus ``prefetch`` (batches prepared ahead on a side stream, `TopDownPipeline`; MindSpore's dataset engine prefetches by itself)."""
+    plus ``prefetch`` (batches prepared ahead on a side stream, `_BatchPipeline`; MindSpore's dataset engine prefetches by itself).
+    ``method`` "bottomup" / "imagefolder_bottomup" is evaluation only and gives a `BottomUpPipeline` of one image per batch."""
     if method not in FINAL_COLUMN_MAP:
-        raise ValueError(f"method `{method}` is outside the top-down hot path (supported: {sorted(FINAL_COLUMN_MAP)})")
+        raise ValueError(f"method `{method}` is not supported (supported: {sorted(FINAL_COLUMN_MAP)})")
+    bottomup = method in ("bottomup", "imagefolder_bottomup")
+    if bottomup and is_train:
+        raise ValueError("bottom-up training data is not implemented")
     key = "train" if is_train else "val"
     column_names, final_column_names = COLUMN_MAP[method][key], FINAL_COLUMN_MAP[method][key]
     transform_funcs = _convert_names_to_transform(transforms, is_train=is_train, config=config)
+    if bottomup:
+        logging.info(f"Set batch_size = 1 for `{method}` evaluation method.")
+        batch_size = 1
     logging.info(f"pipeline: {[type(t).__name__ for t in transform_funcs]}, batch {batch_size}")
-    return TopDownPipeline(dataset, transform_funcs, column_names, final_column_names, batch_size, is_train, normalize, normalize_mean,
+    pipeline = BottomUpPipeline if bottomup else TopDownPipeline
+    return pipeline(dataset, transform_funcs, column_names, final_column_names, batch_size, is_train, normalize, normalize_mean,
                            normalize_std, hwc_to_chw, num_workers, prefetch=prefetch)
 
 

@@ -1,0 +1,260 @@
+"""Bottom-up evaluation transforms: rescale / resize to the network input and the pad (reference:
+mindpose/data/transform/bottomup_transform.py:26-85, :143-301, :601-645).
+
+Names, constructors, config keys and the keys ``transform(state)`` returns are the reference's.  The geometry - the target size,
+``center``, ``scale``, ``image_shape`` - is the reference's own Python / numpy arithmetic.  ``transform`` is the host (numpy) path;
+the pipeline (data_factory.py ``BottomUpPipeline``) recognises these transforms, records their geometry with ``geometry`` and does
+the pixel work of a batch in ONE launch (``mp_resize_pad_normalize`` for rescale + pad, ``mp_warp_affine`` for resize), for which
+the host path is the oracle.
+
+``cv2.resize`` and ``cv2.warpAffine`` are restated from OpenCV's 8-bit fixed-point linear paths [cv2-knowledge]: cv2 is not a
+dependency and parity with cv2 itself is unpinned.  The training transforms (random affine, flip, target generation) are not
+implemented.
+"""
+import ctypes
+from typing import Any, Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from ... import _lib
+from ...register import register
+from ..column_names import COLUMN_MAP
+from .topdown_transform import get_affine_transform
+
+__all__ = ["BottomUpTransform", "BottomUpRescale", "BottomUpResize", "BottomUpPad", "resize_linear_u8", "warp_affine_linear_u8",
+           "launch_resize_pad_normalize"]
+
+
+def _resize_terms(dst: int, src: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """Source index and the two 11-bit coefficients of every destination coordinate of one axis: scale = src / dst in double,
+    f = (float)((d + 0.5) * scale - 0.5), s = floor(f), f -= s; s < 0 -> (0, 0); s >= src - 1 -> (src - 1, 0); the coefficients
+    are saturate_cast<short>((1 - f) * 2048) and saturate_cast<short>(f * 2048) (round half to even)."""
+    scale = src / dst
+    f = ((np.arange(dst, dtype=np.float64) + 0.5) * scale - 0.5).astype(np.float32)
+    s = np.floor(f).astype(np.int32)
+    f = f - s.astype(np.float32)
+    low, high = s < 0, s >= src - 1
+    s = np.where(low, 0, np.where(high, src - 1, s))
+    f = np.where(low | high, np.float32(0), f).astype(np.float32)
+    c0 = np.clip(np.rint((np.float32(1) - f) * np.float32(2048)), -32768, 32767).astype(np.int32)
+    c1 = np.clip(np.rint(f * np.float32(2048)), -32768, 32767).astype(np.int32)
+    return s, c0, c1
+
+
+def resize_linear_u8(image: np.ndarray, size: Tuple[int, int]) -> np.ndarray:
+    """``cv2.resize(image, (w, h), interpolation=cv2.INTER_LINEAR)`` of a uint8 [H, W, C] image: horizontal pass int32
+    S[sx] * a0 + S[sx + 1] * a1, vertical pass (((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2, saturated."""
+    image = np.asarray(image)
+    if image.dtype != np.uint8 or image.ndim != 3:
+        raise ValueError(f"image must be uint8 [H, W, C], got {image.dtype} {image.shape}")
+    tw, th = int(size[0]), int(size[1])
+    h, w = image.shape[:2]
+    sx, a0, a1 = _resize_terms(tw, w)
+    sy, b0, b1 = _resize_terms(th, h)
+    src = image.astype(np.int32)
+    rows = src[:, sx] * a0[None, :, None] + src[:, np.minimum(sx + 1, w - 1)] * a1[None, :, None]  # [H, tw, C]
+    r0, r1 = rows[sy], rows[np.minimum(sy + 1, h - 1)]
+    out = (((b0[:, None, None] * (r0 >> 4)) >> 16) + ((b1[:, None, None] * (r1 >> 4)) >> 16) + 2) >> 2
+    return np.clip(out, 0, 255).astype(np.uint8)
+
+
+def warp_affine_linear_u8(image: np.ndarray, trans: np.ndarray, size: Tuple[int, int]) -> np.ndarray:
+    """``cv2.warpAffine(image, trans, (w, h), flags=cv2.INTER_LINEAR)`` of a uint8 [H, W, C] image, border constant 0: the matrix
+    inverted in double, coordinates in 10-bit fixed point quantised to 1 / 32 pixel, exact 15-bit bilinear weights - the
+    arithmetic of ``mp_warp_affine`` (csrc/loader_ops.hip)."""
+    img = np.asarray(image)
+    h, w, _ = img.shape
+    out_w, out_h = int(size[0]), int(size[1])
+    m = np.array(trans, dtype=np.float64).reshape(2, 3)
+    det = m[0, 0] * m[1, 1] - m[0, 1] * m[1, 0]
+    det = 1.0 / det if det != 0 else 0.0
+    i00, i01, i10, i11 = m[1, 1] * det, m[0, 1] * -det, m[1, 0] * -det, m[0, 0] * det
+    i02, i12 = -i00 * m[0, 2] - i01 * m[1, 2], -i10 * m[0, 2] - i11 * m[1, 2]
+    xs, ys = np.arange(out_w, dtype=np.float64), np.arange(out_h, dtype=np.float64)
+    big_x = ((np.rint((i01 * ys + i02) * 1024.0).astype(np.int64) + 16)[:, None] + np.rint(i00 * xs * 1024.0).astype(np.int64)[None]) >> 5
+    big_y = ((np.rint((i11 * ys + i12) * 1024.0).astype(np.int64) + 16)[:, None] + np.rint(i10 * xs * 1024.0).astype(np.int64)[None]) >> 5
+    sx, sy = np.clip(big_x >> 5, -32768, 32767), np.clip(big_y >> 5, -32768, 32767)
+    fx, fy = big_x & 31, big_y & 31
+    acc = np.zeros((out_h, out_w, img.shape[2]), np.int64)
+    for dy, dx, weight in ((0, 0, (32 - fx) * (32 - fy) * 32), (0, 1, fx * (32 - fy) * 32), (1, 0, (32 - fx) * fy * 32),
+                           (1, 1, fx * fy * 32)):
+        yy, xx = sy + dy, sx + dx
+        inside = (yy >= 0) & (yy < h) & (xx >= 0) & (xx < w)
+        px = img[np.clip(yy, 0, h - 1), np.clip(xx, 0, w - 1)].astype(np.int64)
+        acc += np.where(inside[..., None], px, 0) * weight[..., None]
+    return np.minimum((acc + (1 << 14)) >> 15, 255).astype(np.uint8)
+
+
+def launch_resize_pad_normalize(images: Sequence[torch.Tensor], target_sizes: Sequence[Tuple[int, int]], padded_size: Tuple[int, int],
+                                mean, std) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One ``mp_resize_pad_normalize`` launch: image ``i`` (CUDA uint8 [H, W, 3], all views of one buffer or separate tensors)
+    resized to ``target_sizes[i]`` = (w, h), zero-padded to ``padded_size`` = (w, h), normalised with ``mean`` / ``std`` (of the
+    0..1 range) and written as planes.  Returns (image [N, 3, PH, PW] fp32, mask [N, PH, PW] uint8)."""
+    lib = _lib.load()
+    n = len(images)
+    if n == 0 or len(target_sizes) != n:
+        raise ValueError("one target size per image, at least one image")
+    dev = images[0].device
+    for im in images:
+        if not im.is_cuda or im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3 or not im.is_contiguous():
+            raise _lib.MindposeHipError("source images must be contiguous CUDA uint8 tensors [H, W, 3] (no CPU fallback)")
+    pw, ph = int(padded_size[0]), int(padded_size[1])
+    base = min(im.data_ptr() for im in images)
+    offs = torch.tensor([im.data_ptr() - base for im in images], dtype=torch.int64, device=dev)
+    hw = torch.tensor([[im.shape[0], im.shape[1]] for im in images], dtype=torch.int32, device=dev)
+    twh = (ctypes.c_int * (2 * n))(*[int(v) for size in target_sizes for v in size[:2]])
+    out = torch.empty(n, 3, ph, pw, device=dev, dtype=torch.float32)
+    mask = torch.empty(n, ph, pw, device=dev, dtype=torch.uint8)
+    m3 = (ctypes.c_float * 3)(*[float(np.float32(v * 255.0)) for v in mean])
+    s3 = (ctypes.c_float * 3)(*[float(np.float32(v * 255.0)) for v in std])
+    _lib.check(lib.mp_resize_pad_normalize(base, _lib.ptr(offs), _lib.ptr(hw), twh, _lib.ptr(out), _lib.ptr(mask), n, ph, pw, m3, s3,
+                                           _lib.stream()), "mp_resize_pad_normalize")
+    return out, mask
+
+
+class BottomUpTransform:
+    """Base of the bottom-up transforms (bottomup_transform.py:26-85): ``is_train``, ``config`` and the parsed ``_transform_cfg``.
+    A child implements ``transform(state) -> dict`` of the updated keys."""
+
+    def __init__(self, is_train: bool = True, config: Optional[Dict[str, Any]] = None) -> None:
+        self.is_train = is_train
+        self.config = config if config else dict()
+        self._transform_cfg = self.load_transform_cfg()
+        self._required_field = self.setup_required_field()
+
+    def setup_required_field(self) -> List[str]:
+        return COLUMN_MAP["bottomup"]["train" if self.is_train else "val"]
+
+    def load_transform_cfg(self) -> Dict[str, Any]:
+        """:54-85 - same keys (a missing one is a KeyError), same derived ``flip_index``."""
+        cfg = dict()
+        cfg["image_size"] = np.array(self.config["image_size"])
+        cfg["max_image_size"] = np.array(self.config["max_image_size"])
+        cfg["heatmap_sizes"] = np.array(self.config["heatmap_sizes"])
+        assert len(cfg["image_size"]) == 2
+        for x in cfg["heatmap_sizes"]:
+            assert len(x) == 2
+        flip_pairs = np.array(self.config["flip_pairs"])
+        if len(flip_pairs.shape) == 2:
+            flip_index = flip_pairs[:, ::-1].flatten()
+            flip_index = np.insert(flip_index, 0, 0)
+        else:
+            flip_index = flip_pairs
+        cfg["flip_pairs"] = flip_pairs
+        cfg["flip_index"] = flip_index
+        cfg["pixel_std"] = float(self.config["pixel_std"])
+        cfg["tag_per_joint"] = self.config["tag_per_joint"]
+        return cfg
+
+    def transform(self, state: Dict[str, Any]) -> Dict[str, Any]:
+        raise NotImplementedError("Child class must implement this method.")
+
+    def __call__(self, *args: Any) -> Tuple[np.ndarray, ...]:
+        states = dict(zip(self._required_field, args))
+        states.update(self.transform(states))
+        return tuple(np.asarray(states[k]) for k in self._required_field)
+
+
+@register("transform", extra_name="bottomup_rescale")
+class BottomUpRescale(BottomUpTransform):
+    """Rescale the image into ``max_image_size`` keeping its aspect ratio (:143-208)."""
+
+    def _get_new_size(self, image_size: Tuple[int, int], max_size: Tuple[int, int]) -> Tuple[int, int]:
+        w, h = image_size
+        max_w, max_h = max_size
+        if w < h:  # portrait: the limits swap
+            max_w, max_h = max_h, max_w
+        if w / h > max_w / max_h:
+            target_w = max_w
+            target_h = round(h * max_w / w)
+        else:
+            target_h = max_h
+            target_w = round(w * max_h / h)
+        return int(target_w), int(target_h)
+
+    def geometry(self, width: int, height: int) -> Dict[str, Any]:
+        """center, scale and image_shape = (target_w, target_h) of an image of this size: everything but the pixels."""
+        target_size = self._get_new_size([width, height], self._transform_cfg["max_image_size"])
+        pixel_std = self._transform_cfg["pixel_std"]
+        return dict(center=np.array([round(width / 2), round(height / 2)]), scale=np.array([width / pixel_std, height / pixel_std]),
+                    image_shape=target_size)
+
+    def transform(self, state: Dict[str, Any]) -> Dict[str, Any]:
+        """Required: image.  Returned: image, center, scale, image_shape."""
+        image = state["image"]
+        height, width = image.shape[:2]
+        out = self.geometry(width, height)
+        out["image"] = resize_linear_u8(image, out["image_shape"])
+        return out
+
+
+@register("transform", extra_name="bottomup_resize")
+class BottomUpResize(BottomUpTransform):
+    """Resize so that the short side becomes ``size`` and both sides multiples of ``base_length``, by an affine warp about the
+    image centre (:211-301)."""
+
+    def __init__(self, is_train: bool = True, config: Optional[Dict[str, Any]] = None, size: int = 512, base_length: int = 64) -> None:
+        super().__init__(is_train, config)
+        self.size = size
+        self.base_length = base_length
+
+    @staticmethod
+    def _ceil_to_base_length(x: int, base_length: int) -> int:
+        return int(np.ceil(x / base_length)) * base_length
+
+    def _get_new_size(self, image_size: Tuple[int, int], size: int, base_length: int = 64,
+                      pixel_std: float = 200.0) -> Tuple[Tuple[int, int], np.ndarray, np.ndarray]:
+        w, h = image_size
+        min_size = self._ceil_to_base_length(size, base_length)
+        if w < h:
+            target_w = min_size
+            target_h = self._ceil_to_base_length(min_size / w * h, base_length)
+            scale_w = w / pixel_std
+            scale_h = target_h / target_w * w / pixel_std
+        else:
+            target_h = min_size
+            target_w = self._ceil_to_base_length(min_size / h * w, base_length)
+            scale_h = h / pixel_std
+            scale_w = target_w / target_h * h / pixel_std
+        center = np.array([round(w / 2), round(h / 2)])
+        scale = np.array([scale_w, scale_h])
+        return (target_w, target_h), center, scale
+
+    def geometry(self, width: int, height: int) -> Dict[str, Any]:
+        """center, scale, image_shape and the 2 x 3 warp matrix ``_trans`` of an image of this size."""
+        target_size, center, scale = self._get_new_size([width, height], self.size, base_length=self.base_length,
+                                                        pixel_std=self._transform_cfg["pixel_std"])
+        return dict(center=center, scale=scale, image_shape=target_size, _trans=get_affine_transform(center, scale, 0, target_size))
+
+    def transform(self, state: Dict[str, Any]) -> Dict[str, Any]:
+        """Required: image.  Returned: image, mask, center, scale, image_shape."""
+        image = state["image"]
+        height, width = image.shape[:2]
+        out = self.geometry(width, height)
+        out["image"] = warp_affine_linear_u8(image, out.pop("_trans"), out["image_shape"])
+        out["mask"] = np.ones(out["image"].shape[:2], dtype=np.uint8)
+        return out
+
+
+@register("transform", extra_name="bottomup_pad")
+class BottomUpPad(BottomUpTransform):
+    """Zero-pad on the right and bottom to ``max_image_size`` (swapped for a portrait image) and make the mask (:601-645)."""
+
+    def padded_size(self, width: int, height: int) -> Tuple[int, int]:
+        target_width, target_height = (int(v) for v in self._transform_cfg["max_image_size"])
+        if width < height:
+            target_height, target_width = target_width, target_height
+        assert target_width >= width
+        assert target_height >= height
+        return target_width, target_height
+
+    def transform(self, state: Dict[str, Any]) -> Dict[str, Any]:
+        """Required: image.  Returned: image, mask."""
+        image = state["image"]
+        height, width = image.shape[:2]
+        target_width, target_height = self.padded_size(width, height)
+        image = np.pad(image, ((0, target_height - height), (0, target_width - width), (0, 0)))
+        mask = np.zeros((target_height, target_width), dtype=np.uint8)
+        mask[:height, :width] = 1
+        return dict(image=image, mask=mask)

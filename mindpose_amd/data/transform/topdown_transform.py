@@ -224,6 +224,35 @@ def get_warp_matrix(theta: float, size_input: np.ndarray, size_dst: np.ndarray, 
     return matrix
 
 
+def launch_warp_affine(images: Sequence[torch.Tensor], index: Sequence[int], mats: np.ndarray, out_hw: Tuple[int, int], normalize: bool,
+                       out: Optional[torch.Tensor], mean, std, flips=None) -> torch.Tensor:
+    """One ``mp_warp_affine`` launch: crop ``i`` is image ``index[i]`` through the 2 x 3 matrix ``mats[i]`` at ``out_hw`` = (h, w) -
+    [N, 3, h, w] fp32 normalised planes, or the warped uint8 [N, h, w, 3] pixels without ``normalize``."""
+    lib = _lib.load()
+    h, w = int(out_hw[0]), int(out_hw[1])
+    n = len(index)
+    dev = images[0].device
+    for im in images:
+        if not im.is_cuda or im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3 or not im.is_contiguous():
+            raise _lib.MindposeHipError("source images must be contiguous CUDA uint8 tensors [H, W, 3] (no CPU fallback)")
+    base = images[0].data_ptr()
+    offs = torch.tensor([images[i].data_ptr() - base for i in index], dtype=torch.int64, device=dev)
+    hw = torch.tensor([[images[i].shape[0], images[i].shape[1]] for i in index], dtype=torch.int32, device=dev)
+    tr = torch.from_numpy(np.ascontiguousarray(mats, dtype=np.float64).reshape(n, 6)).to(dev)
+    fl = None if flips is None else torch.tensor([int(bool(f)) for f in flips], dtype=torch.int32, device=dev)
+    if out is None:
+        out = (torch.empty(n, 3, h, w, device=dev, dtype=torch.float32) if normalize
+               else torch.empty(n, h, w, 3, device=dev, dtype=torch.uint8))
+    want = (n, 3, h, w) if normalize else (n, h, w, 3)
+    if tuple(out.shape) != want or not out.is_contiguous() or out.dtype != (torch.float32 if normalize else torch.uint8):
+        raise ValueError(f"out must be a contiguous {want} tensor")
+    m3 = (ctypes.c_float * 3)(*[float(np.float32(v * 255.0)) for v in mean])
+    s3 = (ctypes.c_float * 3)(*[float(np.float32(v * 255.0)) for v in std])
+    _lib.check(lib.mp_warp_affine(base, _lib.ptr(offs), _lib.ptr(hw), _lib.ptr(fl), _lib.ptr(tr), _lib.ptr(out), n, h, w, int(normalize),
+                                  m3, s3, _lib.stream()), "mp_warp_affine")
+    return out
+
+
 @register("transform", extra_name="topdown_affine")
 class TopDownAffine:
     """Affine crop of one instance (topdown_transform.py:157-262): matrix on the host, pixels on the GPU."""
@@ -247,29 +276,8 @@ class TopDownAffine:
 
     def _launch(self, images: Sequence[torch.Tensor], index: Sequence[int], mats: np.ndarray, normalize: bool,
                 out: Optional[torch.Tensor], mean, std, flips=None) -> torch.Tensor:
-        lib = _lib.load()
         w, h = (int(v) for v in self._transform_cfg["image_size"])
-        n = len(index)
-        dev = images[0].device
-        for im in images:
-            if not im.is_cuda or im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3 or not im.is_contiguous():
-                raise _lib.MindposeHipError("source images must be contiguous CUDA uint8 tensors [H, W, 3] (no CPU fallback)")
-        base = images[0].data_ptr()
-        offs = torch.tensor([images[i].data_ptr() - base for i in index], dtype=torch.int64, device=dev)
-        hw = torch.tensor([[images[i].shape[0], images[i].shape[1]] for i in index], dtype=torch.int32, device=dev)
-        tr = torch.from_numpy(np.ascontiguousarray(mats, dtype=np.float64).reshape(n, 6)).to(dev)
-        fl = None if flips is None else torch.tensor([int(bool(f)) for f in flips], dtype=torch.int32, device=dev)
-        if out is None:
-            out = (torch.empty(n, 3, h, w, device=dev, dtype=torch.float32) if normalize
-                   else torch.empty(n, h, w, 3, device=dev, dtype=torch.uint8))
-        want = (n, 3, h, w) if normalize else (n, h, w, 3)
-        if tuple(out.shape) != want or not out.is_contiguous() or out.dtype != (torch.float32 if normalize else torch.uint8):
-            raise ValueError(f"out must be a contiguous {want} tensor")
-        m3 = (ctypes.c_float * 3)(*[float(np.float32(v * 255.0)) for v in mean])
-        s3 = (ctypes.c_float * 3)(*[float(np.float32(v * 255.0)) for v in std])
-        _lib.check(lib.mp_warp_affine(base, _lib.ptr(offs), _lib.ptr(hw), _lib.ptr(fl), _lib.ptr(tr), _lib.ptr(out), n, h, w, int(normalize),
-                                      m3, s3, _lib.stream()), "mp_warp_affine")
-        return out
+        return launch_warp_affine(images, index, mats, (h, w), normalize, out, mean, std, flips)
 
     def crop_batch(self, images: Union[torch.Tensor, Sequence[torch.Tensor]], centers: np.ndarray, scales: np.ndarray,
                    rotations: Optional[np.ndarray] = None, image_index: Optional[Sequence[int]] = None,

@@ -1,7 +1,10 @@
 """Bottom-up (associative-embedding) inference engine (reference: mindpose/engine/inferencer/bottomup_inferencer.py:18-250).
 
-The network and the decoder run on the HIP path (``EvalNet(net, BottomUpHeatMapAEDecoder)``); the grouping
-(``match_by_tag``), the optional missing-joint refinement and the back-projection are host numpy, as in the reference.
+The network and the decoder run on the HIP path (``EvalNet(net, BottomUpHeatMapAEDecoder)``); the grouping (``match_by_tag``)
+and the back-projection are host numpy, as in the reference.  The optional missing-joint refinement runs on the device
+(``mp_bottomup_refine_missing``, one launch per batch): the full-resolution maps never travel to the host - only the located tags
+of the grouped persons ([J_total, L]) come down and their mean tags ([P, L]) go up.  Maps that already live on the CPU take the
+host function ``refine_missing_joint``.
 """
 from functools import partial
 from typing import Any, Dict, Iterable, List, Optional, Tuple
@@ -9,6 +12,7 @@ from typing import Any, Dict, Iterable, List, Optional, Tuple
 import numpy as np
 import torch
 
+from ... import _lib
 from ...data.transform.utils import transform_keypoints
 from ...models import EvalNet
 from ...models.decoders import BottomUpHeatMapAEDecoder
@@ -73,12 +77,55 @@ class BottomUpHeatMapAEInferencer:
         keypoints = self._match(val_k, tag_k, ind_k)
         scores = [[person[:, 2].mean() for person in people] for people in keypoints]
         if self._inference_cfg["refine_missing_joint"]:
-            heatmap = heatmap.cpu().numpy()
-            tagging_heatmap = tagging_heatmap.cpu().numpy()
-            for i in range(len(keypoints)):
-                for j in range(len(keypoints[i])):
-                    keypoints[i][j] = refine_missing_joint(heatmap[i], tagging_heatmap[i], keypoints[i][j])
+            if heatmap.is_cuda:
+                self._refine_on_device(keypoints, heatmap, tagging_heatmap)
+            else:
+                heatmap = heatmap.numpy()
+                tagging_heatmap = tagging_heatmap.numpy()
+                if tagging_heatmap.shape[1] != heatmap.shape[1]:  # one tag map for all joints (tag_per_joint=False)
+                    tagging_heatmap = np.broadcast_to(tagging_heatmap, heatmap.shape[:2] + tagging_heatmap.shape[2:])
+                for i in range(len(keypoints)):
+                    for j in range(len(keypoints[i])):
+                        keypoints[i][j] = refine_missing_joint(heatmap[i], tagging_heatmap[i], keypoints[i][j])
         return keypoints, scores
+
+    @staticmethod
+    def _refine_on_device(keypoints: List[np.ndarray], heatmap: torch.Tensor, tagging_heatmap: torch.Tensor) -> None:
+        """``refine_missing_joint`` for every person of the batch, in place: one indexed read of the located tags, the mean tag per
+        person with the reference's own ``np.mean`` on the host, one ``mp_bottomup_refine_missing`` launch, the reference's rule
+        ``found[j, 2] > 0 and keypoints[j, 2] == 0`` on the downloaded ``found`` [P, K, 3]."""
+        n, k, h, w = heatmap.shape
+        ktag, num_tags = tagging_heatmap.shape[1], tagging_heatmap.shape[4]
+        persons, index, counts = [], [], []
+        for i in range(len(keypoints)):
+            for person in keypoints[i]:
+                located = person[:, :2].astype(np.int32)
+                joints = np.flatnonzero(person[:, 2] > 0)
+                if joints.size == 0:  # (grouping builds a person from at least one detection)
+                    continue
+                persons.append((i, person))
+                counts.append(joints.size)
+                index.append(np.stack([np.full(joints.size, i), joints if ktag > 1 else np.zeros_like(joints),
+                                       np.clip(located[joints, 1], 0, h - 1), np.clip(located[joints, 0], 0, w - 1)]))
+        if not persons:
+            return
+        dev = heatmap.device
+        heatmap = _lib.require_cuda_f32(heatmap, "heatmap")
+        tagging_heatmap = _lib.require_cuda_f32(tagging_heatmap, "tagging_heatmap")
+        img, ch, ys, xs = torch.from_numpy(np.concatenate(index, axis=1).astype(np.int64)).to(dev)
+        tags = tagging_heatmap[img, ch, ys, xs].cpu().numpy()  # [J_total, L]
+        starts = np.concatenate([[0], np.cumsum(counts)])
+        mean_tag = np.stack([np.mean(tags[starts[p]:starts[p + 1]], axis=0) for p in range(len(persons))]).astype(np.float32)
+        mean_dev = torch.from_numpy(np.ascontiguousarray(mean_tag)).to(dev)
+        image_dev = torch.tensor([i for i, _ in persons], dtype=torch.int32, device=dev)
+        found = torch.empty(len(persons), k, 3, device=dev, dtype=torch.float32)
+        _lib.check(_lib.load().mp_bottomup_refine_missing(_lib.ptr(heatmap), _lib.ptr(tagging_heatmap), _lib.ptr(mean_dev),
+                                                          _lib.ptr(image_dev), len(persons), n, k, h, w, int(ktag > 1 or k == 1),
+                                                          num_tags, _lib.ptr(found), _lib.stream()), "mp_bottomup_refine_missing")
+        found = found.cpu().numpy()
+        for (_, person), rows in zip(persons, found):
+            fill = (rows[:, 2] > 0) & (person[:, 2] == 0)
+            person[fill, :3] = rows[fill]
 
     def _match(self, val_k, tag_k, ind_k) -> List[np.ndarray]:
         cfg = self._inference_cfg

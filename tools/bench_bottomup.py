@@ -7,19 +7,32 @@
 - decoder: BottomUpHeatMapAEDecoder (two launches) at the eval map size 256 x 416 (N = 1) and 256 x 256 (N = 32), microseconds per
   image and the fraction of 8 TB/s reached on its algorithmic bytes (reads: 17 full-resolution heat maps + 34 half-resolution
   channels; writes: heatmap_raw + tagging);
-- match_by_tag: host milliseconds per image on the decoder's output of random maps.
+- match_by_tag: host milliseconds per image on the decoder's output of random maps;
+- resize_pad_normalize: ``mp_resize_pad_normalize`` of one 640 x 480 source to 832 x 512 (the evaluation input), device microseconds and
+  the fraction of 8 TB/s on its algorithmic bytes (read: the uint8 source; written: three fp32 planes + the mask);
+- refine: the missing-joint refinement of P = 1, 10, 30 persons at the 256 x 416 map - the device path (tag gather, mean tags, one
+  ``mp_bottomup_refine_missing`` launch, the download of ``found``) against the host path (``refine_missing_joint`` per person after
+  the two ``.cpu()`` copies of the maps), wall milliseconds per batch, and the kernel alone in device microseconds.
 Forward sizes are the recipe's eval images: 512 x 512 (N = 1 and 32) and 512 x 832 (N = 1).
+
+``--only NAME`` runs one section in this process; without it every section runs in a child process of its own under a time limit
+(``--section-timeout`` seconds), and a section that fails or overruns ends the run.
 """
 import argparse
 import json
 import os
+import subprocess
 import sys
 import time
 
+import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import mindpose_amd as mp  # noqa: E402
+from mindpose_amd import _lib  # noqa: E402
+from mindpose_amd.data.transform.bottomup_transform import launch_resize_pad_normalize  # noqa: E402
+from mindpose_amd.engine.inferencer.bottomup_inferencer import BottomUpHeatMapAEInferencer, refine_missing_joint  # noqa: E402
 from mindpose_amd.utils.match import match_by_tag  # noqa: E402
 
 DEV = torch.device("cuda:0")
@@ -68,13 +81,88 @@ def decoder(n, h, w, steps):
                 mb_per_image=round(nbytes / n / 1e6, 2), match_ms_per_image=round(match_ms, 3))
 
 
+def resize_pad_normalize(steps):
+    src_w, src_h, tw, th, pw, ph = 640, 480, 683, 512, 832, 512
+    image = torch.randint(0, 256, (src_h, src_w, 3), dtype=torch.uint8, generator=torch.Generator().manual_seed(0)).to(DEV)
+    mean, std = (0.485, 0.456, 0.406), (0.229, 0.224, 0.255)
+    ms = _time(lambda: launch_resize_pad_normalize([image], [(tw, th)], (pw, ph), mean, std), steps)  # (with the wrapper's two small uploads)
+    # the kernel alone: the C entry on prepared arguments
+    import ctypes
+    lib = _lib.load()
+    offs, hw = torch.zeros(1, dtype=torch.int64, device=DEV), torch.tensor([[src_h, src_w]], dtype=torch.int32, device=DEV)
+    out, mask = torch.empty(1, 3, ph, pw, device=DEV), torch.empty(1, ph, pw, dtype=torch.uint8, device=DEV)
+    twh = (ctypes.c_int * 2)(tw, th)
+    m3 = (ctypes.c_float * 3)(*[v * 255.0 for v in mean])
+    s3 = (ctypes.c_float * 3)(*[v * 255.0 for v in std])
+    kernel_ms = _time(lambda: lib.mp_resize_pad_normalize(_lib.ptr(image), _lib.ptr(offs), _lib.ptr(hw), twh, _lib.ptr(out), _lib.ptr(mask), 1,
+                                                          ph, pw, m3, s3, _lib.stream()), steps)
+    nbytes = src_h * src_w * 3 + ph * pw * (3 * 4 + 1)
+    return dict(src=[src_w, src_h], target=[tw, th], padded=[pw, ph], kernel_us=round(kernel_ms * 1000, 2), call_us=round(ms * 1000, 2),
+                mb=round(nbytes / 1e6, 2), hbm_fraction=round(nbytes / (kernel_ms * 1e-3) / HBM, 4))
+
+
+def refine(persons, steps, h=256, w=416, k=17, num_tags=1):
+    g = torch.Generator().manual_seed(persons)
+    heat = torch.rand(1, k, h, w, generator=g).to(DEV)
+    tagging = torch.rand(1, k, h, w, num_tags, generator=g).to(DEV)
+    people = np.zeros((persons, k, 3 + num_tags), np.float32)  # every person: ten located joints, seven to refine
+    rng = np.random.RandomState(persons)
+    for p in range(persons):
+        joints = rng.permutation(k)[:10]
+        people[p, joints, 0], people[p, joints, 1], people[p, joints, 2] = rng.randint(0, w, 10), rng.randint(0, h, 10), 0.5
+
+    def device():
+        BottomUpHeatMapAEInferencer._refine_on_device([people.copy()], heat, tagging)
+
+    def host():  # what the inferencer ran before: both maps to the host, then numpy per person
+        hm, tg = heat.cpu().numpy(), tagging.cpu().numpy()
+        for person in people.copy():
+            refine_missing_joint(hm[0], tg[0], person)
+
+    def wall(fn, reps):
+        fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1000 / reps
+
+    lib = _lib.load()
+    mean = torch.rand(persons, num_tags, generator=g).to(DEV)
+    img = torch.zeros(persons, dtype=torch.int32, device=DEV)
+    found = torch.empty(persons, k, 3, device=DEV)
+    kernel_ms = _time(lambda: lib.mp_bottomup_refine_missing(_lib.ptr(heat), _lib.ptr(tagging), _lib.ptr(mean), _lib.ptr(img), persons, 1, k, h,
+                                                             w, 1, num_tags, _lib.ptr(found), _lib.stream()), steps)
+    nbytes = persons * k * h * w * 4 * (1 + num_tags)
+    return dict(persons=persons, h=h, w=w, device_ms=round(wall(device, steps), 3), host_ms=round(wall(host, max(2, steps // 5)), 3),
+                kernel_us=round(kernel_ms * 1000, 2), hbm_fraction=round(nbytes / (kernel_ms * 1e-3) / HBM, 4))
+
+
+SECTIONS = {
+    "forward": lambda steps: [forward(a, n, h, w, steps) for a in ("O0", "O2") for n, h, w in ((1, 512, 512), (32, 512, 512), (1, 512, 832))],
+    "decoder": lambda steps: [decoder(1, 256, 416, steps), decoder(32, 256, 256, steps)],
+    "resize_pad_normalize": resize_pad_normalize,
+    "refine": lambda steps: [refine(p, steps) for p in (1, 10, 30)],
+}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--only", choices=sorted(SECTIONS), help="run this section in this process and print its JSON")
+    ap.add_argument("--sections", default=",".join(SECTIONS), help="comma-separated sections to run (each in a child process)")
+    ap.add_argument("--section-timeout", type=int, default=600, help="seconds per section")
     args = ap.parse_args()
-    res = dict(workload="higher_hrnet_w32_bottomup",
-               forward=[forward(a, n, h, w, args.steps) for a in ("O0", "O2") for n, h, w in ((1, 512, 512), (32, 512, 512), (1, 512, 832))],
-               decoder=[decoder(1, 256, 416, args.steps), decoder(32, 256, 256, args.steps)])
+    if args.only:
+        print(json.dumps(SECTIONS[args.only](args.steps)))
+        return
+    res = dict(workload="higher_hrnet_w32_bottomup")
+    for name in args.sections.split(","):
+        # a fresh child per section, each under its own time limit; a section that fails or overruns ends the run
+        out = subprocess.run([sys.executable, os.path.abspath(__file__), "--only", name, "--steps", str(args.steps)], stdout=subprocess.PIPE,
+                             timeout=args.section_timeout, check=True)
+        res[name] = json.loads(out.stdout.decode().strip().splitlines()[-1])
     print(json.dumps(res))
 
 
