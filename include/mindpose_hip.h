@@ -567,6 +567,48 @@ int mp_bottomup_refine_missing(const float* heatmap_raw_dev, const float* taggin
                                const int* person_image_dev, int num_persons, int n, int k, int h, int w, int tag_per_joint,
                                int num_tags, float* found_dev, mp_stream_t stream);
 
+/* ---- bottom-up training ends: masked heat-map MSE, associative-embedding loss, target generation (bottomup_train_ops.hip) -------
+ * Every entry validates before any HIP call (NULL -> MP_ERR_NULL, bad extents / strides -> MP_ERR_SHAPE), fully writes its
+ * outputs and is deterministic: no atomics, fixed-order reductions.
+ *
+ * mp_joints_mse_mask_fwd / _bwd (mindpose/models/loss/mse.py:47-72, JointsMSELossWithMask):
+ *   loss = sum((pred - target)^2 * mask[n,h,w]) / (n k h w)  - masked pixels count in the divisor;
+ *   grad_pred = 2 (pred - target) mask grad_out[0] / (n k h w)  (grad_out NULL = 1).
+ *   pred, target and grad_pred are [n,k,h,w] VIEWS given by element strides of batch / channel / row (*_sn, *_sc, *_sr; the column
+ *   stride is 1), mask is an [n,h,w] view (fp32, or one byte per pixel with mask_is_u8) with batch / row strides: a corner of a
+ *   padded target and the heat-map channels of a stage tensor are read and written in place.  16-byte accesses when w, the
+ *   strides and the base addresses allow.  workspace >= mp_joints_mse_mask_workspace_bytes(n, k), else MP_ERR_WORKSPACE.
+ *
+ * mp_ae_loss_fwd / _bwd (mindpose/models/loss/ae.py:40-89, AELoss with reduction "mean"; eps = 0.01):
+ *   tags [n,k,hw] fp32 with a batch stride (the tag channels of a stage tensor; k = 1 without tag_per_joint), tag_ind [n,m,k,2]
+ *   int32 = (flat pixel index, flag) contiguous; loss2 = (push, pull), each the mean over n.  The backward takes grad_out2 = the
+ *   two upstream gradients and writes grad_tags [n,k,hw] (batch stride): zero but for the indexed pixels, persons that share a
+ *   pixel summed in ascending m.  An index outside [0, hw) counts as flag 0.  m <= 256, else MP_ERR_UNSUPPORTED.
+ *   workspace >= mp_ae_loss_workspace_bytes(n).
+ *
+ * mp_bottomup_target (mindpose/data/transform/bottomup_transform.py:527-598, BottomUpGenerateTarget for a batch):
+ *   keypoints [n,s,m,k,3] fp32 already scaled per stage, counts [n] int32 persons per image (rows beyond are ignored),
+ *   stage_wh_host [s][2] = (W, H) on the host; target [n,s,k,hmax,wmax] fp32 = max over persons of the Gaussian, 0 in the padding
+ *   of smaller stages; tag_ind [n,s,max_num,k,2] int32 (tag_per_joint) or [n,s,max_num,2].  s <= 8, m and max_num <= 256 and a
+ *   whole 3 sigma, else MP_ERR_UNSUPPORTED. */
+size_t mp_joints_mse_mask_workspace_bytes(int n, int k);
+int mp_joints_mse_mask_fwd(const float* pred_dev, long long pred_sn, long long pred_sc, long long pred_sr, const float* target_dev,
+                           long long target_sn, long long target_sc, long long target_sr, const void* mask_dev, int mask_is_u8,
+                           long long mask_sn, long long mask_sr, float* loss_dev, void* workspace_dev, size_t workspace_bytes, int n,
+                           int k, int h, int w, mp_stream_t stream);
+int mp_joints_mse_mask_bwd(const float* pred_dev, long long pred_sn, long long pred_sc, long long pred_sr, const float* target_dev,
+                           long long target_sn, long long target_sc, long long target_sr, const void* mask_dev, int mask_is_u8,
+                           long long mask_sn, long long mask_sr, const float* grad_out_dev, float* grad_pred_dev, long long grad_sn,
+                           long long grad_sc, long long grad_sr, int n, int k, int h, int w, mp_stream_t stream);
+size_t mp_ae_loss_workspace_bytes(int n);
+int mp_ae_loss_fwd(const float* tags_dev, long long tag_batch_stride, const int32_t* tag_ind_dev, float* loss2_dev,
+                   void* workspace_dev, size_t workspace_bytes, int n, int m, int k, int hw, mp_stream_t stream);
+int mp_ae_loss_bwd(const float* tags_dev, long long tag_batch_stride, const int32_t* tag_ind_dev, const float* grad_out2_dev,
+                   float* grad_tags_dev, long long grad_batch_stride, int n, int m, int k, int hw, mp_stream_t stream);
+int mp_bottomup_target(const float* keypoints_dev, const int* counts_dev, const int* stage_wh_host, float* target_dev,
+                       int32_t* tag_ind_dev, int n, int s, int m, int k, int hmax, int wmax, int max_num, int tag_per_joint,
+                       double sigma, mp_stream_t stream);
+
 /* fp16 (amp O2) training passes over channel-blocked fp16 activations; same contracts as mp_bn_train_fwd / _bwd and
  * mp_fuse_upsample_sum_bwd (statistics, gamma / beta gradients and the workspace stay fp32 / fp64; mp_bn_workspace_bytes) */
 int mp_f16_bn_train_fwd(const void* z_dev, const float* gamma_dev, const float* beta_dev, const void* res_dev, void* y_dev,

@@ -27,6 +27,7 @@ def env_on(name: str, default: bool = True) -> bool:
 c_f32p = ctypes.c_void_p  # device pointers travel as integers
 c_int = ctypes.c_int
 c_size_t = ctypes.c_size_t
+c_i64 = ctypes.c_longlong  # element strides of a view
 
 
 class ConvDesc(ctypes.Structure):
@@ -197,6 +198,17 @@ _PROTOTYPES = {
     "mp_bottomup_refine_missing": (c_int, [c_f32p] * 4 + [c_int] * 7 + [c_f32p, ctypes.c_void_p]),
     "mp_resize_pad_normalize": (c_int, [c_f32p] * 3 + [ctypes.POINTER(ctypes.c_int)] + [c_f32p] * 2 + [c_int] * 3
                                 + [ctypes.POINTER(ctypes.c_float)] * 2 + [ctypes.c_void_p]),
+    # bottom-up training ends (bottomup_train_ops.hip): strided masked MSE, AE loss, batched target generation
+    "mp_joints_mse_mask_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "mp_joints_mse_mask_fwd": (c_int, [c_f32p] + [c_i64] * 3 + [c_f32p] + [c_i64] * 3 + [c_f32p, c_int] + [c_i64] * 2
+                               + [c_f32p, c_f32p, c_size_t] + [c_int] * 4 + [ctypes.c_void_p]),
+    "mp_joints_mse_mask_bwd": (c_int, [c_f32p] + [c_i64] * 3 + [c_f32p] + [c_i64] * 3 + [c_f32p, c_int] + [c_i64] * 2
+                               + [c_f32p, c_f32p] + [c_i64] * 3 + [c_int] * 4 + [ctypes.c_void_p]),
+    "mp_ae_loss_workspace_bytes": (c_size_t, [c_int]),
+    "mp_ae_loss_fwd": (c_int, [c_f32p, c_i64, c_f32p, c_f32p, c_f32p, c_size_t] + [c_int] * 4 + [ctypes.c_void_p]),
+    "mp_ae_loss_bwd": (c_int, [c_f32p, c_i64, c_f32p, c_f32p, c_f32p, c_i64] + [c_int] * 4 + [ctypes.c_void_p]),
+    "mp_bottomup_target": (c_int, [c_f32p, c_f32p, ctypes.POINTER(ctypes.c_int), c_f32p, c_f32p] + [c_int] * 8
+                           + [ctypes.c_double, ctypes.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOTYPES)

@@ -1,8 +1,8 @@
-from .bottomup_transform import BottomUpPad, BottomUpRescale, BottomUpResize, BottomUpTransform  # noqa: F401
+from .bottomup_transform import BottomUpGenerateTarget, BottomUpPad, BottomUpRescale, BottomUpResize, BottomUpTransform  # noqa: F401
 from .topdown_transform import (TopDownAffine, TopDownBoxToCenterScale, TopDownGenerateTarget,  # noqa: F401
                                 TopDownHalfBodyTransform, TopDownHorizontalRandomFlip, TopDownRandomScaleRotation,
                                 fliplr_joints, get_affine_transform, get_warp_matrix)
 
 __all__ = ["TopDownGenerateTarget", "TopDownBoxToCenterScale", "TopDownAffine", "TopDownHorizontalRandomFlip",
            "TopDownHalfBodyTransform", "TopDownRandomScaleRotation", "fliplr_joints", "get_affine_transform", "get_warp_matrix",
-           "BottomUpTransform", "BottomUpRescale", "BottomUpResize", "BottomUpPad"]
+           "BottomUpTransform", "BottomUpRescale", "BottomUpResize", "BottomUpPad", "BottomUpGenerateTarget"]

@@ -8,8 +8,11 @@ the pixel work of a batch in ONE launch (``mp_resize_pad_normalize`` for rescale
 the host path is the oracle.
 
 ``cv2.resize`` and ``cv2.warpAffine`` are restated from OpenCV's 8-bit fixed-point linear paths [cv2-knowledge]: cv2 is not a
-dependency and parity with cv2 itself is unpinned.  The training transforms (random affine, flip, target generation) are not
-implemented.
+dependency and parity with cv2 itself is unpinned.
+
+``BottomUpGenerateTarget`` (:463-598) writes the ``target`` / ``tag_ind`` arrays of the training losses: ``transform`` is the
+reference's numpy arithmetic for one image, ``generate_batch`` one ``mp_bottomup_target`` launch for a batch on the device.  The
+train-time augmentations (random affine, flip) are not implemented, and no pipeline runs in train mode.
 """
 import ctypes
 from typing import Any, Dict, List, Optional, Sequence, Tuple
@@ -21,9 +24,10 @@ from ... import _lib
 from ...register import register
 from ..column_names import COLUMN_MAP
 from .topdown_transform import get_affine_transform
+from .utils import pad_to_same
 
-__all__ = ["BottomUpTransform", "BottomUpRescale", "BottomUpResize", "BottomUpPad", "resize_linear_u8", "warp_affine_linear_u8",
-           "launch_resize_pad_normalize"]
+__all__ = ["BottomUpTransform", "BottomUpRescale", "BottomUpResize", "BottomUpPad", "BottomUpGenerateTarget", "resize_linear_u8",
+           "warp_affine_linear_u8", "launch_resize_pad_normalize"]
 
 
 def _resize_terms(dst: int, src: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -258,3 +262,100 @@ class BottomUpPad(BottomUpTransform):
         mask = np.zeros((target_height, target_width), dtype=np.uint8)
         mask[:height, :width] = 1
         return dict(image=image, mask=mask)
+
+
+@register("transform", extra_name="bottomup_generate_target")
+class BottomUpGenerateTarget(BottomUpTransform):
+    """Heat maps and tag positions of every resolution level from the key points (:463-598).
+
+    ``transform`` needs ``keypoints`` - one [M, K, 3] array per level, already in that level's pixels - and returns ``target``
+    [S, K, Hmax, Wmax] fp32 (smaller levels zero-padded) and ``tag_ind`` [S, max_num, K, 2] int32 ([S, max_num, 2] without
+    ``tag_per_joint``), each entry (flat index of the rounded centre, 1) or (0, 0).
+    """
+
+    def __init__(self, is_train: bool = True, config: Optional[Dict[str, Any]] = None, sigma: float = 2.0, max_num: int = 30) -> None:
+        super().__init__(is_train=is_train, config=config)
+        self.sigma = sigma
+        self.max_num = max_num
+
+    def transform(self, state: Dict[str, Any]) -> Dict[str, Any]:
+        targets, tag_inds = [], []
+        for keypoints, heatmap_size in zip(state["keypoints"], self._transform_cfg["heatmap_sizes"]):
+            target, tag_ind = self._generate_heatmap_and_tag_ind(np.asarray(keypoints), heatmap_size)
+            targets.append(target)
+            tag_inds.append(tag_ind)
+        return dict(target=np.stack(pad_to_same(targets)), tag_ind=np.stack(tag_inds))
+
+    def _generate_heatmap_and_tag_ind(self, keypoints: np.ndarray, heatmap_size: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+        """One level (:527-598).  The heat map of a joint is the maximum over the persons of a (6 sigma + 1)^2 Gaussian patch
+        around the joint's rounded position (Python ``round``: half to even) with the sub-pixel offset kept; a patch is skipped
+        when its window misses the map; the tag index is written only when the rounded centre is inside.  The arithmetic of the
+        exponent stays in the key points' float32, operation by operation, as numpy leaves a float32 scalar against Python
+        numbers."""
+        width, height = (int(v) for v in heatmap_size)
+        num_persons, num_joints, _ = keypoints.shape
+        if num_persons > self.max_num:
+            raise ValueError(f"Number of persons in one image `{num_persons}` exceeds the maximum num: `{self.max_num}`")
+        tag_per_joint = self._transform_cfg["tag_per_joint"]
+        target = np.zeros((num_joints, height, width), dtype=np.float32)
+        tag_ind = np.zeros((self.max_num, num_joints, 2) if tag_per_joint else (self.max_num, 2), dtype=np.int32)
+
+        radius = self.sigma * 3  # 3-sigma rule
+        side = 2 * radius + 1
+        gx = np.arange(0, side, 1, np.float32)
+        gy = gx[:, None]
+        centre = side // 2
+        for m in range(num_persons):
+            for j in range(num_joints):
+                pt = keypoints[m, j]
+                if not pt[2] > 0:
+                    continue
+                mu_x, mu_y = round(pt[0]), round(pt[1])
+                left, top = int(mu_x - radius), int(mu_y - radius)
+                right, bottom = int(mu_x + radius + 1), int(mu_y + radius + 1)
+                if left >= width or top >= height or right < 0 or bottom < 0:
+                    continue
+                cx = centre + pt[0] - mu_x
+                cy = centre + pt[1] - mu_y
+                patch = np.exp(-((gx - cx) ** 2 + (gy - cy) ** 2) / (2 * self.sigma**2))
+                x0, x1 = max(0, left), min(right, width)
+                y0, y1 = max(0, top), min(bottom, height)
+                target[j, y0:y1, x0:x1] = np.maximum(target[j, y0:y1, x0:x1], patch[y0 - top:y1 - top, x0 - left:x1 - left])
+                if mu_x >= width or mu_y >= height or mu_x < 0 or mu_y < 0:
+                    continue
+                if tag_per_joint:
+                    tag_ind[m, j] = (mu_y * width + mu_x, 1)
+                else:
+                    tag_ind[m] = (mu_y * width + mu_x, 1)
+        return target, tag_ind
+
+    def generate_batch(self, keypoints: torch.Tensor, num_persons: Sequence[int]) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The device path: one ``mp_bottomup_target`` launch for a batch.  ``keypoints`` is CUDA fp32 [N, S, M, K, 3] (level
+        ``s`` of image ``n`` in that level's pixels, rows beyond ``num_persons[n]`` ignored); returns ``target``
+        [N, S, K, Hmax, Wmax] fp32 and ``tag_ind`` [N, S, max_num, K, 2] int32 ([N, S, max_num, 2] without ``tag_per_joint``)."""
+        lib = _lib.load()
+        if not torch.is_tensor(keypoints) or not keypoints.is_cuda:
+            raise _lib.MindposeHipError("keypoints must be a CUDA tensor: the HIP path has no CPU fallback")
+        sizes = np.asarray(self._transform_cfg["heatmap_sizes"]).reshape(-1, 2)
+        if keypoints.dim() != 5 or keypoints.shape[1] != len(sizes) or keypoints.shape[4] != 3:
+            raise ValueError(f"keypoints must be [N, S = {len(sizes)}, M, K, 3], got {tuple(keypoints.shape)}")
+        n, s, m, k, _ = keypoints.shape
+        counts = np.asarray(num_persons.cpu() if torch.is_tensor(num_persons) else num_persons).astype(np.int64).reshape(-1)
+        if counts.shape[0] != n or (counts < 0).any() or (counts > m).any():
+            raise ValueError(f"num_persons must hold one count in [0, M = {m}] per image, got {counts.tolist()}")
+        if (counts > self.max_num).any():
+            raise ValueError(f"Number of persons in one image `{int(counts.max())}` exceeds the maximum num: `{self.max_num}`")
+        if float(self.sigma * 3).is_integer() is False:
+            raise ValueError("the device path needs a whole 3 * sigma (the reference's patch and window only agree there)")
+        keypoints = keypoints.float().contiguous()
+        tag_per_joint = bool(self._transform_cfg["tag_per_joint"])
+        wmax, hmax = int(sizes[:, 0].max()), int(sizes[:, 1].max())
+        counts_dev = torch.tensor(counts, dtype=torch.int32, device=keypoints.device)
+        target = torch.empty(n, s, k, hmax, wmax, device=keypoints.device, dtype=torch.float32)
+        tag_shape = (n, s, self.max_num, k, 2) if tag_per_joint else (n, s, self.max_num, 2)
+        tag_ind = torch.empty(tag_shape, device=keypoints.device, dtype=torch.int32)
+        wh = (ctypes.c_int * (2 * s))(*[int(v) for v in sizes.reshape(-1)])
+        _lib.check(lib.mp_bottomup_target(_lib.ptr(keypoints), _lib.ptr(counts_dev), wh, _lib.ptr(target), _lib.ptr(tag_ind), n, s, m, k,
+                                          hmax, wmax, int(self.max_num), int(tag_per_joint), float(self.sigma), _lib.stream()),
+                   "mp_bottomup_target")
+        return target, tag_ind
