@@ -148,7 +148,10 @@ typedef struct mp_conv_desc {
  * alignment is in the packing, mp_f16_pack_weight mode 3); phase (py, px) writes output pixels (2 y + py, 2 x + px) and reads its
  * weights from slice 2 py + px of the packed buffer (four slices of mp_f16_packed_weight_bytes(cout, cin, 2, 2) bytes each).
  * One-tile and persistent multi-tile variants only; no residual; statistics: the backward sums (mp_f16_conv2d_fwd_stats mode 2,
- * partial slots = four times a phase's). */
+ * partial slots = four times a phase's).  The same sums from four launches: mp_f16_conv2d_fwd_stats mode 2 also accepts ONE phase
+ * on its own (no flag; 2x2 taps, out_mul 2, the phase in out_off_y / out_off_x, one-tile / multi-tile variants): partials_dev is
+ * then the buffer of the merged launch of the same variant (4 x mp_f16_conv_stats_parts of the one-phase desc) and the launch
+ * fills slots [phase x parts, (phase + 1) x parts) of every channel block. */
 #define MP_CONV_PHASES4 2
 
 /* bytes of the packed weight buffer for a (cout, cin, kh, kw) kernel */

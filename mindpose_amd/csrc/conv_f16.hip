@@ -1008,18 +1008,27 @@ static int f16_prepare_stats(const mp_conv_desc* desc, int variant, const void* 
     if (!st || !st->partials_dev) return MP_ERR_NULL;
     int rc = f16_build_launch(desc, variant, x, packed_w, scale, shift, res1, nullptr, out, L);
     if (rc != MP_OK) return rc;
-    if (!f16_stats_shape_ok(desc)) return MP_ERR_UNSUPPORTED;
-    if (st->mode != 1 && st->mode != 2) return MP_ERR_UNSUPPORTED;
     const bool phases4 = (desc->flags & MP_CONV_PHASES4) != 0;
+    // ONE phase (py, px) = (out_off_y, out_off_x) of a stride-2 data gradient launched on its own (backward sums only): it fills its
+    // quarter of the partials the merged MP_CONV_PHASES4 launch of the same variant would leave - slot  phase * (slots per phase) +
+    // tile - so four such launches and the merged one hand the BatchNorm the same sums in the same order
+    const bool one_phase = !phases4 && desc->kh == 2 && desc->stride == 1 && desc->out_mul == 2 && desc->out_rep == 1 &&
+                           desc->out_off_y <= 1 && desc->out_off_x <= 1 && st->mode == 2;
+    if (!f16_stats_shape_ok(desc) && !one_phase) return MP_ERR_UNSUPPORTED;
+    if (st->mode != 1 && st->mode != 2) return MP_ERR_UNSUPPORTED;
     if (phases4 && st->mode != 2) return MP_ERR_UNSUPPORTED;
-    const int parts = f16_stats_parts(L);
+    if (one_phase && (f16_variant_wreg(L.variant) || f16_variant_ws(L.variant))) return MP_ERR_UNSUPPORTED;  // as the merged launch
+    const int per_phase = f16_stats_parts(L);
+    const int parts = one_phase ? 4 * per_phase : per_phase;
     if (st->partials_bytes < (size_t)L.p.C8out * parts * 16 * sizeof(float)) return MP_ERR_WORKSPACE;
     L.p.st_mode = st->mode;
     L.p.st_nparts = parts;
-    L.p.st_part = st->partials_dev;
+    L.p.st_part = st->partials_dev + (one_phase ? (size_t)(2 * desc->out_off_y + desc->out_off_x) * per_phase * 16 : (size_t)0);
     if (st->mode == 2) {
         if (!st->z_dev || (st->relu != 0 && !st->y_dev)) return MP_ERR_NULL;
-        if (desc->stride != 1 || desc->out_mul != (phases4 ? 2 : 1) || desc->out_off_y != 0 || desc->out_off_x != 0) return MP_ERR_UNSUPPORTED;
+        if (desc->stride != 1 || desc->out_mul != ((phases4 || one_phase) ? 2 : 1) ||
+            (!one_phase && (desc->out_off_y != 0 || desc->out_off_x != 0)))
+            return MP_ERR_UNSUPPORTED;
         L.p.st_relu = st->relu != 0 ? 1 : 0;
         L.p.st_z = st->z_dev;
         L.p.st_y = st->relu != 0 ? st->y_dev : nullptr;

@@ -176,6 +176,10 @@ def branch_streams_enabled() -> bool:
     return _BRANCH_STREAMS_ON[0] if env is None else env == "1"
 
 
+def _rows_on_side_streams() -> bool:
+    """Do the rows of an exchange unit run on the branch side streams (``MINDPOSE_TRAIN_FUSE_STREAMS=0``: all on the current one)?"""
+    return branch_streams_enabled() and os.environ.get("MINDPOSE_TRAIN_FUSE_STREAMS", "1") != "0"
+
 
 def join_branch_streams(device) -> None:
     """The current stream waits for every branch / row side stream of ``device`` (a segmented capture ends each backward segment
@@ -352,7 +356,7 @@ class HRModule(nn.Module):
         # (four) launches of ~10 us that ran one after the other: row i > 0 goes to side stream i, like the branches above
         # (MINDPOSE_TRAIN_FUSE_STREAMS=0: all rows on the current stream).
         row_streams = None
-        if rows > 1 and xs[0].is_cuda and branch_streams_enabled() and os.environ.get("MINDPOSE_TRAIN_FUSE_STREAMS", "1") != "0":
+        if rows > 1 and xs[0].is_cuda and _rows_on_side_streams():
             cur = torch.cuda.current_stream(xs[0].device)
             row_streams = _branch_streams(xs[0].device, rows - 1)
             for st in row_streams:
@@ -540,7 +544,10 @@ class HRNet(Backbone):
                         t = _train_conv_bn(seq, t)
                     xs.append(t)
             mods = list(getattr(self, f"stage{idx}"))
-            chain = os.environ.get("MINDPOSE_TRAIN_CHAIN_MODULES", "1") != "0"
+            # chaining leaves out the fork in front of a module because row i of the previous one RAN on the side stream branch i
+            # starts on: only true while the rows go to the side streams (MINDPOSE_TRAIN_FUSE_STREAMS=0 keeps them on the current
+            # stream - a branch started without the fork would then read its input with no order behind the row that wrote it)
+            chain = os.environ.get("MINDPOSE_TRAIN_CHAIN_MODULES", "1") != "0" and _rows_on_side_streams()
             for k, mod in enumerate(mods):
                 first, last = k == 0, k == len(mods) - 1
                 xs = mod.train_forward(xs, fork=first or not chain, join=last or not chain)

@@ -325,15 +325,17 @@ def _pack16(lib, w, cout, cin, k, mode, py=0, px=0, owner=None):
 
 
 def phases4_enabled() -> bool:
-    """``MINDPOSE_DGRAD_PHASES4=0``: the stride-2 3x3 data gradient as four phase launches (A/B; the results are bit-identical)."""
+    """``MINDPOSE_DGRAD_PHASES4=0``: the stride-2 3x3 data gradient as four phase launches (A/B; bit-identical: the
+    four launches take the one launch's variant and leave the same BatchNorm backward sums in the same slots)."""
     return _lib.env_on("MINDPOSE_DGRAD_PHASES4")
 
 
 def _dgrad16_stride2(lib, w, owner, dz, dx, n, cin, cout, h, wd, ho, wo, ones, zeros, below=None):
     """Data gradient of a 3x3 stride-2 padding-1 conv: four 2x2 sub-pixel phase convs over dz, each writing every second pixel
     of dx - as ONE launch (MP_CONV_PHASES4; phase = second grid dimension) when the weight has an owner whose four packings share
-    a buffer, else as four launches.  ``below`` = (z, y, relu) of the BatchNorm whose output this conv read: the one launch then
-    also masks the gradient and leaves that BatchNorm's backward sums (returns (partials, n_parts), else (None, 0))."""
+    a buffer, else as four launches.  ``below`` = (z, y, relu) of the BatchNorm whose output this conv read: the launch(es) then
+    also mask the gradient and leave that BatchNorm's backward sums (returns (partials, n_parts), else (None, 0)) - the four
+    launches of MINDPOSE_DGRAD_PHASES4=0 in the slots, and so the order, of the one launch."""
     if owner is not None and phases4_enabled():
         for py in (0, 1):
             for px in (0, 1):
@@ -344,11 +346,23 @@ def _dgrad16_stride2(lib, w, owner, dz, dx, n, cin, cout, h, wd, ho, wo, ones, z
             return _conv16_stats_launch(lib, d, dz, parent, ones, zeros, dx, None, 2, z=below[0], y=below[1], relu=below[2])
         _conv16_launch(lib, d, dz, parent, ones, zeros, dx, "conv dgrad phases")
         return None, 0
-    for py in (0, 1):
-        for px in (0, 1):
-            d = _desc(n, cout, ho, wo, cin, 2, 1, 0, 0, ho, wo, h, wd, out_mul=2, off_y=py, off_x=px)
-            _conv16_launch(lib, d, dz, _pack16(lib, w, cin, cout, 2, 3, py, px, owner=owner), ones, zeros, dx, "conv dgrad phase")
-    return None, 0
+    slices = {(py, px): _pack16(lib, w, cin, cout, 2, 3, py, px, owner=owner) for py in (0, 1) for px in (0, 1)}
+    part, n_parts = None, 0
+    if owner is not None and below is not None:
+        # four launches that leave what the one launch leaves: each phase runs the variant the merged launch takes and fills its
+        # quarter of that launch's partial sums (same tiles, same slots) - the switch changes the launch count, not the arithmetic
+        parent = owner.__dict__["_mp_pack_parents"][(True, cin, cout, 2, 3)]
+        dm = _desc(n, cout, ho, wo, cin, 2, 1, 0, 0, ho, wo, h, wd, out_mul=2, flags=_lib.MP_CONV_PHASES4)
+        stats = dict(mode=2, z=below[0], y=below[1], relu=below[2])
+        v = tune_conv_variant(lib, dm, dz, parent, ones, zeros, None, None, dx, half=True, stats=stats)
+        part, n_parts = _stats_alloc(lib, dm, v, (cin + 7) // 8, dx.device)
+    for (py, px), packed in slices.items():
+        d = _desc(n, cout, ho, wo, cin, 2, 1, 0, 0, ho, wo, h, wd, out_mul=2, off_y=py, off_x=px)
+        if part is not None:
+            _conv16_stats_launch(lib, d, dz, packed, ones, zeros, dx, None, 2, z=below[0], y=below[1], relu=below[2], into=(v, part))
+        else:
+            _conv16_launch(lib, d, dz, packed, ones, zeros, dx, "conv dgrad phase")
+    return part, n_parts
 
 
 def repack_weights(module):
@@ -999,16 +1013,21 @@ def _pre_capable(lib, d) -> bool:
     return hit
 
 
-def _conv16_stats_launch(lib, d, x, packed, scale, shift, out, res1, mode, z=None, y=None, relu=0, pre=None):
+def _conv16_stats_launch(lib, d, x, packed, scale, shift, out, res1, mode, z=None, y=None, relu=0, pre=None, into=None):
     """The tuned conv launch with epilogue statistics (mode 1 forward / 2 backward); returns (partials, n_parts) or (None, 0) after
     a PLAIN launch when the tuned variant has no statistics build.  ``pre`` = dict(scale, shift, y, relu): ``x`` is the RAW output of
     the conv below and the launch applies that layer's BatchNorm on its operand, writing the activation to ``pre["y"]`` (the caller
-    checked `_pre_capable`)."""
+    checked `_pre_capable`).  ``into`` = (variant, partials): one phase of a stride-2 data gradient, launched with the merged
+    launch's variant into the merged launch's partial-sum buffer (`_dgrad16_stride2`)."""
     stats = dict(mode=mode, z=z, y=y, relu=relu)
     if pre is not None:
         stats["pre"] = pre
-    v = tune_conv_variant(lib, d, x, packed, scale, shift, res1, None, out, half=True, stats=stats)
-    part, n_parts = _stats_alloc(lib, d, v, (d.cout + 7) // 8, out.device)
+    if into is not None:
+        v, part = into
+        n_parts = part.numel() // (((d.cout + 7) // 8) * 16)
+    else:
+        v = tune_conv_variant(lib, d, x, packed, scale, shift, res1, None, out, half=True, stats=stats)
+        part, n_parts = _stats_alloc(lib, d, v, (d.cout + 7) // 8, out.device)
     if pre is not None and (part is None or v < 0):
         raise _lib.MindposeHipError("no conv variant applies the BatchNorm on its operand for a shape _pre_capable admitted")
     if part is None:
@@ -1350,8 +1369,7 @@ def _chain16_bwd_steps(lib, groups, dy, out_link, in_link, needs_dx, res_is_inpu
                 if res1 is not None:
                     raise NotImplementedError("a residual chain starts with a stride-1 conv")
                 if k == 3:
-                    use = below if (below is not None and tuple(below[0].shape) == tuple(dx.shape) and phases4_enabled()
-                                    and (_bn_fuse_parts() & 16)) else None
+                    use = below if (below is not None and tuple(below[0].shape) == tuple(dx.shape) and (_bn_fuse_parts() & 16)) else None
                     part, n_parts = _dgrad16_stride2(lib, w, G["weight"], dz, dx, n, cin, cout, h, wd, ho, wo, ones, zeros,
                                                      below=use[:3] if use is not None else None)
                     if part is not None:

@@ -173,6 +173,59 @@ def test_stride2_dgrad_four_phases_in_one_launch_equal_four_launches(case, varia
                                  _lib.ptr(one), _lib.stream()) != 0
 
 
+@pytest.mark.parametrize("relu", [0, 1])
+@pytest.mark.parametrize("case,variant", [pytest.param(c, -1, id=f"case{i}-heuristic") for i, c in enumerate(fm.PHASES4_CASES)]
+                         + fm.served_pairs(fm.PHASES4_CASES, fm.PHASES4_VARIANTS, fm.phases4_case_desc))
+def test_stride2_dgrad_backward_sums_from_four_phase_launches_equal_the_merged_launch(case, variant, relu):
+    """mp_f16_conv2d_fwd_stats mode 2 on ONE phase (MINDPOSE_DGRAD_PHASES4=0): four launches fill the partial-sum buffer of the merged
+    MP_CONV_PHASES4 launch slot for slot - masked gradient and partials bit-identical; a buffer sized for one phase is refused."""
+    n, cin, cout, h, w = case
+    g = torch.Generator().manual_seed(sum(case) + 11)
+    ho, wo = h // 2, w // 2
+    wdev = (torch.randn(cout, cin, 3, 3, generator=g) / (cin * 9) ** 0.5).to(DEV)
+    dza = _to_c8(torch.randn(n, cout, ho, wo, generator=g))
+    za, ya = _to_c8(torch.randn(n, cin, h, w, generator=g)), _to_c8(torch.randn(n, cin, h, w, generator=g))
+    ones = torch.ones((cin + 15) // 16 * 16, device=DEV)
+    zeros = torch.zeros_like(ones)
+    nb = LIB.mp_f16_packed_weight_bytes(cin, cout, 2, 2)
+    packed = torch.empty(4 * (nb // 2), device=DEV, dtype=torch.float16)
+    for py in (0, 1):
+        for px in (0, 1):
+            sl = packed[(2 * py + px) * (nb // 2):]
+            _lib.check(LIB.mp_f16_pack_weight(_lib.ptr(wdev), sl.data_ptr(), cin, cout, 2, 2, 3, py, px, _lib.stream()), "pack")
+    d = _desc(n, cout, ho, wo, cin, 2, 1, 0, ho, wo, oh=h, ow=w, mul=2)
+    d.flags = _lib.MP_CONV_PHASES4
+    parts = LIB.mp_f16_conv_stats_parts(ctypes.byref(d), variant)
+    assert parts > 0 and parts % 4 == 0
+    c8 = (cin + 7) // 8
+
+    def stats(buf):
+        return _lib.ConvStats(mode=2, relu=relu, partials=buf.data_ptr(), partials_bytes=buf.numel() * 4, z=_lib.ptr(za),
+                              y=_lib.ptr(ya) if relu else None)
+    one, four = ActC8(n, cin, h, w, DEV), ActC8(n, cin, h, w, DEV)
+    p_one = torch.full((c8 * parts * 16,), float("nan"), device=DEV)
+    p_four = torch.full((c8 * parts * 16,), float("nan"), device=DEV)
+    st = stats(p_one)
+    _lib.check(LIB.mp_f16_conv2d_fwd_stats(ctypes.byref(d), variant, _lib.ptr(dza), _lib.ptr(packed), _lib.ptr(ones), _lib.ptr(zeros), None,
+                                           _lib.ptr(one), ctypes.byref(st), _lib.stream()), "merged")
+    small = torch.empty(c8 * (parts // 4) * 16, device=DEV)
+    for py in (0, 1):
+        for px in (0, 1):
+            dd = _desc(n, cout, ho, wo, cin, 2, 1, 0, ho, wo, oh=h, ow=w, mul=2, oy=py, ox=px)
+            assert LIB.mp_f16_conv_stats_parts(ctypes.byref(dd), variant) in (0, parts // 4)
+            sl = packed[(2 * py + px) * (nb // 2):]
+            st4 = stats(p_four)
+            _lib.check(LIB.mp_f16_conv2d_fwd_stats(ctypes.byref(dd), variant, _lib.ptr(dza), sl.data_ptr(), _lib.ptr(ones), _lib.ptr(zeros),
+                                                   None, _lib.ptr(four), ctypes.byref(st4), _lib.stream()), "phase")
+            sts = stats(small)
+            assert LIB.mp_f16_conv2d_fwd_stats(ctypes.byref(dd), variant, _lib.ptr(dza), sl.data_ptr(), _lib.ptr(ones), _lib.ptr(zeros),
+                                               None, _lib.ptr(four), ctypes.byref(sts), _lib.stream()) != 0
+    torch.cuda.synchronize()
+    assert not torch.isnan(p_one).any()
+    assert torch.equal(p_one, p_four)
+    assert torch.equal(_from_c8(one), _from_c8(four))
+
+
 @pytest.mark.parametrize("c,h,w,relu,with_res", [(32, 64, 48, True, True), (64, 16, 12, True, False), (17, 8, 6, False, False),
                                                  (48, 24, 18, True, True)])
 def test_bn_train_f16_fwd_bwd_vs_torch(c, h, w, relu, with_res):

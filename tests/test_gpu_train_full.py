@@ -20,18 +20,9 @@ pytestmark = pytest.mark.gpu
 
 import mindpose_amd as mp  # noqa: E402
 from oracle import nets as onets  # noqa: E402
+from tests.train_oracle import data as _data  # noqa: E402
 
 DEV = torch.device("cuda:0")
-
-
-def _data(n, h, w, seed=11):
-    g = torch.Generator().manual_seed(seed)
-    x = torch.randn(n, 3, h, w, generator=g)
-    kp = torch.empty(n, 17, 3)
-    kp[..., 0] = torch.rand(n, 17, generator=g) * (w + 40) - 20
-    kp[..., 1] = torch.rand(n, 17, generator=g) * (h + 40) - 20
-    kp[..., 2] = (torch.rand(n, 17, generator=g) < 0.7).float()
-    return x, kp
 
 
 def _build(amp):
@@ -45,7 +36,7 @@ def _build(amp):
     return net, nwl, opt
 
 
-def test_config4_step_at_full_size_graph_with_branch_streams_equals_eager():
+def test_config4_step_at_full_size_graph_with_branch_streams_equals_eager(monkeypatch):
     from mindpose_amd.utils import DynamicLossScaleManager, GraphedTrainStep
     n = int(os.environ.get("MINDPOSE_TEST_FULL_BATCH", "48"))
     x, kp = _data(n, 256, 192)
@@ -78,6 +69,18 @@ def test_config4_step_at_full_size_graph_with_branch_streams_equals_eager():
     before = opt_g.flat.clone()
     step(x, target, weight)
     assert step.updated and not torch.equal(opt_g.flat, before)
+    # the rows of the exchange units on the current stream (MINDPOSE_TRAIN_FUSE_STREAMS=0; the modules of a stage then fork and join
+    # one by one): at this size the launches are long enough to overlap, so an edge missing from the captured graph would show
+    del step, net_g, nwl_g, opt_g
+    monkeypatch.setenv("MINDPOSE_TRAIN_FUSE_STREAMS", "0")
+    net_r, nwl_r, opt_r = _build(True)
+    step_r = GraphedTrainStep(nwl_r, opt_r, (x, target, weight), loss_scale_manager=DynamicLossScaleManager(init_loss_scale=scale),
+                              warmup=2)
+    opt_r.grads.rearm()
+    step_r.graph.replay()
+    torch.cuda.synchronize()
+    assert float(step_r.static_loss) == float(loss_e.detach())
+    assert torch.equal(opt_r.grads.arena, arena_e), "captured step with MINDPOSE_TRAIN_FUSE_STREAMS=0 differs from the eager single-stream step"
 
 
 def test_fp32_training_forward_loss_at_256x192_vs_oracle():
@@ -97,64 +100,11 @@ def test_fp32_training_forward_loss_at_256x192_vs_oracle():
 def test_o2_training_step_vs_oracle_amp_emulation():
     """Loss and every parameter gradient of the amp-O2 HIP step against the oracle's amp-O2 emulation (fp16 operands and cell
     outputs, fp32 accumulation / statistics) - and, as the yardstick for how far two fp16 roundings of the same graph may sit
-    apart, against the oracle's fp32 gradients: the HIP path must be at least as close to fp32 as the emulation is (x1.5)."""
-    net = mp.init_synthetic(mp.create_network("hrnet_w32", "hrnet_head"), seed=0)
-    cpu_state = {k: v.detach().cpu().clone() for k, v in net.state_dict().items()}  # before the network moves to the GPU
-
-    def leaf_params():
-        d = {k: v.clone() for k, v in cpu_state.items()}
-        for k, v in d.items():
-            if v.dtype.is_floating_point and not k.endswith(("moving_mean", "moving_variance")):
-                v.requires_grad_()
-        return d
-
-    x, kp = _data(4, 128, 96)
-    net = net.to(DEV).train()
-    mp.models.auto_mixed_precision(net, "O2")
-    tgt = mp.TopDownGenerateTarget(config=dict(image_size=[96, 128], heatmap_size=[24, 32]), sigma=2.0)
-    target, weight = tgt(kp.to(DEV))
-    nwl = mp.create_network_with_loss(net, mp.create_loss("joint_mse", use_target_weight=True), has_extra_inputs=True)
-    scale = 1024.0
-    loss = nwl(x.to(DEV), target, weight)
-    (loss * scale).backward()
-    got = {k: (v.grad / scale).double().cpu().flatten() for k, v in net.named_parameters()}
-
-    def oracle(amp):
-        p = leaf_params()
-        out = onets.net_forward_train(p, x, "hrnet_w32", "hrnet_head", amp=amp)
-        l = (((out - target.cpu()) ** 2) * weight.cpu()[..., None, None]).mean()
-        (l * scale).backward()
-        return float(l.detach()), {k: (p[k].grad / scale).double().flatten() for k in got}
-
-    l_amp, g_amp = oracle(True)
-    l_f32, g_f32 = oracle(False)
-    assert abs(float(loss.detach()) - l_amp) <= 5e-3 * abs(l_amp), (float(loss.detach()), l_amp, l_f32)
-
-    def cos(a, b):
-        return float((a @ b) / (a.norm() * b.norm()).clamp_min(1e-300))
-
-    c_amp = {k: cos(got[k], g_amp[k]) for k in got}          # HIP O2 vs the emulation
-    c_hip_f32 = {k: cos(got[k], g_f32[k]) for k in got}      # HIP O2 vs fp32 truth
-    c_emu_f32 = {k: cos(g_amp[k], g_f32[k]) for k in got}    # emulation vs fp32 truth
-    all_hip, all_amp, all_f32 = (torch.cat([d[k] for k in got]) for d in (got, g_amp, g_f32))
-    print(f"O2 step: loss {float(loss.detach()):.6f} / emulation {l_amp:.6f} / fp32 {l_f32:.6f}; global cosine vs emulation "
-          f"{cos(all_hip, all_amp):.5f}, vs fp32 {cos(all_hip, all_f32):.5f} (emulation vs fp32 {cos(all_amp, all_f32):.5f}); "
-          f"per-tensor vs emulation median {np.median(list(c_amp.values())):.5f} min {min(c_amp.values()):.4f}")
-    assert cos(all_hip, all_amp) > 0.98 and np.median(list(c_amp.values())) > 0.99 and min(c_amp.values()) > 0.9
-    # VERDICT r2: per-tensor floor 0.97 (measured minimum 0.9736: BatchNorm parameters of the deepest layers, whose gradient is a
-    # small difference of large sums - the emulation itself sits that far from the fp32 gradient on them)
-    low = sorted((k for k in got if c_amp[k] < 0.98), key=lambda k: c_amp[k])
-    for k in low[:8]:
-        print(f"  lowest: {k} numel {got[k].numel()} cos(hip, emu) {c_amp[k]:.4f} cos(hip, f32) {c_hip_f32[k]:.4f} "
-              f"cos(emu, f32) {c_emu_f32[k]:.4f}")
-    assert min(c_amp.values()) > 0.97
-    # distance to the fp32 gradients: not worse than the op-by-op emulation of the reference's recipe
-    assert 1 - cos(all_hip, all_f32) <= 1.5 * (1 - cos(all_amp, all_f32)) + 1e-4
-    assert np.median([1 - c for c in c_hip_f32.values()]) <= 1.5 * np.median([1 - c for c in c_emu_f32.values()]) + 1e-4
-    # one layer from the loss: tight against the emulation
-    for name in ("head.head.weight", "head.head.bias"):
-        rel = float((got[name] - g_amp[name]).abs().max() / g_amp[name].abs().max())
-        assert rel < 5e-3, (name, rel)
+    apart, against the oracle's fp32 gradients: the HIP path must be at least as close to fp32 as the emulation is (x1.5).
+    The step, the two oracle runs and the acceptance live in tests/train_oracle.py (the switch matrix shares them)."""
+    from tests import train_oracle
+    loss, got = train_oracle.hip_step()
+    train_oracle.check_against_oracle(loss, got)
 
 
 def test_eval_between_graphed_steps_sees_updated_weights():
