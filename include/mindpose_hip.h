@@ -531,6 +531,29 @@ int mp_resize_pad_normalize(const uint8_t* src_dev, const long long* src_offsets
                             float* out_dev, uint8_t* mask_dev, int n, int pad_h, int pad_w, const float mean[3],
                             const float stddev[3], mp_stream_t stream);
 
+/* Bottom-up train-time augmentation of a batch in ONE launch (mindpose/data/transform/bottomup_transform.py:304-460
+ * BottomUpRandomAffine, :88-140 BottomUpHorizontalRandomFlip, data_factory.py:129-133 Normalize + HWC2CHW): the bilinear warp of
+ * the image and the nearest-neighbour warp of the mask into every heat-map stage, each mirrored afterwards where flip says so.
+ *   src / src_offsets / src_hw        the uint8 HWC source images, packed as for mp_warp_affine
+ *   mask_src / mask_offsets           one uint8 [H, W] mask per image at the SOURCE resolution (src_hw serves both), byte offsets
+ *                                     inside mask_src (device, [n] int64); the reference tiles this plane over the stages
+ *   trans        [n][s + 1][6] fp64 (device): the 2x3 FORWARD matrices, the s stages first, the image last
+ *   flip         NULL or [n] int32 (device): non-zero mirrors the OUTPUTS after the warp - the value computed for column x lands
+ *                in column out_w - 1 - x of the image and W_i - 1 - x of stage i's corner (affine, then flip: the reference's
+ *                order; NOT mp_warp_affine's flip of the source)
+ *   stage_wh_host [s][2] (W_i, H_i), a HOST array
+ *   image        [n, 3, out_h, out_w] fp32: mp_warp_affine's normalised planes to the bit (mean / stddev already times 255)
+ *   mask         [n, s, hmax, wmax] uint8: cv2.warpAffine(..., INTER_NEAREST), border 0, in the [:H_i, :W_i] corner of stage i,
+ *                0 in the padding [cv2-knowledge; parity with cv2 itself is unpinned]
+ * Every byte of both outputs is written; integer / fixed-point arithmetic up to the final normalise, no atomics.  Validation
+ * before any HIP call: NULL -> MP_ERR_NULL; s outside 1..8 -> MP_ERR_UNSUPPORTED; non-positive extents, a stage larger than
+ * (hmax, wmax), a zero stddev or n > 65535 -> MP_ERR_SHAPE. */
+int mp_bottomup_train_augment(const uint8_t* src_dev, const long long* src_offsets_dev, const int* src_hw_dev,
+                              const uint8_t* mask_src_dev, const long long* mask_offsets_dev, const double* trans_dev,
+                              const int* flip_dev, const int* stage_wh_host, float* image_dev, uint8_t* mask_dev, int n, int s,
+                              int out_h, int out_w, int hmax, int wmax, const float mean[3], const float stddev[3],
+                              mp_stream_t stream);
+
 /* ---- bottom-up (associative-embedding) decoder, BottomUpHeatMapAEDecoder -------------------------------------------------
  * Replaces mindpose/models/decoders/bottom_up_decoder.py:81-203 (the ~10 MindSpore ops of decode()) with two launches.
  * stages[0 .. num_stages-1]: the model outputs in the reference's order, stages[num_stages-1] the full-resolution one (its h, w

@@ -198,6 +198,8 @@ _PROTOTYPES = {
     "mp_bottomup_refine_missing": (c_int, [c_f32p] * 4 + [c_int] * 7 + [c_f32p, ctypes.c_void_p]),
     "mp_resize_pad_normalize": (c_int, [c_f32p] * 3 + [ctypes.POINTER(ctypes.c_int)] + [c_f32p] * 2 + [c_int] * 3
                                 + [ctypes.POINTER(ctypes.c_float)] * 2 + [ctypes.c_void_p]),
+    "mp_bottomup_train_augment": (c_int, [c_f32p] * 7 + [ctypes.POINTER(ctypes.c_int)] + [c_f32p] * 2 + [c_int] * 6
+                                  + [ctypes.POINTER(ctypes.c_float)] * 2 + [ctypes.c_void_p]),
     # bottom-up training ends (bottomup_train_ops.hip): strided masked MSE, AE loss, batched target generation
     "mp_joints_mse_mask_workspace_bytes": (c_size_t, [c_int, c_int]),
     "mp_joints_mse_mask_fwd": (c_int, [c_f32p] + [c_i64] * 3 + [c_f32p] + [c_i64] * 3 + [c_f32p, c_int] + [c_i64] * 2

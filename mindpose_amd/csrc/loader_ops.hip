@@ -280,3 +280,181 @@ extern "C" int mp_resize_pad_normalize(const uint8_t* src, const long long* src_
     }
     return MP_OK;
 }
+
+// ---- bottom-up train-time augmentation of a batch in ONE launch: BottomUpRandomAffine + BottomUpHorizontalRandomFlip + Normalize +
+// HWC2CHW (bottomup_transform.py:304-460, :88-140, data_factory.py:129-133).  Per image the 2x3 matrices of the s heat-map stages and
+// of the image arrive together; a workgroup owns 256 thread-groups of ONE plane - the image or the mask of one stage - so the inverse
+// matrix is formed once per workgroup and the plane kind never diverges inside a wave.
+//   image: warp_affine_kernel<true>'s arithmetic, expression by expression (INTER_LINEAR, 1 / 32 pixel, 15-bit weights, normalise)
+//   mask:  cv2.warpAffine(mask, M, (W_i, H_i), flags=INTER_NEAREST) [cv2-knowledge, PARITY UNPINNED: cv2 is not installed here]:
+//          the same inverse and the same AB_BITS = 10 coordinate terms with round_delta = 512,
+//          X = (cvRound((i01 y + i02) 1024) + 512 + cvRound(i00 x 1024)) >> 10, saturate_cast<short>, the source pixel when it lies
+//          inside, else 0; written into the [:H_i, :W_i] corner of the stage's [hmax, wmax] plane, 0 in the padding.
+// The flip follows the warp (the reference's order): the value computed for column x is stored at column W - 1 - x.  It cannot be
+// folded into the matrix bit-exactly, because the fixed-point column terms are rounded per destination column - so the thread that
+// stores columns [4g, 4g + 4) computes the mirrored columns and the 16-byte vector leaves in reversed order.
+// Integer arithmetic up to the normalise; every byte of both outputs is written here (no memset pass), no atomics.
+namespace mp {
+namespace {
+
+constexpr int kAugMaxStages = 8;  // (W_i, H_i) of every stage travel in the kernel arguments
+
+struct AugParams {
+    const uint8_t* src;
+    const long long* src_off;
+    const int* src_hw;
+    const uint8_t* msrc;
+    const long long* msrc_off;
+    const double* trans;  // [n, s + 1, 6]: stages first, the image last
+    const int* flip;
+    float* image;   // [n, 3, out_h, out_w]
+    uint8_t* mask;  // [n, s, hmax, wmax]
+    int s, out_h, out_w, hmax, wmax;
+    int img_tiles, mask_tiles;  // workgroups per image plane set / per stage plane
+    float m[3], sd[3];
+    int wh[kAugMaxStages][2];
+};
+
+__device__ __forceinline__ int saturate_short(int v) { return v < -32768 ? -32768 : (v > 32767 ? 32767 : v); }
+
+// VEC adjacent destination pixels of one image row, all three planes
+template <int VEC>
+__device__ __forceinline__ void augment_image_group(const AugParams& p, const double* inv, const uint8_t* __restrict__ img, int H, int W,
+                                                    bool mirror, int n, int g) {
+    const int gpr = p.out_w / VEC;
+    if (g >= p.out_h * gpr) return;
+    const int y = g / gpr, x0 = (g - y * gpr) * VEC;
+    const int X0 = cv_round((inv[1] * y + inv[2]) * 1024.0) + 16, Y0 = cv_round((inv[4] * y + inv[5]) * 1024.0) + 16;
+    float v[3][VEC];
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) {
+        const int x = mirror ? p.out_w - 1 - (x0 + e) : x0 + e;  // the column this value is computed for
+        const int adelta = cv_round(inv[0] * x * 1024.0), bdelta = cv_round(inv[3] * x * 1024.0);
+        const int X = (X0 + adelta) >> 5, Y = (Y0 + bdelta) >> 5;
+        const int sx = saturate_short(X >> 5), sy = saturate_short(Y >> 5);
+        const int fx = X & 31, fy = Y & 31;
+        const int w00 = (32 - fx) * (32 - fy) * 32, w01 = fx * (32 - fy) * 32, w10 = (32 - fx) * fy * 32, w11 = fx * fy * 32;
+        int acc[3] = {0, 0, 0};
+        auto tap = [&](int yy, int xx, int w) {
+            if (w != 0 && yy >= 0 && yy < H && xx >= 0 && xx < W) {
+                const uint8_t* px = img + ((size_t)yy * W + xx) * 3;
+                acc[0] += w * px[0]; acc[1] += w * px[1]; acc[2] += w * px[2];
+            }
+        };
+        tap(sy, sx, w00); tap(sy, sx + 1, w01); tap(sy + 1, sx, w10); tap(sy + 1, sx + 1, w11);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            int u = (acc[c] + (1 << 14)) >> 15;
+            u = u > 255 ? 255 : u;
+            v[c][e] = ((float)u - p.m[c]) / p.sd[c];
+        }
+    }
+    const size_t plane = (size_t)p.out_h * p.out_w;
+    float* __restrict__ o = p.image + (size_t)n * 3 * plane + (size_t)y * p.out_w + x0;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        if constexpr (VEC == 4) *reinterpret_cast<float4*>(o + c * plane) = make_float4(v[c][0], v[c][1], v[c][2], v[c][3]);
+        else o[c * plane] = v[c][0];
+    }
+}
+
+// VEC adjacent pixels of one row of one stage's [hmax, wmax] mask plane
+template <int VEC>
+__device__ __forceinline__ void augment_mask_group(const AugParams& p, const double* inv, const uint8_t* __restrict__ msk, int H, int W,
+                                                   bool mirror, int n, int stage, int g) {
+    const int gpr = p.wmax / VEC;
+    if (g >= p.hmax * gpr) return;
+    const int y = g / gpr, x0 = (g - y * gpr) * VEC;
+    const int sw = p.wh[stage][0], sh = p.wh[stage][1];
+    uint8_t v[VEC];
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) v[e] = 0;
+    if (y < sh) {
+        const int X0 = cv_round((inv[1] * y + inv[2]) * 1024.0) + 512, Y0 = cv_round((inv[4] * y + inv[5]) * 1024.0) + 512;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+            if (x0 + e >= sw) continue;
+            const int x = mirror ? sw - 1 - (x0 + e) : x0 + e;
+            const int sx = saturate_short((X0 + cv_round(inv[0] * x * 1024.0)) >> 10);
+            const int sy = saturate_short((Y0 + cv_round(inv[3] * x * 1024.0)) >> 10);
+            if (sx >= 0 && sx < W && sy >= 0 && sy < H) v[e] = msk[(size_t)sy * W + sx];
+        }
+    }
+    uint8_t* __restrict__ o = p.mask + (((size_t)n * p.s + stage) * p.hmax + y) * p.wmax + x0;
+    if constexpr (VEC == 4) *reinterpret_cast<uchar4*>(o) = make_uchar4(v[0], v[1], v[2], v[3]);
+    else o[0] = v[0];
+}
+
+// VI / VM = 4: four destination pixels per thread, one 16-byte store per fp32 plane / one 4-byte store of the mask; 1 = the scalar
+// form for widths (or base addresses) that do not allow it
+template <int VI, int VM>
+__global__ __launch_bounds__(256) void bottomup_train_augment_kernel(AugParams p) {
+    const int n = blockIdx.y;
+    int tile = blockIdx.x;
+    const bool is_image = tile < p.img_tiles;
+    int stage = p.s;  // the index of this plane's matrix
+    if (!is_image) {
+        tile -= p.img_tiles;
+        stage = tile / p.mask_tiles;
+        tile -= stage * p.mask_tiles;
+    }
+    __shared__ double inv[6];
+    if (threadIdx.x == 0) {
+        // cv::warpAffine without WARP_INVERSE_MAP: invert M in double (as warp_affine_kernel does)
+        const double* M = p.trans + ((size_t)n * (p.s + 1) + stage) * 6;
+        double D = M[0] * M[4] - M[1] * M[3];
+        D = D != 0.0 ? 1.0 / D : 0.0;
+        const double A11 = M[4] * D, A22 = M[0] * D;
+        const double i0 = A11, i1 = M[1] * (-D), i3 = M[3] * (-D), i4 = A22;
+        inv[0] = i0; inv[1] = i1; inv[3] = i3; inv[4] = i4;
+        inv[2] = -i0 * M[2] - i1 * M[5];
+        inv[5] = -i3 * M[2] - i4 * M[5];
+    }
+    __syncthreads();
+    const int H = p.src_hw[2 * n], W = p.src_hw[2 * n + 1];
+    const bool mirror = p.flip && p.flip[n] != 0;
+    const int g = tile * 256 + threadIdx.x;
+    if (is_image) augment_image_group<VI>(p, inv, p.src + p.src_off[n], H, W, mirror, n, g);
+    else augment_mask_group<VM>(p, inv, p.msrc + p.msrc_off[n], H, W, mirror, n, stage, g);
+}
+
+}  // namespace
+}  // namespace mp
+
+extern "C" int mp_bottomup_train_augment(const uint8_t* src, const long long* src_offsets, const int* src_hw, const uint8_t* mask_src,
+                                         const long long* mask_offsets, const double* trans, const int* flip, const int* stage_wh_host,
+                                         float* image, uint8_t* mask, int n, int s, int out_h, int out_w, int hmax, int wmax,
+                                         const float mean[3], const float stddev[3], mp_stream_t stream) {
+    if (!src || !src_offsets || !src_hw || !mask_src || !mask_offsets || !trans || !stage_wh_host || !image || !mask || !mean || !stddev)
+        return MP_ERR_NULL;
+    if (s < 1 || s > mp::kAugMaxStages) return MP_ERR_UNSUPPORTED;
+    if (n <= 0 || n > 65535 || out_h <= 0 || out_w <= 0 || hmax <= 0 || wmax <= 0) return MP_ERR_SHAPE;
+    if (stddev[0] == 0.f || stddev[1] == 0.f || stddev[2] == 0.f) return MP_ERR_SHAPE;
+    for (int i = 0; i < s; ++i) {
+        const int w = stage_wh_host[2 * i], h = stage_wh_host[2 * i + 1];
+        if (w <= 0 || h <= 0 || w > wmax || h > hmax) return MP_ERR_SHAPE;
+    }
+    if ((long long)out_h * out_w > (1LL << 30) || (long long)hmax * wmax > (1LL << 30)) return MP_ERR_SHAPE;  // group indices are int
+    // 16-byte stores need every row of every plane on a 16-byte boundary, the 4-byte mask stores every mask row on a 4-byte one
+    const bool wide_i = out_w % 4 == 0 && (uintptr_t)image % 16 == 0;
+    const bool wide_m = wmax % 4 == 0 && (uintptr_t)mask % 4 == 0;
+    mp::AugParams p{};
+    p.src = src; p.src_off = src_offsets; p.src_hw = src_hw;
+    p.msrc = mask_src; p.msrc_off = mask_offsets;
+    p.trans = trans; p.flip = flip;
+    p.image = image; p.mask = mask;
+    p.s = s; p.out_h = out_h; p.out_w = out_w; p.hmax = hmax; p.wmax = wmax;
+    const long long img_groups = (long long)out_h * (out_w / (wide_i ? 4 : 1)), mask_groups = (long long)hmax * (wmax / (wide_m ? 4 : 1));
+    p.img_tiles = (int)((img_groups + 255) / 256);
+    p.mask_tiles = (int)((mask_groups + 255) / 256);
+    const long long tiles = (long long)p.img_tiles + (long long)s * p.mask_tiles;
+    if (tiles > 0x7fffffffLL) return MP_ERR_SHAPE;
+    for (int c = 0; c < 3; ++c) { p.m[c] = mean[c]; p.sd[c] = stddev[c]; }
+    for (int i = 0; i < s; ++i) { p.wh[i][0] = stage_wh_host[2 * i]; p.wh[i][1] = stage_wh_host[2 * i + 1]; }
+    const dim3 grid((unsigned)tiles, (unsigned)n), block(256);
+    if (wide_i && wide_m) hipLaunchKernelGGL((mp::bottomup_train_augment_kernel<4, 4>), grid, block, 0, mp::as_stream(stream), p);
+    else if (wide_i) hipLaunchKernelGGL((mp::bottomup_train_augment_kernel<4, 1>), grid, block, 0, mp::as_stream(stream), p);
+    else if (wide_m) hipLaunchKernelGGL((mp::bottomup_train_augment_kernel<1, 4>), grid, block, 0, mp::as_stream(stream), p);
+    else hipLaunchKernelGGL((mp::bottomup_train_augment_kernel<1, 1>), grid, block, 0, mp::as_stream(stream), p);
+    return mp::check_launch();
+}

@@ -11,8 +11,15 @@ the host path is the oracle.
 dependency and parity with cv2 itself is unpinned.
 
 ``BottomUpGenerateTarget`` (:463-598) writes the ``target`` / ``tag_ind`` arrays of the training losses: ``transform`` is the
-reference's numpy arithmetic for one image, ``generate_batch`` one ``mp_bottomup_target`` launch for a batch on the device.  The
-train-time augmentations (random affine, flip) are not implemented, and no pipeline runs in train mode.
+reference's numpy arithmetic for one image, ``generate_batch`` one ``mp_bottomup_target`` launch for a batch on the device.
+
+The train-time augmentations ``BottomUpRandomAffine`` (:304-460) and ``BottomUpHorizontalRandomFlip`` (:88-140) have the same two
+forms: ``transform`` is the host path - the reference's random draws through the global ``np.random`` in its order, its matrices and
+key-point arithmetic, the mask through ``warp_affine_nearest_u8`` (``cv2.warpAffine(..., INTER_NEAREST)`` restated [cv2-knowledge],
+parity with cv2 itself unpinned) - and ``bottomup_augment_batch`` draws per image exactly as the two ``transform`` s would, computes
+the key points on the host with the same functions and does the pixel work of the batch - the image warp, every stage's mask warp,
+the flip, Normalize and HWC2CHW - in ONE ``mp_bottomup_train_augment`` launch.  Its result is what ``generate_batch`` and
+``AEMultiLoss`` take.  No pipeline runs in train mode yet.
 """
 import ctypes
 from typing import Any, Dict, List, Optional, Sequence, Tuple
@@ -23,11 +30,15 @@ import torch
 from ... import _lib
 from ...register import register
 from ..column_names import COLUMN_MAP
-from .topdown_transform import get_affine_transform
-from .utils import pad_to_same
+from .topdown_transform import fliplr_joints, get_affine_transform
+from .utils import pad_to_same, warp_affine_joints
 
-__all__ = ["BottomUpTransform", "BottomUpRescale", "BottomUpResize", "BottomUpPad", "BottomUpGenerateTarget", "resize_linear_u8",
-           "warp_affine_linear_u8", "launch_resize_pad_normalize"]
+__all__ = ["BottomUpTransform", "BottomUpRescale", "BottomUpResize", "BottomUpPad", "BottomUpGenerateTarget", "BottomUpRandomAffine",
+           "BottomUpHorizontalRandomFlip", "bottomup_augment_batch", "resize_linear_u8", "warp_affine_linear_u8",
+           "warp_affine_nearest_u8", "launch_resize_pad_normalize"]
+
+NORMALIZE_MEAN = (0.485, 0.456, 0.406)  # data_factory.py:78-79 (the reference's std really ends in 0.255)
+NORMALIZE_STD = (0.229, 0.224, 0.255)
 
 
 def _resize_terms(dst: int, src: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -63,6 +74,16 @@ def resize_linear_u8(image: np.ndarray, size: Tuple[int, int]) -> np.ndarray:
     return np.clip(out, 0, 255).astype(np.uint8)
 
 
+def _invert_affine(trans: np.ndarray) -> Tuple[float, float, float, float, float, float]:
+    """The inverse of a 2 x 3 forward matrix as ``cv::warpAffine`` forms it (no WARP_INVERSE_MAP), in double."""
+    m = np.array(trans, dtype=np.float64).reshape(2, 3)
+    det = m[0, 0] * m[1, 1] - m[0, 1] * m[1, 0]
+    det = 1.0 / det if det != 0 else 0.0
+    i00, i01, i10, i11 = m[1, 1] * det, m[0, 1] * -det, m[1, 0] * -det, m[0, 0] * det
+    i02, i12 = -i00 * m[0, 2] - i01 * m[1, 2], -i10 * m[0, 2] - i11 * m[1, 2]
+    return i00, i01, i02, i10, i11, i12
+
+
 def warp_affine_linear_u8(image: np.ndarray, trans: np.ndarray, size: Tuple[int, int]) -> np.ndarray:
     """``cv2.warpAffine(image, trans, (w, h), flags=cv2.INTER_LINEAR)`` of a uint8 [H, W, C] image, border constant 0: the matrix
     inverted in double, coordinates in 10-bit fixed point quantised to 1 / 32 pixel, exact 15-bit bilinear weights - the
@@ -70,11 +91,7 @@ def warp_affine_linear_u8(image: np.ndarray, trans: np.ndarray, size: Tuple[int,
     img = np.asarray(image)
     h, w, _ = img.shape
     out_w, out_h = int(size[0]), int(size[1])
-    m = np.array(trans, dtype=np.float64).reshape(2, 3)
-    det = m[0, 0] * m[1, 1] - m[0, 1] * m[1, 0]
-    det = 1.0 / det if det != 0 else 0.0
-    i00, i01, i10, i11 = m[1, 1] * det, m[0, 1] * -det, m[1, 0] * -det, m[0, 0] * det
-    i02, i12 = -i00 * m[0, 2] - i01 * m[1, 2], -i10 * m[0, 2] - i11 * m[1, 2]
+    i00, i01, i02, i10, i11, i12 = _invert_affine(trans)
     xs, ys = np.arange(out_w, dtype=np.float64), np.arange(out_h, dtype=np.float64)
     big_x = ((np.rint((i01 * ys + i02) * 1024.0).astype(np.int64) + 16)[:, None] + np.rint(i00 * xs * 1024.0).astype(np.int64)[None]) >> 5
     big_y = ((np.rint((i11 * ys + i12) * 1024.0).astype(np.int64) + 16)[:, None] + np.rint(i10 * xs * 1024.0).astype(np.int64)[None]) >> 5
@@ -88,6 +105,27 @@ def warp_affine_linear_u8(image: np.ndarray, trans: np.ndarray, size: Tuple[int,
         px = img[np.clip(yy, 0, h - 1), np.clip(xx, 0, w - 1)].astype(np.int64)
         acc += np.where(inside[..., None], px, 0) * weight[..., None]
     return np.minimum((acc + (1 << 14)) >> 15, 255).astype(np.uint8)
+
+
+def warp_affine_nearest_u8(mask: np.ndarray, trans: np.ndarray, size: Tuple[int, int]) -> np.ndarray:
+    """``cv2.warpAffine(mask, trans, (w, h), flags=cv2.INTER_NEAREST)`` of a uint8 [H, W] (or [H, W, C]) array, border constant 0
+    [cv2-knowledge]: the matrix inverted in double as in ``warp_affine_linear_u8``, the 10-bit fixed-point coordinate terms of a
+    row and of a column rounded separately, X = (cvRound((i01 y + i02) 1024) + 512 + cvRound(i00 x 1024)) >> 10 and likewise Y,
+    saturated to int16; the source pixel when (X, Y) lies inside the array, else 0.  cv2 is not a dependency: parity with cv2
+    itself is UNPINNED, exactly as for the linear warp.  The mask arithmetic of ``mp_bottomup_train_augment``."""
+    src = np.asarray(mask)
+    if src.dtype != np.uint8 or src.ndim not in (2, 3):
+        raise ValueError(f"mask must be uint8 [H, W] or [H, W, C], got {src.dtype} {src.shape}")
+    h, w = src.shape[:2]
+    out_w, out_h = int(size[0]), int(size[1])
+    i00, i01, i02, i10, i11, i12 = _invert_affine(trans)
+    xs, ys = np.arange(out_w, dtype=np.float64), np.arange(out_h, dtype=np.float64)
+    sx = ((np.rint((i01 * ys + i02) * 1024.0).astype(np.int64) + 512)[:, None] + np.rint(i00 * xs * 1024.0).astype(np.int64)[None]) >> 10
+    sy = ((np.rint((i11 * ys + i12) * 1024.0).astype(np.int64) + 512)[:, None] + np.rint(i10 * xs * 1024.0).astype(np.int64)[None]) >> 10
+    sx, sy = np.clip(sx, -32768, 32767), np.clip(sy, -32768, 32767)
+    inside = (sx >= 0) & (sx < w) & (sy >= 0) & (sy < h)
+    px = src[np.clip(sy, 0, h - 1), np.clip(sx, 0, w - 1)]
+    return np.where(inside if src.ndim == 2 else inside[..., None], px, 0).astype(np.uint8)
 
 
 def launch_resize_pad_normalize(images: Sequence[torch.Tensor], target_sizes: Sequence[Tuple[int, int]], padded_size: Tuple[int, int],
@@ -158,6 +196,36 @@ class BottomUpTransform:
         states = dict(zip(self._required_field, args))
         states.update(self.transform(states))
         return tuple(np.asarray(states[k]) for k in self._required_field)
+
+
+@register("transform", extra_name="bottomup_horizontal_random_flip")
+class BottomUpHorizontalRandomFlip(BottomUpTransform):
+    """Random horizontal flip of the augmented sample (:88-140): the image, the ``[:height, :width]`` corner of every stage's mask
+    and every stage's key points (mirrored in that stage's width, left / right joints swapped)."""
+
+    def __init__(self, is_train: bool = True, config: Optional[Dict[str, Any]] = None, flip_prob: float = 0.5) -> None:
+        super().__init__(is_train, config)
+        self.flip_prob = flip_prob
+
+    def draw(self) -> bool:
+        """The one random number of a sample (:128): flip or not."""
+        return bool(np.random.rand() <= self.flip_prob)
+
+    def flip_keypoints(self, keypoints: np.ndarray) -> np.ndarray:
+        """[S, M, K, 3] key points, stage i mirrored in stage i's width, in place (:135-137)."""
+        for i, heatmap_size in enumerate(self._transform_cfg["heatmap_sizes"]):
+            keypoints[i] = fliplr_joints(keypoints[i], heatmap_size[0], flip_index=self._transform_cfg["flip_index"])
+        return keypoints
+
+    def transform(self, state: Dict[str, Any]) -> Dict[str, Any]:
+        """Required: image, mask, keypoints.  Returned: image, mask, keypoints (mask and keypoints are changed in place)."""
+        image, keypoints, mask = state["image"], state["keypoints"], state["mask"]
+        if self.draw():
+            image = np.ascontiguousarray(image[:, ::-1])  # cv2.flip(image, 1)
+            for i, (width, height) in enumerate(self._transform_cfg["heatmap_sizes"]):
+                mask[i, :height, :width] = mask[i, :height, :width][:, ::-1].copy()  # the padding does not move
+            self.flip_keypoints(keypoints)
+        return dict(image=image, keypoints=keypoints, mask=mask)
 
 
 @register("transform", extra_name="bottomup_rescale")
@@ -262,6 +330,150 @@ class BottomUpPad(BottomUpTransform):
         mask = np.zeros((target_height, target_width), dtype=np.uint8)
         mask[:height, :width] = 1
         return dict(image=image, mask=mask)
+
+
+@register("transform", extra_name="bottomup_random_affine")
+class BottomUpRandomAffine(BottomUpTransform):
+    """Random scale, rotation and translation about the image centre (:304-460): the image is warped to ``image_size``, the mask
+    and the key points of stage i to ``heatmap_sizes[i]``, each by a matrix of its own from the same draw."""
+
+    def __init__(self, is_train: bool = True, config: Optional[Dict[str, Any]] = None, rot_factor: float = 30.0,
+                 scale_factor: Tuple[float, float] = (0.75, 1.5), scale_type: str = "short", trans_factor: float = 40.0) -> None:
+        super().__init__(is_train=is_train, config=config)
+        self.max_rotation = rot_factor
+        self.min_scale = scale_factor[0]
+        self.max_scale = scale_factor[1]
+        self.scale_type = scale_type
+        self.trans_factor = trans_factor
+
+    def _get_scale(self, image_size: Tuple[int, int], resized_size: Tuple[int, int]) -> np.ndarray:
+        """The source extent that maps onto ``resized_size`` with its aspect ratio (:337-363): the long or the short side of the
+        image fills the output."""
+        if self.scale_type not in ("long", "short"):
+            raise ValueError(f"Unknown scale type: {self.scale_type}")
+        w, h = image_size
+        w_resized, h_resized = resized_size
+        fit_height = (w / w_resized < h / h_resized) == (self.scale_type == "long")
+        if fit_height:
+            w_pad, h_pad = h / h_resized * w_resized, h
+        else:
+            w_pad, h_pad = w, w / w_resized * h_resized
+        return np.array([w_pad, h_pad], dtype=np.float32)
+
+    def draw(self, width: int, height: int) -> Dict[str, Any]:
+        """The random numbers of one sample, drawn from the global ``np.random`` in the reference's order with its argument
+        expressions (:389-409): scale, rotation and - only with a positive ``trans_factor`` - dx, then dy."""
+        center = np.array((width / 2, height / 2))
+        img_scale = np.array([width, height], dtype=np.float32)
+        aug_scale = np.random.uniform(self.min_scale, self.max_scale)
+        img_scale *= aug_scale
+        aug_rot = np.random.uniform(-self.max_rotation, self.max_rotation)
+        pixel_std = self._transform_cfg["pixel_std"]
+        if self.trans_factor > 0:
+            dx = np.random.randint(-self.trans_factor * img_scale[0] / pixel_std, self.trans_factor * img_scale[0] / pixel_std)
+            dy = np.random.randint(-self.trans_factor * img_scale[1] / pixel_std, self.trans_factor * img_scale[1] / pixel_std)
+            center[0] += dx
+            center[1] += dy
+        return dict(center=center, img_scale=img_scale, rot=aug_rot)
+
+    def matrices(self, draw: Dict[str, Any]) -> np.ndarray:
+        """The 2 x 3 forward matrices of a draw, float64 [S + 1, 2, 3]: the heat-map stages first, the image last (:414-444)."""
+        pixel_std = self._transform_cfg["pixel_std"]
+        sizes = list(self._transform_cfg["heatmap_sizes"]) + [self._transform_cfg["image_size"]]
+        return np.stack([get_affine_transform(center=draw["center"], scale=self._get_scale(draw["img_scale"], size) / pixel_std,
+                                              rot=draw["rot"], output_size=size, pixel_std=pixel_std) for size in sizes])
+
+    @staticmethod
+    def warp_keypoints(keypoints: np.ndarray, mats: np.ndarray) -> np.ndarray:
+        """[S, M, K, 3] key points, stage i through ``mats[i]``, in place (:434)."""
+        for i in range(keypoints.shape[0]):
+            keypoints[i, :, :, 0:2] = warp_affine_joints(keypoints[i, :, :, 0:2], mats[i])
+        return keypoints
+
+    def transform(self, state: Dict[str, Any]) -> Dict[str, Any]:
+        """Required: image (uint8 [H, W, 3]), mask (uint8 [S, H, W]), keypoints (float32 [S, M, K, 3], changed in place).
+        Returned: image at ``image_size``, mask [S, Hmax, Wmax] (stage i in its ``[:H_i, :W_i]`` corner), keypoints."""
+        image, mask, keypoints = state["image"], state["mask"], state["keypoints"]
+        height, width = image.shape[:2]
+        mats = self.matrices(self.draw(width, height))
+        masks = [warp_affine_nearest_u8(mask[i], mats[i], (int(size[0]), int(size[1])))
+                 for i, size in enumerate(self._transform_cfg["heatmap_sizes"])]
+        self.warp_keypoints(keypoints, mats)
+        image_size = self._transform_cfg["image_size"]
+        image = warp_affine_linear_u8(image, mats[-1], (int(image_size[0]), int(image_size[1])))
+        return dict(image=image, mask=np.stack(pad_to_same(masks)), keypoints=keypoints)
+
+
+def bottomup_augment_batch(affine: BottomUpRandomAffine, flip: Optional[BottomUpHorizontalRandomFlip], images: Sequence[torch.Tensor],
+                           masks: Sequence[torch.Tensor], keypoints: Sequence[np.ndarray], normalize_mean=NORMALIZE_MEAN,
+                           normalize_std=NORMALIZE_STD, out: Optional[torch.Tensor] = None) -> Dict[str, Any]:
+    """The two augmentations, Normalize and HWC2CHW for a batch: the device path.
+
+    ``images[i]`` is a contiguous CUDA uint8 [H, W, 3] tensor, ``masks[i]`` the contiguous CUDA uint8 [H, W] mask of the same image
+    (the plane the reference dataset tiles over the stages), ``keypoints[i]`` a host float32 [M_i, K, 3] array in source pixels.
+    Per image, in batch order, ``affine.draw`` and then ``flip.draw()`` consume the global ``np.random`` exactly as the two
+    ``transform`` s run sample by sample would; the S stage key-point sets come from the very functions ``transform`` uses, padded
+    to M = max(M_i); matrices and flags are uploaded and ONE ``mp_bottomup_train_augment`` launch does the pixel work.
+
+    Returns ``dict(image [N, 3, h, w] fp32 - ``out`` when given -, mask [N, S, Hmax, Wmax] uint8, keypoints [N, S, M, K, 3] CUDA fp32,
+    num_persons [N] int32 on the host)``: ``BottomUpGenerateTarget.generate_batch(keypoints, num_persons)`` takes the last two as
+    they are, ``AEMultiLoss(preds, target, mask, tag_ind)`` the mask."""
+    n = len(images)
+    if n == 0 or len(masks) != n or len(keypoints) != n:
+        raise ValueError("one mask and one key-point array per image, at least one image")
+    for im, mk in zip(images, masks):
+        if not torch.is_tensor(im) or not torch.is_tensor(mk) or not im.is_cuda or not mk.is_cuda:
+            raise _lib.MindposeHipError("images and masks must be CUDA uint8 tensors: the HIP path has no CPU fallback")
+        if im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3 or not im.is_contiguous():
+            raise ValueError("every image must be a contiguous uint8 [H, W, 3] tensor")
+        if mk.dtype != torch.uint8 or tuple(mk.shape) != tuple(im.shape[:2]) or not mk.is_contiguous():
+            raise ValueError("every mask must be a contiguous uint8 [H, W] tensor of its image's size")
+    lib = _lib.load()
+    dev = images[0].device
+    cfg = affine._transform_cfg
+    sizes = np.asarray(cfg["heatmap_sizes"]).reshape(-1, 2)
+    s = len(sizes)
+    out_w, out_h = (int(v) for v in cfg["image_size"])
+    wmax, hmax = int(sizes[:, 0].max()), int(sizes[:, 1].max())
+    mats, flags, stage_kps = [], [], []
+    for im, kp in zip(images, keypoints):
+        kp = np.asarray(kp, dtype=np.float32)
+        if kp.ndim != 3 or kp.shape[2] != 3:
+            raise ValueError(f"keypoints must be [M, K, 3] per image, got {kp.shape}")
+        drawn = affine.draw(int(im.shape[1]), int(im.shape[0]))
+        flipped = flip.draw() if flip is not None else False
+        m = affine.matrices(drawn)
+        staged = affine.warp_keypoints(np.repeat(kp[None], s, axis=0), m)  # np.repeat copies: the caller's array is not changed
+        if flipped:
+            flip.flip_keypoints(staged)
+        mats.append(m)
+        flags.append(int(flipped))
+        stage_kps.append(staged)
+    k = stage_kps[0].shape[2]
+    if any(a.shape[2] != k for a in stage_kps):
+        raise ValueError("every image must have the same number of joints")
+    num_persons = np.array([a.shape[1] for a in stage_kps], dtype=np.int32)
+    kp_all = np.zeros((n, s, max(1, int(num_persons.max())), k, 3), np.float32)
+    for i, a in enumerate(stage_kps):
+        kp_all[i, :, :a.shape[1]] = a
+    base = min(im.data_ptr() for im in images)
+    mbase = min(mk.data_ptr() for mk in masks)
+    offs = torch.tensor([[im.data_ptr() - base for im in images], [mk.data_ptr() - mbase for mk in masks]], dtype=torch.int64, device=dev)
+    hw = torch.tensor([[im.shape[0], im.shape[1]] for im in images], dtype=torch.int32, device=dev)
+    trans = torch.from_numpy(np.ascontiguousarray(np.stack(mats), dtype=np.float64).reshape(n, s + 1, 6)).to(dev)
+    fl = None if flip is None else torch.tensor(flags, dtype=torch.int32, device=dev)
+    if out is None:
+        out = torch.empty(n, 3, out_h, out_w, device=dev, dtype=torch.float32)
+    elif tuple(out.shape) != (n, 3, out_h, out_w) or out.dtype != torch.float32 or not out.is_contiguous() or not out.is_cuda:
+        raise ValueError(f"out must be a contiguous CUDA fp32 {(n, 3, out_h, out_w)} tensor")
+    mask_out = torch.empty(n, s, hmax, wmax, device=dev, dtype=torch.uint8)
+    wh = (ctypes.c_int * (2 * s))(*[int(v) for v in sizes.reshape(-1)])
+    m3 = (ctypes.c_float * 3)(*[float(np.float32(v * 255.0)) for v in normalize_mean])
+    s3 = (ctypes.c_float * 3)(*[float(np.float32(v * 255.0)) for v in normalize_std])
+    _lib.check(lib.mp_bottomup_train_augment(base, _lib.ptr(offs[0]), _lib.ptr(hw), mbase, _lib.ptr(offs[1]), _lib.ptr(trans), _lib.ptr(fl), wh,
+                                             _lib.ptr(out), _lib.ptr(mask_out), n, s, out_h, out_w, hmax, wmax, m3, s3, _lib.stream()),
+               "mp_bottomup_train_augment")
+    return dict(image=out, mask=mask_out, keypoints=torch.from_numpy(kp_all).to(dev), num_persons=num_persons)
 
 
 @register("transform", extra_name="bottomup_generate_target")

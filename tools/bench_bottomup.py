@@ -12,7 +12,13 @@
   the fraction of 8 TB/s on its algorithmic bytes (read: the uint8 source; written: three fp32 planes + the mask);
 - refine: the missing-joint refinement of P = 1, 10, 30 persons at the 256 x 416 map - the device path (tag gather, mean tags, one
   ``mp_bottomup_refine_missing`` launch, the download of ``found``) against the host path (``refine_missing_joint`` per person after
-  the two ``.cpu()`` copies of the maps), wall milliseconds per batch, and the kernel alone in device microseconds.
+  the two ``.cpu()`` copies of the maps), wall milliseconds per batch, and the kernel alone in device microseconds;
+- train_augment: the train-time augmentation of a batch, N = 32 sources of 640 x 480 to a 512 x 512 image and the 128 / 256 mask
+  stages, half of the images flipped: the ONE ``mp_bottomup_train_augment`` launch on prepared arguments in device microseconds
+  against the same work composed from what existed before it, in the same run - ``mp_warp_affine`` of the batch, ``mp_flip_width``
+  of the flipped half (the other half copied), and the masks by torch indexing (fixed-point coordinates, gather, ``where``, mirror,
+  pad) from matrices already inverted and uploaded; the two results are compared bit for bit first.  Fraction of 8 TB/s on the
+  algorithmic bytes (read: the uint8 sources and masks; written: three fp32 planes and the padded uint8 mask stages).
 Forward sizes are the recipe's eval images: 512 x 512 (N = 1 and 32) and 512 x 832 (N = 1).
 
 ``--only NAME`` runs one section in this process; without it every section runs in a child process of its own under a time limit
@@ -139,11 +145,88 @@ def refine(persons, steps, h=256, w=416, k=17, num_tags=1):
                 kernel_us=round(kernel_ms * 1000, 2), hbm_fraction=round(nbytes / (kernel_ms * 1e-3) / HBM, 4))
 
 
+def train_augment(steps, n=32, src_w=640, src_h=480):
+    import ctypes
+    from mindpose_amd.data.transform.bottomup_transform import _invert_affine
+    cfg = dict(image_size=[512, 512], max_image_size=[512, 512], heatmap_sizes=[[128, 128], [256, 256]], flip_pairs=[[1, 2]], pixel_std=200.0,
+               tag_per_joint=True)
+    affine = mp.BottomUpRandomAffine(config=cfg)
+    g = torch.Generator().manual_seed(0)
+    images = torch.randint(0, 256, (n, src_h, src_w, 3), dtype=torch.uint8, generator=g).to(DEV)
+    masks = (torch.rand(n, src_h, src_w, generator=g) > 0.2).to(torch.uint8).to(DEV)
+    np.random.seed(0)
+    mats = np.stack([affine.matrices(affine.draw(src_w, src_h)) for _ in range(n)])  # [n, 3, 2, 3]: stages, then the image
+    flags = [1] * (n // 2) + [0] * (n - n // 2)
+    sizes, (out_w, out_h) = cfg["heatmap_sizes"], cfg["image_size"]
+    s, wmax, hmax = len(sizes), 256, 256
+    lib = _lib.load()
+    offs = torch.arange(n, dtype=torch.int64, device=DEV) * (src_h * src_w * 3)
+    moffs = torch.arange(n, dtype=torch.int64, device=DEV) * (src_h * src_w)
+    hw = torch.tensor([[src_h, src_w]] * n, dtype=torch.int32, device=DEV)
+    trans = torch.from_numpy(np.ascontiguousarray(mats.reshape(n, s + 1, 6))).to(DEV)
+    fl = torch.tensor(flags, dtype=torch.int32, device=DEV)
+    out = torch.empty(n, 3, out_h, out_w, device=DEV)
+    mask_out = torch.empty(n, s, hmax, wmax, dtype=torch.uint8, device=DEV)
+    wh = (ctypes.c_int * (2 * s))(*[v for size in sizes for v in size])
+    mean, std = (0.485, 0.456, 0.406), (0.229, 0.224, 0.255)
+    m3 = (ctypes.c_float * 3)(*[float(np.float32(v * 255.0)) for v in mean])
+    s3 = (ctypes.c_float * 3)(*[float(np.float32(v * 255.0)) for v in std])
+
+    def fused():
+        _lib.check(lib.mp_bottomup_train_augment(_lib.ptr(images), _lib.ptr(offs), _lib.ptr(hw), _lib.ptr(masks), _lib.ptr(moffs), _lib.ptr(trans),
+                                                 _lib.ptr(fl), wh, _lib.ptr(out), _lib.ptr(mask_out), n, s, out_h, out_w, hmax, wmax, m3, s3,
+                                                 _lib.stream()), "mp_bottomup_train_augment")
+
+    # the composition: its constant operands are prepared outside the timed region
+    trans_image = trans[:, s].contiguous()
+    warped, composed = torch.empty_like(out), torch.empty_like(out)
+    composed_mask = torch.zeros_like(mask_out)
+    flagged = fl.bool()[:, None, None]
+    stage_terms = []
+    for j, (w, h) in enumerate(sizes):
+        inv = torch.tensor([_invert_affine(mats[i, j]) for i in range(n)], dtype=torch.float64, device=DEV)  # [n, 6]: i00 i01 i02 i10 i11 i12
+        stage_terms.append((inv, torch.arange(w, dtype=torch.float64, device=DEV), torch.arange(h, dtype=torch.float64, device=DEV)))
+    flat_masks = masks.reshape(n, -1)
+
+    def compose_image():
+        _lib.check(lib.mp_warp_affine(_lib.ptr(images), _lib.ptr(offs), _lib.ptr(hw), None, _lib.ptr(trans_image), _lib.ptr(warped), n, out_h,
+                                      out_w, 1, m3, s3, _lib.stream()), "mp_warp_affine")
+        _lib.check(lib.mp_flip_width(_lib.ptr(warped), _lib.ptr(composed), n // 2, 3, out_h, out_w, _lib.stream()), "mp_flip_width")
+        composed[n // 2:].copy_(warped[n // 2:])
+
+    def compose_masks():
+        for j, (inv, xs, ys) in enumerate(stage_terms):
+            w, h = sizes[j]
+            sx = ((torch.round((inv[:, 1, None] * ys + inv[:, 2, None]) * 1024.0).long() + 512)[:, :, None]
+                  + torch.round(inv[:, 0, None] * xs * 1024.0).long()[:, None, :]) >> 10
+            sy = ((torch.round((inv[:, 4, None] * ys + inv[:, 5, None]) * 1024.0).long() + 512)[:, :, None]
+                  + torch.round(inv[:, 3, None] * xs * 1024.0).long()[:, None, :]) >> 10
+            inside = (sx >= 0) & (sx < src_w) & (sy >= 0) & (sy < src_h)
+            flat = (sy.clamp(0, src_h - 1) * src_w + sx.clamp(0, src_w - 1)).reshape(n, -1)
+            plane = torch.where(inside, torch.gather(flat_masks, 1, flat).reshape(n, h, w), 0)
+            composed_mask[:, j, :h, :w] = torch.where(flagged, plane.flip(2), plane)
+
+    fused()
+    compose_image()
+    compose_masks()
+    torch.cuda.synchronize()
+    if not torch.equal(out.view(torch.int32), composed.view(torch.int32)) or not torch.equal(mask_out, composed_mask):
+        raise RuntimeError("the fused launch and the composition disagree")
+    fused_ms = _time(fused, steps)
+    image_ms, masks_ms = _time(compose_image, steps), _time(compose_masks, steps)
+    nbytes = n * (src_h * src_w * 4 + out_h * out_w * 12 + s * hmax * wmax)
+    return dict(n=n, src=[src_w, src_h], image=[out_w, out_h], stages=sizes, flipped=n // 2, fused_us=round(fused_ms * 1000, 2),
+                composed_us=round((image_ms + masks_ms) * 1000, 2), composed_image_us=round(image_ms * 1000, 2),
+                composed_masks_us=round(masks_ms * 1000, 2), ratio=round((image_ms + masks_ms) / fused_ms, 2), mb=round(nbytes / 1e6, 2),
+                hbm_fraction=round(nbytes / (fused_ms * 1e-3) / HBM, 4))
+
+
 SECTIONS = {
     "forward": lambda steps: [forward(a, n, h, w, steps) for a in ("O0", "O2") for n, h, w in ((1, 512, 512), (32, 512, 512), (1, 512, 832))],
     "decoder": lambda steps: [decoder(1, 256, 416, steps), decoder(32, 256, 256, steps)],
     "resize_pad_normalize": resize_pad_normalize,
     "refine": lambda steps: [refine(p, steps) for p in (1, 10, 30)],
+    "train_augment": train_augment,
 }
 
 
