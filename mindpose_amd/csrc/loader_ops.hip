@@ -1,81 +1,122 @@
-// Loader-side kernel of the top-down path: the crop that feeds the network.
-//   cv2.warpAffine(image, trans, (w, h), flags=INTER_LINEAR)   topdown_transform.py:211-216 / :249-254
-//   vision.Normalize(mean*255, std*255) + vision.HWC2CHW()      data_factory.py:129-133
-// fused into one pass: one thread per destination pixel reads <= 4 source pixels (HWC uint8) and writes three fp32
-// planes (or the warped uint8 HWC pixel when only the warp is wanted).
-//
-// The interpolation restates OpenCV's fixed-point INTER_LINEAR path [cv2-knowledge, PARITY UNPINNED: cv2 is not
-// installed here]: the 2x3 matrix is inverted in double, destination coordinates are mapped with AB_BITS = 10
-// fixed-point (per-column / per-row terms rounded separately with cvRound, + round_delta 16), quantised to 1/32 pixel
-// (INTER_BITS = 5), the four bilinear weights are the exact products (32-fx)(32-fy)*32 ... of the 15-bit table, the
-// result is (sum + 2^14) >> 15, BORDER_CONSTANT with value 0.
+// Loader-side pixel kernels: each reads HWC uint8 sources and writes what the network or the loss takes in one pass.
+// The interpolations restate OpenCV's 8-bit fixed-point paths [cv2-knowledge, PARITY UNPINNED: cv2 is not installed here].  They are
+// spelled out here once; each is ONE set of device functions below, shared by every kernel that needs it.
+//   warp, both modes (cv::warpAffine without WARP_INVERSE_MAP, BORDER_CONSTANT 0): the 2x3 matrix is inverted in double
+//     (invert_affine); destination (x, y) maps through AB_BITS = 10 fixed point, the per-row and per-column terms rounded separately
+//     with cvRound: X = cvRound((i01 y + i02) 1024) + round_delta + cvRound(i00 x 1024), likewise Y (row_terms + the column term).
+//   INTER_LINEAR (sample_linear): round_delta 16, X >> 5 is the coordinate in 1/32 pixel (INTER_BITS = 5), its integer part
+//     saturate_cast<short>; the four bilinear weights are the exact products (32-fx)(32-fy)*32 ... of the 15-bit table, the result is
+//     (sum + 2^14) >> 15.
+//   INTER_NEAREST (augment_mask_group): round_delta 512, X >> 10, saturate_cast<short>; the source pixel when it lies inside.
+//   resize, INTER_LINEAR (resize_term + resize_pad_normalize_kernel): scale = src / dst in double; f = (float)((d + 0.5) * scale -
+//     0.5), s = floor(f), f -= s; s < 0 -> (0, 0), s >= src - 1 -> (src - 1, 0); coefficients saturate_cast<short>((1 - f) * 2048),
+//     saturate_cast<short>(f * 2048) (INTER_RESIZE_COEF_BITS = 11); horizontal pass int32 S[sx] * a0 + S[sx + 1] * a1; vertical pass
+//     (((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2, saturated to 0..255.
+// Everything up to the normalise is integer arithmetic on those terms, so no result depends on the thread mapping.
 #include "common.h"
 
 #pragma clang fp contract(off)  // the rounding points of the coordinate arithmetic are part of the result
 
 namespace mp {
-
 namespace {
 
 __device__ __forceinline__ int cv_round(double v) { return (int)rint(v); }  // cvRound: nearest, ties to even
 
+__device__ __forceinline__ int saturate_short(int v) { return v < -32768 ? -32768 : (v > 32767 ? 32767 : v); }
+
+__device__ __forceinline__ void invert_affine(const double* M, double inv[6]) {
+    double D = M[0] * M[4] - M[1] * M[3];
+    D = D != 0.0 ? 1.0 / D : 0.0;
+    const double A11 = M[4] * D, A22 = M[0] * D;
+    const double i0 = A11, i1 = M[1] * (-D), i3 = M[3] * (-D), i4 = A22;
+    inv[0] = i0; inv[1] = i1; inv[3] = i3; inv[4] = i4;
+    inv[2] = -i0 * M[2] - i1 * M[5];
+    inv[5] = -i3 * M[2] - i4 * M[5];
+}
+
+// the fixed-point terms of destination row y
+__device__ __forceinline__ void row_terms(const double* inv, int y, int round_delta, int& X0, int& Y0) {
+    X0 = cv_round((inv[1] * y + inv[2]) * 1024.0) + round_delta;
+    Y0 = cv_round((inv[4] * y + inv[5]) * 1024.0) + round_delta;
+}
+
+// The INTER_LINEAR sample of destination column x of the row whose terms are (X0, Y0): v[c] in 0..255.  mirror_src reads the source
+// at the mirrored column - cv2.flip(image, 1) BEFORE the warp; the coordinates and weights do not change, so it is bit-identical
+// to warping a flipped copy.
+__device__ __forceinline__ void sample_linear(const double* inv, const uint8_t* __restrict__ img, int H, int W, bool mirror_src, int X0,
+                                              int Y0, int x, int v[3]) {
+    const int X = (X0 + cv_round(inv[0] * x * 1024.0)) >> 5, Y = (Y0 + cv_round(inv[3] * x * 1024.0)) >> 5;
+    const int sx = saturate_short(X >> 5), sy = saturate_short(Y >> 5);
+    const int fx = X & 31, fy = Y & 31;
+    const int w00 = (32 - fx) * (32 - fy) * 32, w01 = fx * (32 - fy) * 32, w10 = (32 - fx) * fy * 32, w11 = fx * fy * 32;
+    int acc[3] = {0, 0, 0};
+    auto tap = [&](int yy, int xx, int w) {
+        if (w != 0 && yy >= 0 && yy < H && xx >= 0 && xx < W) {
+            const uint8_t* px = img + ((size_t)yy * W + (mirror_src ? W - 1 - xx : xx)) * 3;
+            acc[0] += w * px[0]; acc[1] += w * px[1]; acc[2] += w * px[2];
+        }
+    };
+    tap(sy, sx, w00); tap(sy, sx + 1, w01); tap(sy + 1, sx, w10); tap(sy + 1, sx + 1, w11);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        v[c] = (acc[c] + (1 << 14)) >> 15;
+        v[c] = v[c] > 255 ? 255 : v[c];
+    }
+}
+
+struct NormConst { float m[3], s[3]; };  // vision.Normalize: mean and std of the 0..255 range
+
+// false for a zero std (MP_ERR_SHAPE at every entry point)
+inline bool fill_norm(const float mean[3], const float stddev[3], NormConst& nc) {
+    for (int c = 0; c < 3; ++c) { nc.m[c] = mean[c]; nc.s[c] = stddev[c]; }
+    return stddev[0] != 0.f && stddev[1] != 0.f && stddev[2] != 0.f;
+}
+
+// Normalize + HWC2CHW of VEC adjacent pixels u[e][c]: (u - mean) / std, a true division, into the three planes that start at o -
+// one 16-byte store per plane for VEC == 4, a scalar store otherwise
+template <int VEC>
+__device__ __forceinline__ void normalize_store(const NormConst& nc, const int (&u)[VEC][3], float* __restrict__ o, size_t plane) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        float f[VEC];
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) f[e] = ((float)u[e][c] - nc.m[c]) / nc.s[c];
+        if constexpr (VEC == 4) *reinterpret_cast<float4*>(o + c * plane) = make_float4(f[0], f[1], f[2], f[3]);
+        else o[c * plane] = f[0];
+    }
+}
+
+// four adjacent pixels per thread leave by one store of 4 * elem_bytes: the row width and the base address must allow it
+inline bool wide_stores(int width, const void* base, size_t elem_bytes) {
+    return width % 4 == 0 && (uintptr_t)base % (4 * elem_bytes) == 0;
+}
+
+// ---- cv2.warpAffine(image, trans, (w, h), flags=INTER_LINEAR) (topdown_transform.py:211-216 / :249-254), with NORMALIZE fused with
+// vision.Normalize(mean*255, std*255) + vision.HWC2CHW() (data_factory.py:129-133): one thread per destination pixel reads <= 4
+// source pixels and writes three fp32 planes, or the warped uint8 HWC pixel when only the warp is wanted.
 template <bool NORMALIZE>
 __global__ __launch_bounds__(256) void warp_affine_kernel(const uint8_t* __restrict__ src, const long long* __restrict__ src_off,
                                                           const int* __restrict__ src_hw, const int* __restrict__ flip,
-                                                          const double* __restrict__ trans, void* __restrict__ out, int out_h, int out_w, float m0, float m1,
-                                                          float m2, float s0, float s1, float s2) {
+                                                          const double* __restrict__ trans, void* __restrict__ out, int out_h, int out_w,
+                                                          NormConst nc) {
     const int n = blockIdx.y;
     __shared__ double inv[6];
-    if (threadIdx.x == 0) {
-        // cv::warpAffine without WARP_INVERSE_MAP: invert M in double
-        const double* M = trans + (size_t)n * 6;
-        double D = M[0] * M[4] - M[1] * M[3];
-        D = D != 0.0 ? 1.0 / D : 0.0;
-        const double A11 = M[4] * D, A22 = M[0] * D;
-        const double i0 = A11, i1 = M[1] * (-D), i3 = M[3] * (-D), i4 = A22;
-        inv[0] = i0; inv[1] = i1; inv[3] = i3; inv[4] = i4;
-        inv[2] = -i0 * M[2] - i1 * M[5];
-        inv[5] = -i3 * M[2] - i4 * M[5];
-    }
+    if (threadIdx.x == 0) invert_affine(trans + (size_t)n * 6, inv);
     __syncthreads();
     const int H = src_hw[2 * n], W = src_hw[2 * n + 1];
-    // cv2.flip(image, 1) before the warp (TopDownHorizontalRandomFlip) = sampling the original at the mirrored column:
-    // the fixed-point coordinates and the bilinear weights are symmetric, so the result is bit-identical
-    const bool mirror = flip && flip[n] != 0;
+    const bool mirror = flip && flip[n] != 0;  // TopDownHorizontalRandomFlip: the flip precedes the warp
     const uint8_t* __restrict__ img = src + src_off[n];
     const int total = out_h * out_w;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
         const int y = i / out_w, x = i - y * out_w;
-        const int adelta = cv_round(inv[0] * x * 1024.0), bdelta = cv_round(inv[3] * x * 1024.0);
-        const int X0 = cv_round((inv[1] * y + inv[2]) * 1024.0) + 16, Y0 = cv_round((inv[4] * y + inv[5]) * 1024.0) + 16;
-        const int X = (X0 + adelta) >> 5, Y = (Y0 + bdelta) >> 5;
-        int sx = X >> 5, sy = Y >> 5;
-        sx = sx < -32768 ? -32768 : (sx > 32767 ? 32767 : sx);  // saturate_cast<short>
-        sy = sy < -32768 ? -32768 : (sy > 32767 ? 32767 : sy);
-        const int fx = X & 31, fy = Y & 31;
-        const int w00 = (32 - fx) * (32 - fy) * 32, w01 = fx * (32 - fy) * 32, w10 = (32 - fx) * fy * 32, w11 = fx * fy * 32;
-        int acc[3] = {0, 0, 0};
-        auto tap = [&](int yy, int xx, int w) {
-            if (w != 0 && yy >= 0 && yy < H && xx >= 0 && xx < W) {
-                const uint8_t* px = img + ((size_t)yy * W + (mirror ? W - 1 - xx : xx)) * 3;
-                acc[0] += w * px[0]; acc[1] += w * px[1]; acc[2] += w * px[2];
-            }
-        };
-        tap(sy, sx, w00); tap(sy, sx + 1, w01); tap(sy + 1, sx, w10); tap(sy + 1, sx + 1, w11);
-        int v[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            v[c] = (acc[c] + (1 << 14)) >> 15;
-            v[c] = v[c] > 255 ? 255 : v[c];
-        }
+        int X0, Y0, v[1][3];
+        row_terms(inv, y, 16, X0, Y0);
+        sample_linear(inv, img, H, W, mirror, X0, Y0, x, v[0]);
         if constexpr (NORMALIZE) {
-            float* o = reinterpret_cast<float*>(out) + (size_t)n * 3 * total;
-            o[i] = ((float)v[0] - m0) / s0;
-            o[total + i] = ((float)v[1] - m1) / s1;
-            o[2 * total + i] = ((float)v[2] - m2) / s2;
+            normalize_store<1>(nc, v, reinterpret_cast<float*>(out) + (size_t)n * 3 * total + i, total);
         } else {
             uint8_t* o = reinterpret_cast<uint8_t*>(out) + ((size_t)n * total + i) * 3;
-            o[0] = (uint8_t)v[0]; o[1] = (uint8_t)v[1]; o[2] = (uint8_t)v[2];
+            o[0] = (uint8_t)v[0][0]; o[1] = (uint8_t)v[0][1]; o[2] = (uint8_t)v[0][2];
         }
     }
 }
@@ -91,16 +132,13 @@ extern "C" int mp_warp_affine(const uint8_t* src, const long long* src_offsets, 
     if (!src || !src_offsets || !src_hw || !trans || !out) return MP_ERR_NULL;
     if (n <= 0 || out_h <= 0 || out_w <= 0 || n > 65535) return MP_ERR_SHAPE;
     if (normalize && (!mean || !stddev)) return MP_ERR_NULL;
-    if (normalize && (stddev[0] == 0.f || stddev[1] == 0.f || stddev[2] == 0.f)) return MP_ERR_SHAPE;
+    NormConst nc{};
+    if (normalize && !fill_norm(mean, stddev, nc)) return MP_ERR_SHAPE;
     const int total = out_h * out_w;
     int bx = (total + 255) / 256;
     if (bx > 1024) bx = 1024;
-    if (normalize)
-        hipLaunchKernelGGL(warp_affine_kernel<true>, dim3(bx, n), dim3(256), 0, as_stream(stream), src, src_offsets, src_hw, flip, trans, out,
-                           out_h, out_w, mean[0], mean[1], mean[2], stddev[0], stddev[1], stddev[2]);
-    else
-        hipLaunchKernelGGL(warp_affine_kernel<false>, dim3(bx, n), dim3(256), 0, as_stream(stream), src, src_offsets, src_hw, flip, trans, out,
-                           out_h, out_w, 0.f, 0.f, 0.f, 1.f, 1.f, 1.f);
+    const auto kernel = normalize ? warp_affine_kernel<true> : warp_affine_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(bx, n), dim3(256), 0, as_stream(stream), src, src_offsets, src_hw, flip, trans, out, out_h, out_w, nc);
     return check_launch();
 }
 
@@ -146,14 +184,8 @@ extern "C" int mp_flip_width(const float* in, float* out, int n, int c, int h, i
 
 // ---- bottom-up evaluation input: BottomUpRescale + BottomUpPad + Normalize + HWC2CHW in one pass (bottomup_transform.py:143-208,
 // :601-645, data_factory.py:129-133).  cv2.resize(image, (tw, th), INTER_LINEAR) on uint8 HWC, zero pad on the right and bottom to
-// (PH, PW), (v - mean) / std per channel, written as three fp32 planes; the mask (1 inside the resized image) leaves by the same launch.
+// (PH, PW), written as three fp32 planes; the mask (1 inside the resized image) leaves by the same launch.
 // The pad happens on the uint8 image, BEFORE Normalize: a padded pixel is (0 - mean) / std, not 0.
-//
-// The interpolation restates OpenCV's 8-bit fixed-point linear resize [cv2-knowledge, PARITY UNPINNED: cv2 is not installed here]:
-// scale = src / dst in double; f = (float)((d + 0.5) * scale - 0.5), s = floor(f), f -= s; s < 0 -> (0, 0), s >= src - 1 ->
-// (src - 1, 0); coefficients saturate_cast<short>((1 - f) * 2048), saturate_cast<short>(f * 2048) (INTER_RESIZE_COEF_BITS = 11);
-// horizontal pass int32 S[sx] * a0 + S[sx + 1] * a1; vertical pass (((b0 * (r0 >> 4)) >> 16) + ((b1 * (r1 >> 4)) >> 16) + 2) >> 2,
-// saturated to 0..255.  Integer arithmetic after the coefficients: the result does not depend on the thread mapping.
 namespace mp {
 namespace {
 
@@ -166,7 +198,7 @@ struct RpnParams {
     float* out;     // [n, 3, PH, PW]
     uint8_t* mask;  // [n, PH, PW]
     int ph, pw;
-    float m[3], s[3];
+    NormConst norm;
     int twh[kRpnMaxImages][2];
 };
 
@@ -200,17 +232,16 @@ __global__ __launch_bounds__(256) void resize_pad_normalize_kernel(RpnParams p) 
     const size_t plane = (size_t)p.ph * p.pw;
     float* __restrict__ o = p.out + (size_t)n * 3 * plane + (size_t)y * p.pw;
     uint8_t* __restrict__ mk = p.mask + (size_t)n * plane + (size_t)y * p.pw;
-    const float pad0 = (0.f - p.m[0]) / p.s[0], pad1 = (0.f - p.m[1]) / p.s[1], pad2 = (0.f - p.m[2]) / p.s[2];
     const double scale_x = (double)W / (double)tw;
     const int groups = (p.pw + VEC - 1) / VEC;
     for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += gridDim.x * blockDim.x) {
-        float v[3][VEC];
+        int u[VEC][3];
         uint8_t in[VEC];
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
             const int x = g * VEC + e;
             in[e] = (y < th && x < tw) ? 1 : 0;
-            v[0][e] = pad0; v[1][e] = pad1; v[2][e] = pad2;
+            u[e][0] = u[e][1] = u[e][2] = 0;  // the pad
             if (in[e]) {
                 int sx, a0, a1;
                 resize_term(x, scale_x, W, sx, a0, a1);
@@ -221,22 +252,14 @@ __global__ __launch_bounds__(256) void resize_pad_normalize_kernel(RpnParams p) 
                 for (int c = 0; c < 3; ++c) {
                     const int h0 = r0[sx * 3 + c] * a0 + r0[sx1 * 3 + c] * a1;
                     const int h1 = r1[sx * 3 + c] * a0 + r1[sx1 * 3 + c] * a1;
-                    int u = (((row[2] * (h0 >> 4)) >> 16) + ((row[3] * (h1 >> 4)) >> 16) + 2) >> 2;
-                    u = u < 0 ? 0 : (u > 255 ? 255 : u);
-                    v[c][e] = ((float)u - p.m[c]) / p.s[c];
+                    const int t = (((row[2] * (h0 >> 4)) >> 16) + ((row[3] * (h1 >> 4)) >> 16) + 2) >> 2;
+                    u[e][c] = t < 0 ? 0 : (t > 255 ? 255 : t);
                 }
             }
         }
-        if constexpr (VEC == 4) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c)
-                *reinterpret_cast<float4*>(o + c * plane + (size_t)g * 4) = make_float4(v[c][0], v[c][1], v[c][2], v[c][3]);
-            *reinterpret_cast<uchar4*>(mk + (size_t)g * 4) = make_uchar4(in[0], in[1], in[2], in[3]);
-        } else {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) o[c * plane + g] = v[c][0];
-            mk[g] = in[0];
-        }
+        normalize_store<VEC>(p.norm, u, o + (size_t)g * VEC, plane);
+        if constexpr (VEC == 4) *reinterpret_cast<uchar4*>(mk + (size_t)g * 4) = make_uchar4(in[0], in[1], in[2], in[3]);
+        else mk[g] = in[0];
     }
 }
 
@@ -248,17 +271,18 @@ extern "C" int mp_resize_pad_normalize(const uint8_t* src, const long long* src_
                                        mp_stream_t stream) {
     if (!src || !src_offsets || !src_hw || !dst_wh_host || !out || !mask || !mean || !stddev) return MP_ERR_NULL;
     if (n <= 0 || pad_h <= 0 || pad_w <= 0 || pad_h > 65535) return MP_ERR_SHAPE;
-    if (stddev[0] == 0.f || stddev[1] == 0.f || stddev[2] == 0.f) return MP_ERR_SHAPE;
+    mp::NormConst nc;
+    if (!mp::fill_norm(mean, stddev, nc)) return MP_ERR_SHAPE;
     for (int i = 0; i < n; ++i) {
         const int tw = dst_wh_host[2 * i], th = dst_wh_host[2 * i + 1];
         if (tw <= 0 || th <= 0 || tw > pad_w || th > pad_h) return MP_ERR_SHAPE;
     }
     const size_t plane = (size_t)pad_h * pad_w;
-    // 16-byte stores need every row of every plane on a 16-byte boundary (and the mask rows on a 4-byte one)
-    const bool wide = pad_w % 4 == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)mask % 4 == 0;
+    const bool wide = mp::wide_stores(pad_w, out, 4) && mp::wide_stores(pad_w, mask, 1);
     const int groups = wide ? pad_w / 4 : pad_w;
     int bx = (groups + 255) / 256;
     if (bx > 64) bx = 64;
+    const auto kernel = wide ? mp::resize_pad_normalize_kernel<4> : mp::resize_pad_normalize_kernel<1>;
     for (int i0 = 0; i0 < n; i0 += mp::kRpnMaxImages) {  // one launch for a batch of up to 32 images
         const int cnt = n - i0 < mp::kRpnMaxImages ? n - i0 : mp::kRpnMaxImages;
         mp::RpnParams p{};
@@ -269,12 +293,9 @@ extern "C" int mp_resize_pad_normalize(const uint8_t* src, const long long* src_
         p.mask = mask + (size_t)i0 * plane;
         p.ph = pad_h;
         p.pw = pad_w;
-        for (int c = 0; c < 3; ++c) { p.m[c] = mean[c]; p.s[c] = stddev[c]; }
+        p.norm = nc;
         for (int i = 0; i < cnt; ++i) { p.twh[i][0] = dst_wh_host[2 * (i0 + i)]; p.twh[i][1] = dst_wh_host[2 * (i0 + i) + 1]; }
-        if (wide)
-            hipLaunchKernelGGL(mp::resize_pad_normalize_kernel<4>, dim3(bx, pad_h, cnt), dim3(256), 0, mp::as_stream(stream), p);
-        else
-            hipLaunchKernelGGL(mp::resize_pad_normalize_kernel<1>, dim3(bx, pad_h, cnt), dim3(256), 0, mp::as_stream(stream), p);
+        hipLaunchKernelGGL(kernel, dim3(bx, pad_h, cnt), dim3(256), 0, mp::as_stream(stream), p);
         const int rc = mp::check_launch();
         if (rc != MP_OK) return rc;
     }
@@ -285,15 +306,14 @@ extern "C" int mp_resize_pad_normalize(const uint8_t* src, const long long* src_
 // HWC2CHW (bottomup_transform.py:304-460, :88-140, data_factory.py:129-133).  Per image the 2x3 matrices of the s heat-map stages and
 // of the image arrive together; a workgroup owns 256 thread-groups of ONE plane - the image or the mask of one stage - so the inverse
 // matrix is formed once per workgroup and the plane kind never diverges inside a wave.
-//   image: warp_affine_kernel<true>'s arithmetic, expression by expression (INTER_LINEAR, 1 / 32 pixel, 15-bit weights, normalise)
-//   mask:  cv2.warpAffine(mask, M, (W_i, H_i), flags=INTER_NEAREST) [cv2-knowledge, PARITY UNPINNED: cv2 is not installed here]:
-//          the same inverse and the same AB_BITS = 10 coordinate terms with round_delta = 512,
-//          X = (cvRound((i01 y + i02) 1024) + 512 + cvRound(i00 x 1024)) >> 10, saturate_cast<short>, the source pixel when it lies
-//          inside, else 0; written into the [:H_i, :W_i] corner of the stage's [hmax, wmax] plane, 0 in the padding.
+//   image: sample_linear + normalize_store, i.e. mp_warp_affine's planes to the bit
+//   mask:  cv2.warpAffine(mask, M, (W_i, H_i), flags=INTER_NEAREST), written into the [:H_i, :W_i] corner of the stage's
+//          [hmax, wmax] plane, 0 in the padding.
 // The flip follows the warp (the reference's order): the value computed for column x is stored at column W - 1 - x.  It cannot be
 // folded into the matrix bit-exactly, because the fixed-point column terms are rounded per destination column - so the thread that
-// stores columns [4g, 4g + 4) computes the mirrored columns and the 16-byte vector leaves in reversed order.
-// Integer arithmetic up to the normalise; every byte of both outputs is written here (no memset pass), no atomics.
+// stores columns [4g, 4g + 4) computes the mirrored columns and the 16-byte vector leaves in reversed order.  (warp_affine_kernel's
+// mirror is the other one: of the SOURCE, before the warp.)
+// Every byte of both outputs is written here (no memset pass), no atomics.
 namespace mp {
 namespace {
 
@@ -311,11 +331,9 @@ struct AugParams {
     uint8_t* mask;  // [n, s, hmax, wmax]
     int s, out_h, out_w, hmax, wmax;
     int img_tiles, mask_tiles;  // workgroups per image plane set / per stage plane
-    float m[3], sd[3];
+    NormConst norm;
     int wh[kAugMaxStages][2];
 };
-
-__device__ __forceinline__ int saturate_short(int v) { return v < -32768 ? -32768 : (v > 32767 ? 32767 : v); }
 
 // VEC adjacent destination pixels of one image row, all three planes
 template <int VEC>
@@ -324,38 +342,13 @@ __device__ __forceinline__ void augment_image_group(const AugParams& p, const do
     const int gpr = p.out_w / VEC;
     if (g >= p.out_h * gpr) return;
     const int y = g / gpr, x0 = (g - y * gpr) * VEC;
-    const int X0 = cv_round((inv[1] * y + inv[2]) * 1024.0) + 16, Y0 = cv_round((inv[4] * y + inv[5]) * 1024.0) + 16;
-    float v[3][VEC];
+    int X0, Y0, u[VEC][3];
+    row_terms(inv, y, 16, X0, Y0);
 #pragma unroll
-    for (int e = 0; e < VEC; ++e) {
-        const int x = mirror ? p.out_w - 1 - (x0 + e) : x0 + e;  // the column this value is computed for
-        const int adelta = cv_round(inv[0] * x * 1024.0), bdelta = cv_round(inv[3] * x * 1024.0);
-        const int X = (X0 + adelta) >> 5, Y = (Y0 + bdelta) >> 5;
-        const int sx = saturate_short(X >> 5), sy = saturate_short(Y >> 5);
-        const int fx = X & 31, fy = Y & 31;
-        const int w00 = (32 - fx) * (32 - fy) * 32, w01 = fx * (32 - fy) * 32, w10 = (32 - fx) * fy * 32, w11 = fx * fy * 32;
-        int acc[3] = {0, 0, 0};
-        auto tap = [&](int yy, int xx, int w) {
-            if (w != 0 && yy >= 0 && yy < H && xx >= 0 && xx < W) {
-                const uint8_t* px = img + ((size_t)yy * W + xx) * 3;
-                acc[0] += w * px[0]; acc[1] += w * px[1]; acc[2] += w * px[2];
-            }
-        };
-        tap(sy, sx, w00); tap(sy, sx + 1, w01); tap(sy + 1, sx, w10); tap(sy + 1, sx + 1, w11);
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            int u = (acc[c] + (1 << 14)) >> 15;
-            u = u > 255 ? 255 : u;
-            v[c][e] = ((float)u - p.m[c]) / p.sd[c];
-        }
-    }
+    for (int e = 0; e < VEC; ++e)  // the value stored at column x0 + e is computed for the mirrored column
+        sample_linear(inv, img, H, W, false, X0, Y0, mirror ? p.out_w - 1 - (x0 + e) : x0 + e, u[e]);
     const size_t plane = (size_t)p.out_h * p.out_w;
-    float* __restrict__ o = p.image + (size_t)n * 3 * plane + (size_t)y * p.out_w + x0;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        if constexpr (VEC == 4) *reinterpret_cast<float4*>(o + c * plane) = make_float4(v[c][0], v[c][1], v[c][2], v[c][3]);
-        else o[c * plane] = v[c][0];
-    }
+    normalize_store<VEC>(p.norm, u, p.image + (size_t)n * 3 * plane + (size_t)y * p.out_w + x0, plane);
 }
 
 // VEC adjacent pixels of one row of one stage's [hmax, wmax] mask plane
@@ -370,7 +363,8 @@ __device__ __forceinline__ void augment_mask_group(const AugParams& p, const dou
 #pragma unroll
     for (int e = 0; e < VEC; ++e) v[e] = 0;
     if (y < sh) {
-        const int X0 = cv_round((inv[1] * y + inv[2]) * 1024.0) + 512, Y0 = cv_round((inv[4] * y + inv[5]) * 1024.0) + 512;
+        int X0, Y0;
+        row_terms(inv, y, 512, X0, Y0);
 #pragma unroll
         for (int e = 0; e < VEC; ++e) {
             if (x0 + e >= sw) continue;
@@ -399,17 +393,7 @@ __global__ __launch_bounds__(256) void bottomup_train_augment_kernel(AugParams p
         tile -= stage * p.mask_tiles;
     }
     __shared__ double inv[6];
-    if (threadIdx.x == 0) {
-        // cv::warpAffine without WARP_INVERSE_MAP: invert M in double (as warp_affine_kernel does)
-        const double* M = p.trans + ((size_t)n * (p.s + 1) + stage) * 6;
-        double D = M[0] * M[4] - M[1] * M[3];
-        D = D != 0.0 ? 1.0 / D : 0.0;
-        const double A11 = M[4] * D, A22 = M[0] * D;
-        const double i0 = A11, i1 = M[1] * (-D), i3 = M[3] * (-D), i4 = A22;
-        inv[0] = i0; inv[1] = i1; inv[3] = i3; inv[4] = i4;
-        inv[2] = -i0 * M[2] - i1 * M[5];
-        inv[5] = -i3 * M[2] - i4 * M[5];
-    }
+    if (threadIdx.x == 0) invert_affine(p.trans + ((size_t)n * (p.s + 1) + stage) * 6, inv);
     __syncthreads();
     const int H = p.src_hw[2 * n], W = p.src_hw[2 * n + 1];
     const bool mirror = p.flip && p.flip[n] != 0;
@@ -429,16 +413,15 @@ extern "C" int mp_bottomup_train_augment(const uint8_t* src, const long long* sr
         return MP_ERR_NULL;
     if (s < 1 || s > mp::kAugMaxStages) return MP_ERR_UNSUPPORTED;
     if (n <= 0 || n > 65535 || out_h <= 0 || out_w <= 0 || hmax <= 0 || wmax <= 0) return MP_ERR_SHAPE;
-    if (stddev[0] == 0.f || stddev[1] == 0.f || stddev[2] == 0.f) return MP_ERR_SHAPE;
+    mp::AugParams p{};
+    if (!mp::fill_norm(mean, stddev, p.norm)) return MP_ERR_SHAPE;
     for (int i = 0; i < s; ++i) {
         const int w = stage_wh_host[2 * i], h = stage_wh_host[2 * i + 1];
         if (w <= 0 || h <= 0 || w > wmax || h > hmax) return MP_ERR_SHAPE;
+        p.wh[i][0] = w; p.wh[i][1] = h;
     }
     if ((long long)out_h * out_w > (1LL << 30) || (long long)hmax * wmax > (1LL << 30)) return MP_ERR_SHAPE;  // group indices are int
-    // 16-byte stores need every row of every plane on a 16-byte boundary, the 4-byte mask stores every mask row on a 4-byte one
-    const bool wide_i = out_w % 4 == 0 && (uintptr_t)image % 16 == 0;
-    const bool wide_m = wmax % 4 == 0 && (uintptr_t)mask % 4 == 0;
-    mp::AugParams p{};
+    const bool wide_i = mp::wide_stores(out_w, image, 4), wide_m = mp::wide_stores(wmax, mask, 1);
     p.src = src; p.src_off = src_offsets; p.src_hw = src_hw;
     p.msrc = mask_src; p.msrc_off = mask_offsets;
     p.trans = trans; p.flip = flip;
@@ -449,12 +432,8 @@ extern "C" int mp_bottomup_train_augment(const uint8_t* src, const long long* sr
     p.mask_tiles = (int)((mask_groups + 255) / 256);
     const long long tiles = (long long)p.img_tiles + (long long)s * p.mask_tiles;
     if (tiles > 0x7fffffffLL) return MP_ERR_SHAPE;
-    for (int c = 0; c < 3; ++c) { p.m[c] = mean[c]; p.sd[c] = stddev[c]; }
-    for (int i = 0; i < s; ++i) { p.wh[i][0] = stage_wh_host[2 * i]; p.wh[i][1] = stage_wh_host[2 * i + 1]; }
-    const dim3 grid((unsigned)tiles, (unsigned)n), block(256);
-    if (wide_i && wide_m) hipLaunchKernelGGL((mp::bottomup_train_augment_kernel<4, 4>), grid, block, 0, mp::as_stream(stream), p);
-    else if (wide_i) hipLaunchKernelGGL((mp::bottomup_train_augment_kernel<4, 1>), grid, block, 0, mp::as_stream(stream), p);
-    else if (wide_m) hipLaunchKernelGGL((mp::bottomup_train_augment_kernel<1, 4>), grid, block, 0, mp::as_stream(stream), p);
-    else hipLaunchKernelGGL((mp::bottomup_train_augment_kernel<1, 1>), grid, block, 0, mp::as_stream(stream), p);
+    const auto kernel = wide_i ? (wide_m ? mp::bottomup_train_augment_kernel<4, 4> : mp::bottomup_train_augment_kernel<4, 1>)
+                               : (wide_m ? mp::bottomup_train_augment_kernel<1, 4> : mp::bottomup_train_augment_kernel<1, 1>);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)tiles, (unsigned)n), dim3(256), 0, mp::as_stream(stream), p);
     return mp::check_launch();
 }

@@ -30,6 +30,7 @@ import torch
 from ... import _lib
 from ...register import register
 from ..column_names import COLUMN_MAP
+from ._launch import norm255, source_batch
 from .topdown_transform import fliplr_joints, get_affine_transform
 from .utils import pad_to_same, warp_affine_joints
 
@@ -84,20 +85,31 @@ def _invert_affine(trans: np.ndarray) -> Tuple[float, float, float, float, float
     return i00, i01, i02, i10, i11, i12
 
 
+def _warp_coords(trans: np.ndarray, size: Tuple[int, int], round_delta: int, shift: int) -> Tuple[np.ndarray, np.ndarray]:
+    """The fixed-point source coordinates (X, Y), int64 [h, w] each, of every pixel of a (w, h) destination as ``cv::warpAffine``
+    forms them: the matrix inverted in double, the 10-bit terms of a row and of a column rounded separately,
+    X = (cvRound((i01 y + i02) 1024) + round_delta + cvRound(i00 x 1024)) >> shift and likewise Y."""
+    out_w, out_h = int(size[0]), int(size[1])
+    i00, i01, i02, i10, i11, i12 = _invert_affine(trans)
+    xs, ys = np.arange(out_w, dtype=np.float64), np.arange(out_h, dtype=np.float64)
+
+    def grid(col, row, offset):
+        return ((np.rint((row * ys + offset) * 1024.0).astype(np.int64) + round_delta)[:, None]
+                + np.rint(col * xs * 1024.0).astype(np.int64)[None]) >> shift
+
+    return grid(i00, i01, i02), grid(i10, i11, i12)
+
+
 def warp_affine_linear_u8(image: np.ndarray, trans: np.ndarray, size: Tuple[int, int]) -> np.ndarray:
     """``cv2.warpAffine(image, trans, (w, h), flags=cv2.INTER_LINEAR)`` of a uint8 [H, W, C] image, border constant 0: the matrix
     inverted in double, coordinates in 10-bit fixed point quantised to 1 / 32 pixel, exact 15-bit bilinear weights - the
     arithmetic of ``mp_warp_affine`` (csrc/loader_ops.hip)."""
     img = np.asarray(image)
     h, w, _ = img.shape
-    out_w, out_h = int(size[0]), int(size[1])
-    i00, i01, i02, i10, i11, i12 = _invert_affine(trans)
-    xs, ys = np.arange(out_w, dtype=np.float64), np.arange(out_h, dtype=np.float64)
-    big_x = ((np.rint((i01 * ys + i02) * 1024.0).astype(np.int64) + 16)[:, None] + np.rint(i00 * xs * 1024.0).astype(np.int64)[None]) >> 5
-    big_y = ((np.rint((i11 * ys + i12) * 1024.0).astype(np.int64) + 16)[:, None] + np.rint(i10 * xs * 1024.0).astype(np.int64)[None]) >> 5
+    big_x, big_y = _warp_coords(trans, size, 16, 5)
     sx, sy = np.clip(big_x >> 5, -32768, 32767), np.clip(big_y >> 5, -32768, 32767)
     fx, fy = big_x & 31, big_y & 31
-    acc = np.zeros((out_h, out_w, img.shape[2]), np.int64)
+    acc = np.zeros(big_x.shape + (img.shape[2],), np.int64)
     for dy, dx, weight in ((0, 0, (32 - fx) * (32 - fy) * 32), (0, 1, fx * (32 - fy) * 32), (1, 0, (32 - fx) * fy * 32),
                            (1, 1, fx * fy * 32)):
         yy, xx = sy + dy, sx + dx
@@ -117,12 +129,7 @@ def warp_affine_nearest_u8(mask: np.ndarray, trans: np.ndarray, size: Tuple[int,
     if src.dtype != np.uint8 or src.ndim not in (2, 3):
         raise ValueError(f"mask must be uint8 [H, W] or [H, W, C], got {src.dtype} {src.shape}")
     h, w = src.shape[:2]
-    out_w, out_h = int(size[0]), int(size[1])
-    i00, i01, i02, i10, i11, i12 = _invert_affine(trans)
-    xs, ys = np.arange(out_w, dtype=np.float64), np.arange(out_h, dtype=np.float64)
-    sx = ((np.rint((i01 * ys + i02) * 1024.0).astype(np.int64) + 512)[:, None] + np.rint(i00 * xs * 1024.0).astype(np.int64)[None]) >> 10
-    sy = ((np.rint((i11 * ys + i12) * 1024.0).astype(np.int64) + 512)[:, None] + np.rint(i10 * xs * 1024.0).astype(np.int64)[None]) >> 10
-    sx, sy = np.clip(sx, -32768, 32767), np.clip(sy, -32768, 32767)
+    sx, sy = (np.clip(v, -32768, 32767) for v in _warp_coords(trans, size, 512, 10))
     inside = (sx >= 0) & (sx < w) & (sy >= 0) & (sy < h)
     px = src[np.clip(sy, 0, h - 1), np.clip(sx, 0, w - 1)]
     return np.where(inside if src.ndim == 2 else inside[..., None], px, 0).astype(np.uint8)
@@ -137,19 +144,12 @@ def launch_resize_pad_normalize(images: Sequence[torch.Tensor], target_sizes: Se
     n = len(images)
     if n == 0 or len(target_sizes) != n:
         raise ValueError("one target size per image, at least one image")
-    dev = images[0].device
-    for im in images:
-        if not im.is_cuda or im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3 or not im.is_contiguous():
-            raise _lib.MindposeHipError("source images must be contiguous CUDA uint8 tensors [H, W, 3] (no CPU fallback)")
+    base, offs, hw, dev = source_batch(images)
     pw, ph = int(padded_size[0]), int(padded_size[1])
-    base = min(im.data_ptr() for im in images)
-    offs = torch.tensor([im.data_ptr() - base for im in images], dtype=torch.int64, device=dev)
-    hw = torch.tensor([[im.shape[0], im.shape[1]] for im in images], dtype=torch.int32, device=dev)
     twh = (ctypes.c_int * (2 * n))(*[int(v) for size in target_sizes for v in size[:2]])
     out = torch.empty(n, 3, ph, pw, device=dev, dtype=torch.float32)
     mask = torch.empty(n, ph, pw, device=dev, dtype=torch.uint8)
-    m3 = (ctypes.c_float * 3)(*[float(np.float32(v * 255.0)) for v in mean])
-    s3 = (ctypes.c_float * 3)(*[float(np.float32(v * 255.0)) for v in std])
+    m3, s3 = norm255(mean, std)
     _lib.check(lib.mp_resize_pad_normalize(base, _lib.ptr(offs), _lib.ptr(hw), twh, _lib.ptr(out), _lib.ptr(mask), n, ph, pw, m3, s3,
                                            _lib.stream()), "mp_resize_pad_normalize")
     return out, mask
@@ -421,15 +421,11 @@ def bottomup_augment_batch(affine: BottomUpRandomAffine, flip: Optional[BottomUp
     n = len(images)
     if n == 0 or len(masks) != n or len(keypoints) != n:
         raise ValueError("one mask and one key-point array per image, at least one image")
-    for im, mk in zip(images, masks):
-        if not torch.is_tensor(im) or not torch.is_tensor(mk) or not im.is_cuda or not mk.is_cuda:
-            raise _lib.MindposeHipError("images and masks must be CUDA uint8 tensors: the HIP path has no CPU fallback")
-        if im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3 or not im.is_contiguous():
-            raise ValueError("every image must be a contiguous uint8 [H, W, 3] tensor")
-        if mk.dtype != torch.uint8 or tuple(mk.shape) != tuple(im.shape[:2]) or not mk.is_contiguous():
-            raise ValueError("every mask must be a contiguous uint8 [H, W] tensor of its image's size")
+    base, offs, hw, dev = source_batch(images, layout_error=ValueError)
+    mbase, moffs, _, _ = source_batch(masks, pixel=(), layout_error=ValueError)
+    if any(tuple(mk.shape) != tuple(im.shape[:2]) for im, mk in zip(images, masks)):
+        raise ValueError("every mask must be a contiguous uint8 [H, W] tensor of its image's size")
     lib = _lib.load()
-    dev = images[0].device
     cfg = affine._transform_cfg
     sizes = np.asarray(cfg["heatmap_sizes"]).reshape(-1, 2)
     s = len(sizes)
@@ -456,10 +452,6 @@ def bottomup_augment_batch(affine: BottomUpRandomAffine, flip: Optional[BottomUp
     kp_all = np.zeros((n, s, max(1, int(num_persons.max())), k, 3), np.float32)
     for i, a in enumerate(stage_kps):
         kp_all[i, :, :a.shape[1]] = a
-    base = min(im.data_ptr() for im in images)
-    mbase = min(mk.data_ptr() for mk in masks)
-    offs = torch.tensor([[im.data_ptr() - base for im in images], [mk.data_ptr() - mbase for mk in masks]], dtype=torch.int64, device=dev)
-    hw = torch.tensor([[im.shape[0], im.shape[1]] for im in images], dtype=torch.int32, device=dev)
     trans = torch.from_numpy(np.ascontiguousarray(np.stack(mats), dtype=np.float64).reshape(n, s + 1, 6)).to(dev)
     fl = None if flip is None else torch.tensor(flags, dtype=torch.int32, device=dev)
     if out is None:
@@ -468,9 +460,8 @@ def bottomup_augment_batch(affine: BottomUpRandomAffine, flip: Optional[BottomUp
         raise ValueError(f"out must be a contiguous CUDA fp32 {(n, 3, out_h, out_w)} tensor")
     mask_out = torch.empty(n, s, hmax, wmax, device=dev, dtype=torch.uint8)
     wh = (ctypes.c_int * (2 * s))(*[int(v) for v in sizes.reshape(-1)])
-    m3 = (ctypes.c_float * 3)(*[float(np.float32(v * 255.0)) for v in normalize_mean])
-    s3 = (ctypes.c_float * 3)(*[float(np.float32(v * 255.0)) for v in normalize_std])
-    _lib.check(lib.mp_bottomup_train_augment(base, _lib.ptr(offs[0]), _lib.ptr(hw), mbase, _lib.ptr(offs[1]), _lib.ptr(trans), _lib.ptr(fl), wh,
+    m3, s3 = norm255(normalize_mean, normalize_std)
+    _lib.check(lib.mp_bottomup_train_augment(base, _lib.ptr(offs), _lib.ptr(hw), mbase, _lib.ptr(moffs), _lib.ptr(trans), _lib.ptr(fl), wh,
                                              _lib.ptr(out), _lib.ptr(mask_out), n, s, out_h, out_w, hmax, wmax, m3, s3, _lib.stream()),
                "mp_bottomup_train_augment")
     return dict(image=out, mask=mask_out, keypoints=torch.from_numpy(kp_all).to(dev), num_persons=num_persons)

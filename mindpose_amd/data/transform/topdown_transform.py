@@ -13,7 +13,6 @@ host (a handful of flops per box), the pixel work - cv2.warpAffine + Normalize +
 a batch of boxes (``TopDownAffine.crop_batch`` -> ``mp_warp_affine``) that writes straight into the network's NCHW fp32
 input buffer, instead of three per-sample passes in dataset worker processes.
 """
-import ctypes
 from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
@@ -21,6 +20,7 @@ import torch
 
 from ... import _lib
 from ...register import register
+from ._launch import norm255, source_batch
 
 
 @register("transform", extra_name="topdown_generate_target")
@@ -231,13 +231,7 @@ def launch_warp_affine(images: Sequence[torch.Tensor], index: Sequence[int], mat
     lib = _lib.load()
     h, w = int(out_hw[0]), int(out_hw[1])
     n = len(index)
-    dev = images[0].device
-    for im in images:
-        if not im.is_cuda or im.dtype != torch.uint8 or im.dim() != 3 or im.shape[2] != 3 or not im.is_contiguous():
-            raise _lib.MindposeHipError("source images must be contiguous CUDA uint8 tensors [H, W, 3] (no CPU fallback)")
-    base = images[0].data_ptr()
-    offs = torch.tensor([images[i].data_ptr() - base for i in index], dtype=torch.int64, device=dev)
-    hw = torch.tensor([[images[i].shape[0], images[i].shape[1]] for i in index], dtype=torch.int32, device=dev)
+    base, offs, hw, dev = source_batch(images, index)
     tr = torch.from_numpy(np.ascontiguousarray(mats, dtype=np.float64).reshape(n, 6)).to(dev)
     fl = None if flips is None else torch.tensor([int(bool(f)) for f in flips], dtype=torch.int32, device=dev)
     if out is None:
@@ -246,8 +240,7 @@ def launch_warp_affine(images: Sequence[torch.Tensor], index: Sequence[int], mat
     want = (n, 3, h, w) if normalize else (n, h, w, 3)
     if tuple(out.shape) != want or not out.is_contiguous() or out.dtype != (torch.float32 if normalize else torch.uint8):
         raise ValueError(f"out must be a contiguous {want} tensor")
-    m3 = (ctypes.c_float * 3)(*[float(np.float32(v * 255.0)) for v in mean])
-    s3 = (ctypes.c_float * 3)(*[float(np.float32(v * 255.0)) for v in std])
+    m3, s3 = norm255(mean, std)
     _lib.check(lib.mp_warp_affine(base, _lib.ptr(offs), _lib.ptr(hw), _lib.ptr(fl), _lib.ptr(tr), _lib.ptr(out), n, h, w, int(normalize),
                                   m3, s3, _lib.stream()), "mp_warp_affine")
     return out

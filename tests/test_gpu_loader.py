@@ -235,3 +235,28 @@ def test_prefetched_batches_equal_the_synchronous_ones(tmp_path):
     next(it)
     it.close()
     assert not [t for t in threading.enumerate() if t.name == "mindpose-loader-prefetch" and t.is_alive()]
+
+
+def test_warp_only_with_flips_views_of_one_buffer():
+    """The uint8 output (normalize = 0) together with per-image flips: the mirror of the source, the clamp and the HWC store at
+    once, on two odd-sized images that are views of one buffer, through a rotation + translation that leaves part of the output
+    outside the source."""
+    from mindpose_amd.data.transform.bottomup_transform import warp_affine_linear_u8
+    from mindpose_amd.data.transform.topdown_transform import launch_warp_affine
+    rng = np.random.RandomState(3)
+    shapes = [(13, 9, 3), (7, 11, 3)]
+    imgs = [rng.randint(0, 256, s).astype(np.uint8) for s in shapes]
+    buf = torch.from_numpy(np.concatenate([i.reshape(-1) for i in imgs])).to(DEV)
+    first = int(np.prod(shapes[0]))
+    views = [buf[:first].view(shapes[0]), buf[first:].view(shapes[1])]
+    c, s = np.cos(0.6), np.sin(0.6)
+    mats = np.array([[[c, -s, 3.5], [s, c, -2.25]], [[0.8 * c, 0.8 * s, -1.5], [-0.8 * s, 0.8 * c, 4.0]]])
+    flips = [1, 0]
+    got = launch_warp_affine(views, [0, 1], mats, (10, 6), False, None, mp.TopDownAffine.NORMALIZE_MEAN, mp.TopDownAffine.NORMALIZE_STD,
+                             flips=flips).cpu().numpy()
+    assert got.shape == (2, 10, 6, 3) and got.dtype == np.uint8
+    for i in range(2):
+        src = np.ascontiguousarray(imgs[i][:, ::-1]) if flips[i] else imgs[i]
+        want = warp_affine_linear_u8(src, mats[i], (6, 10))
+        assert (want == 0).all(axis=2).any() and (want != 0).any(), i  # partly outside the source, partly inside
+        assert np.array_equal(got[i], want), i

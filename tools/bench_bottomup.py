@@ -37,6 +37,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import mindpose_amd as mp  # noqa: E402
 from mindpose_amd import _lib  # noqa: E402
+from mindpose_amd.data.transform._launch import norm255, source_batch  # noqa: E402
 from mindpose_amd.data.transform.bottomup_transform import launch_resize_pad_normalize  # noqa: E402
 from mindpose_amd.engine.inferencer.bottomup_inferencer import BottomUpHeatMapAEInferencer, refine_missing_joint  # noqa: E402
 from mindpose_amd.utils.match import match_by_tag  # noqa: E402
@@ -95,11 +96,10 @@ def resize_pad_normalize(steps):
     # the kernel alone: the C entry on prepared arguments
     import ctypes
     lib = _lib.load()
-    offs, hw = torch.zeros(1, dtype=torch.int64, device=DEV), torch.tensor([[src_h, src_w]], dtype=torch.int32, device=DEV)
+    _, offs, hw, _ = source_batch([image])
     out, mask = torch.empty(1, 3, ph, pw, device=DEV), torch.empty(1, ph, pw, dtype=torch.uint8, device=DEV)
     twh = (ctypes.c_int * 2)(tw, th)
-    m3 = (ctypes.c_float * 3)(*[v * 255.0 for v in mean])
-    s3 = (ctypes.c_float * 3)(*[v * 255.0 for v in std])
+    m3, s3 = norm255(mean, std)
     kernel_ms = _time(lambda: lib.mp_resize_pad_normalize(_lib.ptr(image), _lib.ptr(offs), _lib.ptr(hw), twh, _lib.ptr(out), _lib.ptr(mask), 1,
                                                           ph, pw, m3, s3, _lib.stream()), steps)
     nbytes = src_h * src_w * 3 + ph * pw * (3 * 4 + 1)
@@ -160,17 +160,14 @@ def train_augment(steps, n=32, src_w=640, src_h=480):
     sizes, (out_w, out_h) = cfg["heatmap_sizes"], cfg["image_size"]
     s, wmax, hmax = len(sizes), 256, 256
     lib = _lib.load()
-    offs = torch.arange(n, dtype=torch.int64, device=DEV) * (src_h * src_w * 3)
-    moffs = torch.arange(n, dtype=torch.int64, device=DEV) * (src_h * src_w)
-    hw = torch.tensor([[src_h, src_w]] * n, dtype=torch.int32, device=DEV)
+    _, offs, hw, _ = source_batch(list(images))
+    _, moffs, _, _ = source_batch(list(masks), pixel=())
     trans = torch.from_numpy(np.ascontiguousarray(mats.reshape(n, s + 1, 6))).to(DEV)
     fl = torch.tensor(flags, dtype=torch.int32, device=DEV)
     out = torch.empty(n, 3, out_h, out_w, device=DEV)
     mask_out = torch.empty(n, s, hmax, wmax, dtype=torch.uint8, device=DEV)
     wh = (ctypes.c_int * (2 * s))(*[v for size in sizes for v in size])
-    mean, std = (0.485, 0.456, 0.406), (0.229, 0.224, 0.255)
-    m3 = (ctypes.c_float * 3)(*[float(np.float32(v * 255.0)) for v in mean])
-    s3 = (ctypes.c_float * 3)(*[float(np.float32(v * 255.0)) for v in std])
+    m3, s3 = norm255((0.485, 0.456, 0.406), (0.229, 0.224, 0.255))
 
     def fused():
         _lib.check(lib.mp_bottomup_train_augment(_lib.ptr(images), _lib.ptr(offs), _lib.ptr(hw), _lib.ptr(masks), _lib.ptr(moffs), _lib.ptr(trans),
