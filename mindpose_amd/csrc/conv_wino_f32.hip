@@ -33,6 +33,8 @@ constexpr int kTP = 48;   // tile pitch of V (floats), tiles per workgroup <= 48
 constexpr int kXP = 52;   // tile pitch of the accumulator exchange
 constexpr int kVFloats = 16 * kCK * kTP;
 constexpr int kXFloats = 16 * 16 * kXP;
+constexpr size_t kMaxLds = 150 * 1024;    // dynamic LDS a launch may ask for
+constexpr int kGroupTeamsMinWgs = 128;    // image-grouped bands take two teams when that still leaves this many workgroups
 
 __device__ __forceinline__ void wg_barrier() {
     // LDS traffic of this wave done, then the workgroup barrier; global loads stay in flight (a __syncthreads() would drain them)
@@ -46,6 +48,9 @@ __device__ __forceinline__ void wg_barrier() {
 // are consecutive tiles, not neighbours in a row.
 // TEAMS = 2: 512 threads = two teams of four waves on ONE band: the teams share the raw rows, the input transform (done by team 0)
 // and V, and each computes its own 32 output channels of a 64-channel cout tile - the transform work per MFMA halves.
+// GROUP with TEAMS = 2: the same sharing of the grouped raw planes and V, but the transform is split the other way - every thread
+// of BOTH teams takes one tile (XF1 below) instead of team 0's threads taking two: the pair form's 64 patch registers beside the
+// per-element staging offsets do not fit the 256 registers of an eight-wave workgroup (hipcc spilled 8 of them).
 template <int NI, bool QROW, bool GROUP, int TEAMS>
 __global__ __launch_bounds__(256 * TEAMS, TEAMS == 1 ? 2 : 1) void conv_wino_f32_kernel(const WinoParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -133,13 +138,17 @@ __global__ __launch_bounds__(256 * TEAMS, TEAMS == 1 ? 2 : 1) void conv_wino_f32
 
     // transform item of this thread: (cin, pair of adjacent tiles); the threads beyond the item count repeat the first items
     // (same values to the same addresses) so that the transform needs no branch
+    // XF1 (image-grouped bands, two teams): (cin, ONE tile) items over all 512 threads - both teams transform, half the patch
+    // registers of the pair form, which the eight-wave workgroup has no room for
+    constexpr bool XF1 = GROUP && TEAMS == 2;
     const int pairs = p.M >> 1;
     int xf_raw = 0, xf_rawb = 0, xf_v = 0;  // patch of the first tile, of the second tile (GROUP), V offset of the pair
     {
-        const int items = kCK * pairs;  // <= 192
-        const unsigned t = (unsigned)tid % (unsigned)items;
-        const unsigned c = fastdiv(t, pairs, p.magic_pairs);
-        const unsigned tile0 = (t - c * pairs) * 2;
+        const int per_c = XF1 ? p.M : pairs;
+        const int items = kCK * per_c;  // <= 192 (XF1: <= 384)
+        const unsigned t = (unsigned)(XF1 ? tid_wg : tid) % (unsigned)items;
+        const unsigned c = XF1 ? t / (unsigned)per_c : fastdiv(t, pairs, p.magic_pairs);
+        const unsigned tile0 = (t - c * per_c) * (XF1 ? 1 : 2);
         auto patch = [&](unsigned tile) {
             unsigned g = 0, r = tile;
             if constexpr (GROUP) {
@@ -150,7 +159,7 @@ __global__ __launch_bounds__(256 * TEAMS, TEAMS == 1 ? 2 : 1) void conv_wino_f32
             return (int)(c * p.cin_plane + g * p.img_plane + (2 * ty) * p.Wp + 2 * tx);
         };
         xf_raw = patch(tile0);
-        xf_rawb = GROUP ? patch(tile0 + 1) : xf_raw + 2;
+        xf_rawb = XF1 ? xf_raw : GROUP ? patch(tile0 + 1) : xf_raw + 2;
         xf_v = c * kTP + tile0;
     }
 
@@ -200,13 +209,16 @@ __global__ __launch_bounds__(256 * TEAMS, TEAMS == 1 ? 2 : 1) void conv_wino_f32
     // input transform of one chunk: raw[rb] -> V[vb]; split in three parts so that the MFMA stream can be woven between them
     // columns 0..3 = patch of the first tile; the second tile's patch is columns 2..5 (its row neighbour) or, GROUP, its own
     // four columns 4..7 (consecutive tiles need not be neighbours there)
-    constexpr int XC = GROUP ? 8 : 6, XB = GROUP ? 4 : 2;
+    constexpr int XC = XF1 ? 4 : GROUP ? 8 : 6, XB = XF1 ? 0 : GROUP ? 4 : 2;
     float xd[4][XC], xt[4][XC];
     auto xf_read = [&](int rb) {
         const float* __restrict__ src = lds_raw + rb * raw_buf + xf_raw;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            if constexpr (GROUP) {
+            if constexpr (XF1) {
+                const float2 a0 = *reinterpret_cast<const float2*>(src + r * p.Wp), a1 = *reinterpret_cast<const float2*>(src + r * p.Wp + 2);
+                xd[r][0] = a0.x; xd[r][1] = a0.y; xd[r][2] = a1.x; xd[r][3] = a1.y;
+            } else if constexpr (GROUP) {
                 const float* __restrict__ srcb = lds_raw + rb * raw_buf + xf_rawb;
                 const float2 a0 = *reinterpret_cast<const float2*>(src + r * p.Wp), a1 = *reinterpret_cast<const float2*>(src + r * p.Wp + 2);
                 const float2 b0 = *reinterpret_cast<const float2*>(srcb + r * p.Wp), b1 = *reinterpret_cast<const float2*>(srcb + r * p.Wp + 2);
@@ -232,6 +244,11 @@ __global__ __launch_bounds__(256 * TEAMS, TEAMS == 1 ? 2 : 1) void conv_wino_f32
         float* __restrict__ dst = lds_v + vb * kVFloats + xf_v;
         float va[4], vbv[4];
         va[0] = xt[i][0] - xt[i][2]; va[1] = xt[i][1] + xt[i][2]; va[2] = xt[i][2] - xt[i][1]; va[3] = xt[i][1] - xt[i][3];
+        if constexpr (XF1) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) dst[(i * 4 + j) * (kCK * kTP)] = va[j];
+            return;
+        }
         vbv[0] = xt[i][XB] - xt[i][XB + 2]; vbv[1] = xt[i][XB + 1] + xt[i][XB + 2]; vbv[2] = xt[i][XB + 2] - xt[i][XB + 1];
         vbv[3] = xt[i][XB + 1] - xt[i][XB + 3];
 #pragma unroll
@@ -295,7 +312,7 @@ __global__ __launch_bounds__(256 * TEAMS, TEAMS == 1 ? 2 : 1) void conv_wino_f32
             for (int nb = 0; nb < 2; ++nb) acc[i][mb][nb] = (f32x4){0.f, 0.f, 0.f, 0.f};
     stage_store(0);
     wg_barrier();
-    if (team == 0) {
+    if (XF1 || team == 0) {
         xf_read(0);
         xf_cols();
 #pragma unroll
@@ -319,7 +336,7 @@ __global__ __launch_bounds__(256 * TEAMS, TEAMS == 1 ? 2 : 1) void conv_wino_f32
         MP_STAMP(t0);
         stage_load(ch + 2);
         const float* __restrict__ vcur = lds_v + par * kVFloats + a_base;
-        if (TEAMS == 1 || team == 0) xf_read(par ^ 1);
+        if (TEAMS == 1 || XF1 || team == 0) xf_read(par ^ 1);
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
 #pragma unroll
@@ -333,7 +350,7 @@ __global__ __launch_bounds__(256 * TEAMS, TEAMS == 1 ? 2 : 1) void conv_wino_f32
 #pragma unroll
                     for (int nb = 0; nb < 2; ++nb)
                         acc[i][mb][nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[mb], ucur[i][nb][q], acc[i][mb][nb], 0, 0, 0);
-                if (TEAMS == 1 || team == 0) {  // (team: wave-uniform)
+                if (TEAMS == 1 || XF1 || team == 0) {  // (team: wave-uniform)
                     if (q == 0 && i == 1) xf_cols();
                     if (q == 0 && i >= 2) xf_rows_write(par ^ 1, i - 2);
                     if (q == 1 && i < 2) xf_rows_write(par ^ 1, i + 2);
@@ -544,9 +561,17 @@ int wino_configure(const mp_conv_desc* d, WinoLaunch& L) {
         const long long wgs2 = (long long)((p.Cout_pad16 + 63) / 64) * ((d->h + 2 * tr - 1) / (2 * tr)) * d->n;
         if (wgs2 >= 256) L.teams = 2;
     }
+    // image-grouped bands: every 32-channel cout tile restages and retransforms the same G images (eightfold at 256 channels), so
+    // the shared transform pays with fewer workgroups than above: 256 -> 256 at 8x6, N = 128 is 128 two-team workgroups, one on
+    // every second CU.  Alone on the chip that launch is slower than 256 one-team workgroups (72 against 62 us); inside the
+    // inference plan, where the other branches' lanes take the CUs it leaves, the step gains 1.8 %
+    if (L.group && p.Cout_pad16 >= 64 && !(d->flags & MP_CONV_SHARES_CUS) && p.tpi > 0) {
+        const int g = kTP / p.tpi < d->n ? kTP / p.tpi : d->n;
+        if (g > 0 && (long long)((p.Cout_pad16 + 63) / 64) * ((d->n + g - 1) / g) >= kGroupTeamsMinWgs) L.teams = 2;
+    }
     if (const char* e = knob("MP_WINO_TEAMS")) {  // experiments
         if (atoi(e) == 1) L.teams = 1;
-        if (atoi(e) == 2 && !L.group) L.teams = 2;
+        if (atoi(e) == 2) L.teams = 2;
     }
     p.n_ct = (p.Cout_pad16 + 32 * L.teams - 1) / (32 * L.teams);
     if (L.group) {
@@ -561,6 +586,10 @@ int wino_configure(const mp_conv_desc* d, WinoLaunch& L) {
         p.Wp = d->w + 4;  // even: 8-byte patch reads
         p.img_plane = p.Rin * p.Wp;
         p.cin_plane = (p.G * p.img_plane + 3) / 4 * 4;
+        if (L.teams == 2 && (size_t)2 * (kCK * p.cin_plane + 4) * 4 + (size_t)2 * kXFloats * 4 > kMaxLds) {  // tall narrow maps: the
+            L.teams = 1;                                                                                    // second exchange buffer does not fit
+            p.n_ct = (p.Cout_pad16 + 31) / 32;
+        }
         p.bands = (d->n + p.G - 1) / p.G;  // image groups
         p.total_blocks = p.n_ct * p.bands;
         p.upr = d->h * d->w / 4;
@@ -595,7 +624,7 @@ int wino_configure(const mp_conv_desc* d, WinoLaunch& L) {
     const size_t raw_bytes = (size_t)2 * (kCK * p.cin_plane + 4) * 4, v_bytes = (size_t)2 * kVFloats * 4, x_bytes = (size_t)L.teams * kXFloats * 4;
     L.lds_bytes = raw_bytes + (v_bytes > x_bytes ? v_bytes : x_bytes);
     L.ni = (kCK * p.upc + 256 * L.teams - 1) / (256 * L.teams);
-    if (L.lds_bytes > 150 * 1024) return MP_ERR_UNSUPPORTED;
+    if (L.lds_bytes > kMaxLds) return MP_ERR_UNSUPPORTED;
     return MP_OK;
 }
 
@@ -614,6 +643,8 @@ int wino_launch(const WinoLaunch& L0, hipStream_t s) {
     // QROW: the four tiles of an epilogue item are eight consecutive pixels of two rows
     const bool qrow = !L.group && L.p.M == kTP && L.p.TW % 4 == 0 && L.p.H % L.p.R == 0;
     if (L.group) {
+        if (L.teams == 2)  // 512 staging threads over at most 8 x 48 units: always one unit per thread
+            return L.ni == 1 ? go(conv_wino_f32_kernel<1, false, true, 2>) : MP_ERR_UNSUPPORTED;
         switch (L.ni) {
             case 1: return go(conv_wino_f32_kernel<1, false, true, 1>);
             case 2: return go(conv_wino_f32_kernel<2, false, true, 1>);

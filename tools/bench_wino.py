@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """fp32 Winograd F(2x2,3x3) kernel against the direct MFMA kernel and torch on the HRNet branch shapes.
-   python tools/bench_wino.py [N]"""
+   python tools/bench_wino.py [N]      (MP_WINO_TEAMS / MP_WINO_TILES force a workgroup form, e.g. MP_WINO_TEAMS=1 for the one-team
+   form of the image-grouped 256->256 @8x6 layer)"""
 import ctypes, os, statistics, sys
+os.environ.setdefault("MINDPOSE_EXPERIMENT_KNOBS", "1")  # the MP_* knobs are honoured only then
 import torch
 import torch.nn.functional as F
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -57,7 +59,7 @@ for cin, cout, h, w in SHAPES:
 import numpy as np
 dbg = torch.zeros(1 << 20, dtype=torch.int64, device=dev)
 if lib.mp_debug_set_stamp_buffer(dbg.data_ptr(), dbg.numel() * 8) == 0:
-    for cin, cout, h, w in SHAPES[:4]:
+    for cin, cout, h, w in SHAPES[:4] + SHAPES[-1:]:
         x = torch.randn(n, cin, h, w, device=dev); wt = torch.randn(cout, cin, 3, 3, device=dev)
         scale = torch.ones(cout, device=dev); shift = torch.zeros(cout, device=dev); ow = torch.empty(n, cout, h, w, device=dev)
         d = _lib.ConvDesc(n=n, cin=cin, h=h, w=w, cout=cout, kh=3, kw=3, stride=1, pad_top=1, pad_left=1, conv_h=h, conv_w=w, out_h=h,
