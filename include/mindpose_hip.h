@@ -583,6 +583,24 @@ int mp_bottomup_gather(const float* heatmap_raw_dev, const float* tagging_dev, c
                        int n, int k, int h, int w, int tag_per_joint, int num_tags, int max_num, int shift_coordinate,
                        float* val_k_dev, float* ind_k_dev, float* tag_k_dev, mp_stream_t stream);
 
+/* mp_bottomup_parse_nms_topk_flip: mp_bottomup_parse_nms_topk for the flip test (mindpose/engine/inferencer/bottomup_inferencer.py:
+ * 252-297, _MultiRunNet), folding the outputs of the horizontally mirrored image into the same launch.  flipped_stages[i] is the
+ * output of the mirrored run beside stages[i] (same c, h, w, has_tags, else MP_ERR_SHAPE); flip_index_host [k] is a HOST array, joint
+ * j of the plain run meeting channel flip_index[j] of the mirrored one.  At stage resolution, before any resize (the resize has no
+ * half-pixel centres, so it does not commute with the mirror; each of its four taps is the averaged value):
+ *     heat_i[n,j,y,x] = (stages_i[n,j,y,x] + flipped_i[n,flip_index[j],y,w_i-1-x]) * 0.5f     (one fp32 add, one fp32 multiply)
+ * and on the last axis of tagging [n,k,H,W,2L] the L plain tags stages_i[n,k+j,y,x] in stage order, then the L mirrored-back tags
+ * flipped_i[n,k+flip_index[j],y,w_i-1-x] in the same order; everything after that (stage mean, the un-mirrored mask, NMS, per-tile
+ * top-k, the workspace) is mp_bottomup_parse_nms_topk's, and mp_bottomup_gather follows with num_tags = 2L.  The mirrored maps are
+ * never flipped, averaged or concatenated in memory.
+ * Refusals, all before the launch: a NULL array or data pointer MP_ERR_NULL; a flip_index entry outside [0, k) MP_ERR_SHAPE (the
+ * entry copies the index into the kernel parameters, so no caller can make the kernel read outside a stage); tag_per_joint == 0
+ * (the reference indexes the single tag channel with the k-long flip_index: out of range), k > 64 or 2L > 4 MP_ERR_UNSUPPORTED. */
+int mp_bottomup_parse_nms_topk_flip(const mp_bottomup_stage* stages_host, const mp_bottomup_stage* flipped_stages_host,
+                                    const int32_t* flip_index_host, int num_stages, const uint8_t* mask_dev, int mask_h, int mask_w,
+                                    int n, int k, int tag_per_joint, int nms_kernel, int max_num, float* heatmap_raw_dev,
+                                    float* tagging_dev, void* workspace_dev, size_t workspace_bytes, mp_stream_t stream);
+
 /* mp_bottomup_refine_missing (mindpose/engine/inferencer/bottomup_inferencer.py:189-250, refine_missing_joint): for every person p
  * of a batch's person list (image person_image[p], mean tag mean_tag [P, L] formed by the caller) and every joint, the first
  * arg-max in flat index over the joint's H x W map of  heatmap_raw - rint(sqrt(sum_l (tagging_l - mean_tag_l)^2))  in fp32 (tag

@@ -194,6 +194,8 @@ _PROTOTYPES = {
     "mp_bottomup_workspace_bytes": (c_size_t, [c_int] * 5),
     "mp_bottomup_parse_nms_topk": (c_int, [ctypes.POINTER(BottomUpStage), c_int, c_f32p] + [c_int] * 7 + [c_f32p, c_f32p, c_f32p, c_size_t,
                                                                                                      ctypes.c_void_p]),
+    "mp_bottomup_parse_nms_topk_flip": (c_int, [ctypes.POINTER(BottomUpStage)] * 2 + [ctypes.POINTER(ctypes.c_int32), c_int, c_f32p]
+                                        + [c_int] * 7 + [c_f32p, c_f32p, c_f32p, c_size_t, ctypes.c_void_p]),
     "mp_bottomup_gather": (c_int, [c_f32p, c_f32p, c_f32p, c_size_t] + [c_int] * 8 + [c_f32p, c_f32p, c_f32p, ctypes.c_void_p]),
     "mp_bottomup_refine_missing": (c_int, [c_f32p] * 4 + [c_int] * 7 + [c_f32p, ctypes.c_void_p]),
     "mp_resize_pad_normalize": (c_int, [c_f32p] * 3 + [ctypes.POINTER(ctypes.c_int)] + [c_f32p] * 2 + [c_int] * 3

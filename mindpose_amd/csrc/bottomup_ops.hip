@@ -25,6 +25,12 @@
 //   - shift_coordinate quirk: masked_select returns the max_num selected pixels in FLAT-INDEX order, but the offsets are added
 //     to ind_k, which is in VALUE order: entry m gets sign(diff) * 0.25 of the m-th smallest selected flat index.
 //
+// Flip test (bottomup_inferencer.py:252-297 of the reference, _MultiRunNet): bu_parse_flip_kernel is the same kernel body reading a
+// second set of stage tensors, the outputs of the horizontally mirrored image.  Every tap of a heat map is
+// (a[k][y][x] + b[f[k]][y][ws - 1 - x]) * 0.5f at STAGE resolution (the resize has no half-pixel centres, so mirroring and resizing
+// do not commute), and the tags of the mirrored run, b[K + f[k]][y][ws - 1 - x], follow the plain ones on the last axis of
+// tagging (num_tags = 2 L).  The mirrored maps are never flipped, gathered, averaged or concatenated in memory.
+//
 // fp contraction is OFF in this file: the resize / mean arithmetic restates MindSpore's fp32 expressions and is compared
 // bit-for-bit with a CPU restatement on dyadic inputs.
 #include "common.h"
@@ -46,6 +52,7 @@ constexpr int kBuMaxM = 64;
 constexpr int kBuMergeKeys = 4096;
 constexpr int kBuMergeThreads = 512;
 constexpr int kBuMaxTags = 4;
+constexpr int kBuFlipMaxJoints = 64;  // the flip form carries the joint permutation by value in its kernel parameters
 
 struct BuStage {
     const float* data;  // [N, C, Hs, Ws]
@@ -66,6 +73,28 @@ struct BuParseParams {
     unsigned long long* slab;     // [N, K, tiles, M]
 };
 
+// the mirrored run of the flip test: the stage tensors of net(flip_W(image)), shaped as st[], and the joint permutation
+struct BuFlip {
+    const float* data[kBuMaxStages];
+    int index[kBuFlipMaxJoints];  // joint k reads channel index[k] of the mirrored run; every entry validated on the host
+};
+
+// One pixel of a stage plane as the resize sees it.  kTapPlain: the plane itself.  kTapMean: the flip test's heat map, the mean of
+// the plane and the mirrored run's plane read at the mirrored column (one add, one multiply).  kTapMirror: the mirrored run alone.
+enum { kTapPlain, kTapMean, kTapMirror };
+
+template <int TAP>
+struct BuTap {
+    const float* __restrict__ a;  // plane of the plain run (unused by kTapMirror)
+    const float* __restrict__ b;  // plane of the mirrored run (unused by kTapPlain)
+    int iw;
+    __device__ __forceinline__ float operator()(int y, int x) const {
+        if (TAP == kTapPlain) return a[(size_t)y * iw + x];
+        const float m = b[(size_t)y * iw + (iw - 1 - x)];
+        return TAP == kTapMirror ? m : (a[(size_t)y * iw + x] + m) * 0.5f;
+    }
+};
+
 __device__ __forceinline__ unsigned ordered_bits(float v) {
     unsigned u = __float_as_uint(v);
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
@@ -81,25 +110,35 @@ __device__ __forceinline__ unsigned long long topk_key(float v, int flat) {
 }
 
 // ResizeBilinear sample (align_corners=False, half_pixel_centers=False) of one plane at output pixel (y, x)
-__device__ __forceinline__ float resize_bilinear(const float* __restrict__ plane, int ih, int iw, float sy, float sx, int y, int x) {
+template <int TAP>
+__device__ __forceinline__ float resize_bilinear(const BuTap<TAP>& tap, int ih, int iw, float sy, float sx, int y, int x) {
     const float fy = (float)y * sy, fx = (float)x * sx;
     const int y0 = min((int)floorf(fy), ih - 1), x0 = min((int)floorf(fx), iw - 1);
     const int y1 = min(y0 + 1, ih - 1), x1 = min(x0 + 1, iw - 1);
     const float dy = fy - (float)y0, dx = fx - (float)x0;
-    const float a = plane[(size_t)y0 * iw + x0], b = plane[(size_t)y0 * iw + x1];
-    const float c = plane[(size_t)y1 * iw + x0], d = plane[(size_t)y1 * iw + x1];
+    const float a = tap(y0, x0), b = tap(y0, x1);
+    const float c = tap(y1, x0), d = tap(y1, x1);
     const float top = a + (b - a) * dx;
     const float bot = c + (d - c) * dx;
     return top + (bot - top) * dy;
 }
 
-// masked stage mean at (n, k, y, x), inside the map
-__device__ __forceinline__ float aggregate(const BuParseParams& p, int n, int k, int y, int x) {
+// plane of channel c of image n of stage s, in the plain run and (FLIP) in the mirrored run at channel cf
+template <int TAP>
+__device__ __forceinline__ BuTap<TAP> stage_tap(const BuStage& s, const float* flipped, int n, int c, int cf) {
+    const size_t hw = (size_t)s.h * s.w;
+    return BuTap<TAP>{s.data + ((size_t)n * s.c + c) * hw, TAP == kTapPlain ? nullptr : flipped + ((size_t)n * s.c + cf) * hw, s.w};
+}
+
+// masked stage mean at (n, k, y, x), inside the map; FLIP: of the flip test's averaged heat maps, kf = the mirrored run's channel
+template <bool FLIP>
+__device__ __forceinline__ float aggregate(const BuParseParams& p, const BuFlip* fl, int n, int k, int kf, int y, int x) {
+    constexpr int kTap = FLIP ? kTapMean : kTapPlain;
     const BuStage& full = p.st[p.ns - 1];
-    float v = full.data[(((size_t)n * full.c + k) * p.h + y) * p.w + x];
+    float v = stage_tap<kTap>(full, FLIP ? fl->data[p.ns - 1] : nullptr, n, k, kf)(y, x);
     for (int i = 0; i < p.ns - 1; ++i) {
         const BuStage& s = p.st[i];
-        v = v + resize_bilinear(s.data + ((size_t)n * s.c + k) * s.h * s.w, s.h, s.w, s.sy, s.sx, y, x);
+        v = v + resize_bilinear(stage_tap<kTap>(s, FLIP ? fl->data[i] : nullptr, n, k, kf), s.h, s.w, s.sy, s.sx, y, x);
     }
     if (p.ns > 1) v = v / (float)p.ns;
     const int my = min((int)floorf((float)y * p.msy), p.mh - 1), mx = min((int)floorf((float)x * p.msx), p.mw - 1);
@@ -128,16 +167,19 @@ __device__ __forceinline__ void bitonic_sort_desc(unsigned long long* s) {
     }
 }
 
-__global__ __launch_bounds__(kBuThreads) void bu_parse_kernel(BuParseParams p) {
+// the body of both parse kernels; FLIP folds the mirrored run in (fl, else unused).  tag_per_joint is set under FLIP.
+template <bool FLIP>
+__device__ __forceinline__ void bu_parse_body(const BuParseParams& p, const BuFlip* fl) {
     __shared__ float halo[kBuHaloPix];
     __shared__ unsigned long long keys[kBuTilePix];
     const int tile = blockIdx.x, k = blockIdx.y, n = blockIdx.z;
+    const int kf = FLIP ? fl->index[k] : k;  // uniform per workgroup
     const int ty0 = (tile / p.tiles_x) * kBuTileH, tx0 = (tile % p.tiles_x) * kBuTileW;
     const int r = p.r, hw = kBuTileW + 2 * r, hh = kBuTileH + 2 * r;
 
     for (int i = threadIdx.x; i < hh * hw; i += kBuThreads) {
         const int y = ty0 + i / hw - r, x = tx0 + i % hw - r;
-        halo[i] = (y >= 0 && y < p.h && x >= 0 && x < p.w) ? aggregate(p, n, k, y, x) : -INFINITY;
+        halo[i] = (y >= 0 && y < p.h && x >= 0 && x < p.w) ? aggregate<FLIP>(p, fl, n, k, kf, y, x) : -INFINITY;
     }
     __syncthreads();
 
@@ -160,11 +202,14 @@ __global__ __launch_bounds__(kBuThreads) void bu_parse_kernel(BuParseParams p) {
                 for (int dx = -r; dx <= r; ++dx) mx = fmaxf(mx, halo[(ly + r + dy) * hw + lx + r + dx]);
             key = topk_key(mx == v ? v : 0.0f, flat);
             if (tags_here) {
+                float* tg = p.tagging + (((size_t)n * p.ktag + kt) * plane + flat) * p.num_tags;
                 for (int i = 0; i < p.ns; ++i) {
                     const BuStage& s = p.st[i];
                     if (s.tag_slot < 0) continue;
-                    const float t = resize_bilinear(s.data + ((size_t)n * s.c + p.k + kt) * s.h * s.w, s.h, s.w, s.sy, s.sx, y, x);
-                    p.tagging[(((size_t)n * p.ktag + kt) * plane + flat) * p.num_tags + s.tag_slot] = t;
+                    tg[s.tag_slot] = resize_bilinear(stage_tap<kTapPlain>(s, nullptr, n, p.k + kt, 0), s.h, s.w, s.sy, s.sx, y, x);
+                    if (FLIP)  // the mirrored run's tags take the second half of the axis, in the same stage order
+                        tg[p.num_tags / 2 + s.tag_slot] =
+                            resize_bilinear(stage_tap<kTapMirror>(s, fl->data[i], n, 0, p.k + kf), s.h, s.w, s.sy, s.sx, y, x);
                 }
             }
         }
@@ -175,6 +220,10 @@ __global__ __launch_bounds__(kBuThreads) void bu_parse_kernel(BuParseParams p) {
     unsigned long long* out = p.slab + (((size_t)n * p.k + k) * p.tiles + tile) * p.m;
     for (int i = threadIdx.x; i < p.m; i += kBuThreads) out[i] = keys[i];
 }
+
+__global__ __launch_bounds__(kBuThreads) void bu_parse_kernel(BuParseParams p) { bu_parse_body<false>(p, nullptr); }
+
+__global__ __launch_bounds__(kBuThreads) void bu_parse_flip_kernel(BuParseParams p, BuFlip fl) { bu_parse_body<true>(p, &fl); }
 
 struct BuGatherParams {
     const float* raw;
@@ -340,14 +389,15 @@ size_t mp_bottomup_workspace_bytes(int n, int k, int h, int w, int max_num) {
     return (size_t)n * k * bu_tiles(h, w) * max_num * sizeof(unsigned long long);
 }
 
-int mp_bottomup_parse_nms_topk(const mp_bottomup_stage* stages, int num_stages, const uint8_t* mask_dev, int mask_h, int mask_w,
-                               int n, int k, int tag_per_joint, int nms_kernel, int max_num, float* heatmap_raw_dev,
-                               float* tagging_dev, void* workspace_dev, size_t workspace_bytes, mp_stream_t stream) {
+// Validates the arguments of a parse entry and fills the kernel parameters; tags_per_stage = 1, or 2 for the flip form, whose
+// every tag stage also contributes the mirrored run's tags.
+static int bu_parse_params(const mp_bottomup_stage* stages, int num_stages, const uint8_t* mask_dev, int mask_h, int mask_w, int n, int k,
+                           int tag_per_joint, int nms_kernel, int max_num, float* heatmap_raw_dev, float* tagging_dev,
+                           void* workspace_dev, size_t workspace_bytes, int tags_per_stage, BuParseParams& p) {
     if (!stages || !mask_dev || !heatmap_raw_dev || !tagging_dev) return MP_ERR_NULL;
     if (num_stages < 1 || num_stages > kBuMaxStages || n <= 0 || k <= 0 || mask_h <= 0 || mask_w <= 0) return MP_ERR_SHAPE;
     if (nms_kernel != 1 && nms_kernel != 3 && nms_kernel != 5 && nms_kernel != 7) return MP_ERR_UNSUPPORTED;
     if (max_num < 1 || max_num > kBuMaxM) return MP_ERR_UNSUPPORTED;
-    BuParseParams p{};
     const mp_bottomup_stage& full = stages[num_stages - 1];
     p.h = full.h;
     p.w = full.w;
@@ -362,7 +412,7 @@ int mp_bottomup_parse_nms_topk(const mp_bottomup_stage* stages, int num_stages, 
         p.st[i] = BuStage{s.data_dev, s.c, s.h, s.w, s.has_tags ? slot : -1, (float)s.h / (float)p.h, (float)s.w / (float)p.w};
         slot += s.has_tags ? 1 : 0;
     }
-    if (slot == 0 || slot > kBuMaxTags) return MP_ERR_UNSUPPORTED;
+    if (slot == 0 || slot * tags_per_stage > kBuMaxTags) return MP_ERR_UNSUPPORTED;
     const size_t need = mp_bottomup_workspace_bytes(n, k, p.h, p.w, max_num);
     if (!workspace_dev || workspace_bytes < need) return MP_ERR_WORKSPACE;
     p.ns = num_stages;
@@ -374,7 +424,7 @@ int mp_bottomup_parse_nms_topk(const mp_bottomup_stage* stages, int num_stages, 
     p.n = n;
     p.k = k;
     p.tag_per_joint = tag_per_joint ? 1 : 0;
-    p.num_tags = slot;
+    p.num_tags = slot * tags_per_stage;
     p.r = nms_kernel / 2;
     p.m = max_num;
     p.tiles_x = bu_tiles_x(p.w);
@@ -383,7 +433,45 @@ int mp_bottomup_parse_nms_topk(const mp_bottomup_stage* stages, int num_stages, 
     p.tagging = tagging_dev;
     p.slab = reinterpret_cast<unsigned long long*>(workspace_dev);
     if (n > 65535 || k > 65535) return MP_ERR_SHAPE;
+    return MP_OK;
+}
+
+int mp_bottomup_parse_nms_topk(const mp_bottomup_stage* stages, int num_stages, const uint8_t* mask_dev, int mask_h, int mask_w,
+                               int n, int k, int tag_per_joint, int nms_kernel, int max_num, float* heatmap_raw_dev,
+                               float* tagging_dev, void* workspace_dev, size_t workspace_bytes, mp_stream_t stream) {
+    BuParseParams p{};
+    const int rc = bu_parse_params(stages, num_stages, mask_dev, mask_h, mask_w, n, k, tag_per_joint, nms_kernel, max_num,
+                                   heatmap_raw_dev, tagging_dev, workspace_dev, workspace_bytes, 1, p);
+    if (rc != MP_OK) return rc;
     hipLaunchKernelGGL(bu_parse_kernel, dim3((unsigned)p.tiles, (unsigned)k, (unsigned)n), dim3(kBuThreads), 0, as_stream(stream), p);
+    return check_launch();
+}
+
+int mp_bottomup_parse_nms_topk_flip(const mp_bottomup_stage* stages, const mp_bottomup_stage* flipped_stages,
+                                    const int32_t* flip_index_host, int num_stages, const uint8_t* mask_dev, int mask_h, int mask_w,
+                                    int n, int k, int tag_per_joint, int nms_kernel, int max_num, float* heatmap_raw_dev,
+                                    float* tagging_dev, void* workspace_dev, size_t workspace_bytes, mp_stream_t stream) {
+    if (!stages || !flipped_stages || !flip_index_host) return MP_ERR_NULL;
+    if (k <= 0) return MP_ERR_SHAPE;
+    if (!tag_per_joint || k > kBuFlipMaxJoints) return MP_ERR_UNSUPPORTED;
+    BuFlip fl{};
+    for (int j = 0; j < k; ++j) {  // the kernel indexes the mirrored stages with these: none may leave [0, k)
+        if (flip_index_host[j] < 0 || flip_index_host[j] >= k) return MP_ERR_SHAPE;
+        fl.index[j] = flip_index_host[j];
+    }
+    BuParseParams p{};
+    const int rc = bu_parse_params(stages, num_stages, mask_dev, mask_h, mask_w, n, k, tag_per_joint, nms_kernel, max_num,
+                                   heatmap_raw_dev, tagging_dev, workspace_dev, workspace_bytes, 2, p);
+    if (rc != MP_OK) return rc;
+    for (int i = 0; i < num_stages; ++i) {
+        const mp_bottomup_stage& s = stages[i];
+        const mp_bottomup_stage& f = flipped_stages[i];
+        if (!f.data_dev) return MP_ERR_NULL;
+        if (f.c != s.c || f.h != s.h || f.w != s.w || (f.has_tags != 0) != (s.has_tags != 0)) return MP_ERR_SHAPE;
+        fl.data[i] = f.data_dev;
+    }
+    hipLaunchKernelGGL(bu_parse_flip_kernel, dim3((unsigned)p.tiles, (unsigned)k, (unsigned)n), dim3(kBuThreads), 0, as_stream(stream),
+                       p, fl);
     return check_launch();
 }
 

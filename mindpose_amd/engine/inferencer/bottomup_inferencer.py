@@ -5,19 +5,54 @@ and the back-projection are host numpy, as in the reference.  The optional missi
 (``mp_bottomup_refine_missing``, one launch per batch): the full-resolution maps never travel to the host - only the located tags
 of the grouped persons ([J_total, L]) come down and their mean tags ([P, L]) go up.  Maps that already live on the CPU take the
 host function ``refine_missing_joint``.
+
+Flip TTA (``hflip_tta``, the reference's ``_MultiRunNet``, :252-297): the backbone and head run on the image and its mirror, and the
+decoder folds the mirrored run into its own first launch (``decode_flip_aggregated``); the two decodes the reference computes and
+throws away (:270, :272) are skipped.
 """
 from functools import partial
 from typing import Any, Dict, Iterable, List, Optional, Tuple
 
 import numpy as np
 import torch
+import torch.nn as nn
 
 from ... import _lib
 from ...data.transform.utils import transform_keypoints
 from ...models import EvalNet
 from ...models.decoders import BottomUpHeatMapAEDecoder
+from ...models.layers import flip_pair_batched
 from ...register import register
 from ...utils.match import match_by_tag
+
+
+class _MultiRunNet(nn.Module):
+    """Running the inference twice with horizontal-flip TTA (bottomup_inferencer.py:252-297); what is computed, and where the
+    reference's own expression cannot run, is in ``BottomUpHeatMapAEDecoder.decode_flip_aggregated``."""
+
+    def __init__(self, net: EvalNet, decoder: BottomUpHeatMapAEDecoder, flip_index: np.ndarray) -> None:
+        super().__init__()
+        self.net = net
+        self.decoder = decoder
+        self.flip_index = decoder.check_flip_index(flip_index)
+
+    @torch.no_grad()
+    def forward(self, image: torch.Tensor, mask: torch.Tensor) -> Tuple[torch.Tensor, ...]:
+        raw_net = self.net.net  # EvalNet.net: backbone + head
+        # planned network under amp O2 / O3: both runs as ONE 2N-image forward, its halves handed to the decoder as views.  The fp16
+        # kernels give the same bits whatever the tile shape; the tuner may pick another fp32 form for the 2N shapes, so fp32 keeps
+        # the two forwards (as topdown_inferencer._MultiRunNet)
+        if hasattr(raw_net, "forward_flip_pair") and getattr(raw_net, "amp_level", "O0") != "O0" and flip_pair_batched():
+            n = image.shape[0]
+            both = raw_net.forward_flip_pair(image)
+            outputs, flipped = [o[:n] for o in both], [o[n:] for o in both]
+        else:
+            outputs = [o.clone() for o in raw_net(image)]  # the plan's output buffers are reused by the second run
+            if hasattr(raw_net, "get_plan"):  # planned network: the mirror goes straight into its input buffer (mp_flip_width)
+                flipped = raw_net(image, flip_width=True)
+            else:
+                flipped = raw_net(torch.flip(image, dims=[3]))
+        return self.decoder.decode_flip_aggregated(outputs, flipped, self.flip_index, mask)
 
 
 @register("inferencer", extra_name="bottomup_heatmap_ae")
@@ -36,7 +71,13 @@ class BottomUpHeatMapAEInferencer:
         if self._inference_cfg["hflip_tta"] and not self._inference_cfg["has_heatmap_output"]:
             raise ValueError("flip TTA need heatmap output.")
         if self._inference_cfg["hflip_tta"]:
-            raise NotImplementedError("bottom-up flip TTA (hflip_tta=True) is not implemented on the HIP path yet")
+            if not isinstance(self.decoder, BottomUpHeatMapAEDecoder):
+                raise NotImplementedError("bottom-up flip TTA on the HIP path needs the HIP decoder (BottomUpHeatMapAEDecoder): "
+                                          "its first launch is what folds the mirrored run in")
+            self._multi_run_net = _MultiRunNet(self.net, self.decoder, self._inference_cfg["flip_index"])  # ValueError: bad flip_index
+            self._multi_run_net.eval()
+        else:
+            self._multi_run_net = None
 
     def load_inference_cfg(self) -> Dict[str, Any]:
         """bottomup_inferencer.py:66-89."""
@@ -58,7 +99,9 @@ class BottomUpHeatMapAEInferencer:
         returns one record ``{pred [P, K, 3 + L], score [P], image_path}`` per image (:91-187)."""
         outputs = []
         for data in dataset:
-            if self._inference_cfg["has_heatmap_output"]:
+            if self._inference_cfg["hflip_tta"]:
+                preds = self._multi_run_net(data["image"], data["mask"])
+            elif self._inference_cfg["has_heatmap_output"]:
                 preds, _ = self.net(data["image"], data["mask"])
             else:
                 preds = self.net(data["image"], data["mask"])

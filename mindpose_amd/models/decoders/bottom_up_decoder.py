@@ -8,9 +8,14 @@ global top ``max_num`` and the tag gather in the other.
 Reproduced reference quirk (``shift_coordinate=True``): the +-0.25 offsets are taken at the selected pixels in FLAT-INDEX order
 (MindSpore's ``masked_select``) but added to ``ind_k``, which is in VALUE order, so entry m of ``ind_k`` gets the offset of the
 m-th smallest selected flat index, not of its own pixel.  The drop-in contract is the reference's output, quirk included.
+
+``decode_flip_aggregated`` is the flip test (the reference's ``_MultiRunNet``, engine/inferencer/bottomup_inferencer.py:252-297):
+the same two launches, the first reading the mirrored run's outputs beside the plain ones (``mp_bottomup_parse_nms_topk_flip``).
 """
+import ctypes
 from typing import List, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from ... import _lib
@@ -19,6 +24,8 @@ from .decoder import Decoder
 
 _MAX_NUM_LIMIT = 64  # csrc/bottomup_ops.hip kBuMaxM
 _MAX_LOWER_STAGES = 3
+_FLIP_MAX_JOINTS = 64  # csrc/bottomup_ops.hip kBuFlipMaxJoints
+_MAX_TAGS = 4  # csrc/bottomup_ops.hip kBuMaxTags
 
 
 @register("decoder", extra_name="bottomup_heatmap_ae")
@@ -67,7 +74,59 @@ class BottomUpHeatMapAEDecoder(Decoder):
 
         ``heatmap`` / ``tagging_heatmap`` are the lists ``decouple_output`` makes; both must be channel slices of the same
         stage tensors (the kernels read each stage once, heat maps and tags together)."""
+        return self._launch(self._stages(heatmap, tagging_heatmap), mask)
+
+    def decode_flip_aggregated(self, outputs: Sequence[torch.Tensor], flipped_outputs: Sequence[torch.Tensor],
+                               flip_index: Sequence[int], mask: torch.Tensor) -> Tuple[torch.Tensor, ...]:
+        """The flip test's aggregation and decode (reference: engine/inferencer/bottomup_inferencer.py:269-297) in the decoder's two
+        launches.  ``outputs`` are the raw stage outputs A of ``net(image)``, ``flipped_outputs`` those of ``net(flip_W(image))``,
+        B; ``flip_index`` f is the joint permutation of ``load_inference_cfg``.  Returns ``decode``'s five tensors with
+        tagging [N, K, H, W, 2L] and tag_k [N, K, M, 2L], L = the number of tag stages.
+
+        Per stage i, at stage resolution, before any resize (``ops.ResizeBilinear`` here has no half-pixel centres, so resizing and
+        mirroring do not commute; every tap of the resize is the averaged value):
+
+            heat_i[n, k, y, x] = (A_i[n, k, y, x] + B_i[n, f[k], y, Ws_i - 1 - x]) * 0.5        (one fp32 add, one fp32 multiply)
+
+        and the last axis of tagging holds the plain tags A_i[n, K + k, y, x] of the tag stages in stage order, then the
+        flipped-back tags B_i[n, K + f[k], y, Ws_i - 1 - x] in the same order.  ``decode`` of those lists follows unchanged: stage
+        mean, the same un-mirrored mask, NMS, top-k, tag gather, shift quirk.  B is read mirrored inside the launch: there is no
+        flip, gather, average or concat pass over the maps.
+
+        Two oddities of the reference:
+
+        1. It writes ``(heatmap + flipped_heatmap) * 0.5`` on Python lists, which concatenates the lists and then fails on
+           ``list * float``: as written it runs for no ``num_stages``.  This builds the evident intent, the per-stage mean above.
+        2. ``_flip_back`` indexes the tag tensors with the K-long ``flip_index`` too.  With ``tag_per_joint=False`` (one tag
+           channel) that is out of range in the reference: ``ValueError`` here.  A ``flip_index`` that is not a permutation of
+           ``range(num_joints)`` would silently give ``len(flip_index)`` channels there: ``ValueError`` here."""
+        index = self.check_flip_index(flip_index)
+        heatmap, tagging_heatmap = self.decouple_output(outputs)
         stages = self._stages(heatmap, tagging_heatmap)
+        flipped = self._stages(*self.decouple_output(flipped_outputs))
+        for i, ((a, _), (b, _)) in enumerate(zip(stages, flipped)):
+            if a.shape != b.shape or a.device != b.device:
+                raise ValueError(f"stage {i} of the mirrored run is {tuple(b.shape)}, of the plain run {tuple(a.shape)}")
+        return self._launch(stages, mask, flipped, index)
+
+    def check_flip_index(self, flip_index) -> np.ndarray:
+        """``flip_index`` as int32 [num_joints], after the checks of the flip test: ``ValueError`` unless it is a permutation of
+        ``range(num_joints)`` and the decoder has one tag channel per joint, two tag slots per tag stage and a joint count the
+        kernel carries."""
+        if not self.tag_per_joint:
+            raise ValueError("flip TTA needs tag_per_joint=True: the flip index permutes one tag channel per joint")
+        index = np.asarray(flip_index.cpu() if torch.is_tensor(flip_index) else flip_index)
+        if index.ndim != 1 or index.size != self.num_joints or index.dtype.kind not in "iu" or \
+                not np.array_equal(np.sort(index), np.arange(self.num_joints)):
+            raise ValueError(f"flip_index must be a permutation of range({self.num_joints}), got {index.tolist()}")
+        if self.num_joints > _FLIP_MAX_JOINTS:
+            raise ValueError(f"flip TTA carries at most {_FLIP_MAX_JOINTS} joints on the HIP path, got {self.num_joints}")
+        if 2 * sum(bool(a) for a in self.with_ae_loss[:self.num_stages]) > _MAX_TAGS:
+            raise ValueError(f"flip TTA doubles the tags: at most {_MAX_TAGS // 2} stages may carry them")
+        return np.ascontiguousarray(index, dtype=np.int32)
+
+    def _launch(self, stages, mask, flipped=None, flip_index=None):
+        """The two launches on ``stages`` (``_stages``); with ``flipped`` / ``flip_index`` the first one is the flip form."""
         full = stages[-1][0]
         dev = full.device
         n, k, h, w = full.shape[0], self.num_joints, full.shape[2], full.shape[3]
@@ -81,7 +140,7 @@ class BottomUpHeatMapAEDecoder(Decoder):
             raise TypeError(f"mask must be bool or uint8, got {mask.dtype}")
         mask = mask.to(dev).to(torch.uint8).contiguous()
         ktag = k if self.tag_per_joint else 1
-        num_tags = sum(1 for _, has in stages if has)
+        num_tags = sum(1 for _, has in stages if has) * (1 if flipped is None else 2)
         m = self.max_num
         f32 = dict(device=dev, dtype=torch.float32)
         heatmap_raw = torch.empty(n, k, h, w, **f32)
@@ -92,13 +151,21 @@ class BottomUpHeatMapAEDecoder(Decoder):
         lib = _lib.load()
         ws_bytes = lib.mp_bottomup_workspace_bytes(n, k, h, w, m)
         ws = torch.empty((ws_bytes + 7) // 8, device=dev, dtype=torch.int64)
-        descs = (_lib.BottomUpStage * len(stages))(*[
-            _lib.BottomUpStage(data=t.data_ptr(), c=t.shape[1], h=t.shape[2], w=t.shape[3], has_tags=int(has)) for t, has in stages])
+
+        def describe(items):
+            return (_lib.BottomUpStage * len(items))(*[
+                _lib.BottomUpStage(data=t.data_ptr(), c=t.shape[1], h=t.shape[2], w=t.shape[3], has_tags=int(has)) for t, has in items])
+
         stream = _lib.stream()
         nms = self.nms_kernel if self.use_nms else 1
-        _lib.check(lib.mp_bottomup_parse_nms_topk(descs, len(stages), _lib.ptr(mask), mask.shape[1], mask.shape[2], n, k,
-                                                  int(self.tag_per_joint), nms, m, _lib.ptr(heatmap_raw), _lib.ptr(tagging),
-                                                  _lib.ptr(ws), ws_bytes, stream), "mp_bottomup_parse_nms_topk")
+        tail = (len(stages), _lib.ptr(mask), mask.shape[1], mask.shape[2], n, k, int(self.tag_per_joint), nms, m,
+                _lib.ptr(heatmap_raw), _lib.ptr(tagging), _lib.ptr(ws), ws_bytes, stream)
+        if flipped is None:
+            _lib.check(lib.mp_bottomup_parse_nms_topk(describe(stages), *tail), "mp_bottomup_parse_nms_topk")
+        else:
+            index = flip_index.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+            _lib.check(lib.mp_bottomup_parse_nms_topk_flip(describe(stages), describe(flipped), index, *tail),
+                       "mp_bottomup_parse_nms_topk_flip")
         _lib.check(lib.mp_bottomup_gather(_lib.ptr(heatmap_raw), _lib.ptr(tagging), _lib.ptr(ws), ws_bytes, n, k, h, w,
                                           int(self.tag_per_joint), num_tags, m, int(self.shift_coordinate), _lib.ptr(val_k),
                                           _lib.ptr(ind_k), _lib.ptr(tag_k), stream), "mp_bottomup_gather")

@@ -19,12 +19,18 @@
   of the flipped half (the other half copied), and the masks by torch indexing (fixed-point coordinates, gather, ``where``, mirror,
   pad) from matrices already inverted and uploaded; the two results are compared bit for bit first.  Fraction of 8 TB/s on the
   algorithmic bytes (read: the uint8 sources and masks; written: three fp32 planes and the padded uint8 mask stages).
+- flip_tta: the flip test.  The parse launch alone at the recipe shape (N = 1, stages 128 x 128 with 34 channels and 256 x 256 with 17,
+  NMS 3, max_num 30): ``mp_bottomup_parse_nms_topk_flip`` beside the plain ``mp_bottomup_parse_nms_topk``, alternated in rounds of
+  device-event timings (median and min - max over the rounds) with the algorithmic bytes of each (flip: both runs' stages read,
+  ``tagging`` twice as wide, ``heatmap_raw`` once); and the wall milliseconds of one ``infer`` batch (N = 1, 512 x 512, amp O2,
+  missing-joint refinement on) with ``MINDPOSE_FLIP_BATCHED`` 1 and 0, alternated the same way;
 Forward sizes are the recipe's eval images: 512 x 512 (N = 1 and 32) and 512 x 832 (N = 1).
 
 ``--only NAME`` runs one section in this process; without it every section runs in a child process of its own under a time limit
 (``--section-timeout`` seconds), and a section that fails or overruns ends the run.
 """
 import argparse
+import ctypes
 import json
 import os
 import subprocess
@@ -218,12 +224,77 @@ def train_augment(steps, n=32, src_w=640, src_h=480):
                 hbm_fraction=round(nbytes / (fused_ms * 1e-3) / HBM, 4))
 
 
+def _spread(values):
+    v = sorted(values)
+    return dict(median=round(v[len(v) // 2], 3), min=round(v[0], 3), max=round(v[-1], 3))
+
+
+def flip_tta(steps, rounds=7):
+    lib = _lib.load()
+    n, k, h, w, m = 1, 17, 256, 256, 30
+    g = torch.Generator().manual_seed(0)
+    runs = [[torch.rand(n, 2 * k, h // 2, w // 2, generator=g).to(DEV), torch.rand(n, k, h, w, generator=g).to(DEV)] for _ in range(2)]
+    mask = torch.ones(n, 2 * h, 2 * w, dtype=torch.uint8, device=DEV)
+    raw = torch.empty(n, k, h, w, device=DEV)
+    tagging = torch.empty(n, k, h, w, 2, device=DEV)
+    ws_bytes = lib.mp_bottomup_workspace_bytes(n, k, h, w, m)
+    ws = torch.empty(ws_bytes // 8, device=DEV, dtype=torch.int64)
+    descs = [(_lib.BottomUpStage * 2)(*[_lib.BottomUpStage(data=t.data_ptr(), c=t.shape[1], h=t.shape[2], w=t.shape[3], has_tags=int(i == 0))
+                                        for i, t in enumerate(run)]) for run in runs]
+    index = (ctypes.c_int32 * k)(0, 2, 1, 4, 3, 6, 5, 8, 7, 10, 9, 12, 11, 14, 13, 16, 15)
+    tail = (2, _lib.ptr(mask), 2 * h, 2 * w, n, k, 1, 3, m, _lib.ptr(raw), _lib.ptr(tagging), _lib.ptr(ws), ws_bytes)
+
+    def plain():
+        _lib.check(lib.mp_bottomup_parse_nms_topk(descs[0], *tail, _lib.stream()), "mp_bottomup_parse_nms_topk")
+
+    def flip():
+        _lib.check(lib.mp_bottomup_parse_nms_topk_flip(descs[0], descs[1], index, *tail, _lib.stream()), "mp_bottomup_parse_nms_topk_flip")
+
+    times = dict(plain=[], flip=[])
+    for _ in range(rounds):  # alternated: a drift of the machine meets both alike
+        times["plain"].append(_time(plain, steps) * 1000)
+        times["flip"].append(_time(flip, steps) * 1000)
+    stage_bytes = 4 * n * (2 * k * (h // 2) * (w // 2) + k * h * w)
+    nbytes = dict(plain=stage_bytes + 4 * n * k * h * w * 2, flip=2 * stage_bytes + 4 * n * k * h * w * 3)
+    res = dict(parse_launch_us={name: dict(_spread(t), mb=round(nbytes[name] / 1e6, 2)) for name, t in times.items()})
+    res["parse_launch_ratio"] = round(res["parse_launch_us"]["flip"]["median"] / res["parse_launch_us"]["plain"]["median"], 3)
+
+    net = mp.init_synthetic(mp.create_network("hrnet_w32", "higher_hrnet_head"), seed=0).to(DEV).eval()
+    mp.models.auto_mixed_precision(net, "O2")
+    dec = mp.create_decoder("bottomup_heatmap_ae", use_nms=True, nms_kernel=3, max_num=m)
+    cfg = dict(has_heatmap_output=True, hflip_tta=True, joint_order=JOINT_ORDER, vis_thr=0.1, ignore_too_much=False, use_rounded_norm=True,
+               tag_thr=1.0, pixel_std=200.0, downsample_scale=2, refine_missing_joint=True,
+               flip_pairs=[[1, 2], [3, 4], [5, 6], [7, 8], [9, 10], [11, 12], [13, 14], [15, 16]])
+    inf = BottomUpHeatMapAEInferencer(mp.create_eval_network(net, dec), config=cfg, decoder=dec)
+    batch = dict(image=torch.randn(1, 3, 512, 512, generator=g).to(DEV), mask=torch.ones(1, 512, 512, dtype=torch.bool, device=DEV),
+                 center=np.array([[256.0, 256.0]], np.float32), scale=np.array([[2.56, 2.56]], np.float32),
+                 image_shape=np.array([[512, 512]], np.float32))
+
+    def wall(batched):
+        os.environ["MINDPOSE_FLIP_BATCHED"] = batched
+        inf.infer([batch])  # (the first call of a setting records its plan)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            records = inf.infer([batch])  # ends in the downloads of the decoded arrays: synchronised
+        return (time.perf_counter() - t0) * 1000 / steps, len(records[0]["pred"])
+
+    infer = {"1": [], "0": []}
+    for _ in range(rounds):
+        for batched in ("1", "0"):
+            ms, persons = wall(batched)
+            infer[batched].append(ms)
+    res["infer_batch_ms"] = dict(batched=_spread(infer["1"]), two_forwards=_spread(infer["0"]), persons=persons)
+    return res
+
+
 SECTIONS = {
     "forward": lambda steps: [forward(a, n, h, w, steps) for a in ("O0", "O2") for n, h, w in ((1, 512, 512), (32, 512, 512), (1, 512, 832))],
     "decoder": lambda steps: [decoder(1, 256, 416, steps), decoder(32, 256, 256, steps)],
     "resize_pad_normalize": resize_pad_normalize,
     "refine": lambda steps: [refine(p, steps) for p in (1, 10, 30)],
     "train_augment": train_augment,
+    "flip_tta": flip_tta,
 }
 
 
