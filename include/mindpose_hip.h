@@ -611,6 +611,26 @@ int mp_bottomup_refine_missing(const float* heatmap_raw_dev, const float* taggin
                                const int* person_image_dev, int num_persons, int n, int k, int h, int w, int tag_per_joint,
                                int num_tags, float* found_dev, mp_stream_t stream);
 
+/* mp_bottomup_match_by_tag (bottomup_match.hip; mindpose/utils/match.py:15-116, match_by_tag, for a batch): groups the decoder's
+ * detections of n images in ONE launch, one wave64 per image, bit-equal to the host function: scipy's rectangular
+ * linear_sum_assignment (tie order included), numpy's float32 mean / norm and the reference's dict semantics are restated in the
+ * kernel file's header.  val_k [n, k, m], tag_k [n, k, m, L], ind_k [n, k, m, 2]; joint_order_host [k] is a HOST array, a permutation
+ * of 0 .. k - 1, checked and copied by the entry.  people [n, k * m, k, 3 + L] receives person p of image i at people[i, p], in
+ * the order the groups were opened; a person's [k, 3 + L] block is zeroed when its group is opened and, for status[i] == 0, nothing
+ * beyond counts[i] persons is ever written (k * m is an exact bound: every detection opens at most one group).  status[i] == 1: a
+ * visible detection of image i carries a NaN or infinite tag (scipy raises on such a matrix), found before anything is written;
+ * status[i] == 2: finite tags so far apart that a float32 distance overflows, found while the costs are scanned - the persons of the
+ * earlier steps may have been written.  Either way counts[i] is 0 and the caller runs the host function for that image.  workspace >= mp_bottomup_match_workspace_bytes.
+ * Before any HIP call: n == 0 -> MP_OK without a launch; NULL -> MP_ERR_NULL; non-positive extents or a joint_order that is no
+ * permutation -> MP_ERR_SHAPE; k > 64, m > 64, L > 4 or k * m > 1024 -> MP_ERR_UNSUPPORTED (mp_bottomup_match_supported answers
+ * 1 / 0 for the same limits, host-only); a missing or short workspace -> MP_ERR_WORKSPACE. */
+int mp_bottomup_match_supported(int k, int m, int num_tags);
+size_t mp_bottomup_match_workspace_bytes(int n, int k, int m, int num_tags);
+int mp_bottomup_match_by_tag(const float* val_k_dev, const float* tag_k_dev, const float* ind_k_dev, int n, int k, int m, int num_tags,
+                             const int* joint_order_host, float vis_thr, float tag_thr, int ignore_too_much, int use_rounded_norm,
+                             float* people_dev, int* counts_dev, int* status_dev, void* workspace_dev, size_t workspace_bytes,
+                             mp_stream_t stream);
+
 /* ---- bottom-up training ends: masked heat-map MSE, associative-embedding loss, target generation (bottomup_train_ops.hip) -------
  * Every entry validates before any HIP call (NULL -> MP_ERR_NULL, bad extents / strides -> MP_ERR_SHAPE), fully writes its
  * outputs and is deterministic: no atomics, fixed-order reductions.

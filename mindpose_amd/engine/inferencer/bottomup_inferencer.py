@@ -1,7 +1,9 @@
 """Bottom-up (associative-embedding) inference engine (reference: mindpose/engine/inferencer/bottomup_inferencer.py:18-250).
 
-The network and the decoder run on the HIP path (``EvalNet(net, BottomUpHeatMapAEDecoder)``); the grouping (``match_by_tag``)
-and the back-projection are host numpy, as in the reference.  The optional missing-joint refinement runs on the device
+The network and the decoder run on the HIP path (``EvalNet(net, BottomUpHeatMapAEDecoder)``), and so does the grouping: one
+``mp_bottomup_match_by_tag`` launch per batch (``match_by_tag_batch``), bit-equal to the host ``match_by_tag``, which serves arrays
+that live on the CPU, extents outside the kernel's limits and ``MINDPOSE_MATCH_DEVICE=0``.  The back-projection is host numpy, as
+in the reference.  The optional missing-joint refinement runs on the device
 (``mp_bottomup_refine_missing``, one launch per batch): the full-resolution maps never travel to the host - only the located tags
 of the grouped persons ([J_total, L]) come down and their mean tags ([P, L]) go up.  Maps that already live on the CPU take the
 host function ``refine_missing_joint``.
@@ -23,7 +25,7 @@ from ...models import EvalNet
 from ...models.decoders import BottomUpHeatMapAEDecoder
 from ...models.layers import flip_pair_batched
 from ...register import register
-from ...utils.match import match_by_tag
+from ...utils.match import match_by_tag, match_by_tag_batch, match_on_device_supported
 
 
 class _MultiRunNet(nn.Module):
@@ -171,10 +173,15 @@ class BottomUpHeatMapAEInferencer:
             person[fill, :3] = rows[fill]
 
     def _match(self, val_k, tag_k, ind_k) -> List[np.ndarray]:
+        """Grouping of the batch: one ``mp_bottomup_match_by_tag`` launch when the decoder's arrays live on the device and are inside
+        the entry's limits (``MINDPOSE_MATCH_DEVICE=0``: never), else the host function image by image - the same arrays either way."""
         cfg = self._inference_cfg
-        fn = partial(match_by_tag, joint_order=cfg["joint_order"], vis_thr=cfg["vis_thr"], tag_thr=cfg["tag_thr"],
-                     ignore_too_much=cfg["ignore_too_much"], use_rounded_norm=cfg["use_rounded_norm"])
-        return list(map(fn, val_k.cpu().numpy(), tag_k.cpu().numpy(), ind_k.cpu().numpy()))
+        kwargs = dict(joint_order=cfg["joint_order"], vis_thr=cfg["vis_thr"], tag_thr=cfg["tag_thr"],
+                      ignore_too_much=cfg["ignore_too_much"], use_rounded_norm=cfg["use_rounded_norm"])
+        if val_k.is_cuda and tag_k.is_cuda and ind_k.is_cuda and _lib.env_on("MINDPOSE_MATCH_DEVICE") \
+                and match_on_device_supported(val_k.shape[1], val_k.shape[2], tag_k.shape[3]):
+            return match_by_tag_batch(val_k, tag_k, ind_k, **kwargs)
+        return list(map(partial(match_by_tag, **kwargs), val_k.cpu().numpy(), tag_k.cpu().numpy(), ind_k.cpu().numpy()))
 
 
 def refine_missing_joint(heatmap: np.ndarray, tagging_heatmap: np.ndarray, keypoints: np.ndarray) -> np.ndarray:

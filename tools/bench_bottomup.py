@@ -24,6 +24,12 @@
   device-event timings (median and min - max over the rounds) with the algorithmic bytes of each (flip: both runs' stages read,
   ``tagging`` twice as wide, ``heatmap_raw`` once); and the wall milliseconds of one ``infer`` batch (N = 1, 512 x 512, amp O2,
   missing-joint refinement on) with ``MINDPOSE_FLIP_BATCHED`` 1 and 0, alternated the same way;
+- match: the grouping at the recipe's K = 17, M = 30, L = 1, for N = 1 and N = 32 images whose detections are drawn around 5, 20 and
+  500 person centres (tags a centre's integer plus normal noise of 0.25; values uniform, nine in ten above ``vis_thr``): the host
+  ``match_by_tag`` map (with the three ``.cpu()`` copies the inferencer made) against ``match_by_tag_batch`` (one launch, its two
+  downloads and the per-image copies), wall milliseconds per batch in alternated rounds (median and min - max), the persons found,
+  and the ``mp_bottomup_match_by_tag`` launch alone on prepared buffers in device microseconds.  Both paths are compared bit for
+  bit first.
 Forward sizes are the recipe's eval images: 512 x 512 (N = 1 and 32) and 512 x 832 (N = 1).
 
 ``--only NAME`` runs one section in this process; without it every section runs in a child process of its own under a time limit
@@ -46,7 +52,7 @@ from mindpose_amd import _lib  # noqa: E402
 from mindpose_amd.data.transform._launch import norm255, source_batch  # noqa: E402
 from mindpose_amd.data.transform.bottomup_transform import launch_resize_pad_normalize  # noqa: E402
 from mindpose_amd.engine.inferencer.bottomup_inferencer import BottomUpHeatMapAEInferencer, refine_missing_joint  # noqa: E402
-from mindpose_amd.utils.match import match_by_tag  # noqa: E402
+from mindpose_amd.utils.match import match_by_tag, match_by_tag_batch  # noqa: E402
 
 DEV = torch.device("cuda:0")
 HBM = 8e12
@@ -288,6 +294,52 @@ def flip_tta(steps, rounds=7):
     return res
 
 
+def match(steps, rounds=5, k=17, m=30, num_tags=1):
+    lib = _lib.load()
+    out = []
+    for n in (1, 32):
+        for centres in (5, 20, 500):
+            rng = np.random.RandomState(centres + n)
+            tag = (rng.randint(0, centres, (n, k, m, 1)) + 0.25 * rng.randn(n, k, m, num_tags)).astype(np.float32)
+            val, tag, ind = (torch.from_numpy(a).to(DEV) for a in (rng.rand(n, k, m).astype(np.float32), tag,
+                                                                   rng.randint(0, 256, (n, k, m, 2)).astype(np.float32)))
+
+            def host():
+                return [match_by_tag(v, t, i, JOINT_ORDER) for v, t, i in zip(val.cpu().numpy(), tag.cpu().numpy(), ind.cpu().numpy())]
+
+            def device():
+                return match_by_tag_batch(val, tag, ind, JOINT_ORDER)
+
+            want, got = host(), device()
+            if any(g.shape != w.shape or not np.array_equal(g.view(np.uint32), w.view(np.uint32)) for g, w in zip(got, want)):
+                raise RuntimeError("the device grouping and the host function disagree")
+
+            def wall(fn, reps):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(reps):
+                    fn()  # both end in downloads: synchronised
+                return (time.perf_counter() - t0) * 1000 / reps
+
+            times = dict(host=[], device=[])
+            for _ in range(rounds):  # alternated: a drift of the machine meets both alike
+                times["host"].append(wall(host, max(1, steps // (4 if n == 1 else 20))))
+                times["device"].append(wall(device, steps))
+            people = torch.empty(n, k * m, k, 3 + num_tags, device=DEV)
+            meta = torch.empty(2, n, dtype=torch.int32, device=DEV)
+            ws_bytes = lib.mp_bottomup_match_workspace_bytes(n, k, m, num_tags)
+            ws = torch.empty(ws_bytes // 4, device=DEV)
+            order = (ctypes.c_int * k)(*JOINT_ORDER)
+            kernel_ms = _time(lambda: lib.mp_bottomup_match_by_tag(_lib.ptr(val), _lib.ptr(tag), _lib.ptr(ind), n, k, m, num_tags, order, 0.1, 1.0,
+                                                                   0, 1, _lib.ptr(people), _lib.ptr(meta[0]), _lib.ptr(meta[1]), _lib.ptr(ws),
+                                                                   ws_bytes, _lib.stream()), steps)
+            host_ms, device_ms = _spread(times["host"]), _spread(times["device"])
+            out.append(dict(n=n, centres=centres, persons=[int(min(len(w) for w in want)), int(max(len(w) for w in want))],
+                            host_ms=host_ms, device_ms=device_ms, ratio=round(host_ms["median"] / device_ms["median"], 2),
+                            kernel_us=round(kernel_ms * 1000, 2)))
+    return out
+
+
 SECTIONS = {
     "forward": lambda steps: [forward(a, n, h, w, steps) for a in ("O0", "O2") for n, h, w in ((1, 512, 512), (32, 512, 512), (1, 512, 832))],
     "decoder": lambda steps: [decoder(1, 256, 416, steps), decoder(32, 256, 256, steps)],
@@ -295,6 +347,7 @@ SECTIONS = {
     "refine": lambda steps: [refine(p, steps) for p in (1, 10, 30)],
     "train_augment": train_augment,
     "flip_tta": flip_tta,
+    "match": match,
 }
 
 
