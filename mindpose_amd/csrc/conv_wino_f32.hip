@@ -36,6 +36,7 @@ constexpr int kXFloats = 16 * 16 * kXP;
 constexpr size_t kMaxLds = 150 * 1024;    // dynamic LDS a launch may ask for
 constexpr int kGroupTeamsMinWgs = 128;    // image-grouped bands take two teams when that still leaves this many workgroups
 
+
 __device__ __forceinline__ void wg_barrier() {
     // LDS traffic of this wave done, then the workgroup barrier; global loads stay in flight (a __syncthreads() would drain them)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -54,6 +55,10 @@ __device__ __forceinline__ void wg_barrier() {
 template <int NI, bool QROW, bool GROUP, int TEAMS>
 __global__ __launch_bounds__(256 * TEAMS, TEAMS == 1 ? 2 : 1) void conv_wino_f32_kernel(const WinoParams p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
+    // The tile seam and the early epilogue loads (both below) are one-team matters: measured per layer, the two-team
+    // forms - one chunk per loop trip under a run-time parity, 8 to 32 chunks per tile, at the 256-register ceiling - lose more to
+    // the seam's switches in every chunk than a tile's prologue costs them, and show nothing for the early loads.
+    constexpr bool kSeam = TEAMS == 1, kEpiEarly = TEAMS == 1;
     const int raw_buf = kCK * p.cin_plane + 4;  // + one float4 that absorbs the stores of threads without a staging unit
     float* __restrict__ lds_raw = smem;                 // [2][raw_buf]
     float* __restrict__ lds_v = smem + 2 * raw_buf;     // [2][16][kCK][kTP]
@@ -276,6 +281,20 @@ __global__ __launch_bounds__(256 * TEAMS, TEAMS == 1 ? 2 : 1) void conv_wino_f32
         for (int i = tid_wg; i < n4; i += 256 * TEAMS) z[i] = zero;
     }
     wg_barrier();  // zero fill complete
+    // One team, even chunk count (launch-uniform): ONE stream of chunks over the workgroup's tiles.  The staging slots of a tile's
+    // last two chunks - which have no chunk n, n + 1 to fetch - carry chunks 0 and 1 of the NEXT tile into raw[0] / raw[1] (the
+    // parities match; the raw buffers survive the epilogue), and its first U fragments take the slot of the last chunk's refill.  A
+    // tile after the first then starts with both raw buffers and U in place: its prologue is the chunk-0 transform and one
+    // barrier.  Odd chunk counts keep the per-tile prologue: the pair loop runs one chunk past the end there and relies on that
+    // chunk's U being out of range.
+    auto seam = [&]() { return kSeam && !(p.n_chunks & 1); };  // (recomputed where used: one scalar bit test, no live register)
+    if (seam()) {  // the first tile's chunks 0 and 1, once per workgroup
+        stage_store(0);
+#pragma unroll
+        for (int i = 0; i < NI; ++i) vin[i] = vin1[i];
+        stage_store(1);
+        wg_barrier();
+    }
 
     // epilogue constants of this thread (tile-independent part)
     const int plane_o = HW;
@@ -303,6 +322,11 @@ __global__ __launch_bounds__(256 * TEAMS, TEAMS == 1 ? 2 : 1) void conv_wino_f32
     for (int it = 0; it < p.tiles_per_wg; ++it) {
     if (tile_first + it >= p.total_blocks) break;  // workgroup-uniform
     MP_STAMP(t_tile);
+    auto has_next = [&]() { return it + 1 < p.tiles_per_wg && tile_first + it + 1 < p.total_blocks; };
+    // seam: chunk n - 2 switches the input side to the next tile before its stage_load, chunk n - 1 the U offsets before its
+    // refills, and from there on the slots count the next tile's chunks; without a next tile nothing switches and both slots
+    // stay out of range (zeros)
+    const int ch_seam = seam() && has_next() ? p.n_chunks - 2 : 0x3fffffff;
     f32x4 acc[4][3][2];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -310,31 +334,47 @@ __global__ __launch_bounds__(256 * TEAMS, TEAMS == 1 ? 2 : 1) void conv_wino_f32
         for (int mb = 0; mb < 3; ++mb)
 #pragma unroll
             for (int nb = 0; nb < 2; ++nb) acc[i][mb][nb] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    stage_store(0);
-    wg_barrier();
+    if (!seam()) {
+        stage_store(0);
+        wg_barrier();
+    }
     if (XF1 || team == 0) {
         xf_read(0);
         xf_cols();
 #pragma unroll
         for (int i = 0; i < 4; ++i) xf_rows_write(0, i);
     }
+    if (!seam()) {
 #pragma unroll
-    for (int i = 0; i < NI; ++i) vin[i] = vin1[i];
-    stage_store(1);
+        for (int i = 0; i < NI; ++i) vin[i] = vin1[i];
+        stage_store(1);
+    }
     wg_barrier();
     MP_STAMP(t_pro);
     s_pro += t_pro - t_tile;
 
     // chunk ch: the 48 MFMAs of this wave over V[ch & 1], with the input transform of chunk ch + 1 (raw[(ch + 1) & 1] ->
-    // V[(ch + 1) & 1]) woven between them; the raw rows of chunk ch + 2 fly in from global memory meanwhile.  The body is
-    // branch-free and the same for every chunk (past the last chunk the buffer loads are out of range and return zeros, the
-    // transform works on stale rows into a V buffer nobody reads): one loop, no peeled copy, the accumulators stay put.
+    // V[(ch + 1) & 1]) woven between them; the raw rows of chunk ch + 2 fly in from global memory meanwhile.  One loop body for
+    // every chunk, no peeled copy, the accumulators stay put.  The seam's two switches hang on workgroup-uniform tests - the input
+    // side can only switch in an even-parity chunk, the U offsets in an odd-parity one, so the pair body tests each once.  Past a
+    // tile's last chunk the transform works on rows the V of no chunk is made of, into a V buffer nobody reads (with an odd chunk
+    // count: only the pair loop's overrun chunk, against zero U), and without a seam the buffer loads are out of range: zeros.
+    // (A uniform branch around that last transform spilled 20 - 250 bytes per lane in every one-team instantiation and cost the
+    // grouped two-team one 6 %: DESIGN 4.6.)
     const int a_base = wave * 4 * (kCK * kTP) + lq * kTP + lr;
     // (one team: two chunks per trip - the buffer parities are constants; an odd chunk count runs one chunk past the end, zeros
     // times zeros, see above.  Two teams, at the 256-register ceiling, spill with the double-length body: one chunk per trip)
     auto chunk = [&](int ch, const int par) {
         MP_STAMP(t0);
-        stage_load(ch + 2);
+        if (par == 0 && ch == ch_seam) {  // after the tile's last real stage_load (chunk n - 3)
+            tile_coords(tile_first + it + 1);
+            tile_rows();
+            rs_x = make_rsrc(p.x + (size_t)n * p.Cin * HW, (size_t)n_img * p.Cin * HW * 4);
+        }
+        if (par == 1 && ch == ch_seam + 1) {  // after the U loads for chunk n - 1 (issued in chunk n - 2)
+            tile_u();
+        }
+        stage_load(ch >= ch_seam ? ch + 2 - p.n_chunks : ch + 2);
         const float* __restrict__ vcur = lds_v + par * kVFloats + a_base;
         if (TEAMS == 1 || XF1 || team == 0) xf_read(par ^ 1);
 #pragma unroll
@@ -357,7 +397,7 @@ __global__ __launch_bounds__(256 * TEAMS, TEAMS == 1 ? 2 : 1) void conv_wino_f32
                 }
             }
             __builtin_amdgcn_sched_barrier(0);  // the refill below must not move above the MFMAs that read these registers' old values
-            load_u_half(ch + 1, q);
+            load_u_half(ch > ch_seam ? ch + 1 - p.n_chunks : ch + 1, q);
         }
         MP_STAMP(t3);
         stage_store(par);
@@ -380,8 +420,16 @@ __global__ __launch_bounds__(256 * TEAMS, TEAMS == 1 ? 2 : 1) void conv_wino_f32
     // the four tiles 4 quad .. 4 quad + 3; QROW (launch condition: full 48-tile bands, TW % 4 == 0): those
     // four tiles are eight consecutive pixels of two rows -> 16-byte residual loads and stores.  The residual loads are issued
     // before the accumulators go to LDS, so their latency runs under the exchange.
-    const int e_ct = ct, e_n = n, e_y0 = y0;
-    const size_t img_o = (size_t)n_img * p.Cout * plane_o * 4;
+    // the tile whose OUTPUT side this is: ct / n / y0 / n_img have moved on to the next tile inside the chunk loop (seam), so its
+    // coordinates are worked out again here - scalar arithmetic - instead of being carried through the loop
+    int e_ct, e_n, e_y0, e_nimg;
+    {
+        const int k_ct = ct, k_n = n, k_y0 = y0, k_nimg = n_img;
+        tile_coords(tile_first + it);
+        e_ct = ct; e_n = n; e_y0 = y0; e_nimg = n_img;
+        ct = k_ct; n = k_n; y0 = k_y0; n_img = k_nimg;
+    }
+    const size_t img_o = (size_t)e_nimg * p.Cout * plane_o * 4;
     const __amdgpu_buffer_rsrc_t rs_o = make_rsrc(p.out + (size_t)e_n * p.Cout * plane_o, img_o);
     const __amdgpu_buffer_rsrc_t rs_r1 = make_rsrc(p.res1 ? p.res1 + (size_t)e_n * p.Cout * plane_o : p.out, p.res1 ? img_o : 0);
     const __amdgpu_buffer_rsrc_t rs_r2 = make_rsrc(p.res2 ? p.res2 + (size_t)e_n * p.Cout * plane_o : p.out, p.res2 ? img_o : 0);
@@ -389,8 +437,9 @@ __global__ __launch_bounds__(256 * TEAMS, TEAMS == 1 ? 2 : 1) void conv_wino_f32
 #pragma unroll
     for (int e = 0; e < (QROW ? 1 : 4); ++e)
         pix[e] = (pix_rel[e] != kOob && e_y0 + pix_row[e] < p.H) ? pix_rel[e] + (unsigned)(e_y0 * p.W) * 4u : kOob;
-    // the next tile of this workgroup: its first raw rows and U fragments are requested now and land during the epilogue
-    if (it + 1 < p.tiles_per_wg && tile_first + it + 1 < p.total_blocks) {
+    // the next tile of this workgroup (odd chunk counts; even ones did this in the last two chunks): its first raw rows and U
+    // fragments are requested now and land during the epilogue
+    if (!seam() && has_next()) {
         tile_coords(tile_first + it + 1);
         tile_rows();
         tile_u();
@@ -405,6 +454,18 @@ __global__ __launch_bounds__(256 * TEAMS, TEAMS == 1 ? 2 : 1) void conv_wino_f32
     f32x4 r1q[2][2][2], r2q[2][2][2];
     float2 r1v[2][4][2], r2v[2][4][2];
     unsigned co_off[2];
+    // scale / shift of both halves go out ahead of the residual rows: behind the exchange barrier (a memory clobber) each half
+    // would wait a full load latency for them, the second one behind the first half's stores as well
+    [[maybe_unused]] float e_sc[2], e_sh[2];
+    if constexpr (kEpiEarly) {
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb) {
+            const int co = co_base + nb * 16 + (int)co_l;
+            const int cc = co < p.Cout ? co : 0;
+            e_sc[nb] = p.scale[cc];
+            e_sh[nb] = p.shift[cc];
+        }
+    }
     auto res_request = [&](int nb) {
         const int co = co_base + nb * 16 + (int)co_l;
         co_off[nb] = co < p.Cout ? (unsigned)co * plane_o * 4u : kOob;  // kOob + pixel offset stays out of range
@@ -444,7 +505,10 @@ __global__ __launch_bounds__(256 * TEAMS, TEAMS == 1 ? 2 : 1) void conv_wino_f32
 #pragma unroll
     for (int nb = 0; nb < 2; ++nb) {
         if (co_base + nb * 16 >= p.Cout_pad16) break;  // wave-uniform; no barrier below
-        if (ep_on) {
+        // every thread runs the half: those without an item (tid >= 192) repeat item 0 with every pixel offset out of range - nothing
+        // loaded, nothing stored.  A divergent skip here would leave a path on which the first half issues no stores, and the waits
+        // of the second half, merged over both paths, would then stand behind the first half's stores.
+        if (kEpiEarly || ep_on) {
             const int co = co_base + nb * 16 + (int)co_l;
             f32x4 pr[4][2];
 #pragma unroll
@@ -452,8 +516,13 @@ __global__ __launch_bounds__(256 * TEAMS, TEAMS == 1 ? 2 : 1) void conv_wino_f32
 #pragma unroll
                 for (int b = 0; b < 2; ++b)
                     pr[i][b] = *reinterpret_cast<const f32x4*>(lds_x + (((nb * 4 + i) * 2 + b) * 16 + co_l) * kXP + quad * 4);
-            const int cc = co < p.Cout ? co : 0;
-            const float sc = p.scale[cc], sh = p.shift[cc];
+            float sc, sh;
+            if constexpr (kEpiEarly) {
+                sc = e_sc[nb]; sh = e_sh[nb];
+            } else {
+                const int cc = co < p.Cout ? co : 0;
+                sc = p.scale[cc]; sh = p.shift[cc];
+            }
             // the four tiles side by side: component e of every vector = tile e; y[a][0] = left pixel of each tile in output
             // row a, y[a][1] = right pixel
             f32x4 y[2][2];
@@ -523,6 +592,19 @@ __global__ __launch_bounds__(256) void pack_weight_wino_kernel(const float* __re
 }
 
 inline unsigned magic_of(unsigned d) { return d <= 1 ? 0u : (unsigned)(0x100000000ULL / d) + 1u; }
+
+// One launcher per kernel instantiation: the dynamic-LDS attribute is a property of the instantiation, so the once-per-device
+// flag must be too (a flag shared through the common function-pointer type would reach only the first kernel a process launches).
+template <auto Kern>
+int wino_go(const WinoLaunch& L, hipStream_t s) {
+    static AttrOnce attr_once;
+    if (attr_once.need()) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipGetLastError();
+    }
+    hipLaunchKernelGGL(Kern, dim3((L.p.total_blocks + L.p.tiles_per_wg - 1) / L.p.tiles_per_wg), dim3(256 * L.teams), L.lds_bytes, s, L.p);
+    return check_launch();
+}
 
 }  // namespace
 
@@ -631,39 +713,28 @@ int wino_configure(const mp_conv_desc* d, WinoLaunch& L) {
 int wino_launch(const WinoLaunch& L0, hipStream_t s) {
     WinoLaunch L = L0;
     L.p.dbg = conv_stamp_buffer((size_t)L.p.total_blocks * 64);
-    auto go = [&](auto kern) {
-        static AttrOnce attr_once;
-        if (attr_once.need()) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipGetLastError();
-        }
-        hipLaunchKernelGGL(kern, dim3((L.p.total_blocks + L.p.tiles_per_wg - 1) / L.p.tiles_per_wg), dim3(256 * L.teams), L.lds_bytes, s, L.p);
-        return check_launch();
-    };
     // QROW: the four tiles of an epilogue item are eight consecutive pixels of two rows
     const bool qrow = !L.group && L.p.M == kTP && L.p.TW % 4 == 0 && L.p.H % L.p.R == 0;
     if (L.group) {
         if (L.teams == 2)  // 512 staging threads over at most 8 x 48 units: always one unit per thread
-            return L.ni == 1 ? go(conv_wino_f32_kernel<1, false, true, 2>) : MP_ERR_UNSUPPORTED;
-        switch (L.ni) {
-            case 1: return go(conv_wino_f32_kernel<1, false, true, 1>);
-            case 2: return go(conv_wino_f32_kernel<2, false, true, 1>);
-            case 3: return go(conv_wino_f32_kernel<3, false, true, 1>);
+            return L.ni == 1 ? wino_go<conv_wino_f32_kernel<1, false, true, 2>>(L, s) : MP_ERR_UNSUPPORTED;
+        switch (L.ni) {  // a group is at most 48 tiles = 48 float4 units per channel: 384 units, two per thread
+            case 1: return wino_go<conv_wino_f32_kernel<1, false, true, 1>>(L, s);
+            case 2: return wino_go<conv_wino_f32_kernel<2, false, true, 1>>(L, s);
             default: return MP_ERR_UNSUPPORTED;
         }
     }
     if (L.teams == 2) {
-        switch (L.ni) {
-            case 1: return qrow ? go(conv_wino_f32_kernel<1, true, false, 2>) : go(conv_wino_f32_kernel<1, false, false, 2>);
-            case 2: return qrow ? go(conv_wino_f32_kernel<2, true, false, 2>) : go(conv_wino_f32_kernel<2, false, false, 2>);
-            case 3: return qrow ? go(conv_wino_f32_kernel<3, true, false, 2>) : go(conv_wino_f32_kernel<3, false, false, 2>);
+        switch (L.ni) {  // 512 staging threads over the at most 768 units wino_configure admits: two per thread
+            case 1: return qrow ? wino_go<conv_wino_f32_kernel<1, true, false, 2>>(L, s) : wino_go<conv_wino_f32_kernel<1, false, false, 2>>(L, s);
+            case 2: return qrow ? wino_go<conv_wino_f32_kernel<2, true, false, 2>>(L, s) : wino_go<conv_wino_f32_kernel<2, false, false, 2>>(L, s);
             default: return MP_ERR_UNSUPPORTED;
         }
     }
     switch (L.ni) {
-        case 1: return qrow ? go(conv_wino_f32_kernel<1, true, false, 1>) : go(conv_wino_f32_kernel<1, false, false, 1>);
-        case 2: return qrow ? go(conv_wino_f32_kernel<2, true, false, 1>) : go(conv_wino_f32_kernel<2, false, false, 1>);
-        case 3: return qrow ? go(conv_wino_f32_kernel<3, true, false, 1>) : go(conv_wino_f32_kernel<3, false, false, 1>);
+        case 1: return qrow ? wino_go<conv_wino_f32_kernel<1, true, false, 1>>(L, s) : wino_go<conv_wino_f32_kernel<1, false, false, 1>>(L, s);
+        case 2: return qrow ? wino_go<conv_wino_f32_kernel<2, true, false, 1>>(L, s) : wino_go<conv_wino_f32_kernel<2, false, false, 1>>(L, s);
+        case 3: return qrow ? wino_go<conv_wino_f32_kernel<3, true, false, 1>>(L, s) : wino_go<conv_wino_f32_kernel<3, false, false, 1>>(L, s);
         default: return MP_ERR_UNSUPPORTED;
     }
 }
