@@ -335,15 +335,19 @@ int blockf16_build(const void* x, const void* w1, const float* scale1, const flo
     p.magic_w = magic_of((unsigned)w);
     p.magic_rw = magic_of((unsigned)((best + 4) * w));
     L.p = p;
-    L.small = (ps1 <= 5 && ps2 <= 3) ? 1 : 0;
+    L.form = (ps1 <= 5 && ps2 <= 3) ? kTile53 : kTile65;
     L.lds_bytes = ((size_t)4 * (p.plane_in + p.plane_mid) + kBlkWUnits + 32 + 1) * 16;
     return MP_OK;
 }
 
 int blockf16_launch(const BlockF16Launch& L, hipStream_t s) {
-    if (L.small >= 4) return blockf16_c64_launch(L, s);
-    if (L.small >= 2) return blockf16_v2_launch(L, s);
-    return L.small ? launch_block<5, 3>(L.p, L.lds_bytes, s) : launch_block<6, 5>(L.p, L.lds_bytes, s);
+    switch (L.form) {
+        case kTile65: return launch_block<6, 5>(L.p, L.lds_bytes, s);
+        case kTile53: return launch_block<5, 3>(L.p, L.lds_bytes, s);
+        case kV2Wave8: case kV2Wave4: return blockf16_v2_launch(L, s);
+        case kC64: case kC128: return blockf16_c64_launch(L, s);
+    }
+    return MP_ERR_UNSUPPORTED;
 }
 
 }  // namespace mp

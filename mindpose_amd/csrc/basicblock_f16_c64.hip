@@ -276,13 +276,13 @@ bool blockf16_c64_build(const void* x, const void* w1, const float* scale1, cons
     p.magic_w = magic_of((unsigned)p.Wp);   // DMA slot -> row
     p.magic_rw = magic_of((unsigned)w);     // pixel -> row
     L.p = p;
-    L.small = c == 64 ? 4 : 5;  // marks this kernel (0 / 1: first structure, 2: second structure of the 32-channel block)
+    L.form = c == 64 ? kC64 : kC128;
     L.lds_bytes = ((size_t)npl * (p.plane_in + p.plane_mid) + 1) * 16;
     return true;
 }
 
 int blockf16_c64_launch(const BlockF16Launch& L, hipStream_t s) {
-    return L.small == 5 ? launch_c64<4, 4, 3>(L.p, L.lds_bytes, s) : launch_c64<2, 8, 6>(L.p, L.lds_bytes, s);
+    return L.form == kC128 ? launch_c64<4, 4, 3>(L.p, L.lds_bytes, s) : launch_c64<2, 8, 6>(L.p, L.lds_bytes, s);
 }
 
 }  // namespace mp

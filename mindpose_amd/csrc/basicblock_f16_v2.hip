@@ -370,7 +370,7 @@ bool blockf16_v2_build(const void* x, const void* w1, const float* scale1, const
     p.dbg = (g_block_stamp_buf && (size_t)p.total_blocks * 2 * 16 * 8 <= g_block_stamp_bytes) ? g_block_stamp_buf : nullptr;
 #endif
     L.p = p;
-    L.small = 2 + shape;  // 2 / 3 mark the second structure (eight / four waves)
+    L.form = shape ? kV2Wave4 : kV2Wave8;
     L.lds_bytes = ((size_t)4 * (2 * p.plane_in + p.plane_mid) + 33 + 32) * 16;
     return true;
 }

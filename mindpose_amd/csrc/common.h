@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include <initializer_list>
+
 #include "../../include/mindpose_hip.h"
 
 namespace mp {
@@ -50,5 +52,18 @@ inline bool knobs_on() {
     return on;
 }
 inline const char* knob(const char* name) { return knobs_on() ? getenv(name) : nullptr; }
+
+// A launch plan (conv_api.hip) holds one launch record per entry.  Every record type comes with two functions beside its
+// declaration: run(record, stream) launches it, describe(record, info) writes the twelve values mp_plan_entry_info reports -
+// info[0] is the record's kind below.  The numbers are ABI (tools and tests read them); the fp32 conv kernels all report kConv.
+enum PlanKind { kConv = 0, kMaxPool = 1, kFuseSum = 2, kConvF16 = 3, kFuseSumF16 = 4, kToC8 = 5, kFromC8 = 6, kBarrier = 7, kBlockF16 = 8,
+                kWinograd = 9, kPwChainF16 = 10, kStemF16 = 11, kStemF32 = 12, kPwChainF32 = 13, kConcat = 14, kColSlice = 15 };
+
+// info[] of an entry: the given values in order, zeros behind them
+inline void fill_info(int64_t info[12], std::initializer_list<int64_t> values) {
+    int i = 0;
+    for (int64_t v : values) info[i++] = v;
+    for (; i < 12; ++i) info[i] = 0;
+}
 
 }  // namespace mp

@@ -3,6 +3,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <type_traits>
+#include <variant>
 #include <vector>
 
 #include "conv_f16.h"
@@ -114,26 +116,81 @@ __global__ __launch_bounds__(256) void pack_weight_batch_kernel(const mp_f16_pac
     reinterpret_cast<float4*>(jb.packed)[u] = make_float4(v[0], v[1], v[2], v[3]);
 }
 
+
 static unsigned long long* g_stamp_buf = nullptr;
 static size_t g_stamp_bytes = 0;
 
 unsigned long long* conv_stamp_buffer(size_t need_bytes) { return (g_stamp_buf && need_bytes <= g_stamp_bytes) ? g_stamp_buf : nullptr; }
 
-struct ConvLaunch {
+// Launch record of the direct MFMA kernel (conv_mfma.h).  An fp32 conv is served by this kernel or - forced variants kPointwise,
+// kGemm, kSmall / kSmall + 1 only - by the streaming 1x1 (PwLaunch), the blocked GEMM (GemmLaunch) or the K-split small-problem
+// kernel (SmallLaunch).
+struct DirectLaunch {
     ConvKParams p;
     int ks, stride, variant;
     size_t lds_bytes;
-    bool pointwise;  // variant kPointwise: the streaming 1x1 kernel (conv_pw_f32.hip), launch record in pw
-    PwLaunch pw;
-    bool gemm;       // variant kGemm: the blocked-GEMM 1x1 kernel (conv_gemm_f32.hip), launch record in gm
-    GemmLaunch gm;
-    bool small_k;    // variant kSmall: the K-split 3x3 kernel for small problems (conv_small_f32.hip), launch record in sm
-    SmallLaunch sm;
 };
+static_assert(kPointwise == V_COUNT && kGemm == V_COUNT + 2 && kSmall == V_COUNT + 3, "the forced-variant indices follow the tile variants");
 
-constexpr int kGemm = V_COUNT + 2;   // forced-variant index of the blocked-GEMM 1x1 kernel (V_COUNT + 1 is the tuner's index of the Winograd form)
-constexpr int kSmall = V_COUNT + 3;  // forced-variant index of the K-split small-problem 3x3 kernel (the tuner's index 11)
-constexpr int kPointwise = V_COUNT;  // forced-variant index of the streaming 1x1 kernel (never chosen by the library heuristic)
+static int run(const DirectLaunch& L, hipStream_t s) {
+    ConvKParams p = L.p;
+    p.dbg = conv_stamp_buffer((size_t)p.total_blocks * 64);
+    switch (L.ks) {
+        case 1: return launch_conv_k1(p, L.stride, L.variant, L.lds_bytes, s);
+        case 2: return launch_conv_k2(p, L.stride, L.variant, L.lds_bytes, s);
+        case 3: return L.stride == 1 ? launch_conv_k3s1(p, L.variant, L.lds_bytes, s) : launch_conv_k3s2(p, L.variant, L.lds_bytes, s);
+        case 7: return launch_conv_k7(p, L.stride, L.variant, L.lds_bytes, s);
+        default: return MP_ERR_UNSUPPORTED;
+    }
+}
+static void describe(const DirectLaunch& L, int64_t info[12]) {
+    int ct, pt;
+    variant_dims(L.variant, ct, pt);
+    fill_info(info, {kConv, L.ks, L.stride, L.variant, L.p.total_blocks, (int64_t)L.lds_bytes, ct, pt, L.p.CK, L.p.G, L.p.R,
+                     variant_light(L.variant) ? 1 : 0});
+}
+
+// The plan's element-wise entries: the arguments of the mp_* call run() makes.
+struct MaxPool { const float* x; float* out; int n, c, h, w; };
+struct FuseSum { const float* base; const float* t[3]; int s[3]; float* out; int n, c, h, w, relu; };  // t[i] up-sampled by s[i]; t[1], t[2] may be null
+struct FuseSumF16 { const void* base; const void* t[3]; int s[3]; void* out; int n, c, h, w, relu; };
+struct ToC8 { const float* x; void* out; int n, c, h, w; };    // NCHW fp32 -> c8 halfs
+struct FromC8 { const void* x; float* out; int n, c, h, w; };  // and back
+struct Concat { const void* a; int ca; const void* b; int cb; void* out; int n, h, w, c8; };  // c8: the layout (else NCHW fp32)
+struct ColSlice { const void* in; void* out; int rows, w_in, start, w_out, c8; };             // columns [start, start + w_out) of every row
+struct Barrier {};  // no launch: the multi-lane replay orders every lane after every other one here
+
+static int run(const MaxPool& r, hipStream_t s) { return mp_maxpool3x3s2_same(r.x, r.out, r.n, r.c, r.h, r.w, s); }
+static int run(const FuseSum& r, hipStream_t s) {
+    return mp_fuse_upsample_sum(r.base, r.t[0], r.s[0], r.t[1], r.s[1], r.t[2], r.s[2], r.out, r.n, r.c, r.h, r.w, r.relu, s);
+}
+static int run(const FuseSumF16& r, hipStream_t s) {
+    return mp_f16_fuse_upsample_sum(r.base, r.t[0], r.s[0], r.t[1], r.s[1], r.t[2], r.s[2], r.out, r.n, r.c, r.h, r.w, r.relu, s);
+}
+static int run(const ToC8& r, hipStream_t s) { return mp_f16_to_c8(r.x, r.out, r.n, r.c, r.h, r.w, s); }
+static int run(const FromC8& r, hipStream_t s) { return mp_f16_from_c8(r.x, r.out, r.n, r.c, r.h, r.w, s); }
+static int run(const Concat& r, hipStream_t s) { return mp_concat_channels(r.a, r.ca, r.b, r.cb, r.out, r.n, r.h, r.w, r.c8, s); }
+static int run(const ColSlice& r, hipStream_t s) { return mp_col_slice(r.in, r.out, r.rows, r.w_in, r.start, r.w_out, r.c8, s); }
+static int run(const Barrier&, hipStream_t) { return MP_OK; }
+static void describe(const MaxPool&, int64_t info[12]) { fill_info(info, {kMaxPool}); }
+static void describe(const FuseSum&, int64_t info[12]) { fill_info(info, {kFuseSum}); }
+static void describe(const FuseSumF16&, int64_t info[12]) { fill_info(info, {kFuseSumF16}); }
+static void describe(const ToC8&, int64_t info[12]) { fill_info(info, {kToC8}); }
+static void describe(const FromC8&, int64_t info[12]) { fill_info(info, {kFromC8}); }
+static void describe(const Concat&, int64_t info[12]) { fill_info(info, {kConcat}); }
+static void describe(const ColSlice&, int64_t info[12]) { fill_info(info, {kColSlice}); }
+static void describe(const Barrier&, int64_t info[12]) { fill_info(info, {kBarrier}); }
+
+// What a plan entry (or one eager conv call) launches: exactly one record.  A new kernel family adds its record type here, run() and
+// describe() beside the type's declaration, and one mp_plan_add_* function.
+using Record = std::variant<DirectLaunch, PwLaunch, GemmLaunch, SmallLaunch, WinoLaunch, StemF32Launch, PwChainF32Launch, ConvF16Launch,
+                            BlockF16Launch, PwChainLaunch, StemF16Launch, MaxPool, FuseSum, FuseSumF16, ToC8, FromC8, Concat, ColSlice, Barrier>;
+template <typename R>
+constexpr bool is_f32_conv = std::is_same_v<R, DirectLaunch> || std::is_same_v<R, PwLaunch> || std::is_same_v<R, GemmLaunch> || std::is_same_v<R, SmallLaunch>;
+
+static int run_record(const Record& rec, hipStream_t s) {
+    return std::visit([s](const auto& r) { return run(r, s); }, rec);
+}
 
 static const int kLdsMax = 150 * 1024;
 
@@ -156,7 +213,7 @@ static int plane_pad(int raw) {  // smallest value >= raw that is == 16 (mod 32)
 }
 
 // geometry for a given variant; returns false when it cannot fit LDS
-static bool configure(const mp_conv_desc& d, int variant, ConvLaunch& L) {
+static bool configure(const mp_conv_desc& d, int variant, DirectLaunch& L) {
     int CT, PT;
     variant_dims(variant, CT, PT);
     if (d.kh == 7 && variant != V_CT64_PT192 && variant != V_CT32_PT192_H) return false;  // only these are built
@@ -228,34 +285,30 @@ static bool configure(const mp_conv_desc& d, int variant, ConvLaunch& L) {
     return L.lds_bytes <= (size_t)kLdsMax;
 }
 
-static int choose_variant(const mp_conv_desc& d, ConvLaunch& best, int forced = -1) {
+static int choose_variant(const mp_conv_desc& d, Record& best, int forced = -1) {
     if (forced == kPointwise) {
-        int rc = pw_configure(&d, best.pw);
-        if (rc != MP_OK) return rc;
-        best.pointwise = true;
-        best.ks = 1; best.stride = 1; best.variant = kPointwise;
-        best.lds_bytes = best.pw.lds_bytes;
-        return MP_OK;
+        PwLaunch L{};
+        int rc = pw_configure(&d, L);
+        if (rc == MP_OK) best = L;
+        return rc;
     }
     if (forced == kGemm) {
-        int rc = gemm_configure(&d, best.gm);
-        if (rc != MP_OK) return rc;
-        best.gemm = true;
-        best.ks = d.kh; best.stride = best.gm.stride; best.variant = kGemm;
-        best.lds_bytes = best.gm.lds_bytes;
-        return MP_OK;
+        GemmLaunch L{};
+        int rc = gemm_configure(&d, L);
+        if (rc == MP_OK) best = L;
+        return rc;
     }
     if (forced == kSmall || forced == kSmall + 1) {  // + 1: the wide form (48 / 64 pixels per workgroup)
-        int rc = small_configure(&d, best.sm, forced - kSmall);
-        if (rc != MP_OK) return rc;
-        best.small_k = true;
-        best.ks = d.kh; best.stride = d.stride; best.variant = forced;
-        best.lds_bytes = best.sm.lds_bytes;
-        return MP_OK;
+        SmallLaunch L{};
+        int rc = small_configure(&d, L, forced - kSmall);
+        if (rc == MP_OK) best = L;
+        return rc;
     }
     if (forced >= 0) {
-        if (forced >= V_COUNT) return MP_ERR_UNSUPPORTED;
-        return configure(d, forced, best) ? MP_OK : MP_ERR_UNSUPPORTED;
+        DirectLaunch L{};
+        if (forced >= V_COUNT || !configure(d, forced, L)) return MP_ERR_UNSUPPORTED;
+        best = L;
+        return MP_OK;
     }
     // cout tile by divisibility; pixel tile 192 unless that leaves the chip under-filled
     int order[V_COUNT];
@@ -270,7 +323,7 @@ static int choose_variant(const mp_conv_desc& d, ConvLaunch& best, int forced = 
     bool have = false;
     double best_score = 0;
     for (int i = 0; i < n; ++i) {
-        ConvLaunch L{};
+        DirectLaunch L{};
         if (!configure(d, order[i], L)) continue;
         int CT, PT;
         variant_dims(order[i], CT, PT);
@@ -308,45 +361,43 @@ static int validate_desc(const mp_conv_desc* d) {
     return MP_OK;
 }
 
-static int launch(const ConvLaunch& L0, hipStream_t s) {
-    if (L0.pointwise) return pw_launch(L0.pw, s);
-    if (L0.gemm) return gemm_launch(L0.gm, s);
-    if (L0.small_k) return small_launch(L0.sm, s);
-    ConvLaunch L = L0;
-    L.p.dbg = (g_stamp_buf && (size_t)L.p.total_blocks * 64 <= g_stamp_bytes) ? g_stamp_buf : nullptr;
-    switch (L.ks) {
-        case 1: return launch_conv_k1(L.p, L.stride, L.variant, L.lds_bytes, s);
-        case 2: return launch_conv_k2(L.p, L.stride, L.variant, L.lds_bytes, s);
-        case 3: return L.stride == 1 ? launch_conv_k3s1(L.p, L.variant, L.lds_bytes, s)
-                                     : launch_conv_k3s2(L.p, L.variant, L.lds_bytes, s);
-        case 7: return launch_conv_k7(L.p, L.stride, L.variant, L.lds_bytes, s);
-        default: return MP_ERR_UNSUPPORTED;
+// the seven operand pointers of a conv launch, into whichever kernel's parameter block
+template <typename P>
+static int set_operands(P& p, const float* x, const float* w, const float* scale, const float* shift, const float* res1, const float* res2,
+                        float* out) {
+    if constexpr (std::is_same_v<P, PwParams>) {
+        if (res2) return MP_ERR_UNSUPPORTED;  // one residual tensor in the streaming kernel
+    } else {
+        p.res2 = res2;
     }
+    p.x = x; p.wp = w; p.scale = scale; p.shift = shift; p.res1 = res1; p.out = out;
+    return MP_OK;
 }
 
-static int build_launch(const mp_conv_desc* desc, const float* x, const float* w, const float* scale,
-                        const float* shift, const float* res1, const float* res2, float* out, ConvLaunch& L,
-                        int forced = -1) {
+static int build_launch(const mp_conv_desc* desc, const float* x, const float* w, const float* scale, const float* shift,
+                        const float* res1, const float* res2, float* out, Record& rec, int forced = -1) {
     int rc = validate_desc(desc);
     if (rc != MP_OK) return rc;
     if (!x || !w || !scale || !shift || !out) return MP_ERR_NULL;
-    rc = choose_variant(*desc, L, forced);
+    rc = choose_variant(*desc, rec, forced);
     if (rc != MP_OK) return rc;
-    if (L.pointwise) {
-        if (res2) return MP_ERR_UNSUPPORTED;  // one residual tensor in the streaming kernel
-        L.pw.p.x = x; L.pw.p.wp = w; L.pw.p.scale = scale; L.pw.p.shift = shift; L.pw.p.res1 = res1; L.pw.p.out = out;
-        return MP_OK;
-    }
-    if (L.gemm) {
-        L.gm.p.x = x; L.gm.p.wp = w; L.gm.p.scale = scale; L.gm.p.shift = shift; L.gm.p.res1 = res1; L.gm.p.res2 = res2; L.gm.p.out = out;
-        return MP_OK;
-    }
-    if (L.small_k) {
-        L.sm.p.x = x; L.sm.p.wp = w; L.sm.p.scale = scale; L.sm.p.shift = shift; L.sm.p.res1 = res1; L.sm.p.res2 = res2; L.sm.p.out = out;
-        return MP_OK;
-    }
-    L.p.x = x; L.p.wp = w; L.p.scale = scale; L.p.shift = shift; L.p.res1 = res1; L.p.res2 = res2; L.p.out = out;
-    return MP_OK;
+    return std::visit([&](auto& L) -> int {
+        if constexpr (is_f32_conv<std::decay_t<decltype(L)>>) return set_operands(L.p, x, w, scale, shift, res1, res2, out);
+        else return MP_ERR_UNSUPPORTED;  // (nothing else comes out of choose_variant)
+    }, rec);
+}
+
+// all four sub-pixel phases of Conv2dTranspose(k=4, s=2, p=1) as one GEMM launch
+static int build_deconv_gemm(const mp_conv_desc* desc, const float* x, const float* packed4, const float* scale, const float* shift,
+                             float* out, Record& rec) {
+    int rc = validate_desc(desc);
+    if (rc != MP_OK) return rc;
+    if (!x || !packed4 || !scale || !shift || !out) return MP_ERR_NULL;
+    GemmLaunch L{};
+    rc = gemm_configure_deconv(desc, L);
+    if (rc != MP_OK) return rc;
+    rec = L;
+    return set_operands(std::get<GemmLaunch>(rec).p, x, packed4, scale, shift, nullptr, nullptr, out);
 }
 
 }  // namespace mp
@@ -355,29 +406,8 @@ using namespace mp;
 
 struct mp_plan {
     struct Entry {
-        int kind;  // 0 conv, 1 maxpool, 2 fuse-sum; fp16 layout: 3 conv, 4 fuse-sum, 5 NCHW fp32 -> c8, 6 c8 -> NCHW fp32;
-                   // 7 = all-lane barrier (no launch), 8 = fused fp16 BasicBlock, 9 = fp32 Winograd conv,
-                   // 10 = fp16 expand + reduce 1x1 chain (stage 1), 11 = fp16 first conv from the fp32 image, 12 = fp32 first conv (streaming form),
-                   // 13 = fp32 expand + reduce 1x1 chain (stage 1), 14 = channel concatenation (s[0] / s[1] channels, relu = c8 layout),
-                   // 15 = column band copy (n rows, c = input width, h = first column, w = band width, relu = c8 layout)
         int lane;  // execution lane: 0 = the caller's stream, 1..3 = the plan's own side streams
-        ConvLaunch conv;
-        ConvF16Launch conv16;
-        BlockF16Launch block16;
-        PwChainLaunch pwchain;
-        PwChainF32Launch pwchain32;
-        StemF16Launch stem16;
-        StemF32Launch stem32;
-        WinoLaunch wino;
-        const void* t16[3];
-        const void* x16;
-        void* out16;
-        const float* x;
-        float* out;
-        int n, c, h, w;
-        const float* t[3];
-        int s[3];
-        int relu;
+        Record rec;
     };
     std::vector<Entry> entries;
     int cur_lane = 0;
@@ -397,28 +427,10 @@ struct mp_plan {
 
 static const int kPlanLanes = 4;
 
-static int run_entry(const mp_plan::Entry& e, mp_stream_t stream) {
-    switch (e.kind) {
-        case 0: return launch(e.conv, as_stream(stream));
-        case 1: return mp_maxpool3x3s2_same(e.x, e.out, e.n, e.c, e.h, e.w, stream);
-        case 2: return mp_fuse_upsample_sum(e.x, e.t[0], e.s[0], e.t[1], e.s[1], e.t[2], e.s[2], e.out, e.n, e.c, e.h, e.w, e.relu, stream);
-        case 3: return f16_launch(e.conv16, as_stream(stream));
-        case 4:
-            return mp_f16_fuse_upsample_sum(e.x16, e.t16[0], e.s[0], e.t16[1], e.s[1], e.t16[2], e.s[2], e.out16, e.n, e.c, e.h, e.w,
-                                            e.relu, stream);
-        case 5: return mp_f16_to_c8(e.x, e.out16, e.n, e.c, e.h, e.w, stream);
-        case 6: return mp_f16_from_c8(e.x16, e.out, e.n, e.c, e.h, e.w, stream);
-        case 7: return MP_OK;
-        case 8: return blockf16_launch(e.block16, as_stream(stream));
-        case 9: return wino_launch(e.wino, as_stream(stream));
-        case 10: return pwchain_launch(e.pwchain, as_stream(stream));
-        case 11: return stemf16_launch(e.stem16, as_stream(stream));
-        case 12: return stemf32_launch(e.stem32, as_stream(stream));
-        case 13: return pwchain32_launch(e.pwchain32, as_stream(stream));
-        case 14: return mp_concat_channels(e.x16, e.s[0], e.t16[0], e.s[1], e.out16, e.n, e.h, e.w, e.relu, stream);
-        case 15: return mp_col_slice(e.x16, e.out16, e.n, e.c, e.h, e.w, e.relu, stream);
-        default: return MP_ERR_UNSUPPORTED;
-    }
+// the tail of every mp_plan_add_*: the record goes on the lane the plan currently records for (a barrier spans them all: lane 0)
+static int push(mp_plan* plan, const Record& rec) {
+    plan->entries.push_back({std::holds_alternative<Barrier>(rec) ? 0 : plan->cur_lane, rec});
+    return MP_OK;
 }
 
 static int hip_rc(hipError_t e) {
@@ -451,13 +463,13 @@ static int run_multi_lane(const mp_plan* plan, hipStream_t main_stream) {
     for (int l = 1; l < nl && rc == MP_OK; ++l) rc = hip_rc(hipStreamWaitEvent(lanes[l], plan->ev_fork, 0));
     for (size_t i = 0; i < plan->entries.size() && rc == MP_OK; ++i) {
         const mp_plan::Entry& e = plan->entries[i];
-        if (e.kind == 7) {
+        if (std::holds_alternative<Barrier>(e.rec)) {
             for (int l = 0; l < nl && rc == MP_OK; ++l) rc = hip_rc(hipEventRecord(plan->ev[l], lanes[l]));
             for (int l = 0; l < nl && rc == MP_OK; ++l)
                 for (int m = 0; m < nl && rc == MP_OK; ++m)
                     if (m != l) rc = hip_rc(hipStreamWaitEvent(lanes[l], plan->ev[m], 0));
         } else {
-            rc = run_entry(e, reinterpret_cast<mp_stream_t>(lanes[e.lane]));
+            rc = run_record(e.rec, lanes[e.lane]);
         }
     }
     // join: the caller's stream continues only after every side lane has drained
@@ -505,10 +517,7 @@ int mp_conv_pack_weight_batch(const mp_f16_pack_job* jobs_dev, const unsigned* f
 
 int mp_conv2d_fwd(const mp_conv_desc* desc, const float* x, const float* packed_w, const float* scale,
                   const float* shift, const float* res1, const float* res2, float* out, mp_stream_t stream) {
-    ConvLaunch L{};
-    int rc = build_launch(desc, x, packed_w, scale, shift, res1, res2, out, L);
-    if (rc != MP_OK) return rc;
-    return launch(L, as_stream(stream));
+    return mp_conv2d_fwd_variant(desc, -1, x, packed_w, scale, shift, res1, res2, out, stream);
 }
 
 int mp_debug_set_stamp_buffer(void* dev_ptr, size_t bytes) {
@@ -524,35 +533,22 @@ int mp_debug_set_stamp_buffer(void* dev_ptr, size_t bytes) {
 
 int mp_conv2d_fwd_variant(const mp_conv_desc* desc, int variant, const float* x, const float* packed_w, const float* scale,
                           const float* shift, const float* res1, const float* res2, float* out, mp_stream_t stream) {
-    ConvLaunch L{};
-    int rc = build_launch(desc, x, packed_w, scale, shift, res1, res2, out, L, variant);
-    if (rc != MP_OK) return rc;
-    return launch(L, as_stream(stream));
+    Record rec;
+    int rc = build_launch(desc, x, packed_w, scale, shift, res1, res2, out, rec, variant);
+    return rc != MP_OK ? rc : run_record(rec, as_stream(stream));
 }
 
 int mp_plan_add_conv_variant(mp_plan* plan, const mp_conv_desc* desc, int variant, const float* x, const float* packed_w,
                              const float* scale, const float* shift, const float* res1, const float* res2, float* out) {
     if (!plan) return MP_ERR_NULL;
-    mp_plan::Entry e{};
-    e.kind = 0;
-    int rc = build_launch(desc, x, packed_w, scale, shift, res1, res2, out, e.conv, variant);
-    if (rc != MP_OK) return rc;
-    e.lane = plan->cur_lane;
-    plan->entries.push_back(e);
-    return MP_OK;
+    Record rec;
+    int rc = build_launch(desc, x, packed_w, scale, shift, res1, res2, out, rec, variant);
+    return rc != MP_OK ? rc : push(plan, rec);
 }
 
-static int build_deconv_gemm(const mp_conv_desc* desc, const float* x, const float* packed4, const float* scale, const float* shift,
-                             float* out, ConvLaunch& L) {
-    int rc = validate_desc(desc);
-    if (rc != MP_OK) return rc;
-    if (!x || !packed4 || !scale || !shift || !out) return MP_ERR_NULL;
-    rc = gemm_configure_deconv(desc, L.gm);
-    if (rc != MP_OK) return rc;
-    L.gemm = true;
-    L.ks = 2; L.stride = 1; L.variant = kGemm; L.lds_bytes = L.gm.lds_bytes;
-    L.gm.p.x = x; L.gm.p.wp = packed4; L.gm.p.scale = scale; L.gm.p.shift = shift; L.gm.p.res1 = nullptr; L.gm.p.res2 = nullptr; L.gm.p.out = out;
-    return MP_OK;
+int mp_plan_add_conv(mp_plan* plan, const mp_conv_desc* desc, const float* x, const float* packed_w,
+                     const float* scale, const float* shift, const float* res1, const float* res2, float* out) {
+    return mp_plan_add_conv_variant(plan, desc, -1, x, packed_w, scale, shift, res1, res2, out);
 }
 
 int mp_deconv4x4s2_gemm_supported(const mp_conv_desc* phase00_desc) {
@@ -563,132 +559,81 @@ int mp_deconv4x4s2_gemm_supported(const mp_conv_desc* phase00_desc) {
 
 int mp_deconv4x4s2_gemm_fwd(const mp_conv_desc* phase00_desc, const float* x, const float* packed4, const float* scale,
                             const float* shift, float* out, mp_stream_t stream) {
-    ConvLaunch L{};
-    int rc = build_deconv_gemm(phase00_desc, x, packed4, scale, shift, out, L);
-    if (rc != MP_OK) return rc;
-    return launch(L, as_stream(stream));
+    Record rec;
+    int rc = build_deconv_gemm(phase00_desc, x, packed4, scale, shift, out, rec);
+    return rc != MP_OK ? rc : run_record(rec, as_stream(stream));
 }
 
 int mp_plan_add_deconv4x4s2_gemm(mp_plan* plan, const mp_conv_desc* phase00_desc, const float* x, const float* packed4,
                                  const float* scale, const float* shift, float* out) {
     if (!plan) return MP_ERR_NULL;
-    mp_plan::Entry e{};
-    e.kind = 0;
-    int rc = build_deconv_gemm(phase00_desc, x, packed4, scale, shift, out, e.conv);
-    if (rc != MP_OK) return rc;
-    e.lane = plan->cur_lane;
-    plan->entries.push_back(e);
-    return MP_OK;
+    Record rec;
+    int rc = build_deconv_gemm(phase00_desc, x, packed4, scale, shift, out, rec);
+    return rc != MP_OK ? rc : push(plan, rec);
 }
 
 mp_plan* mp_plan_create(void) { return new (std::nothrow) mp_plan(); }
 
 void mp_plan_destroy(mp_plan* plan) { delete plan; }
 
-int mp_plan_add_conv(mp_plan* plan, const mp_conv_desc* desc, const float* x, const float* packed_w,
-                     const float* scale, const float* shift, const float* res1, const float* res2, float* out) {
-    if (!plan) return MP_ERR_NULL;
-    mp_plan::Entry e{};
-    e.kind = 0;
-    int rc = build_launch(desc, x, packed_w, scale, shift, res1, res2, out, e.conv);
-    if (rc != MP_OK) return rc;
-    e.lane = plan->cur_lane;
-    plan->entries.push_back(e);
-    return MP_OK;
-}
-
 int mp_plan_add_maxpool(mp_plan* plan, const float* x, float* out, int n, int c, int h, int w) {
     if (!plan || !x || !out) return MP_ERR_NULL;
     if (n <= 0 || c <= 0 || h <= 0 || w <= 0) return MP_ERR_SHAPE;
-    mp_plan::Entry e{};
-    e.kind = 1;
-    e.x = x; e.out = out; e.n = n; e.c = c; e.h = h; e.w = w;
-    e.lane = plan->cur_lane;
-    plan->entries.push_back(e);
-    return MP_OK;
+    return push(plan, MaxPool{x, out, n, c, h, w});
 }
 
 int mp_plan_add_fuse_sum(mp_plan* plan, const float* base, const float* t1, int s1, const float* t2, int s2,
                          const float* t3, int s3, float* out, int n, int c, int h, int w, int relu) {
     if (!plan || !base || !t1 || !out) return MP_ERR_NULL;
     if (n <= 0 || c <= 0 || h <= 0 || w <= 0) return MP_ERR_SHAPE;
-    mp_plan::Entry e{};
-    e.kind = 2;
-    e.x = base; e.out = out; e.n = n; e.c = c; e.h = h; e.w = w; e.relu = relu;
-    e.t[0] = t1; e.t[1] = t2; e.t[2] = t3; e.s[0] = s1; e.s[1] = s2; e.s[2] = s3;
-    e.lane = plan->cur_lane;
-    plan->entries.push_back(e);
-    return MP_OK;
+    return push(plan, FuseSum{base, {t1, t2, t3}, {s1, s2, s3}, out, n, c, h, w, relu});
 }
 
 int mp_plan_add_conv_f16(mp_plan* plan, const mp_conv_desc* desc, int variant, const void* x, const void* packed_w,
                          const float* scale, const float* shift, const void* res1, const void* res2, void* out) {
     if (!plan) return MP_ERR_NULL;
-    mp_plan::Entry e{};
-    e.kind = 3;
-    int rc = f16_build_launch(desc, variant, x, packed_w, scale, shift, res1, res2, out, e.conv16);
-    if (rc != MP_OK) return rc;
-    e.lane = plan->cur_lane;
-    plan->entries.push_back(e);
-    return MP_OK;
+    ConvF16Launch L{};
+    int rc = f16_build_launch(desc, variant, x, packed_w, scale, shift, res1, res2, out, L);
+    return rc != MP_OK ? rc : push(plan, L);
 }
 
 int mp_plan_add_conv_winograd(mp_plan* plan, const mp_conv_desc* desc, const float* x, const float* packed_u, const float* scale,
                               const float* shift, const float* res1, const float* res2, float* out) {
     if (!plan) return MP_ERR_NULL;
-    mp_plan::Entry e{};
-    e.kind = 9;
-    int rc = wino_configure(desc, e.wino);
+    WinoLaunch L{};
+    int rc = wino_configure(desc, L);
     if (rc != MP_OK) return rc;
     if (!x || !packed_u || !scale || !shift || !out) return MP_ERR_NULL;
-    e.wino.p.x = x; e.wino.p.u = packed_u; e.wino.p.scale = scale; e.wino.p.shift = shift; e.wino.p.res1 = res1; e.wino.p.res2 = res2;
-    e.wino.p.out = out;
-    e.lane = plan->cur_lane;
-    plan->entries.push_back(e);
-    return MP_OK;
+    L.p.x = x; L.p.u = packed_u; L.p.scale = scale; L.p.shift = shift; L.p.res1 = res1; L.p.res2 = res2; L.p.out = out;
+    return push(plan, L);
 }
 
 int mp_plan_add_basicblock_f16(mp_plan* plan, const void* x, const void* packed_w1, const float* scale1, const float* shift1,
                                const void* packed_w2, const float* scale2, const float* shift2, void* out, int n, int c, int h,
                                int w, int rows) {
     if (!plan) return MP_ERR_NULL;
-    mp_plan::Entry e{};
-    e.kind = 8;
-    int rc = blockf16_build(x, packed_w1, scale1, shift1, packed_w2, scale2, shift2, out, n, c, h, w, rows, e.block16);
-    if (rc != MP_OK) return rc;
-    e.n = n; e.c = c; e.h = h; e.w = w;
-    e.lane = plan->cur_lane;
-    plan->entries.push_back(e);
-    return MP_OK;
+    BlockF16Launch L{};
+    int rc = blockf16_build(x, packed_w1, scale1, shift1, packed_w2, scale2, shift2, out, n, c, h, w, rows, L);
+    return rc != MP_OK ? rc : push(plan, L);
 }
 
 int mp_plan_add_expand_reduce_f16(mp_plan* plan, const void* mid, const void* res, const void* packed_w3, const float* scale3,
                                   const float* shift3, int relu3, const void* packed_w1, const float* scale1, const float* shift1,
                                   int relu1, void* y, void* z, int n, int cm, int ce, int cr, int h, int w) {
     if (!plan) return MP_ERR_NULL;
-    mp_plan::Entry e{};
-    e.kind = 10;
-    int rc = pwchain_build(mid, res, packed_w3, scale3, shift3, relu3, packed_w1, scale1, shift1, relu1, y, z, n, cm, ce, cr, h, w, e.pwchain);
-    if (rc != MP_OK) return rc;
-    e.n = n; e.c = ce; e.h = h; e.w = w;
-    e.lane = plan->cur_lane;
-    plan->entries.push_back(e);
-    return MP_OK;
+    PwChainLaunch L{};
+    int rc = pwchain_build(mid, res, packed_w3, scale3, shift3, relu3, packed_w1, scale1, shift1, relu1, y, z, n, cm, ce, cr, h, w, L);
+    return rc != MP_OK ? rc : push(plan, L);
 }
 
 int mp_plan_add_expand_reduce(mp_plan* plan, const float* mid, const float* res, const float* x0, const float* packed_wd, const float* scale_d,
                               const float* shift_d, const float* packed_w3, const float* scale3, const float* shift3, const float* packed_w1,
                               const float* scale1, const float* shift1, float* y, float* z, int n, int cm, int ce, int cr, int h, int w) {
     if (!plan) return MP_ERR_NULL;
-    mp_plan::Entry e{};
-    e.kind = 13;
+    PwChainF32Launch L{};
     int rc = pwchain32_build(mid, res, x0, packed_wd, scale_d, shift_d, packed_w3, scale3, shift3, packed_w1, scale1, shift1, y, z, n, cm, ce, cr,
-                             h, w, e.pwchain32);
-    if (rc != MP_OK) return rc;
-    e.n = n; e.c = ce; e.h = h; e.w = w;
-    e.lane = plan->cur_lane;
-    plan->entries.push_back(e);
-    return MP_OK;
+                             h, w, L);
+    return rc != MP_OK ? rc : push(plan, L);
 }
 
 int mp_plan_add_ds_expand_reduce_f16(mp_plan* plan, const void* mid, const void* x0, const void* packed_wd, const float* scale_d,
@@ -696,113 +641,68 @@ int mp_plan_add_ds_expand_reduce_f16(mp_plan* plan, const void* mid, const void*
                                      const void* packed_w1, const float* scale1, const float* shift1, int relu1, void* y, void* z, int n,
                                      int cm, int ce, int cr, int h, int w) {
     if (!plan || !x0) return MP_ERR_NULL;
-    mp_plan::Entry e{};
-    e.kind = 10;
-    int rc = pwchain_build(mid, nullptr, packed_w3, scale3, shift3, relu3, packed_w1, scale1, shift1, relu1, y, z, n, cm, ce, cr, h, w, e.pwchain,
-                           x0, packed_wd, scale_d, shift_d);
-    if (rc != MP_OK) return rc;
-    e.n = n; e.c = ce; e.h = h; e.w = w;
-    e.lane = plan->cur_lane;
-    plan->entries.push_back(e);
-    return MP_OK;
+    PwChainLaunch L{};
+    int rc = pwchain_build(mid, nullptr, packed_w3, scale3, shift3, relu3, packed_w1, scale1, shift1, relu1, y, z, n, cm, ce, cr, h, w, L, x0,
+                           packed_wd, scale_d, shift_d);
+    return rc != MP_OK ? rc : push(plan, L);
 }
 
 int mp_plan_add_dual_pw_f16(mp_plan* plan, const void* x, const void* packed_wa, const float* scale_a, const float* shift_a, int relu_a,
                             const void* packed_wb, const float* scale_b, const float* shift_b, int relu_b, void* ya, void* zb, int n, int cm,
                             int ce, int cr, int h, int w) {
     if (!plan) return MP_ERR_NULL;
-    mp_plan::Entry e{};
-    e.kind = 10;
-    int rc = pwchain_build(x, x, packed_wa, scale_a, shift_a, relu_a, packed_wb, scale_b, shift_b, relu_b, ya, zb, n, cm, ce, cr, h, w, e.pwchain);
-    if (rc != MP_OK) return rc;
-    e.n = n; e.c = ce; e.h = h; e.w = w;
-    e.lane = plan->cur_lane;
-    plan->entries.push_back(e);
-    return MP_OK;
+    PwChainLaunch L{};
+    int rc = pwchain_build(x, x, packed_wa, scale_a, shift_a, relu_a, packed_wb, scale_b, shift_b, relu_b, ya, zb, n, cm, ce, cr, h, w, L);
+    return rc != MP_OK ? rc : push(plan, L);
 }
 
 int mp_plan_add_stem_conv(mp_plan* plan, const float* x, const float* weight, const float* scale, const float* shift, int relu, float* out,
                           int n, int h, int w) {
     if (!plan) return MP_ERR_NULL;
-    mp_plan::Entry e{};
-    e.kind = 12;
-    int rc = stemf32_build(x, weight, scale, shift, relu, out, n, h, w, e.stem32);
-    if (rc != MP_OK) return rc;
-    e.n = n; e.c = 64; e.h = h; e.w = w;
-    e.lane = plan->cur_lane;
-    plan->entries.push_back(e);
-    return MP_OK;
+    StemF32Launch L{};
+    int rc = stemf32_build(x, weight, scale, shift, relu, out, n, h, w, L);
+    return rc != MP_OK ? rc : push(plan, L);
 }
 
 int mp_plan_add_stem_conv_f16(mp_plan* plan, const float* x, const float* weight, const float* scale, const float* shift, int relu,
                               void* out, int n, int h, int w) {
     if (!plan) return MP_ERR_NULL;
-    mp_plan::Entry e{};
-    e.kind = 11;
-    int rc = stemf16_build(x, weight, scale, shift, relu, out, n, h, w, e.stem16);
-    if (rc != MP_OK) return rc;
-    e.n = n; e.c = 64; e.h = h; e.w = w;
-    e.lane = plan->cur_lane;
-    plan->entries.push_back(e);
-    return MP_OK;
+    StemF16Launch L{};
+    int rc = stemf16_build(x, weight, scale, shift, relu, out, n, h, w, L);
+    return rc != MP_OK ? rc : push(plan, L);
 }
 
 int mp_plan_add_fuse_sum_f16(mp_plan* plan, const void* base, const void* t1, int s1, const void* t2, int s2, const void* t3,
                              int s3, void* out, int n, int c, int h, int w, int relu) {
     if (!plan || !base || !t1 || !out) return MP_ERR_NULL;
     if (n <= 0 || c <= 0 || h <= 0 || w <= 0) return MP_ERR_SHAPE;
-    mp_plan::Entry e{};
-    e.kind = 4;
-    e.x16 = base; e.out16 = out; e.n = n; e.c = c; e.h = h; e.w = w; e.relu = relu;
-    e.t16[0] = t1; e.t16[1] = t2; e.t16[2] = t3; e.s[0] = s1; e.s[1] = s2; e.s[2] = s3;
-    e.lane = plan->cur_lane;
-    plan->entries.push_back(e);
-    return MP_OK;
+    return push(plan, FuseSumF16{base, {t1, t2, t3}, {s1, s2, s3}, out, n, c, h, w, relu});
 }
 
 int mp_plan_add_layout_f16(mp_plan* plan, int to_c8, const void* x, void* out, int n, int c, int h, int w) {
     if (!plan || !x || !out) return MP_ERR_NULL;
     if (n <= 0 || c <= 0 || h <= 0 || w <= 0) return MP_ERR_SHAPE;
-    mp_plan::Entry e{};
-    e.kind = to_c8 ? 5 : 6;
-    if (to_c8) { e.x = reinterpret_cast<const float*>(x); e.out16 = out; }
-    else { e.x16 = x; e.out = reinterpret_cast<float*>(out); }
-    e.n = n; e.c = c; e.h = h; e.w = w;
-    e.lane = plan->cur_lane;
-    plan->entries.push_back(e);
-    return MP_OK;
+    if (to_c8) return push(plan, ToC8{reinterpret_cast<const float*>(x), out, n, c, h, w});
+    return push(plan, FromC8{x, reinterpret_cast<float*>(out), n, c, h, w});
 }
 
 int mp_plan_add_concat(mp_plan* plan, const void* a, int ca, const void* b, int cb, void* out, int n, int h, int w, int c8) {
     if (!plan || !a || !b || !out) return MP_ERR_NULL;
     if (n <= 0 || ca <= 0 || cb <= 0 || h <= 0 || w <= 0) return MP_ERR_SHAPE;
     if (c8 && ca % 8 != 0) return MP_ERR_UNSUPPORTED;
-    mp_plan::Entry e{};
-    e.kind = 14;
-    e.x16 = a; e.t16[0] = b; e.out16 = out;
-    e.s[0] = ca; e.s[1] = cb; e.relu = c8 ? 1 : 0;
-    e.n = n; e.c = ca + cb; e.h = h; e.w = w;
-    e.lane = plan->cur_lane;
-    plan->entries.push_back(e);
-    return MP_OK;
+    return push(plan, Concat{a, ca, b, cb, out, n, h, w, c8 ? 1 : 0});
 }
 
 int mp_plan_add_col_slice(mp_plan* plan, const void* in, void* out, int rows, int w_in, int start, int w_out, int c8) {
     if (!plan || !in || !out) return MP_ERR_NULL;
     if (rows <= 0 || w_in <= 0 || w_out <= 0 || start < 0 || start + w_out > w_in) return MP_ERR_SHAPE;
-    mp_plan::Entry e{};
-    e.kind = 15;
-    e.x16 = in; e.out16 = out;
-    e.n = rows; e.c = w_in; e.h = start; e.w = w_out; e.relu = c8 ? 1 : 0;
-    e.lane = plan->cur_lane;
-    plan->entries.push_back(e);
-    return MP_OK;
+    return push(plan, ColSlice{in, out, rows, w_in, start, w_out, c8 ? 1 : 0});
 }
 
 int mp_conv_supported(const mp_conv_desc* desc, int variant) {
     if (validate_desc(desc) != MP_OK) return 0;
-    ConvLaunch L{};
-    return choose_variant(*desc, L, variant) == MP_OK ? 1 : 0;
+    Record rec;
+    return choose_variant(*desc, rec, variant) == MP_OK ? 1 : 0;
 }
 
 int mp_plan_size(const mp_plan* plan) { return plan ? (int)plan->entries.size() : MP_ERR_NULL; }
@@ -811,7 +711,7 @@ int mp_plan_run_range(const mp_plan* plan, int first, int count, mp_stream_t str
     if (!plan) return MP_ERR_NULL;
     if (first < 0 || count < 0 || (size_t)first + count > plan->entries.size()) return MP_ERR_SHAPE;
     for (int i = first; i < first + count; ++i) {
-        int rc = run_entry(plan->entries[i], stream);  // one stream, in order: per-entry timing / profiling
+        int rc = run_record(plan->entries[i].rec, as_stream(stream));  // one stream, in order: per-entry timing / profiling
         if (rc != MP_OK) return rc;
     }
     return MP_OK;
@@ -820,56 +720,7 @@ int mp_plan_run_range(const mp_plan* plan, int first, int count, mp_stream_t str
 int mp_plan_entry_info(const mp_plan* plan, int index, int64_t info[12]) {
     if (!plan || !info) return MP_ERR_NULL;
     if (index < 0 || (size_t)index >= plan->entries.size()) return MP_ERR_SHAPE;
-    const mp_plan::Entry& e = plan->entries[index];
-    for (int i = 0; i < 12; ++i) info[i] = 0;
-    info[0] = e.kind;
-    if (e.kind == 0 && e.conv.pointwise) {
-        info[1] = 1; info[2] = 1; info[3] = kPointwise; info[4] = e.conv.pw.grid; info[5] = (int64_t)e.conv.pw.lds_bytes;
-        info[6] = e.conv.pw.p.Cout; info[7] = 64; info[8] = 64; info[9] = e.conv.pw.cbw; info[10] = e.conv.pw.p.tiles_per_wg;
-        info[11] = e.conv.pw.kq;
-    } else if (e.kind == 0 && e.conv.gemm) {
-        info[1] = e.conv.ks; info[2] = e.conv.gm.stride; info[3] = kGemm; info[11] = e.conv.gm.gather ? 1 : 0; info[4] = (int64_t)e.conv.gm.grid * e.conv.gm.phases; info[5] = (int64_t)e.conv.gm.lds_bytes;
-        info[6] = 64 * e.conv.gm.mi; info[7] = 64 * e.conv.gm.ni; info[8] = 16; info[9] = e.conv.gm.phases; info[10] = 1;
-    } else if (e.kind == 0 && e.conv.small_k) {
-        info[1] = e.conv.ks; info[2] = e.conv.stride; info[3] = e.conv.variant; info[4] = e.conv.sm.grid; info[5] = (int64_t)e.conv.sm.lds_bytes;
-        info[6] = 16; info[7] = 16 * e.conv.sm.p.pt; info[8] = e.conv.sm.p.Cin_pad4; info[9] = 1; info[10] = e.conv.sm.p.rows;
-    } else if (e.kind == 0) {
-        int ct, pt;
-        variant_dims(e.conv.variant, ct, pt);
-        info[1] = e.conv.ks; info[2] = e.conv.stride; info[3] = e.conv.variant; info[4] = e.conv.p.total_blocks;
-        info[5] = (int64_t)e.conv.lds_bytes; info[6] = ct; info[7] = pt; info[8] = e.conv.p.CK; info[9] = e.conv.p.G;
-        info[10] = e.conv.p.R;
-        info[11] = variant_light(e.conv.variant) ? 1 : 0;
-    } else if (e.kind == 3) {
-        int ct, pt;
-        f16_variant_dims(e.conv16.variant, ct, pt);
-        info[1] = e.conv16.ks; info[2] = e.conv16.stride; info[3] = e.conv16.variant; info[4] = e.conv16.p.total_blocks;
-        info[5] = (int64_t)e.conv16.lds_bytes; info[6] = ct; info[7] = pt; info[8] = e.conv16.p.PK * 8; info[9] = e.conv16.p.G;
-        info[10] = e.conv16.p.R;
-        info[11] = f16_variant_light(e.conv16.variant) ? 1 : 0;
-    } else if (e.kind == 9) {
-        info[1] = 3; info[2] = 1; info[3] = 9 /* the tuner's index of the Winograd form */; info[4] = e.wino.p.total_blocks;
-        info[5] = (int64_t)e.wino.lds_bytes; info[6] = 32 * e.wino.teams; info[7] = e.wino.p.M * 4; info[8] = 8; info[9] = 1; info[10] = e.wino.p.R;
-        info[11] = e.wino.ni;
-    } else if (e.kind == 12) {
-        info[1] = 3; info[2] = 2; info[3] = 0; info[4] = e.stem32.p.total_blocks;
-        info[5] = (int64_t)e.stem32.lds_bytes; info[6] = 64; info[7] = 8 * e.stem32.p.Wo; info[8] = 3; info[9] = 1; info[10] = 8;
-    } else if (e.kind == 11) {
-        info[1] = 3; info[2] = 2; info[3] = 0; info[4] = e.stem16.p.total_blocks;
-        info[5] = (int64_t)e.stem16.lds_bytes; info[6] = 64; info[7] = 8 * e.stem16.p.Wo; info[8] = 3; info[9] = 1; info[10] = 8;
-    } else if (e.kind == 13) {
-        info[1] = 1; info[2] = 1; info[3] = (e.pwchain32.ds ? 1 : 0) + (e.pwchain32.red ? 0 : 2); info[4] = e.pwchain32.grid;
-        info[5] = (int64_t)e.pwchain32.lds_bytes; info[6] = 256; info[7] = e.pwchain32.form == 2 ? 32 : 64; info[8] = 64; info[9] = 1; info[10] = 0;
-        info[11] = e.pwchain32.form;  // 4 / 8 waves per workgroup on 64-pixel tiles, 2 = four waves on 32-pixel tiles, two workgroups per CU
-    } else if (e.kind == 10) {
-        info[1] = 1; info[2] = 1; info[3] = e.pwchain.dual ? 1 : e.pwchain.ds ? 2 : 0; info[4] = e.pwchain.p.total_blocks;
-        info[5] = (int64_t)e.pwchain.lds_bytes; info[6] = e.pwchain.ce; info[7] = 64; info[8] = e.pwchain.cm; info[9] = 1; info[10] = 0;
-    } else if (e.kind == 8) {
-        info[1] = 3; info[2] = 1; info[3] = e.block16.small; info[4] = e.block16.p.total_blocks;
-        const int blk_c = e.block16.small == 4 ? 64 : e.block16.small == 5 ? 128 : 32;  // cout tile / cin chunk = the block's width
-        info[5] = (int64_t)e.block16.lds_bytes; info[6] = blk_c; info[7] = e.block16.p.M2; info[8] = blk_c; info[9] = 1;
-        info[10] = e.block16.p.R;
-    }
+    std::visit([info](const auto& r) { describe(r, info); }, plan->entries[index].rec);
     return MP_OK;
 }
 
@@ -887,13 +738,6 @@ int mp_plan_set_lane(mp_plan* plan, int lane) {
     return MP_OK;
 }
 
-int mp_plan_add_barrier(mp_plan* plan) {
-    if (!plan) return MP_ERR_NULL;
-    mp_plan::Entry e{};
-    e.kind = 7;
-    e.lane = 0;
-    plan->entries.push_back(e);
-    return MP_OK;
-}
+int mp_plan_add_barrier(mp_plan* plan) { return plan ? push(plan, Barrier{}) : MP_ERR_NULL; }
 
 }  // extern "C"

@@ -109,19 +109,28 @@ struct BlockF16Params {
     unsigned long long* dbg;         // diagnostic builds (-DMP_BLOCK_STAMPS=1) only: 16 x u64 per (workgroup, wave half)
 };
 
+// which kernel serves a fused block (mp_plan_entry_info reports the number)
+enum BlockForm { kTile65 = 0, kTile53 = 1,      // first structure of the 32-channel block: the <6,5> / <5,3> pixel-tile builds
+                 kV2Wave8 = 2, kV2Wave4 = 3,    // second structure, eight / four waves (the four-wave shape is not built any more)
+                 kC64 = 4, kC128 = 5 };         // 64- / 128-channel block
 struct BlockF16Launch {
     BlockF16Params p;
-    int small;  // 1: the <5,3> pixel-tile build suffices, 0: <6,5>
+    BlockForm form;
     size_t lds_bytes;
 };
 int blockf16_build(const void* x, const void* w1, const float* scale1, const float* shift1, const void* w2, const float* scale2,
                    const float* shift2, void* out, int n, int c, int h, int w, int rows, BlockF16Launch& L);
 int blockf16_launch(const BlockF16Launch& L, hipStream_t s);
-// second structure (basicblock_f16_v2.hip): weights in registers, LDS-DMA bands, 512-thread workgroups; L.small == 2 marks it
+inline int run(const BlockF16Launch& L, hipStream_t s) { return blockf16_launch(L, s); }
+inline void describe(const BlockF16Launch& L, int64_t info[12]) {
+    const int c = L.form == kC64 ? 64 : L.form == kC128 ? 128 : 32;  // cout tile / cin chunk = the block's width
+    fill_info(info, {kBlockF16, 3, 1, L.form, L.p.total_blocks, (int64_t)L.lds_bytes, c, L.p.M2, c, 1, L.p.R});
+}
+// second structure (basicblock_f16_v2.hip): weights in registers, LDS-DMA bands, 512-thread workgroups (form kV2Wave8)
 bool blockf16_v2_build(const void* x, const void* w1, const float* scale1, const float* shift1, const void* w2, const float* scale2,
                        const float* shift2, void* out, int n, int c, int h, int w, int rows, BlockF16Launch& L);
 int blockf16_v2_launch(const BlockF16Launch& L, hipStream_t s);
-// 64-channel block (basicblock_f16_c64.hip): one band per workgroup, cout tile per wave; L.small == 4 marks it
+// 64- / 128-channel block (basicblock_f16_c64.hip): one band per workgroup, cout tile per wave (forms kC64 / kC128)
 bool blockf16_c64_build(const void* x, const void* w1, const float* scale1, const float* shift1, const void* w2, const float* scale2,
                         const float* shift2, void* out, int n, int c, int h, int w, int rows, BlockF16Launch& L);
 int blockf16_c64_launch(const BlockF16Launch& L, hipStream_t s);
@@ -157,6 +166,10 @@ int pwchain_build(const void* mid, const void* res, const void* w3, const float*
                   PwChainLaunch& L, const void* x0 = nullptr, const void* wd = nullptr, const float* scale_d = nullptr,
                   const float* shift_d = nullptr);
 int pwchain_launch(const PwChainLaunch& L, hipStream_t s);
+inline int run(const PwChainLaunch& L, hipStream_t s) { return pwchain_launch(L, s); }
+inline void describe(const PwChainLaunch& L, int64_t info[12]) {
+    fill_info(info, {kPwChainF16, 1, 1, L.dual ? 1 : L.ds ? 2 : 0, L.p.total_blocks, (int64_t)L.lds_bytes, L.ce, 64, L.cm, 1});
+}
 
 // first conv of the network straight from the fp32 NCHW image (stem_f16.hip): 3x3 stride 2 padding 1, 3 -> 64 channels
 struct StemF16Params {
@@ -175,6 +188,10 @@ struct StemF16Launch {
 int stemf16_build(const float* x, const float* w, const float* scale, const float* shift, int relu, void* out, int n, int h, int wd,
                   StemF16Launch& L);
 int stemf16_launch(const StemF16Launch& L, hipStream_t s);
+inline int run(const StemF16Launch& L, hipStream_t s) { return stemf16_launch(L, s); }
+inline void describe(const StemF16Launch& L, int64_t info[12]) {  // 64 couts x 8 output rows per workgroup, one 3-channel chunk
+    fill_info(info, {kStemF16, 3, 2, 0, L.p.total_blocks, (int64_t)L.lds_bytes, 64, 8 * L.p.Wo, 3, 1, 8});
+}
 
 int f16_build_launch(const mp_conv_desc* desc, int variant, const void* x, const void* w, const float* scale,
                      const float* shift, const void* res1, const void* res2, void* out, ConvF16Launch& L);
@@ -190,5 +207,13 @@ int f16_mt_ni(int occ);
 bool f16_configure_ws(const mp_conv_desc& d, int variant, ConvF16Launch& L);
 int f16_ws_launch(const ConvF16Launch& L, hipStream_t s);
 void f16_ws_dims(int v, int& ps, int& csw, int& waves_p);
+
+inline int run(const ConvF16Launch& L, hipStream_t s) { return f16_launch(L, s); }
+inline void describe(const ConvF16Launch& L, int64_t info[12]) {
+    int ct, pt;
+    f16_variant_dims(L.variant, ct, pt);
+    fill_info(info, {kConvF16, L.ks, L.stride, L.variant, L.p.total_blocks, (int64_t)L.lds_bytes, ct, pt, L.p.PK * 8, L.p.G, L.p.R,
+                     f16_variant_light(L.variant) ? 1 : 0});
+}
 
 }  // namespace mp

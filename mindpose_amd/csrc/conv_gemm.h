@@ -40,4 +40,12 @@ int gemm_configure(const mp_conv_desc* d, GemmLaunch& L);  // MP_OK / MP_ERR_UNS
 int gemm_configure_deconv(const mp_conv_desc* phase00, GemmLaunch& L);  // all four phases of Conv2dTranspose(k=4, s=2, p=1)
 int gemm_launch(const GemmLaunch& L, hipStream_t s);
 
+constexpr int kGemm = 10;  // forced-variant index of this kernel (9 is the tuner's index of the Winograd form)
+
+inline int run(const GemmLaunch& L, hipStream_t s) { return gemm_launch(L, s); }
+inline void describe(const GemmLaunch& L, int64_t info[12]) {
+    fill_info(info, {kConv, L.p.kw, L.stride, kGemm, (int64_t)L.grid * L.phases, (int64_t)L.lds_bytes, 64 * L.mi, 64 * L.ni, 16, L.phases, 1,
+                     L.gather ? 1 : 0});
+}
+
 }  // namespace mp

@@ -26,4 +26,11 @@ struct PwLaunch {
 int pw_configure(const mp_conv_desc* d, PwLaunch& L);  // MP_OK / MP_ERR_UNSUPPORTED; pointers left null
 int pw_launch(const PwLaunch& L, hipStream_t s);
 
+constexpr int kPointwise = 8;  // forced-variant index of this kernel (behind the direct kernel's tile variants; never the library's own choice)
+
+inline int run(const PwLaunch& L, hipStream_t s) { return pw_launch(L, s); }
+inline void describe(const PwLaunch& L, int64_t info[12]) {
+    fill_info(info, {kConv, 1, 1, kPointwise, L.grid, (int64_t)L.lds_bytes, L.p.Cout, 64, 64, L.cbw, L.p.tiles_per_wg, L.kq});
+}
+
 }  // namespace mp

@@ -35,4 +35,12 @@ struct SmallLaunch {
 int small_configure(const mp_conv_desc* d, SmallLaunch& L, int wide);  // wide: 48 / 64 pixels per workgroup;  // MP_OK / MP_ERR_UNSUPPORTED; pointers left null
 int small_launch(const SmallLaunch& L, hipStream_t s);
 
+constexpr int kSmall = 11;  // forced-variant index of this kernel; kSmall + 1: its wide form
+
+inline int run(const SmallLaunch& L, hipStream_t s) { return small_launch(L, s); }
+inline void describe(const SmallLaunch& L, int64_t info[12]) {
+    fill_info(info, {kConv, L.p.ks, L.p.stride, kSmall + (L.p.pt > 1 ? 1 : 0), L.grid, (int64_t)L.lds_bytes, 16, 16 * L.p.pt, L.p.Cin_pad4, 1,
+                     L.p.rows});
+}
+
 }  // namespace mp

@@ -21,4 +21,9 @@ int stemf32_build(const float* x, const float* w, const float* scale, const floa
                   StemF32Launch& L);
 int stemf32_launch(const StemF32Launch& L, hipStream_t s);
 
+inline int run(const StemF32Launch& L, hipStream_t s) { return stemf32_launch(L, s); }
+inline void describe(const StemF32Launch& L, int64_t info[12]) {  // 64 couts x 8 output rows per workgroup, one 3-channel chunk
+    fill_info(info, {kStemF32, 3, 2, 0, L.p.total_blocks, (int64_t)L.lds_bytes, 64, 8 * L.p.Wo, 3, 1, 8});
+}
+
 }  // namespace mp

@@ -63,6 +63,11 @@ __device__ __forceinline__ void wino_transform_weight(const float* __restrict__ 
 int wino_pack_launch(const float* w, float* packed, int cout, int cin, int transposed, hipStream_t s);
 int wino_configure(const mp_conv_desc* d, WinoLaunch& L);  // MP_OK / MP_ERR_UNSUPPORTED; pointers left null
 int wino_launch(const WinoLaunch& L, hipStream_t s);
+
+inline int run(const WinoLaunch& L, hipStream_t s) { return wino_launch(L, s); }
+inline void describe(const WinoLaunch& L, int64_t info[12]) {  // info[3]: the tuner's index of the Winograd form
+    fill_info(info, {kWinograd, 3, 1, 9, L.p.total_blocks, (int64_t)L.lds_bytes, 32 * L.teams, L.p.M * 4, 8, 1, L.p.R, L.ni});
+}
 unsigned long long* conv_stamp_buffer(size_t need_bytes);  // conv_api.hip: mp_debug_set_stamp_buffer's buffer when large enough, else null
 
 }  // namespace mp

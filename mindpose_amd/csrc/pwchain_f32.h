@@ -38,4 +38,10 @@ int pwchain32_build(const float* mid, const float* res, const float* x0, const f
                     PwChainF32Launch& L);  // MP_OK / MP_ERR_UNSUPPORTED
 int pwchain32_launch(const PwChainF32Launch& L, hipStream_t s);
 
+inline int run(const PwChainF32Launch& L, hipStream_t s) { return pwchain32_launch(L, s); }
+inline void describe(const PwChainF32Launch& L, int64_t info[12]) {
+    fill_info(info, {kPwChainF32, 1, 1, (L.ds ? 1 : 0) + (L.red ? 0 : 2), L.grid, (int64_t)L.lds_bytes, 256, L.form == 2 ? 32 : 64, 64, 1, 0,
+                     L.form});
+}
+
 }  // namespace mp
