@@ -30,6 +30,7 @@ struct WinoLaunch {
     int ni;
     bool group;  // image-grouped bands
     int teams;   // 1 or 2 four-wave teams per workgroup (2: a 64-channel cout tile on one shared input transform)
+    bool wide;   // teams == 2 only: the 64-channel cout tile on four waves (one per SIMD, 48 accumulators each) instead of eight
 };
 
 // U = G g G^T of one (cout co, cin ci) pair -> out[16] (xi = 4 row + col).  `transposed` = 0: w is [cout][cin][3][3] (forward);

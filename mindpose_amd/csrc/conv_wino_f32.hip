@@ -27,6 +27,10 @@ namespace mp {
 
 namespace {
 
+#ifndef MP_WINO_WIDE_OPTS
+#define MP_WINO_WIDE_OPTS 7
+#endif
+
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 constexpr int kCK = 8;    // input channels per chunk
 constexpr int kTP = 48;   // tile pitch of V (floats), tiles per workgroup <= 48
@@ -36,6 +40,21 @@ constexpr int kXFloats = 16 * 16 * kXP;
 constexpr size_t kMaxLds = 150 * 1024;    // dynamic LDS a launch may ask for
 constexpr int kGroupTeamsMinWgs = 128;    // image-grouped bands take two teams when that still leaves this many workgroups
 
+
+// The four-wave form's chunk body: in-place AGPR accumulation and unpacked adds, as statements whose order the compiler keeps
+__device__ __forceinline__ void wide_mfma(f32x4& acc, float a, float b) {
+    asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+a"(acc) : "v"(a), "v"(b));
+}
+__device__ __forceinline__ float wide_add(float a, float b) {
+    float r;
+    asm volatile("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
+__device__ __forceinline__ float wide_sub(float a, float b) {
+    float r;
+    asm volatile("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+    return r;
+}
 
 __device__ __forceinline__ void wg_barrier() {
     // LDS traffic of this wave done, then the workgroup barrier; global loads stay in flight (a __syncthreads() would drain them)
@@ -52,18 +71,29 @@ __device__ __forceinline__ void wg_barrier() {
 // GROUP with TEAMS = 2: the same sharing of the grouped raw planes and V, but the transform is split the other way - every thread
 // of BOTH teams takes one tile (XF1 below) instead of team 0's threads taking two: the pair form's 64 patch registers beside the
 // per-element staging offsets do not fit the 256 registers of an eight-wave workgroup (hipcc spilled 8 of them).
-template <int NI, bool QROW, bool GROUP, int TEAMS>
-__global__ __launch_bounds__(256 * TEAMS, TEAMS == 1 ? 2 : 1) void conv_wino_f32_kernel(const WinoParams p) {
+// WIDE (with TEAMS = 2): the same 64-channel cout tile on FOUR waves, one per SIMD with 512 registers each - a wave keeps its
+// xi = 4w .. 4w+3 and owns 3 tile blocks x 4 cout blocks = 48 accumulators (AGPRs), 96 MFMAs per chunk, with the staging and the
+// pair-form input transform of all 256 threads in their shadow: no second wave on the SIMD whose VALU / LDS instructions would
+// stall the fp32 MFMA stream.  Same LDS image as the eight-wave form (both exchange buffers over V).
+template <int NI, bool QROW, bool GROUP, int TEAMS, bool WIDE = false>
+__global__ __launch_bounds__(WIDE ? 256 : 256 * TEAMS, TEAMS == 1 ? 2 : 1) void conv_wino_f32_kernel(const WinoParams p) {
+    static_assert(!WIDE || TEAMS == 2, "the four-wave form is a form of the 64-channel cout tile");
     extern __shared__ __attribute__((aligned(16))) float smem[];
+    constexpr int NT = WIDE ? 256 : 256 * TEAMS;  // threads of the workgroup
+    constexpr int NB = WIDE ? 4 : 2;              // 16-channel cout blocks of a wave
     // The tile seam and the early epilogue loads (both below) are one-team matters: measured per layer, the two-team
     // forms - one chunk per loop trip under a run-time parity, 8 to 32 chunks per tile, at the 256-register ceiling - lose more to
     // the seam's switches in every chunk than a tile's prologue costs them, and show nothing for the early loads.
-    constexpr bool kSeam = TEAMS == 1, kEpiEarly = TEAMS == 1;
+    // The four-wave form has the registers for all of it again (MP_WINO_WIDE_OPTS: measurement builds, bit 0 pair body, 1 seam,
+    // 2 early loads).
+    constexpr bool kPair = TEAMS == 1 || (WIDE && (MP_WINO_WIDE_OPTS & 1));
+    constexpr bool kSeam = TEAMS == 1 || (WIDE && (MP_WINO_WIDE_OPTS & 1) && (MP_WINO_WIDE_OPTS & 2));
+    constexpr bool kEpiEarly = TEAMS == 1 || (WIDE && (MP_WINO_WIDE_OPTS & 4));
     const int raw_buf = kCK * p.cin_plane + 4;  // + one float4 that absorbs the stores of threads without a staging unit
     float* __restrict__ lds_raw = smem;                 // [2][raw_buf]
     float* __restrict__ lds_v = smem + 2 * raw_buf;     // [2][16][kCK][kTP]
     const int tid_wg = threadIdx.x;
-    const int team = TEAMS == 1 ? 0 : __builtin_amdgcn_readfirstlane(tid_wg >> 8);
+    const int team = TEAMS == 1 || WIDE ? 0 : __builtin_amdgcn_readfirstlane(tid_wg >> 8);
     float* __restrict__ lds_x = lds_v + team * kXFloats;  // epilogue: [16][16][kXP] per team over the V buffers (never over the raw
                                                           // buffers: their zero halo columns must survive into the next tile)
 
@@ -101,7 +131,7 @@ __global__ __launch_bounds__(256 * TEAMS, TEAMS == 1 ? 2 : 1) void conv_wino_f32
     int idst4[GROUP ? NI : 1][4];  // GROUP: one LDS offset per element of a unit
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
-        const unsigned u = tid_wg + 256 * TEAMS * i;  // every thread of the workgroup stages
+        const unsigned u = tid_wg + NT * i;  // every thread of the workgroup stages
         irel[i] = kOob;
         irow[i] = 0;
         idst[i] = kCK * p.cin_plane;
@@ -145,7 +175,7 @@ __global__ __launch_bounds__(256 * TEAMS, TEAMS == 1 ? 2 : 1) void conv_wino_f32
     // (same values to the same addresses) so that the transform needs no branch
     // XF1 (image-grouped bands, two teams): (cin, ONE tile) items over all 512 threads - both teams transform, half the patch
     // registers of the pair form, which the eight-wave workgroup has no room for
-    constexpr bool XF1 = GROUP && TEAMS == 2;
+    constexpr bool XF1 = GROUP && TEAMS == 2 && !WIDE;  // (four waves: the pair form of the one-team kernel, there is room)
     const int pairs = p.M >> 1;
     int xf_raw = 0, xf_rawb = 0, xf_v = 0;  // patch of the first tile, of the second tile (GROUP), V offset of the pair
     {
@@ -170,10 +200,10 @@ __global__ __launch_bounds__(256 * TEAMS, TEAMS == 1 ? 2 : 1) void conv_wino_f32
 
     // U fragments of this wave: xi = 4 * wave + i, cout block nb, k-step q of the chunk.  U is stored [cin][cout][xi]: the four
     // xi of a wave are ONE 16-byte load per (nb, q) - 4 loads per chunk instead of 16
-    unsigned u_off[2];
+    unsigned u_off[NB];
     auto tile_u = [&]() {
 #pragma unroll
-        for (int nb = 0; nb < 2; ++nb) {
+        for (int nb = 0; nb < NB; ++nb) {
             const int co = (ct * TEAMS + team) * 32 + nb * 16 + lr;
             u_off[nb] = co < p.Cout_pad16 ? (unsigned)((lq * p.Cout_pad16 + co) * 16 + wave * 4) * 4u : kOob;
         }
@@ -182,11 +212,11 @@ __global__ __launch_bounds__(256 * TEAMS, TEAMS == 1 ? 2 : 1) void conv_wino_f32
     const unsigned u_q = (unsigned)(4 * p.Cout_pad16 * 16) * 4u;  // next k-step (4 input channels)
     // ONE register set for the U fragments: the k-step q half of chunk c + 1 is loaded into the registers of the k-step q half of
     // chunk c right after the MFMAs that consumed it (its latency runs under the other half) - no second set, no copies
-    float ucur[4][2][2];
+    float ucur[4][NB][2];
     auto load_u_half = [&](int ch, int q) {
         const unsigned base = (unsigned)(ch * 2 + q) * u_q;
 #pragma unroll
-        for (int nb = 0; nb < 2; ++nb) {
+        for (int nb = 0; nb < NB; ++nb) {
             const f32x4 v = buf_load4(rs_u, u_off[nb] + base);  // kOob + offset stays out of range
 #pragma unroll
             for (int i = 0; i < 4; ++i) ucur[i][nb][q] = v[i];
@@ -199,27 +229,27 @@ __global__ __launch_bounds__(256 * TEAMS, TEAMS == 1 ? 2 : 1) void conv_wino_f32
 #pragma unroll
         for (int i = 0; i < NI; ++i) vin[i] = buf_load4(rs_x, isrc[i] + xo);  // kOob + offset stays out of range
     };
+    auto stage_store_unit = [&](float* __restrict__ d0, int i) {
+        if constexpr (GROUP) {
+            d0[idst4[i][0]] = vin[i].x; d0[idst4[i][1]] = vin[i].y; d0[idst4[i][2]] = vin[i].z; d0[idst4[i][3]] = vin[i].w;
+        } else {
+            float* d = d0 + idst[i];
+            d[0] = vin[i].x; d[1] = vin[i].y; d[2] = vin[i].z; d[3] = vin[i].w;
+        }
+    };
     auto stage_store = [&](int buf) {
         float* __restrict__ d0 = lds_raw + buf * raw_buf;
 #pragma unroll
-        for (int i = 0; i < NI; ++i) {
-            if constexpr (GROUP) {
-                d0[idst4[i][0]] = vin[i].x; d0[idst4[i][1]] = vin[i].y; d0[idst4[i][2]] = vin[i].z; d0[idst4[i][3]] = vin[i].w;
-            } else {
-                float* d = d0 + idst[i];
-                d[0] = vin[i].x; d[1] = vin[i].y; d[2] = vin[i].z; d[3] = vin[i].w;
-            }
-        }
+        for (int i = 0; i < NI; ++i) stage_store_unit(d0, i);
     };
     // input transform of one chunk: raw[rb] -> V[vb]; split in three parts so that the MFMA stream can be woven between them
     // columns 0..3 = patch of the first tile; the second tile's patch is columns 2..5 (its row neighbour) or, GROUP, its own
     // four columns 4..7 (consecutive tiles need not be neighbours there)
     constexpr int XC = XF1 ? 4 : GROUP ? 8 : 6, XB = XF1 ? 0 : GROUP ? 4 : 2;
     float xd[4][XC], xt[4][XC];
-    auto xf_read = [&](int rb) {
+    auto xf_read_row = [&](int rb, int r) {
         const float* __restrict__ src = lds_raw + rb * raw_buf + xf_raw;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
+        {
             if constexpr (XF1) {
                 const float2 a0 = *reinterpret_cast<const float2*>(src + r * p.Wp), a1 = *reinterpret_cast<const float2*>(src + r * p.Wp + 2);
                 xd[r][0] = a0.x; xd[r][1] = a0.y; xd[r][2] = a1.x; xd[r][3] = a1.y;
@@ -235,6 +265,10 @@ __global__ __launch_bounds__(256 * TEAMS, TEAMS == 1 ? 2 : 1) void conv_wino_f32
                 xd[r][0] = a.x; xd[r][1] = a.y; xd[r][2] = a.z; xd[r][3] = a.w; xd[r][4] = c2.x; xd[r][5] = c2.y;
             }
         }
+    };
+    auto xf_read = [&](int rb) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) xf_read_row(rb, r);
     };
     auto xf_cols = [&]() {
 #pragma unroll
@@ -278,7 +312,7 @@ __global__ __launch_bounds__(256 * TEAMS, TEAMS == 1 ? 2 : 1) void conv_wino_f32
         const int n4 = (2 * raw_buf) >> 2;  // raw_buf is a multiple of 4
         float4* z = reinterpret_cast<float4*>(lds_raw);
         const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-        for (int i = tid_wg; i < n4; i += 256 * TEAMS) z[i] = zero;
+        for (int i = tid_wg; i < n4; i += NT) z[i] = zero;
     }
     wg_barrier();  // zero fill complete
     // One team, even chunk count (launch-uniform): ONE stream of chunks over the workgroup's tiles.  The staging slots of a tile's
@@ -327,13 +361,13 @@ __global__ __launch_bounds__(256 * TEAMS, TEAMS == 1 ? 2 : 1) void conv_wino_f32
     // refills, and from there on the slots count the next tile's chunks; without a next tile nothing switches and both slots
     // stay out of range (zeros)
     const int ch_seam = seam() && has_next() ? p.n_chunks - 2 : 0x3fffffff;
-    f32x4 acc[4][3][2];
+    f32x4 acc[4][3][NB];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
         for (int mb = 0; mb < 3; ++mb)
 #pragma unroll
-            for (int nb = 0; nb < 2; ++nb) acc[i][mb][nb] = (f32x4){0.f, 0.f, 0.f, 0.f};
+            for (int nb = 0; nb < NB; ++nb) acc[i][mb][nb] = (f32x4){0.f, 0.f, 0.f, 0.f};
     if (!seam()) {
         stage_store(0);
         wg_barrier();
@@ -406,7 +440,91 @@ __global__ __launch_bounds__(256 * TEAMS, TEAMS == 1 ? 2 : 1) void conv_wino_f32
         MP_STAMP(t5);
         s_mm += t3 - t0; s_st += t4 - t3; s_b2 += t5 - t4;
     };
-    if constexpr (TEAMS == 1) {
+    // Four waves: the same chunk with 96 MFMAs per wave and nobody else on the SIMD, so everything beside the MFMAs has to sit in
+    // their issue shadow by construction.  The MFMAs accumulate in place in AGPRs and the transform's adds are single v_add / v_sub
+    // (no packed adds beside MFMAs) - both as asm statements, which also keeps their order: a (q, xi) group is six slots of two
+    // MFMAs, and each slot carries one slice of side work - the A fragments of the NEXT group (no partner wave hides an operand
+    // read here), a patch row, a patch column of the column step, half a row of the row step or a V store, a staging unit.
+    // The compiler places only the memory instructions, inside their slot (sched_barrier).  (Measured and dropped, DESIGN 4.6:
+    // the slot's side work split behind each of its two MFMAs, with the chunk's barrier moved to slot 45 and the next chunk's
+    // first A fragments fetched behind it - 6 % more cycles in the loop.)
+    auto chunk_wide = [&](int ch, const int par) {
+        MP_STAMP(t0);
+        const float* __restrict__ vcur = lds_v + par * kVFloats + a_base;
+        float av[2][3];
+#pragma unroll
+        for (int mb = 0; mb < 3; ++mb) av[0][mb] = vcur[mb * 16];
+        if (par == 0 && ch == ch_seam) {
+            tile_coords(tile_first + it + 1);
+            tile_rows();
+            rs_x = make_rsrc(p.x + (size_t)n * p.Cin * HW, (size_t)n_img * p.Cin * HW * 4);
+        }
+        if (par == 1 && ch == ch_seam + 1) tile_u();
+        stage_load(ch >= ch_seam ? ch + 2 - p.n_chunks : ch + 2);
+        float* __restrict__ vdst = lds_v + (par ^ 1) * kVFloats + xf_v;
+        float* __restrict__ sdst = lds_raw + par * raw_buf;
+        float wa[4], wb[4];
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int g = q * 4 + i;
+#pragma unroll
+                for (int sl = 0; sl < 6; ++sl) {
+                    const int mb = sl >> 1, nb0 = (sl & 1) * 2;
+                    wide_mfma(acc[i][mb][nb0], av[g & 1][mb], ucur[i][nb0][q]);
+                    wide_mfma(acc[i][mb][nb0 + 1], av[g & 1][mb], ucur[i][nb0 + 1][q]);
+                    if (sl == 0 && g < 7) {
+                        const float* __restrict__ vn = vcur + ((g + 1) & 3) * (kCK * kTP) + ((g + 1) >> 2) * 4 * kTP;
+#pragma unroll
+                        for (int m2 = 0; m2 < 3; ++m2) av[(g + 1) & 1][m2] = vn[m2 * 16];
+                    }
+                    if (g == 0 && sl >= 1 && sl <= 4) xf_read_row(par ^ 1, sl - 1);
+                    if (g == 1) {
+#pragma unroll
+                        for (int c = sl; c < XC; c += 6) {
+                            xt[0][c] = wide_sub(xd[0][c], xd[2][c]);
+                            xt[1][c] = wide_add(xd[1][c], xd[2][c]);
+                            xt[2][c] = wide_sub(xd[2][c], xd[1][c]);
+                            xt[3][c] = wide_sub(xd[1][c], xd[3][c]);
+                        }
+                    }
+                    if (g >= 2 && g <= 5) {
+                        const int r = g - 2;
+                        if (sl == 0) {
+                            wa[0] = wide_sub(xt[r][0], xt[r][2]); wa[1] = wide_add(xt[r][1], xt[r][2]);
+                            wa[2] = wide_sub(xt[r][2], xt[r][1]); wa[3] = wide_sub(xt[r][1], xt[r][3]);
+                        }
+                        if (sl == 1) {
+                            wb[0] = wide_sub(xt[r][XB], xt[r][XB + 2]); wb[1] = wide_add(xt[r][XB + 1], xt[r][XB + 2]);
+                            wb[2] = wide_sub(xt[r][XB + 2], xt[r][XB + 1]); wb[3] = wide_sub(xt[r][XB + 1], xt[r][XB + 3]);
+                        }
+                        if (sl >= 2) *reinterpret_cast<float2*>(vdst + (r * 4 + sl - 2) * (kCK * kTP)) = make_float2(wa[sl - 2], wb[sl - 2]);
+                    }
+                    if (g == 6 && sl >= 1 && sl - 1 < NI) stage_store_unit(sdst, sl - 1);
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+            load_u_half(ch > ch_seam ? ch + 1 - p.n_chunks : ch + 1, q);  // (behind the slot barrier of the MFMAs that read the old values)
+        }
+        MP_STAMP(t3);
+        wg_barrier();
+        MP_STAMP(t5);
+        s_mm += t3 - t0; s_b2 += t5 - t3;
+    };
+    if constexpr (WIDE) {
+        if constexpr (kPair) {
+            for (int ch = 0; ch < p.n_chunks; ch += 2) {
+                chunk_wide(ch, 0);
+                chunk_wide(ch + 1, 1);
+            }
+        } else {
+            for (int ch = 0; ch < p.n_chunks; ++ch) chunk_wide(ch, ch & 1);
+        }
+        // asm MFMA result -> the column step's accumulator reads: the compiler pads nothing behind an asm statement
+        asm volatile("s_nop 15\n\ts_nop 3" ::: "memory");
+    } else if constexpr (kPair) {
         for (int ch = 0; ch < p.n_chunks; ch += 2) {
             chunk(ch, 0);
             chunk(ch + 1, 1);
@@ -451,15 +569,15 @@ __global__ __launch_bounds__(256 * TEAMS, TEAMS == 1 ? 2 : 1) void conv_wino_f32
     // through LDS - both 16-channel halves in ONE exchange ([half][row i][b][cout][tile], the size of the old one-half
     // buffer) and two barriers per tile.  The row step Y[a][b] = sum_i A^T[a][i] P[i][b] is done by the reading thread.
     const int co_base = (e_ct * TEAMS + team) * 32;
-    f32x4 r1q[2][2][2], r2q[2][2][2];
-    float2 r1v[2][4][2], r2v[2][4][2];
-    unsigned co_off[2];
+    f32x4 r1q[NB][2][2], r2q[NB][2][2];
+    float2 r1v[NB][4][2], r2v[NB][4][2];
+    unsigned co_off[NB];
     // scale / shift of both halves go out ahead of the residual rows: behind the exchange barrier (a memory clobber) each half
     // would wait a full load latency for them, the second one behind the first half's stores as well
-    [[maybe_unused]] float e_sc[2], e_sh[2];
+    [[maybe_unused]] float e_sc[NB], e_sh[NB];
     if constexpr (kEpiEarly) {
 #pragma unroll
-        for (int nb = 0; nb < 2; ++nb) {
+        for (int nb = 0; nb < NB; ++nb) {
             const int co = co_base + nb * 16 + (int)co_l;
             const int cc = co < p.Cout ? co : 0;
             e_sc[nb] = p.scale[cc];
@@ -491,7 +609,7 @@ __global__ __launch_bounds__(256 * TEAMS, TEAMS == 1 ? 2 : 1) void conv_wino_f32
     };
     res_request(0);  // the residual rows of the first half fly under the exchange, those of the second under the first half
 #pragma unroll
-    for (int nb = 0; nb < 2; ++nb)
+    for (int nb = 0; nb < NB; ++nb)  // (four waves: nb = 2, 3 is the second 32-channel group - its exchange buffer follows the first)
 #pragma unroll
         for (int mb = 0; mb < 3; ++mb) {
             const f32x4 p0 = acc[0][mb][nb] + acc[1][mb][nb] + acc[2][mb][nb];
@@ -501,9 +619,13 @@ __global__ __launch_bounds__(256 * TEAMS, TEAMS == 1 ? 2 : 1) void conv_wino_f32
             *reinterpret_cast<f32x4*>(dst + 16 * kXP) = p1;
         }
     res_request(1);
+    if constexpr (WIDE) {  // the second group's rows are asked for before the first group's stores, not behind them
+        res_request(2);
+        res_request(3);
+    }
     wg_barrier();
 #pragma unroll
-    for (int nb = 0; nb < 2; ++nb) {
+    for (int nb = 0; nb < NB; ++nb) {
         if (co_base + nb * 16 >= p.Cout_pad16) break;  // wave-uniform; no barrier below
         // every thread runs the half: those without an item (tid >= 192) repeat item 0 with every pixel offset out of range - nothing
         // loaded, nothing stored.  A divergent skip here would leave a path on which the first half issues no stores, and the waits
@@ -602,7 +724,7 @@ int wino_go(const WinoLaunch& L, hipStream_t s) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)hipGetLastError();
     }
-    hipLaunchKernelGGL(Kern, dim3((L.p.total_blocks + L.p.tiles_per_wg - 1) / L.p.tiles_per_wg), dim3(256 * L.teams), L.lds_bytes, s, L.p);
+    hipLaunchKernelGGL(Kern, dim3((L.p.total_blocks + L.p.tiles_per_wg - 1) / L.p.tiles_per_wg), dim3(L.wide ? 256 : 256 * L.teams), L.lds_bytes, s, L.p);
     return check_launch();
 }
 
@@ -706,6 +828,13 @@ int wino_configure(const mp_conv_desc* d, WinoLaunch& L) {
     const size_t raw_bytes = (size_t)2 * (kCK * p.cin_plane + 4) * 4, v_bytes = (size_t)2 * kVFloats * 4, x_bytes = (size_t)L.teams * kXFloats * 4;
     L.lds_bytes = raw_bytes + (v_bytes > x_bytes ? v_bytes : x_bytes);
     L.ni = (kCK * p.upc + 256 * L.teams - 1) / (256 * L.teams);
+    // the wave form of the 64-channel cout tile: four waves, one per SIMD (the kernel comment), or two four-wave teams
+    // row bands by default; image-grouped bands keep eight waves (no gain alone on the chip: DESIGN 4.6)
+    L.wide = L.teams == 2 && !L.group;
+    if (const char* e = knob("MP_WINO_WIDE")) {  // experiments
+        if (atoi(e) == 0) L.wide = false;
+        if (atoi(e) == 1) L.wide = L.teams == 2;
+    }
     if (L.lds_bytes > kMaxLds) return MP_ERR_UNSUPPORTED;
     return MP_OK;
 }
@@ -715,6 +844,22 @@ int wino_launch(const WinoLaunch& L0, hipStream_t s) {
     L.p.dbg = conv_stamp_buffer((size_t)L.p.total_blocks * 64);
     // QROW: the four tiles of an epilogue item are eight consecutive pixels of two rows
     const bool qrow = !L.group && L.p.M == kTP && L.p.TW % 4 == 0 && L.p.H % L.p.R == 0;
+    if (L.wide) {  // 256 staging threads: twice the units per thread of the eight-wave form's ni
+        const int ni = (kCK * L.p.upc + 255) / 256;
+        if (L.group) {
+            switch (ni) {
+                case 1: return wino_go<conv_wino_f32_kernel<1, false, true, 2, true>>(L, s);
+                case 2: return wino_go<conv_wino_f32_kernel<2, false, true, 2, true>>(L, s);
+                default: return MP_ERR_UNSUPPORTED;
+            }
+        }
+        switch (ni) {
+            case 1: return qrow ? wino_go<conv_wino_f32_kernel<1, true, false, 2, true>>(L, s) : wino_go<conv_wino_f32_kernel<1, false, false, 2, true>>(L, s);
+            case 2: return qrow ? wino_go<conv_wino_f32_kernel<2, true, false, 2, true>>(L, s) : wino_go<conv_wino_f32_kernel<2, false, false, 2, true>>(L, s);
+            case 3: return qrow ? wino_go<conv_wino_f32_kernel<3, true, false, 2, true>>(L, s) : wino_go<conv_wino_f32_kernel<3, false, false, 2, true>>(L, s);
+            default: return MP_ERR_UNSUPPORTED;
+        }
+    }
     if (L.group) {
         if (L.teams == 2)  // 512 staging threads over at most 8 x 48 units: always one unit per thread
             return L.ni == 1 ? wino_go<conv_wino_f32_kernel<1, false, true, 2>>(L, s) : MP_ERR_UNSUPPORTED;

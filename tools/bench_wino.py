@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """fp32 Winograd F(2x2,3x3) kernel against the direct MFMA kernel and torch on the HRNet branch shapes.
    python tools/bench_wino.py [N]      (MP_WINO_TEAMS / MP_WINO_TILES force a workgroup form, e.g. MP_WINO_TEAMS=1 for the one-team
-   form of the image-grouped 256->256 @8x6 layer)"""
+   form of the image-grouped 256->256 @8x6 layer, MP_WINO_WIDE=0 / 1 for the eight- / four-wave form of the 64-channel cout tile)
+   python tools/bench_wino.py [N] ab   the 64-channel-tile layers only, eight waves against four in one process, interleaved rounds"""
 import ctypes, os, statistics, sys
 os.environ.setdefault("MINDPOSE_EXPERIMENT_KNOBS", "1")  # the MP_* knobs are honoured only then
 import torch
@@ -27,6 +28,9 @@ def timed(fn, reps=20):
     return statistics.median(ts)
 
 
+AB = len(sys.argv) > 2 and sys.argv[2] == "ab"
+if AB:
+    SHAPES = [(64, 64, 32, 24), (128, 128, 16, 12), (64, 64, 64, 48), (256, 256, 8, 6)]
 for cin, cout, h, w in SHAPES:
     g = torch.Generator(device="cpu").manual_seed(cin * 1000 + h)
     x = torch.randn(n, cin, h, w, generator=g).to(dev)
@@ -47,6 +51,16 @@ for cin, cout, h, w in SHAPES:
                                                        None, _lib.ptr(ow), st), "wino")
     fd = lambda: _lib.check(lib.mp_conv2d_fwd(ctypes.byref(d), _lib.ptr(x), _lib.ptr(pd), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(res), None,
                                               _lib.ptr(od), st), "direct")
+    if AB:  # the knob is read when a launch is configured, i.e. per call: both wave forms of one layer, alternating
+        rounds = {"0": [], "1": []}
+        for _ in range(5):
+            for wide in ("0", "1"):
+                os.environ["MP_WINO_WIDE"] = wide
+                rounds[wide].append(timed(fw))
+        m8, m4 = statistics.median(rounds["0"]), statistics.median(rounds["1"])
+        print(f"{cin:3d}->{cout:3d} {h}x{w} N={n}: eight waves {m8:7.1f} us ({min(rounds['0']):.1f} - {max(rounds['0']):.1f}) | four waves {m4:7.1f} us "
+              f"({min(rounds['1']):.1f} - {max(rounds['1']):.1f}) | x{m8 / m4:.3f}", flush=True)
+        continue
     fw(); fd(); torch.cuda.synchronize()
     ref = torch.relu(F.conv2d(x.double(), wt.double(), padding=1) * scale.double()[None, :, None, None] + shift.double()[None, :, None, None]
                      + res.double())
@@ -58,7 +72,7 @@ for cin, cout, h, w in SHAPES:
 # phase breakdown (diagnostic library: tools/build_stamps.sh, MINDPOSE_HIP_LIB=build/stamps/libmindpose_hip.so)
 import numpy as np
 dbg = torch.zeros(1 << 20, dtype=torch.int64, device=dev)
-if lib.mp_debug_set_stamp_buffer(dbg.data_ptr(), dbg.numel() * 8) == 0:
+if not AB and lib.mp_debug_set_stamp_buffer(dbg.data_ptr(), dbg.numel() * 8) == 0:
     for cin, cout, h, w in SHAPES[:4] + SHAPES[-1:]:
         x = torch.randn(n, cin, h, w, device=dev); wt = torch.randn(cout, cin, 3, 3, device=dev)
         scale = torch.ones(cout, device=dev); shift = torch.zeros(cout, device=dev); ow = torch.empty(n, cout, h, w, device=dev)

@@ -4,6 +4,7 @@
 #   bash tools/variant_builds.sh <source stem> "<tag:flag[,flag...]> ..."   ->  build/<stem>_<tag>/libmindpose_hip.so  (MINDPOSE_HIP_LIB=...)
 # Macros: conv_small_f32  -DMP_SMALL_ABLATE=<mask>  1 no staging, 2 no MFMA loop, 4 no weight loads, 8 no fold        (tools/bench_small.py)
 #         conv_gemm_f32   -DMP_GEMM_ABLATE=<mask>   1 no stores, 2 no MFMA                                            (tools/probes/gemm_expand_probe.py)
+#         conv_wino_f32   -DMP_WINO_WIDE_OPTS=<mask> four-wave form: 1 two chunks per trip, 2 tile seam, 4 early epilogue loads (tools/bench_wino.py N ab)
 #         pwchain_f32     -DPWC_ABLATE=<mask>       1 no y stores, 2 no MFMA, 4 no residual loads                     (tools/bench_pwchain32.py)
 # e.g.  bash tools/variant_builds.sh pwchain_f32 "s:-DPWC_ABLATE=1 m:-DPWC_ABLATE=2 sr:-DPWC_ABLATE=5"
 set -e
