@@ -58,167 +58,6 @@ def _pack(lib, w, cout, cin, k, mode, py=0, px=0, owner=None):
     return _cached_pack(lib, w, owner, False, cout, cin, k, mode, py, px)
 
 
-class Conv2dFn(torch.autograd.Function):
-    """z = conv2d(x, weight) (+ bias); k in {1, 3}, stride in {1, 2}, padding = k // 2."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, stride, padding):
-        lib = _lib.load()
-        x = _lib.require_cuda_f32(x, "x")
-        w = weight.detach().contiguous()
-        n, cin, h, wd = x.shape
-        cout, _, k, _ = w.shape
-        if padding != k // 2 or k not in (1, 3) or stride not in (1, 2):
-            raise NotImplementedError("training path covers k in {1,3}, stride in {1,2}, padding = k//2")
-        ho, wo = (h + 2 * padding - k) // stride + 1, (wd + 2 * padding - k) // stride + 1
-        ones, zeros = _ones_zeros(cout, x.device)
-        shift = bias.detach().contiguous() if bias is not None else zeros
-        z = torch.empty(n, cout, ho, wo, device=x.device, dtype=torch.float32)
-        d = _desc(n, cin, h, wd, cout, k, stride, padding, padding, ho, wo, ho, wo)
-        packed = _pack(lib, w, cout, cin, k, 0, owner=weight)
-        _conv_launch(lib, d, x, packed, ones, shift, z, "mp_conv2d_fwd", packed_u=_pack_winograd(lib, d, w, cout, cin, 5, weight))
-        ctx.save_for_backward(x, w)
-        ctx.stride, ctx.padding, ctx.has_bias = stride, padding, bias is not None
-        ctx.weight_param = weight
-        return z
-
-    @staticmethod
-    def backward(ctx, dz):
-        lib = _lib.load()
-        x, w = ctx.saved_tensors
-        dz = dz.contiguous()
-        n, cin, h, wd = x.shape
-        cout, _, k, _ = w.shape
-        s, pad = ctx.stride, ctx.padding
-        ho, wo = dz.shape[2], dz.shape[3]
-        dx = dw = db = None
-        if ctx.needs_input_grad[0]:
-            ones, zeros = _ones_zeros(cin, x.device)
-            if s == 1:
-                dx = torch.empty_like(x)
-                d = _desc(n, cout, ho, wo, cin, k, 1, k - 1 - pad, k - 1 - pad, h, wd, h, wd)
-                packed = _pack(lib, w, cin, cout, k, 2, owner=ctx.weight_param)
-                # ResidualBlockFn: the gradient that reaches x through the identity is added in this launch's epilogue
-                _conv_launch(lib, d, dz, packed, ones, zeros, dx, "conv dgrad",
-                             packed_u=_pack_winograd(lib, d, w, cin, cout, 6, ctx.weight_param) if k == 3 else None,
-                             res1=getattr(ctx, "dx_residual", None))
-            else:
-                if h != 2 * ho or wd != 2 * wo:
-                    raise NotImplementedError("stride-2 data gradient needs even input extents")
-                if k == 3:
-                    dx = torch.empty_like(x)
-                    for py in (0, 1):
-                        for px in (0, 1):
-                            d = _desc(n, cout, ho, wo, cin, 2, 1, 0, 0, ho, wo, h, wd, out_mul=2, off_y=py, off_x=px)
-                            packed = _pack(lib, w, cin, cout, 2, 3, py, px, owner=ctx.weight_param)
-                            _conv_launch(lib, d, dz, packed, ones, zeros, dx, "conv dgrad phase")
-                else:  # 1x1 stride 2: only even positions receive gradient
-                    dx = torch.zeros_like(x)
-                    d = _desc(n, cout, ho, wo, cin, 1, 1, 0, 0, ho, wo, h, wd, out_mul=2)
-                    packed = _pack(lib, w, cin, cout, 1, 2, owner=ctx.weight_param)
-                    _conv_launch(lib, d, dz, packed, ones, zeros, dx, "conv dgrad 1x1s2")
-        if ctx.needs_input_grad[1]:
-            direct = _direct_grad(ctx.weight_param)  # add straight into the gradient arena: no AccumulateGrad launch
-            dw = direct if direct is not None else torch.empty_like(w)
-            d = _desc(n, cin, h, wd, cout, k, s, pad, pad, ho, wo, ho, wo)
-            ws_bytes = lib.mp_conv_wgrad_workspace_bytes(ctypes.byref(d))
-            ws = torch.empty(max(ws_bytes // 4, 1), device=x.device, dtype=torch.float32)
-            _lib.check(lib.mp_conv_wgrad(ctypes.byref(d), _lib.ptr(x), _lib.ptr(dz), _lib.ptr(dw), int(direct is not None), _lib.ptr(ws),
-                                         ws_bytes, _lib.stream()), "mp_conv_wgrad")
-            if direct is not None:
-                dw = None
-        if ctx.has_bias and ctx.needs_input_grad[2]:
-            db = dz.sum(dim=(0, 2, 3))  # [Cout] reduction of the head conv's bias gradient (17 values)
-        return dx, dw, db, None, None
-
-
-class BatchNormActFn(torch.autograd.Function):
-    """y = act(BN_train(z) (+ res)); updates the moving statistics in place (mindspore.nn.BatchNorm2d training)."""
-
-    @staticmethod
-    def forward(ctx, z, gamma, beta, res, moving_mean, moving_var, relu):
-        lib = _lib.load()
-        z = _lib.require_cuda_f32(z, "z")
-        n, c, h, w = z.shape
-        y = torch.empty_like(z)
-        mean = torch.empty(c, device=z.device)
-        invstd = torch.empty(c, device=z.device)
-        ws_bytes = lib.mp_bn_workspace_bytes(c)
-        ws = torch.empty(ws_bytes // 4 + 1, device=z.device, dtype=torch.float32)
-        g, b = gamma.detach().contiguous(), beta.detach().contiguous()
-        r = res.contiguous() if res is not None else None
-        _lib.check(lib.mp_bn_train_fwd(_lib.ptr(z), _lib.ptr(g), _lib.ptr(b), _lib.ptr(r), _lib.ptr(y), _lib.ptr(mean),
-                                       _lib.ptr(invstd), _lib.ptr(moving_mean), _lib.ptr(moving_var), n, c, h * w, BN_EPS,
-                                       BN_MOMENTUM, int(relu), _lib.ptr(ws), ws_bytes, _lib.stream()), "mp_bn_train_fwd")
-        ctx.save_for_backward(z, y, g, mean, invstd)
-        ctx.relu, ctx.has_res = relu, res is not None
-        ctx.gamma_param, ctx.beta_param = gamma, beta
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        lib = _lib.load()
-        z, y, g, mean, invstd = ctx.saved_tensors
-        dy = dy.contiguous()
-        n, c, h, w = z.shape
-        dz = torch.empty_like(z)
-        dres = torch.empty_like(z) if ctx.has_res else None
-        dgamma = torch.empty(c, device=z.device)
-        dbeta = torch.empty(c, device=z.device)
-        ws_bytes = lib.mp_bn_workspace_bytes(c)
-        ws = torch.empty(ws_bytes // 4 + 1, device=z.device, dtype=torch.float32)
-        ga, ba = _direct_grad(ctx.gamma_param), _direct_grad(ctx.beta_param)  # + straight into the gradient arena
-        if ga is None or ba is None:
-            ga = ba = None
-        _lib.check(lib.mp_bn_train_bwd_acc(_lib.ptr(dy), _lib.ptr(z), _lib.ptr(y), _lib.ptr(g), _lib.ptr(mean), _lib.ptr(invstd),
-                                           _lib.ptr(dz), _lib.ptr(dres), _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(ga), _lib.ptr(ba),
-                                           n, c, h * w, int(ctx.relu), _lib.ptr(ws), ws_bytes, _lib.stream()), "mp_bn_train_bwd")
-        if ga is not None:
-            return dz, None, None, dres, None, None, None
-        return dz, dgamma, dbeta, dres, None, None, None
-
-
-class FuseSumFn(torch.autograd.Function):
-    """out = relu(((base + up(t1)) + up(t2)) + up(t3)); terms at scale 1 are plain adds (hrnet.py:327-339)."""
-
-    @staticmethod
-    def forward(ctx, base, scales, *terms):
-        lib = _lib.load()
-        n, c, h, w = base.shape
-        base = base.contiguous()
-        ts = [t.contiguous() for t in terms]
-        out = torch.empty_like(base)
-        args = []
-        for i in range(3):
-            if i < len(ts):
-                args += [_lib.ptr(ts[i]), int(scales[i])]
-            else:
-                args += [None, 1]
-        _lib.check(lib.mp_fuse_upsample_sum(_lib.ptr(base), *args, _lib.ptr(out), n, c, h, w, 1, _lib.stream()),
-                   "mp_fuse_upsample_sum")
-        ctx.save_for_backward(out)
-        ctx.scales = [int(s) for s in scales[:len(ts)]]
-        return out
-
-    @staticmethod
-    def backward(ctx, dy):
-        lib = _lib.load()
-        (out,) = ctx.saved_tensors
-        dy = dy.contiguous()
-        n, c, h, w = out.shape
-        dbase = torch.empty_like(out)
-        dts = [torch.empty(n, c, h // s, w // s, device=out.device) for s in ctx.scales]
-        args = []
-        for i in range(3):
-            if i < len(dts):
-                args += [_lib.ptr(dts[i]), ctx.scales[i]]
-            else:
-                args += [None, 1]
-        _lib.check(lib.mp_fuse_upsample_sum_bwd(_lib.ptr(dy), _lib.ptr(out), _lib.ptr(dbase), *args, n, c, h, w, 1,
-                                                _lib.stream()), "mp_fuse_upsample_sum_bwd")
-        return (dbase, None, *dts)
-
-
 # ---- amp O2: the same graph on channel-blocked fp16 activations ([N, ceil(C/8), H, W, 8] half tensors) -------------------
 # fp16 conv operands / activations / activation gradients, fp32 accumulation, BatchNorm statistics and every PARAMETER
 # gradient in fp32 (the parameters themselves stay fp32 "master" weights: the pack kernel rounds them to fp16 per step).
@@ -411,10 +250,354 @@ def _ones_zeros16(c: int, device):
     return _ones_zeros((c + 15) // 16 * 16, device)
 
 
-def _conv16_launch(lib, d, x, packed, scale, shift, out, what, res1=None):
-    v = tune_conv_variant(lib, d, x, packed, scale, shift, res1, None, out, half=True)  # one-tile / multi-tile, cached per shape
+def _conv16_run(lib, d, v, x, packed, scale, shift, res1, out, what):
+    """The plain fp16 conv launch with variant ``v`` (`_conv16_launch`, and `_conv16_stats_launch` when ``v`` has no statistics build)."""
     _lib.check(lib.mp_f16_conv2d_fwd(ctypes.byref(d), v, _lib.ptr(x), _lib.ptr(packed), _lib.ptr(scale), _lib.ptr(shift), _lib.ptr(res1),
                                      None, _lib.ptr(out), _lib.stream()), what)
+
+
+def _conv16_launch(lib, d, x, packed, scale, shift, out, what, res1=None):
+    v = tune_conv_variant(lib, d, x, packed, scale, shift, res1, None, out, half=True)  # one-tile / multi-tile, cached per shape
+    _conv16_run(lib, d, v, x, packed, scale, shift, res1, out, what)
+
+
+# ---- one body per cell for both activation types -----------------------------------------------------------------------------------
+# What differs between fp32 NCHW and channel-blocked fp16 is DATA (`_Precision`: how to allocate an activation, its constant
+# epilogue vectors, its pack function and BatchNorm workspace policy); every cell body below is written once against it, and the
+# autograd Functions further down are two-line shells that name their record.  Where the two types launch differently on purpose
+# (another entry point of the library, another route) the bodies branch on ``P.half``, in place.  The launch helpers the tests patch (`_conv16_launch`, `_conv16_stats_launch`,
+# `_wgrad_flush_key`, ...) are never bound into a record: the bodies look them up in the module when they run.
+
+
+def _bn32_workspace(lib, c, device):
+    """The fp32 BatchNorm's workspace: one allocation per call."""
+    ws_bytes = lib.mp_bn_workspace_bytes(c)
+    return torch.empty(ws_bytes // 4 + 1, device=device, dtype=torch.float32), ws_bytes
+
+
+class _Precision:
+    """One activation type: ``alloc(n, c, h, w, device)``, ``ones_zeros(c, device)`` (the constant epilogue vectors),
+    ``pack(lib, w, cout, cin, k, mode, py, px, owner=)``, ``bn_workspace(lib, c, device)`` -> (tensor, bytes)."""
+    __slots__ = ("half", "alloc", "ones_zeros", "pack", "bn_workspace")
+
+    def __init__(self, half, alloc, ones_zeros, pack, bn_workspace):
+        self.half, self.alloc, self.ones_zeros, self.pack, self.bn_workspace = half, alloc, ones_zeros, pack, bn_workspace
+
+
+_F32 = _Precision(False, lambda n, c, h, w, device: torch.empty(n, c, h, w, device=device, dtype=torch.float32), _ones_zeros, _pack,
+                  _bn32_workspace)
+_F16 = _Precision(True, _c8_alloc, _ones_zeros16, _pack16, _bn16_workspace)
+
+
+def _nhw(t):
+    """(N, H, W) of an activation of either type: [N, C, H, W] or [N, C/8, H, W, 8]."""
+    return t.shape[0], t.shape[2], t.shape[3]
+
+
+def _conv_fwd_args(P, lib, x, weight, w, bias, stride, padding):
+    """Geometry check, epilogue vectors, output, descriptor and packed weight of a forward conv:
+    (d, packed, ones, shift, z, (n, cout, ho, wo))."""
+    n, h, wd = _nhw(x)
+    cout, cin, k, _ = w.shape
+    if padding != k // 2 or k not in (1, 3) or stride not in (1, 2):
+        raise NotImplementedError("training path covers k in {1,3}, stride in {1,2}, padding = k//2")
+    ho, wo = (h + 2 * padding - k) // stride + 1, (wd + 2 * padding - k) // stride + 1
+    ones, shift = P.ones_zeros(cout, x.device)
+    if bias is not None and P.half:  # the fp16 epilogue reads whole 16-channel groups: a padded copy
+        shift = torch.zeros_like(shift)
+        shift[:cout] = bias.detach()
+    elif bias is not None:
+        shift = bias.detach().contiguous()
+    z = P.alloc(n, cout, ho, wo, x.device)
+    d = _desc(n, cin, h, wd, cout, k, stride, padding, padding, ho, wo, ho, wo)
+    return d, P.pack(lib, w, cout, cin, k, 0, owner=weight), ones, shift, z, (n, cout, ho, wo)
+
+
+def _conv_forward(P, ctx, x, weight, bias, stride, padding):
+    lib = _lib.load()
+    if not P.half:
+        x = _lib.require_cuda_f32(x, "x")
+    w = weight.detach().contiguous()
+    d, packed, ones, shift, z, _ = _conv_fwd_args(P, lib, x, weight, w, bias, stride, padding)
+    if P.half:
+        _conv16_launch(lib, d, x, packed, ones, shift, z, "mp_f16_conv2d_fwd")
+    else:  # the Winograd form of a 3x3 weight competes in the fp32 tuner
+        _conv_launch(lib, d, x, packed, ones, shift, z, "mp_conv2d_fwd", packed_u=_pack_winograd(lib, d, w, d.cout, d.cin, 5, weight))
+    ctx.save_for_backward(x, w)
+    ctx.stride, ctx.padding, ctx.has_bias = stride, padding, bias is not None
+    ctx.weight_param = weight
+    return z
+
+
+def _conv_dgrad(P, lib, x, w, owner, dz, s, pad, res1=None, below=None):
+    """Data gradient of the conv that read ``x``; ``res1`` is added in the launch's epilogue.  ``below`` (fused chains) = (z, y, relu)
+    of the BatchNorm whose output ``x`` is: the launch also masks the gradient and leaves that BatchNorm's backward sums.
+    Returns (dx, partials, n_parts); partials None when nothing was reduced."""
+    n, h, wd = _nhw(x)
+    cout, cin, k, _ = w.shape
+    ho, wo = dz.shape[2], dz.shape[3]
+    ones, zeros = P.ones_zeros(cin, x.device)
+    if s != 1 and (h != 2 * ho or wd != 2 * wo):
+        raise NotImplementedError("stride-2 data gradient needs even input extents")
+    if s != 1 and res1 is not None:
+        raise NotImplementedError("a residual chain starts with a stride-1 conv")
+    if s != 1 and k == 1 and not P.half:  # 1x1 stride 2 (ResNet down-sample): only the even positions receive gradient
+        dx = torch.zeros_like(x)
+    else:
+        dx = P.alloc(n, cin, h, wd, x.device)
+    if below is not None and tuple(below[0].shape) != tuple(dx.shape):
+        below = None
+    part, n_parts = None, 0
+    if s == 1:
+        d = _desc(n, cout, ho, wo, cin, k, 1, k - 1 - pad, k - 1 - pad, h, wd, h, wd)
+        packed = P.pack(lib, w, cin, cout, k, 2, owner=owner)
+        if below is not None:
+            part, n_parts = _conv16_stats_launch(lib, d, dz, packed, ones, zeros, dx, res1, 2, z=below[0], y=below[1], relu=below[2])
+        elif P.half:
+            _conv16_launch(lib, d, dz, packed, ones, zeros, dx, "conv dgrad", res1=res1)
+        else:
+            _conv_launch(lib, d, dz, packed, ones, zeros, dx, "conv dgrad", res1=res1,
+                         packed_u=_pack_winograd(lib, d, w, cin, cout, 6, owner) if k == 3 else None)
+    elif k == 1:
+        if P.half:
+            dx.zero_()
+        d = _desc(n, cout, ho, wo, cin, 1, 1, 0, 0, ho, wo, h, wd, out_mul=2)
+        packed = P.pack(lib, w, cin, cout, 1, 2, owner=owner)
+        (_conv16_launch if P.half else _conv_launch)(lib, d, dz, packed, ones, zeros, dx, "conv dgrad 1x1s2")
+    elif P.half:  # 3x3 stride 2: one merged launch of the four sub-pixel phases (or four, MINDPOSE_DGRAD_PHASES4=0)
+        part, n_parts = _dgrad16_stride2(lib, w, owner, dz, dx, n, cin, cout, h, wd, ho, wo, ones, zeros, below=below)
+    else:  # ... in fp32: four launches
+        for py in (0, 1):
+            for px in (0, 1):
+                d = _desc(n, cout, ho, wo, cin, 2, 1, 0, 0, ho, wo, h, wd, out_mul=2, off_y=py, off_x=px)
+                packed = _pack(lib, w, cin, cout, 2, 3, py, px, owner=owner)
+                _conv_launch(lib, d, dz, packed, ones, zeros, dx, "conv dgrad phase")
+    return dx, part, n_parts
+
+
+def _wgrad_launch(P, lib, d, x, dz, dw, acc, what, must=False):
+    """THE weight-gradient launch: dW (+)= x (*) dz with its workspace; ``must``: a shape without a kernel is an error here
+    (the transposed conv's 4x4 stride-2 form) instead of the library's."""
+    ws_bytes = (lib.mp_f16_conv_wgrad_workspace_bytes if P.half else lib.mp_conv_wgrad_workspace_bytes)(ctypes.byref(d))
+    if must and ws_bytes == 0:
+        raise _lib.MindposeHipError("transposed-conv weight gradient: unsupported shape")
+    ws = torch.empty(max(ws_bytes // 4, 1), device=x.device, dtype=torch.float32)
+    if P.half:
+        rc = lib.mp_f16_conv_wgrad(ctypes.byref(d), _lib.ptr(x), _lib.ptr(dz), _lib.ptr(dw), 1.0, acc, _lib.ptr(ws), ws_bytes, _lib.stream())
+    else:
+        rc = lib.mp_conv_wgrad(ctypes.byref(d), _lib.ptr(x), _lib.ptr(dz), _lib.ptr(dw), acc, _lib.ptr(ws), ws_bytes, _lib.stream())
+    _lib.check(rc, what)
+
+
+def _wgrad(P, lib, d, x, dz, w, owner, what, queue=False, must=False):
+    """Launch or queue one weight gradient.  With an ``owner`` that allows it the gradient is ADDED into the owner's slot of the
+    gradient arena (no AccumulateGrad launch) - ``queue``: later, grouped with the other layers of this shape - and None is
+    returned; else a fresh tensor."""
+    direct = _direct_grad(owner) if owner is not None else None
+    if direct is not None and queue:
+        _wgrad_enqueue(lib, d, x, dz, direct)
+        return None
+    dw = direct if direct is not None else torch.empty_like(w)
+    _wgrad_launch(P, lib, d, x, dz, dw, int(direct is not None), what, must)
+    return None if direct is not None else dw
+
+
+def _conv_backward(P, ctx, dz):
+    lib = _lib.load()
+    x, w = ctx.saved_tensors
+    dz = dz.contiguous()
+    n, h, wd = _nhw(x)
+    cout, cin, k, _ = w.shape
+    s, pad = ctx.stride, ctx.padding
+    dx = dw = db = None
+    if ctx.needs_input_grad[0]:
+        # ResidualBlock*Fn: the gradient that reaches x through the identity is added in the launch's epilogue
+        dx, _, _ = _conv_dgrad(P, lib, x, w, ctx.weight_param, dz, s, pad, res1=getattr(ctx, "dx_residual", None))
+    if ctx.needs_input_grad[1]:
+        d = _desc(n, cin, h, wd, cout, k, s, pad, pad, dz.shape[2], dz.shape[3], dz.shape[2], dz.shape[3])
+        dw = _wgrad(P, lib, d, x, dz, w, ctx.weight_param, "mp_f16_conv_wgrad" if P.half else "mp_conv_wgrad")
+    if ctx.has_bias and ctx.needs_input_grad[2]:  # the head conv's bias (17 values)
+        db = dz.float().sum(dim=(0, 2, 3)).reshape(-1)[:cout] if P.half else dz.sum(dim=(0, 2, 3))
+    return dx, dw, db, None, None
+
+
+def _bn_fwd_job(P, lib, z, gamma, beta, res, moving_mean, moving_var, relu):
+    """Outputs, saved statistics and workspace of one BatchNorm forward, as the job dict the launchers take."""
+    n, h, w = _nhw(z)
+    c = gamma.numel()
+    ws, ws_bytes = P.bn_workspace(lib, c, z.device)
+    return dict(z=z, g=gamma.detach().contiguous(), b=beta.detach().contiguous(), res=res.contiguous() if res is not None else None,
+                y=torch.empty_like(z), mean=torch.empty(c, device=z.device), invstd=torch.empty(c, device=z.device), mm=moving_mean,
+                mv=moving_var, n=n, c=c, hw=h * w, relu=int(relu), part=None, n_parts=0, ws=ws, ws_bytes=ws_bytes)
+
+
+def _bn_fwd_launch(P, lib, j):
+    """Reduce + apply, moving statistics updated in place."""
+    args = (_lib.ptr(j["z"]), _lib.ptr(j["g"]), _lib.ptr(j["b"]), _lib.ptr(j["res"]), _lib.ptr(j["y"]), _lib.ptr(j["mean"]),
+            _lib.ptr(j["invstd"]), _lib.ptr(j["mm"]), _lib.ptr(j["mv"]), j["n"], j["c"], j["hw"], BN_EPS, BN_MOMENTUM, j["relu"],
+            _lib.ptr(j["ws"]), j["ws_bytes"], _lib.stream())
+    if P.half:
+        _lib.check(lib.mp_f16_bn_train_fwd(*args), "mp_f16_bn_train_fwd")
+    else:
+        _lib.check(lib.mp_bn_train_fwd(*args), "mp_bn_train_fwd")
+
+
+def _bn_forward(P, ctx, z, gamma, beta, res, moving_mean, moving_var, relu):
+    lib = _lib.load()
+    if not P.half:
+        z = _lib.require_cuda_f32(z, "z")
+    j = _bn_fwd_job(P, lib, z, gamma, beta, res, moving_mean, moving_var, relu)
+    _bn_fwd_launch(P, lib, j)
+    ctx.save_for_backward(z, j["y"], j["g"], j["b"], j["mean"], j["invstd"])
+    ctx.relu, ctx.has_res = relu, res is not None
+    ctx.gamma_param, ctx.beta_param = gamma, beta
+    return j["y"]
+
+
+def _bn_bwd_job(P, lib, dy, z, g, b, mean, invstd, gamma, beta, relu):
+    """Outputs and workspace of one BatchNorm backward; ``ga`` / ``ba``: the gradient-arena slots of gamma and beta when BOTH
+    take direct accumulation (then the kernel adds into them), else None.  The caller fills ``yy`` (the mask source), ``dr`` (the
+    residual's gradient) and ``pre`` (sums that came with a pre-masked ``dy``)."""
+    n, h, w = _nhw(z)
+    c = g.numel()
+    ws, ws_bytes = P.bn_workspace(lib, c, z.device)
+    ga, ba = _direct_grad(gamma), _direct_grad(beta)
+    if ga is None or ba is None:
+        ga = ba = None
+    return dict(dy=dy, z=z, g=g, b=b, mean=mean, invstd=invstd, dz=torch.empty_like(z), dgamma=torch.empty(c, device=z.device),
+                dbeta=torch.empty(c, device=z.device), ga=ga, ba=ba, n=n, c=c, hw=h * w, relu=int(relu), ws=ws, ws_bytes=ws_bytes,
+                pre=None, yy=None, dr=None)
+
+
+def _bn_bwd_launch(P, lib, j):
+    """Reduce + apply.  The fp16 kernel re-derives the ReLU mask from z and beta when ``yy`` is None; the fp32 one takes no beta."""
+    head = (_lib.ptr(j["dy"]), _lib.ptr(j["z"]), _lib.ptr(j["yy"]), _lib.ptr(j["g"]))
+    tail = (_lib.ptr(j["mean"]), _lib.ptr(j["invstd"]), _lib.ptr(j["dz"]), _lib.ptr(j["dr"]), _lib.ptr(j["dgamma"]), _lib.ptr(j["dbeta"]),
+            _lib.ptr(j["ga"]), _lib.ptr(j["ba"]), j["n"], j["c"], j["hw"], j["relu"], _lib.ptr(j["ws"]), j["ws_bytes"], _lib.stream())
+    if P.half:
+        _lib.check(lib.mp_f16_bn_train_bwd(*head, _lib.ptr(j["b"]), *tail), "mp_f16_bn_train_bwd")
+    else:
+        _lib.check(lib.mp_bn_train_bwd_acc(*head, *tail), "mp_bn_train_bwd")
+
+
+def _bn_backward(P, ctx, dy):
+    lib = _lib.load()
+    z, y, g, b, mean, invstd = ctx.saved_tensors
+    j = _bn_bwd_job(P, lib, dy.contiguous(), z, g, b, mean, invstd, ctx.gamma_param, ctx.beta_param, ctx.relu)
+    # fp16 without a residual: the ReLU mask is re-derived from z (forward arithmetic), y is not read
+    j["yy"] = None if (P.half and ctx.relu and not ctx.has_res and _lib.env_on("MINDPOSE_BN16_MASK_FROM_Z")) else y
+    j["dr"] = torch.empty_like(z) if ctx.has_res else None
+    _bn_bwd_launch(P, lib, j)
+    if j["ga"] is not None:
+        return j["dz"], None, None, j["dr"], None, None, None
+    return j["dz"], j["dgamma"], j["dbeta"], j["dr"], None, None, None
+
+
+def _scaled_ptrs(ts, scales):
+    """The three (pointer, integer scale) operand slots of the exchange-unit kernels; a slot without a term is (NULL, 1)."""
+    args = []
+    for i in range(3):
+        args += [_lib.ptr(ts[i]), int(scales[i])] if i < len(ts) else [None, 1]
+    return args
+
+
+def _fuse_sum_forward(P, ctx, base, scales, terms):
+    lib = _lib.load()
+    n, h, w = _nhw(base)
+    c = base.shape[1] * (8 if P.half else 1)
+    base = base.contiguous()
+    ts = [t.contiguous() for t in terms]
+    out = torch.empty_like(base)
+    args = (_lib.ptr(base), *_scaled_ptrs(ts, scales), _lib.ptr(out), n, c, h, w, 1, _lib.stream())
+    if P.half:
+        _lib.check(lib.mp_f16_fuse_upsample_sum(*args), "mp_f16_fuse_upsample_sum")
+    else:
+        _lib.check(lib.mp_fuse_upsample_sum(*args), "mp_fuse_upsample_sum")
+    ctx.save_for_backward(out)
+    ctx.scales = [int(s) for s in scales[:len(ts)]]
+    return out
+
+
+def _fuse_sum_backward(P, ctx, dy):
+    """(dbase, dts).  ``ctx.links`` (`FuseSum16Fn`): an operand whose link allows it gets its gradient from a launch of its own
+    that also masks and reduces it for the BatchNorm that produced the operand; the plain kernel writes the rest."""
+    lib = _lib.load()
+    (out,) = ctx.saved_tensors
+    dy = dy.contiguous()
+    n, h, w = _nhw(out)
+    c = out.shape[1] * (8 if P.half else 1)
+    dbase = torch.empty_like(out)
+    dts = [P.alloc(n, c, h // s, w // s, out.device) for s in ctx.scales]
+    plain = [dbase] + dts
+    for k, link in enumerate(getattr(ctx, "links", ())):
+        dst, sc = plain[k], ([1] + ctx.scales)[k]
+        if (link is not None and link.claimed == 1 and (_bn_fuse_parts() & 8) and tuple(link.z.shape) == tuple(dst.shape)):
+            n_parts = lib.mp_f16_fuse_term_stats_parts(n, c, h, w, sc)
+            part = torch.empty(c // 8 * n_parts * 16, device=out.device, dtype=torch.float32)
+            _lib.check(lib.mp_f16_fuse_sum_bwd_term_stats(_lib.ptr(dy), _lib.ptr(out), _lib.ptr(dst), sc, n, c, h, w, 1,
+                                                          _lib.ptr(link.z), _lib.ptr(link.y) if link.relu else None, int(link.relu),
+                                                          _lib.ptr(part), part.numel() * 4, _lib.stream()),
+                       "mp_f16_fuse_sum_bwd_term_stats")
+            link.hand_over(part, n_parts, dst)
+            plain[k] = None
+    if any(p is not None for p in plain):
+        fn = lib.mp_f16_fuse_upsample_sum_bwd if P.half else lib.mp_fuse_upsample_sum_bwd
+        _lib.check(fn(_lib.ptr(dy), _lib.ptr(out), _lib.ptr(plain[0]), *_scaled_ptrs(plain[1:], ctx.scales), n, c, h, w, 1, _lib.stream()),
+                   "mp_fuse_upsample_sum_bwd")
+    return dbase, dts
+
+
+def _deconv_forward(P, ctx, x, weight):
+    lib = _lib.load()
+    if not P.half:
+        x = _lib.require_cuda_f32(x, "x")
+    w = weight.detach().contiguous()
+    n, h, wd = _nhw(x)
+    cin, cout = w.shape[0], w.shape[1]
+    # the fp32 form packs without an owner and keeps out of the gradient arena: `_deconv_backward` finds no owner either
+    ctx.weight_param = weight if P.half else None
+    ones, zeros = P.ones_zeros(cout, x.device)
+    y = P.alloc(n, cout, 2 * h, 2 * wd, x.device)
+    for py in (0, 1):
+        for px in (0, 1):
+            d = _desc(n, cin, h, wd, cout, 2, 1, 1 - py, 1 - px, h, wd, 2 * h, 2 * wd, out_mul=2, off_y=py, off_x=px)
+            packed = P.pack(lib, w, cout, cin, 2, 1, py, px, owner=ctx.weight_param)
+            (_conv16_launch if P.half else _conv_launch)(lib, d, x, packed, ones, zeros, y, "deconv phase")
+    ctx.save_for_backward(x, w)
+    return y
+
+
+def _deconv_backward(P, ctx, dy):
+    lib = _lib.load()
+    x, w = ctx.saved_tensors
+    dy = dy.contiguous()
+    n, h, wd = _nhw(x)
+    cin, cout = w.shape[0], w.shape[1]
+    dx = dw = None
+    if ctx.needs_input_grad[0]:
+        ones, zeros = P.ones_zeros(cin, x.device)
+        dx = P.alloc(n, cin, h, wd, x.device)
+        phase = P.alloc(n, cout, h, wd, x.device)
+        gather = lib.mp_f16_gather_phase if P.half else lib.mp_gather_phase
+        for py in (0, 1):
+            for px in (0, 1):
+                _lib.check(gather(_lib.ptr(dy), _lib.ptr(phase), n, cout, h, wd, py, px, _lib.stream()), "mp_gather_phase")
+                # y_phase[m] = sum_t x[m - (1-p) + t] wp[t]  =>  dx[j] = sum_t dy_phase[j + (1-p) - t] wp[t]:
+                # a 2x2 conv over dy_phase with mirrored taps and padding p; the phases add up through the epilogue
+                d = _desc(n, cout, h, wd, cin, 2, 1, py, px, h, wd, h, wd)
+                packed = P.pack(lib, w, cin, cout, 2, 4, py, px, owner=ctx.weight_param)
+                res1 = dx if (py or px) else None
+                if P.half:
+                    _conv16_launch(lib, d, phase, packed, ones, zeros, dx, "deconv dgrad phase", res1=res1)
+                else:  # the untuned launch
+                    _lib.check(lib.mp_conv2d_fwd(ctypes.byref(d), _lib.ptr(phase), _lib.ptr(packed), _lib.ptr(ones), _lib.ptr(zeros),
+                                                 _lib.ptr(res1), None, _lib.ptr(dx), _lib.stream()), "deconv dgrad phase")
+    if ctx.needs_input_grad[1]:
+        # dW[ci][co][ky][kx] = sum_m x[m][ci] * dy[2m + ky - 1][co]: weight gradient of a 4x4 s2 p1 conv whose input is dy
+        # and whose output gradient is x -> result laid out [ci][co][4][4] = the transposed conv's own weight layout
+        d = _desc(n, cout, 2 * h, 2 * wd, cin, 4, 2, 1, 1, h, wd, h, wd)
+        dw = _wgrad(P, lib, d, dy, x, w, ctx.weight_param, "deconv wgrad", must=True)
+    return dx, dw
 
 
 class ToC8Fn(torch.autograd.Function):
@@ -465,72 +648,40 @@ class FromC8Fn(torch.autograd.Function):
         return out, None
 
 
+class Conv2dFn(torch.autograd.Function):
+    """z = conv2d(x, weight) (+ bias); k in {1, 3}, stride in {1, 2}, padding = k // 2."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, stride, padding):
+        return _conv_forward(_F32, ctx, x, weight, bias, stride, padding)
+
+    @staticmethod
+    def backward(ctx, dz):
+        return _conv_backward(_F32, ctx, dz)
+
+
 class Conv16Fn(torch.autograd.Function):
     """z = conv2d(x, fp16(weight)) (+ bias) on the fp16 matrix cores; k in {1, 3}, stride in {1, 2}, padding = k // 2."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, stride, padding):
-        lib = _lib.load()
-        w = weight.detach().contiguous()
-        n, _, h, wd, _ = x.shape
-        cout, cin, k, _ = w.shape
-        if padding != k // 2 or k not in (1, 3) or stride not in (1, 2):
-            raise NotImplementedError("training path covers k in {1,3}, stride in {1,2}, padding = k//2")
-        ho, wo = (h + 2 * padding - k) // stride + 1, (wd + 2 * padding - k) // stride + 1
-        ones, zeros = _ones_zeros16(cout, x.device)
-        shift = zeros
-        if bias is not None:
-            shift = torch.zeros_like(zeros)
-            shift[:cout] = bias.detach()
-        z = _c8_alloc(n, cout, ho, wo, x.device)
-        d = _desc(n, cin, h, wd, cout, k, stride, padding, padding, ho, wo, ho, wo)
-        packed = _pack16(lib, w, cout, cin, k, 0, owner=weight)
-        _conv16_launch(lib, d, x, packed, ones, shift, z, "mp_f16_conv2d_fwd")
-        ctx.save_for_backward(x, w)
-        ctx.stride, ctx.padding, ctx.has_bias = stride, padding, bias is not None
-        ctx.weight_param = weight
-        return z
+        return _conv_forward(_F16, ctx, x, weight, bias, stride, padding)
 
     @staticmethod
     def backward(ctx, dz):
-        lib = _lib.load()
-        x, w = ctx.saved_tensors
-        dz = dz.contiguous()
-        n, _, h, wd, _ = x.shape
-        cout, cin, k, _ = w.shape
-        s, pad = ctx.stride, ctx.padding
-        ho, wo = dz.shape[2], dz.shape[3]
-        dx = dw = db = None
-        if ctx.needs_input_grad[0]:
-            ones, zeros = _ones_zeros16(cin, x.device)
-            dx = _c8_alloc(n, cin, h, wd, x.device)
-            if s == 1:
-                d = _desc(n, cout, ho, wo, cin, k, 1, k - 1 - pad, k - 1 - pad, h, wd, h, wd)
-                # ResidualBlock16Fn: the gradient that reaches x through the identity is added in this launch's epilogue
-                _conv16_launch(lib, d, dz, _pack16(lib, w, cin, cout, k, 2, owner=ctx.weight_param), ones, zeros, dx, "conv dgrad",
-                               res1=getattr(ctx, "dx_residual", None))
-            else:
-                if h != 2 * ho or wd != 2 * wo:
-                    raise NotImplementedError("stride-2 data gradient needs even input extents")
-                if k == 3:
-                    _dgrad16_stride2(lib, w, ctx.weight_param, dz, dx, n, cin, cout, h, wd, ho, wo, ones, zeros)
-                else:  # 1x1 stride 2 (ResNet down-sample): only the even positions receive gradient
-                    dx.zero_()
-                    d = _desc(n, cout, ho, wo, cin, 1, 1, 0, 0, ho, wo, h, wd, out_mul=2)
-                    _conv16_launch(lib, d, dz, _pack16(lib, w, cin, cout, 1, 2, owner=ctx.weight_param), ones, zeros, dx, "conv dgrad 1x1s2")
-        if ctx.needs_input_grad[1]:
-            direct = _direct_grad(ctx.weight_param)  # add straight into the gradient arena: no AccumulateGrad launch
-            dw = direct if direct is not None else torch.empty_like(w)
-            d = _desc(n, cin, h, wd, cout, k, s, pad, pad, ho, wo, ho, wo)
-            ws_bytes = lib.mp_f16_conv_wgrad_workspace_bytes(ctypes.byref(d))
-            ws = torch.empty(max(ws_bytes // 4, 1), device=x.device, dtype=torch.float32)
-            _lib.check(lib.mp_f16_conv_wgrad(ctypes.byref(d), _lib.ptr(x), _lib.ptr(dz), _lib.ptr(dw), 1.0, int(direct is not None),
-                                             _lib.ptr(ws), ws_bytes, _lib.stream()), "mp_f16_conv_wgrad")
-            if direct is not None:
-                dw = None
-        if ctx.has_bias and ctx.needs_input_grad[2]:
-            db = dz.float().sum(dim=(0, 2, 3)).reshape(-1)[:cout]  # head conv bias (17 values)
-        return dx, dw, db, None, None
+        return _conv_backward(_F16, ctx, dz)
+
+
+class BatchNormActFn(torch.autograd.Function):
+    """y = act(BN_train(z) (+ res)); updates the moving statistics in place (mindspore.nn.BatchNorm2d training)."""
+
+    @staticmethod
+    def forward(ctx, z, gamma, beta, res, moving_mean, moving_var, relu):
+        return _bn_forward(_F32, ctx, z, gamma, beta, res, moving_mean, moving_var, relu)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return _bn_backward(_F32, ctx, dy)
 
 
 class BatchNormAct16Fn(torch.autograd.Function):
@@ -538,47 +689,24 @@ class BatchNormAct16Fn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z, gamma, beta, res, moving_mean, moving_var, relu):
-        lib = _lib.load()
-        n, _, h, w, _ = z.shape
-        c = gamma.numel()
-        y = torch.empty_like(z)
-        mean = torch.empty(c, device=z.device)
-        invstd = torch.empty(c, device=z.device)
-        ws, ws_bytes = _bn16_workspace(lib, c, z.device)
-        g, b = gamma.detach().contiguous(), beta.detach().contiguous()
-        r = res.contiguous() if res is not None else None
-        _lib.check(lib.mp_f16_bn_train_fwd(_lib.ptr(z), _lib.ptr(g), _lib.ptr(b), _lib.ptr(r), _lib.ptr(y), _lib.ptr(mean),
-                                           _lib.ptr(invstd), _lib.ptr(moving_mean), _lib.ptr(moving_var), n, c, h * w, BN_EPS,
-                                           BN_MOMENTUM, int(relu), _lib.ptr(ws), ws_bytes, _lib.stream()), "mp_f16_bn_train_fwd")
-        ctx.save_for_backward(z, y, g, b, mean, invstd)
-        ctx.relu, ctx.has_res = relu, res is not None
-        ctx.gamma_param, ctx.beta_param = gamma, beta
-        return y
+        return _bn_forward(_F16, ctx, z, gamma, beta, res, moving_mean, moving_var, relu)
 
     @staticmethod
     def backward(ctx, dy):
-        lib = _lib.load()
-        z, y, g, b, mean, invstd = ctx.saved_tensors
-        if ctx.relu and not ctx.has_res and _lib.env_on("MINDPOSE_BN16_MASK_FROM_Z"):
-            y = None  # no residual: the ReLU mask is re-derived from z (forward arithmetic), y is not read
-        dy = dy.contiguous()
-        n, _, h, w, _ = z.shape
-        c = g.numel()
-        dz = torch.empty_like(z)
-        dres = torch.empty_like(z) if ctx.has_res else None
-        dgamma = torch.empty(c, device=z.device)
-        dbeta = torch.empty(c, device=z.device)
-        ws, ws_bytes = _bn16_workspace(lib, c, z.device)
-        ga, ba = _direct_grad(ctx.gamma_param), _direct_grad(ctx.beta_param)
-        if ga is None or ba is None:
-            ga = ba = None
-        _lib.check(lib.mp_f16_bn_train_bwd(_lib.ptr(dy), _lib.ptr(z), _lib.ptr(y), _lib.ptr(g), _lib.ptr(b), _lib.ptr(mean),
-                                           _lib.ptr(invstd), _lib.ptr(dz), _lib.ptr(dres), _lib.ptr(dgamma), _lib.ptr(dbeta), _lib.ptr(ga),
-                                           _lib.ptr(ba), n, c, h * w, int(ctx.relu), _lib.ptr(ws), ws_bytes, _lib.stream()),
-                   "mp_f16_bn_train_bwd")
-        if ga is not None:
-            return dz, None, None, dres, None, None, None
-        return dz, dgamma, dbeta, dres, None, None, None
+        return _bn_backward(_F16, ctx, dy)
+
+
+class FuseSumFn(torch.autograd.Function):
+    """out = relu(((base + up(t1)) + up(t2)) + up(t3)); terms at scale 1 are plain adds (hrnet.py:327-339)."""
+
+    @staticmethod
+    def forward(ctx, base, scales, *terms):
+        return _fuse_sum_forward(_F32, ctx, base, scales, terms)
+
+    @staticmethod
+    def backward(ctx, dy):
+        dbase, dts = _fuse_sum_backward(_F32, ctx, dy)
+        return (dbase, None, *dts)
 
 
 class FuseSum16Fn(torch.autograd.Function):
@@ -587,48 +715,12 @@ class FuseSum16Fn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, base, scales, links, *terms):
-        lib = _lib.load()
-        n, c8, h, w, _ = base.shape
-        base = base.contiguous()
-        ts = [t.contiguous() for t in terms]
-        out = torch.empty_like(base)
-        args = []
-        for i in range(3):
-            args += [_lib.ptr(ts[i]), int(scales[i])] if i < len(ts) else [None, 1]
-        _lib.check(lib.mp_f16_fuse_upsample_sum(_lib.ptr(base), *args, _lib.ptr(out), n, c8 * 8, h, w, 1, _lib.stream()),
-                   "mp_f16_fuse_upsample_sum")
-        ctx.save_for_backward(out)
-        ctx.scales = [int(s) for s in scales[:len(ts)]]
-        ctx.links = list(links) if links is not None else [None] * (1 + len(ts))
-        return out
+        ctx.links = list(links) if links is not None else [None] * (1 + len(terms))
+        return _fuse_sum_forward(_F16, ctx, base, scales, terms)
 
     @staticmethod
     def backward(ctx, dy):
-        lib = _lib.load()
-        (out,) = ctx.saved_tensors
-        dy = dy.contiguous()
-        n, c8, h, w, _ = out.shape
-        dbase = torch.empty_like(out)
-        dts = [torch.empty(n, c8, h // s, w // s, 8, device=out.device, dtype=torch.float16) for s in ctx.scales]
-        outs, scs = [dbase] + dts, [1] + ctx.scales
-        plain = [None, None, None, None]
-        for k, (dst, sc, link) in enumerate(zip(outs, scs, ctx.links)):
-            if (link is not None and link.claimed == 1 and (_bn_fuse_parts() & 8) and tuple(link.z.shape) == tuple(dst.shape)):
-                n_parts = lib.mp_f16_fuse_term_stats_parts(n, c8 * 8, h, w, sc)
-                part = torch.empty(c8 * n_parts * 16, device=out.device, dtype=torch.float32)
-                _lib.check(lib.mp_f16_fuse_sum_bwd_term_stats(_lib.ptr(dy), _lib.ptr(out), _lib.ptr(dst), sc, n, c8 * 8, h, w, 1,
-                                                              _lib.ptr(link.z), _lib.ptr(link.y) if link.relu else None, int(link.relu),
-                                                              _lib.ptr(part), part.numel() * 4, _lib.stream()),
-                           "mp_f16_fuse_sum_bwd_term_stats")
-                link.hand_over(part, n_parts, dst)
-            else:
-                plain[k] = dst
-        if any(p is not None for p in plain):
-            args = []
-            for i in range(3):
-                args += [_lib.ptr(plain[i + 1]), ctx.scales[i]] if i < len(dts) else [None, 1]
-            _lib.check(lib.mp_f16_fuse_upsample_sum_bwd(_lib.ptr(dy), _lib.ptr(out), _lib.ptr(plain[0]), *args, n, c8 * 8, h, w, 1,
-                                                        _lib.stream()), "mp_f16_fuse_upsample_sum_bwd")
+        dbase, dts = _fuse_sum_backward(_F16, ctx, dy)
         return (dbase, None, None, *dts)
 
 
@@ -699,61 +791,23 @@ class Deconv16Fn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, weight):
-        lib = _lib.load()
-        w = weight.detach().contiguous()
-        n, _, h, wd, _ = x.shape
-        cin, cout = w.shape[0], w.shape[1]
-        ones, zeros = _ones_zeros16(cout, x.device)
-        y = _c8_alloc(n, cout, 2 * h, 2 * wd, x.device)
-        for py in (0, 1):
-            for px in (0, 1):
-                d = _desc(n, cin, h, wd, cout, 2, 1, 1 - py, 1 - px, h, wd, 2 * h, 2 * wd, out_mul=2, off_y=py, off_x=px)
-                _conv16_launch(lib, d, x, _pack16(lib, w, cout, cin, 2, 1, py, px, owner=weight), ones, zeros, y, "deconv phase")
-        ctx.save_for_backward(x, w)
-        ctx.weight_param = weight
-        return y
+        return _deconv_forward(_F16, ctx, x, weight)
 
     @staticmethod
     def backward(ctx, dy):
-        lib = _lib.load()
-        x, w = ctx.saved_tensors
-        dy = dy.contiguous()
-        n, _, h, wd, _ = x.shape
-        cin, cout = w.shape[0], w.shape[1]
-        dx = dw = None
-        if ctx.needs_input_grad[0]:
-            ones, zeros = _ones_zeros16(cin, x.device)
-            dx = _c8_alloc(n, cin, h, wd, x.device)
-            phase = _c8_alloc(n, cout, h, wd, x.device)
-            first = True
-            for py in (0, 1):
-                for px in (0, 1):
-                    _lib.check(lib.mp_f16_gather_phase(_lib.ptr(dy), _lib.ptr(phase), n, cout, h, wd, py, px, _lib.stream()),
-                               "mp_f16_gather_phase")
-                    # y_phase[m] = sum_t x[m - (1-p) + t] wp[t]  =>  dx[j] = sum_t dy_phase[j + (1-p) - t] wp[t]:
-                    # a 2x2 conv over dy_phase with mirrored taps and padding p
-                    d = _desc(n, cout, h, wd, cin, 2, 1, py, px, h, wd, h, wd)
-                    packed = _pack16(lib, w, cin, cout, 2, 4, py, px, owner=ctx.weight_param)
-                    v = tune_conv_variant(lib, d, phase, packed, ones, zeros, None if first else dx, None, dx, half=True)
-                    _lib.check(lib.mp_f16_conv2d_fwd(ctypes.byref(d), v, _lib.ptr(phase), _lib.ptr(packed), _lib.ptr(ones),
-                                                     _lib.ptr(zeros), None if first else _lib.ptr(dx), None, _lib.ptr(dx),
-                                                     _lib.stream()), "deconv dgrad phase")
-                    first = False
-        if ctx.needs_input_grad[1]:
-            # dW[ci][co][ky][kx] = sum_m x[m][ci] * dy[2m + ky - 1][co]: weight gradient of a 4x4 s2 p1 conv whose input is dy
-            # and whose output gradient is x -> result laid out [ci][co][4][4] = the transposed conv's own weight layout
-            direct = _direct_grad(ctx.weight_param)
-            dw = direct if direct is not None else torch.empty_like(w)
-            d = _desc(n, cout, 2 * h, 2 * wd, cin, 4, 2, 1, 1, h, wd, h, wd)
-            ws_bytes = lib.mp_f16_conv_wgrad_workspace_bytes(ctypes.byref(d))
-            if ws_bytes == 0:
-                raise _lib.MindposeHipError("transposed-conv weight gradient: unsupported shape")
-            ws = torch.empty(ws_bytes // 4, device=x.device, dtype=torch.float32)
-            _lib.check(lib.mp_f16_conv_wgrad(ctypes.byref(d), _lib.ptr(dy), _lib.ptr(x), _lib.ptr(dw), 1.0, int(direct is not None),
-                                             _lib.ptr(ws), ws_bytes, _lib.stream()), "deconv wgrad")
-            if direct is not None:
-                dw = None
-        return dx, dw
+        return _deconv_backward(_F16, ctx, dy)
+
+
+class DeconvFn(torch.autograd.Function):
+    """fp32 NCHW form of ``Deconv16Fn``."""
+
+    @staticmethod
+    def forward(ctx, x, weight):
+        return _deconv_forward(_F32, ctx, x, weight)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return _deconv_backward(_F32, ctx, dy)
 
 
 def stem_conv_bn_relu(x, conv, bn):
@@ -764,59 +818,6 @@ def stem_conv_bn_relu(x, conv, bn):
 
 def maxpool3x3s2_same(x):
     return MaxPoolFn.apply(x)
-
-
-class DeconvFn(torch.autograd.Function):
-    """fp32 NCHW form of ``Deconv16Fn``: four 2x2 phase convs forward, gathered-phase 2x2 convs for the data gradient, the 4x4
-    stride-2 weight-gradient GEMM (roles exchanged) for the weight gradient."""
-
-    @staticmethod
-    def forward(ctx, x, weight):
-        lib = _lib.load()
-        x = _lib.require_cuda_f32(x, "x")
-        w = weight.detach().contiguous()
-        n, cin, h, wd = x.shape
-        cout = w.shape[1]
-        ones, zeros = _ones_zeros(cout, x.device)
-        y = torch.empty(n, cout, 2 * h, 2 * wd, device=x.device, dtype=torch.float32)
-        for py in (0, 1):
-            for px in (0, 1):
-                d = _desc(n, cin, h, wd, cout, 2, 1, 1 - py, 1 - px, h, wd, 2 * h, 2 * wd, out_mul=2, off_y=py, off_x=px)
-                _conv_launch(lib, d, x, _pack(lib, w, cout, cin, 2, 1, py, px), ones, zeros, y, "deconv phase")
-        ctx.save_for_backward(x, w)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        lib = _lib.load()
-        x, w = ctx.saved_tensors
-        dy = dy.contiguous()
-        n, cin, h, wd = x.shape
-        cout = w.shape[1]
-        dx = dw = None
-        if ctx.needs_input_grad[0]:
-            ones, zeros = _ones_zeros(cin, x.device)
-            dx = torch.empty_like(x)
-            phase = torch.empty(n, cout, h, wd, device=x.device, dtype=torch.float32)
-            first = True
-            for py in (0, 1):
-                for px in (0, 1):
-                    _lib.check(lib.mp_gather_phase(_lib.ptr(dy), _lib.ptr(phase), n, cout, h, wd, py, px, _lib.stream()), "mp_gather_phase")
-                    d = _desc(n, cout, h, wd, cin, 2, 1, py, px, h, wd, h, wd)
-                    packed = _pack(lib, w, cin, cout, 2, 4, py, px)
-                    _lib.check(lib.mp_conv2d_fwd(ctypes.byref(d), _lib.ptr(phase), _lib.ptr(packed), _lib.ptr(ones), _lib.ptr(zeros),
-                                                 None if first else _lib.ptr(dx), None, _lib.ptr(dx), _lib.stream()), "deconv dgrad phase")
-                    first = False
-        if ctx.needs_input_grad[1]:
-            dw = torch.empty_like(w)
-            d = _desc(n, cout, 2 * h, 2 * wd, cin, 4, 2, 1, 1, h, wd, h, wd)
-            ws_bytes = lib.mp_conv_wgrad_workspace_bytes(ctypes.byref(d))
-            if ws_bytes == 0:
-                raise _lib.MindposeHipError("transposed-conv weight gradient: unsupported shape")
-            ws = torch.empty(ws_bytes // 4, device=x.device, dtype=torch.float32)
-            _lib.check(lib.mp_conv_wgrad(ctypes.byref(d), _lib.ptr(dy), _lib.ptr(x), _lib.ptr(dw), 0, _lib.ptr(ws), ws_bytes,
-                                         _lib.stream()), "deconv wgrad")
-        return dx, dw
 
 
 def deconv_bn_relu(x, deconv, bn):
@@ -843,8 +844,7 @@ def _is_c8(x) -> bool:
 
 
 class _SubCtx:
-    """The slice of an autograd context the per-cell Functions use, so that a composite Function can drive their static
-    forward / backward methods itself."""
+    """The slice of an autograd context the per-cell bodies use, so that a composite Function can run them itself."""
 
     def __init__(self, n_inputs):
         self.needs_input_grad = (True,) * n_inputs
@@ -854,69 +854,63 @@ class _SubCtx:
         self.saved_tensors = tensors
 
 
-class _ResidualBlockFn(torch.autograd.Function):
+def _residual_forward(P, ctx, x, meta, params):
+    groups = []
+    y = x
+    n_groups = len(meta)
+    for gi, (stride, padding, mm, mv) in enumerate(meta):
+        w, gamma, beta = params[3 * gi: 3 * gi + 3]
+        cc, bc = _SubCtx(5), _SubCtx(7)
+        z = _conv_forward(P, cc, y, w, None, stride, padding)
+        last = gi == n_groups - 1
+        y = _bn_forward(P, bc, z, gamma, beta, x if last else None, mm, mv, True)
+        groups.append((cc, bc))
+    ctx.groups = groups
+    return y
+
+
+def _residual_backward(P, ctx, dy):
+    grads = []
+    g = dy
+    dres = None
+    for gi in range(len(ctx.groups) - 1, -1, -1):
+        cc, bc = ctx.groups[gi]
+        dz, dgamma, dbeta, dr, _, _, _ = _bn_backward(P, bc, g)
+        if dr is not None:
+            dres = dr
+        if gi == 0:
+            cc.dx_residual = dres
+        g, dw, _, _, _ = _conv_backward(P, cc, dz)
+        grads = [dw, dgamma, dbeta] + grads
+    ctx.groups = None
+    return (g, None, *grads)
+
+
+class ResidualBlock16Fn(torch.autograd.Function):
     """A whole residual block - conv+BN+ReLU groups whose last BatchNorm adds the block input and applies the ReLU (BasicBlock: two
-    groups, Bottleneck without down-sample: three) - as ONE autograd node.  Same kernels as the per-cell Functions; what it
-    saves is autograd's separate launch that sums the two gradients reaching the block input: the identity's gradient is added
-    in the epilogue of the first conv's data-gradient launch (104 launches per HRNet-W32 step).  ``CONV`` / ``BN``: the per-cell
-    Functions of the activation type (channel-blocked fp16, or fp32 NCHW)."""
-    CONV = BN = None
-
-    @classmethod
-    def forward(cls, ctx, x, meta, *params):
-        groups = []
-        y = x
-        n_groups = len(meta)
-        for gi, (stride, padding, mm, mv) in enumerate(meta):
-            w, gamma, beta = params[3 * gi: 3 * gi + 3]
-            cc, bc = _SubCtx(5), _SubCtx(7)
-            z = cls.CONV.forward(cc, y, w, None, stride, padding)
-            last = gi == n_groups - 1
-            y = cls.BN.forward(bc, z, gamma, beta, x if last else None, mm, mv, True)
-            groups.append((cc, bc))
-        ctx.groups = groups
-        return y
-
-    @classmethod
-    def backward(cls, ctx, dy):
-        grads = []
-        g = dy
-        dres = None
-        for gi in range(len(ctx.groups) - 1, -1, -1):
-            cc, bc = ctx.groups[gi]
-            dz, dgamma, dbeta, dr, _, _, _ = cls.BN.backward(bc, g)
-            if dr is not None:
-                dres = dr
-            if gi == 0:
-                cc.dx_residual = dres
-            g, dw, _, _, _ = cls.CONV.backward(cc, dz)
-            grads = [dw, dgamma, dbeta] + grads
-        ctx.groups = None
-        return (g, None, *grads)
-
-
-class ResidualBlock16Fn(_ResidualBlockFn):
-    CONV, BN = Conv16Fn, BatchNormAct16Fn
+    groups, Bottleneck without down-sample: three) - as ONE autograd node.  Same launches as the per-cell Functions (it runs
+    their bodies); what it saves is autograd's separate launch that sums the two gradients reaching the block input: the
+    identity's gradient is added in the epilogue of the first conv's data-gradient launch (104 launches per HRNet-W32 step)."""
 
     @staticmethod
     def forward(ctx, x, meta, *params):
-        return _ResidualBlockFn.forward.__func__(ResidualBlock16Fn, ctx, x, meta, *params)
+        return _residual_forward(_F16, ctx, x, meta, params)
 
     @staticmethod
     def backward(ctx, dy):
-        return _ResidualBlockFn.backward.__func__(ResidualBlock16Fn, ctx, dy)
+        return _residual_backward(_F16, ctx, dy)
 
 
-class ResidualBlock32Fn(_ResidualBlockFn):
-    CONV, BN = Conv2dFn, BatchNormActFn
+class ResidualBlock32Fn(torch.autograd.Function):
+    """`ResidualBlock16Fn` on fp32 NCHW."""
 
     @staticmethod
     def forward(ctx, x, meta, *params):
-        return _ResidualBlockFn.forward.__func__(ResidualBlock32Fn, ctx, x, meta, *params)
+        return _residual_forward(_F32, ctx, x, meta, params)
 
     @staticmethod
     def backward(ctx, dy):
-        return _ResidualBlockFn.backward.__func__(ResidualBlock32Fn, ctx, dy)
+        return _residual_backward(_F32, ctx, dy)
 
 
 # ---- amp O2: BatchNorm fused into the neighbouring convs (round 3) ----------------------------------------------------------------
@@ -1031,8 +1025,7 @@ def _conv16_stats_launch(lib, d, x, packed, scale, shift, out, res1, mode, z=Non
     if pre is not None and (part is None or v < 0):
         raise _lib.MindposeHipError("no conv variant applies the BatchNorm on its operand for a shape _pre_capable admitted")
     if part is None:
-        _lib.check(lib.mp_f16_conv2d_fwd(ctypes.byref(d), v, _lib.ptr(x), _lib.ptr(packed), _lib.ptr(scale), _lib.ptr(shift),
-                                         _lib.ptr(res1), None, _lib.ptr(out), _lib.stream()), "mp_f16_conv2d_fwd")
+        _conv16_run(lib, d, v, x, packed, scale, shift, res1, out, "mp_f16_conv2d_fwd")
         return None, 0
     st = _lib.ConvStats(mode=mode, relu=int(relu), partials=part.data_ptr(), partials_bytes=part.numel() * 4,
                         z=_lib.ptr(z), y=_lib.ptr(y) if relu else None)
@@ -1099,10 +1092,7 @@ def _wgrad_flush_key(lib, key, joined: bool = False):
     with torch.cuda.device(dev):
         if n == 1:
             _, x, dz, dw, _ = jobs[0]
-            wsb = lib.mp_f16_conv_wgrad_workspace_bytes(ctypes.byref(d))
-            ws = torch.empty(max(wsb // 4, 1), device=dev, dtype=torch.float32)
-            _lib.check(lib.mp_f16_conv_wgrad(ctypes.byref(d), _lib.ptr(x), _lib.ptr(dz), _lib.ptr(dw), 1.0, 1, _lib.ptr(ws), wsb,
-                                             _lib.stream()), "mp_f16_conv_wgrad")
+            _wgrad_launch(_F16, lib, d, x, dz, dw, 1, "mp_f16_conv_wgrad")
             return
         wsb = lib.mp_f16_conv_wgrad_grouped_workspace_bytes(ctypes.byref(d), n)
         ws = torch.empty(max(wsb // 4, 1), device=dev, dtype=torch.float32)
@@ -1204,10 +1194,7 @@ def _run_bn_fwd_job(lib, j):
                                                 j["ws_bytes"], _lib.stream()), "mp_f16_bn_train_finalize")
         return
     if j["part"] is None:
-        _lib.check(lib.mp_f16_bn_train_fwd(_lib.ptr(j["z"]), _lib.ptr(j["g"]), _lib.ptr(j["b"]), _lib.ptr(j["res"]), _lib.ptr(j["y"]),
-                                           _lib.ptr(j["mean"]), _lib.ptr(j["invstd"]), _lib.ptr(j["mm"]), _lib.ptr(j["mv"]), j["n"], j["c"],
-                                           j["hw"], BN_EPS, BN_MOMENTUM, j["relu"], _lib.ptr(j["ws"]), j["ws_bytes"], _lib.stream()),
-                   "mp_f16_bn_train_fwd")
+        _bn_fwd_launch(_F16, lib, j)
     else:
         _lib.check(lib.mp_f16_bn_train_fwd_stats(_lib.ptr(j["z"]), _lib.ptr(j["g"]), _lib.ptr(j["b"]), _lib.ptr(j["res"]), _lib.ptr(j["y"]),
                                                  _lib.ptr(j["mean"]), _lib.ptr(j["invstd"]), _lib.ptr(j["mm"]), _lib.ptr(j["mv"]), j["n"],
@@ -1218,10 +1205,7 @@ def _run_bn_fwd_job(lib, j):
 def _run_bn_bwd_job(lib, j):
     """The backward counterpart: apply-only on a pre-masked gradient whose sums its producer delivered, else reduce + apply."""
     if j["pre"] is None:
-        _lib.check(lib.mp_f16_bn_train_bwd(_lib.ptr(j["dy"]), _lib.ptr(j["z"]), _lib.ptr(j["yy"]), _lib.ptr(j["g"]), _lib.ptr(j["b"]),
-                                           _lib.ptr(j["mean"]), _lib.ptr(j["invstd"]), _lib.ptr(j["dz"]), _lib.ptr(j["dr"]),
-                                           _lib.ptr(j["dgamma"]), _lib.ptr(j["dbeta"]), _lib.ptr(j["ga"]), _lib.ptr(j["ba"]), j["n"], j["c"],
-                                           j["hw"], j["relu"], _lib.ptr(j["ws"]), j["ws_bytes"], _lib.stream()), "mp_f16_bn_train_bwd")
+        _bn_bwd_launch(_F16, lib, j)
     else:
         _lib.check(lib.mp_f16_bn_train_bwd_stats(_lib.ptr(j["dy"]), _lib.ptr(j["z"]), _lib.ptr(j["g"]), _lib.ptr(j["mean"]),
                                                  _lib.ptr(j["invstd"]), _lib.ptr(j["dz"]), _lib.ptr(j["dgamma"]), _lib.ptr(j["dbeta"]),
@@ -1239,15 +1223,7 @@ def _chain16_fwd_steps(lib, x, meta, residual, res_ext, params):
     for gi, (stride, padding, mm, mv, relu) in enumerate(meta):
         weight, gamma, beta = params[3 * gi: 3 * gi + 3]
         w = weight.detach().contiguous()
-        n, _, h, wd, _ = a.shape
-        cout, cin, k, _ = w.shape
-        if padding != k // 2 or k not in (1, 3) or stride not in (1, 2):
-            raise NotImplementedError("training path covers k in {1,3}, stride in {1,2}, padding = k//2")
-        ho, wo = (h + 2 * padding - k) // stride + 1, (wd + 2 * padding - k) // stride + 1
-        ones, zeros = _ones_zeros16(cout, a.device)
-        z = _c8_alloc(n, cout, ho, wo, a.device)
-        d = _desc(n, cin, h, wd, cout, k, stride, padding, padding, ho, wo, ho, wo)
-        packed = _pack16(lib, w, cout, cin, k, 0, owner=weight)
+        d, packed, ones, zeros, z, (n, cout, ho, wo) = _conv_fwd_args(_F16, lib, a, weight, w, None, stride, padding)
         if pre is not None:  # operand = the raw output below; this launch applies its BatchNorm and writes the activation `a`
             part, n_parts = _conv16_stats_launch(lib, d, pre["z"], packed, ones, zeros, z, None, 1, pre=pre)
             pre = None
@@ -1258,13 +1234,9 @@ def _chain16_fwd_steps(lib, x, meta, residual, res_ext, params):
             _conv16_launch(lib, d, a, packed, ones, zeros, z, "mp_f16_conv2d_fwd")
         last = gi == n_groups - 1
         res = (x if residual else res_ext) if last else None
-        y = torch.empty_like(z)
-        mean = torch.empty(cout, device=z.device)
-        invstd = torch.empty(cout, device=z.device)
-        ws, ws_bytes = _bn16_workspace(lib, cout, z.device)
-        g, b = gamma.detach().contiguous(), beta.detach().contiguous()
-        job = dict(z=z, g=g, b=b, res=res, y=y, mean=mean, invstd=invstd, mm=mm, mv=mv, n=n, c=cout, hw=ho * wo, relu=int(relu),
-                   part=part, n_parts=n_parts, ws=ws, ws_bytes=ws_bytes)
+        job = _bn_fwd_job(_F16, lib, z, gamma, beta, res, mm, mv, relu)
+        job["part"], job["n_parts"] = part, n_parts
+        y = job["y"]
         if not last and part is not None and bn_pre_enabled() and cout % 8 == 0:
             # conv -> BatchNorm -> ReLU -> 3x3 conv (hrnet.py:67-72): when the next conv can take the raw z, only the statistics
             # are finalised here - no pass over z / y; the next launch writes y (the backward pass reads it) on the way
@@ -1279,8 +1251,8 @@ def _chain16_fwd_steps(lib, x, meta, residual, res_ext, params):
                                y=y, relu=int(relu), z=z)
                     job["pre"] = pre
         yield job
-        groups.append(dict(a=a, w=w, weight=weight, gamma=gamma, beta=beta, g=g, b=b, z=z, y=y, mean=mean, invstd=invstd,
-                           stride=stride, padding=padding, relu=bool(relu), res=res is not None))
+        groups.append(dict(a=a, w=w, weight=weight, gamma=gamma, beta=beta, g=job["g"], b=job["b"], z=z, y=y, mean=job["mean"],
+                           invstd=job["invstd"], stride=stride, padding=padding, relu=bool(relu), res=res is not None))
         a = y
     return groups, a
 
@@ -1291,96 +1263,53 @@ def _chain16_bwd_steps(lib, groups, dy, out_link, in_link, needs_dx, res_is_inpu
     dy = dy.contiguous()
     grads = []
     # the gradient reaching the LAST BatchNorm: pre-masked with partial sums when the (only) consumer's data gradient made them
-    link = out_link
-    pre = _link_pre(link, dy)
+    pre = _link_pre(out_link, dy)
     dres = None
     for gi in range(len(groups) - 1, -1, -1):
         G = groups[gi]
         z, y, a, w = G["z"], G["y"], G["a"], G["w"]
-        n, _, ho, wo, _ = z.shape
+        n, ho, wo = _nhw(z)
         cout, cin, k, _ = w.shape
         h, wd = a.shape[2], a.shape[3]
-        dz = torch.empty_like(z)
-        dgamma = torch.empty(cout, device=z.device)
-        dbeta = torch.empty(cout, device=z.device)
-        ws, ws_bytes = _bn16_workspace(lib, cout, z.device)
-        ga, ba = _direct_grad(G["gamma"]), _direct_grad(G["beta"])
-        if ga is None or ba is None:
-            ga = ba = None
-        job = dict(dy=dy, z=z, g=G["g"], b=G["b"], mean=G["mean"], invstd=G["invstd"], dz=dz, dgamma=dgamma, dbeta=dbeta, ga=ga, ba=ba,
-                   n=n, c=cout, hw=ho * wo, relu=int(G["relu"]), ws=ws, ws_bytes=ws_bytes, pre=pre, yy=None, dr=None)
+        job = _bn_bwd_job(_F16, lib, dy, z, G["g"], G["b"], G["mean"], G["invstd"], G["gamma"], G["beta"], G["relu"])
+        job["pre"] = pre
         if pre is not None:  # apply pass only: dy is g = dy * mask, its sums came with it
             if G["res"]:
                 dres = dy
         else:
-            yy = y if (G["relu"] and G["res"]) else None  # no residual: the mask is re-derived from z, y is not read
-            if G["relu"] and not G["res"] and not _lib.env_on("MINDPOSE_BN16_MASK_FROM_Z"):
-                yy = y
-            job["yy"] = yy
-            job["dr"] = torch.empty_like(z) if G["res"] else None
+            # without a residual the mask is re-derived from z, y is not read
+            if G["relu"] and (G["res"] or not _lib.env_on("MINDPOSE_BN16_MASK_FROM_Z")):
+                job["yy"] = y
             if G["res"]:
-                dres = job["dr"]
+                dres = job["dr"] = torch.empty_like(z)
         yield job
-        if ga is not None:
-            dgamma = dbeta = None
-        # ---- conv: weight gradient (a leaf), then the data gradient that feeds the BatchNorm below
+        dz = job["dz"]
+        dgamma, dbeta = (None, None) if job["ga"] is not None else (job["dgamma"], job["dbeta"])
+        # ---- conv: weight gradient (a leaf; into the arena: queued, launched with the other layers of this shape), then the data
+        # gradient that feeds the BatchNorm below
         s, pad = G["stride"], G["padding"]
-        direct = _direct_grad(G["weight"])
         d = _desc(n, cin, h, wd, cout, k, s, pad, pad, ho, wo, ho, wo)
-        if direct is not None:  # into the gradient arena: queued, launched with the other layers of this shape
-            _wgrad_enqueue(lib, d, a, dz, direct)
-            dw = None
-        else:
-            dw = torch.empty_like(w)
-            wsb = lib.mp_f16_conv_wgrad_workspace_bytes(ctypes.byref(d))
-            wws = torch.empty(max(wsb // 4, 1), device=z.device, dtype=torch.float32)
-            _lib.check(lib.mp_f16_conv_wgrad(ctypes.byref(d), _lib.ptr(a), _lib.ptr(dz), _lib.ptr(dw), 1.0, 0, _lib.ptr(wws), wsb,
-                                             _lib.stream()), "mp_f16_conv_wgrad")
+        dw = _wgrad(_F16, lib, d, a, dz, w, G["weight"], "mp_f16_conv_wgrad", queue=True)
         pre = None
         dx = None
         if gi > 0 or needs_dx:
-            ones, zeros = _ones_zeros16(cin, z.device)
-            dx = _c8_alloc(n, cin, h, wd, z.device)
             res1 = dres if (gi == 0 and res_is_input) else None  # the chain input's second path: added in this launch's epilogue
             # which BatchNorm does this gradient reach?  the previous group's - or, across nodes, the producer of the chain input
-            below = None
+            below = link = None
             if gi > 0:
                 if _bn_fuse_parts() & 2:
-                    P = groups[gi - 1]
-                    below = (P["z"], P["y"], P["relu"], None)
+                    prev = groups[gi - 1]
+                    below = (prev["z"], prev["y"], prev["relu"])
             elif in_link is not None and in_link.claimed == 1 and (_bn_fuse_parts() & 4):
-                below = (in_link.z, in_link.y, in_link.relu, in_link)
-            if s == 1:
-                dd = _desc(n, cout, ho, wo, cin, k, 1, k - 1 - pad, k - 1 - pad, h, wd, h, wd)
-                packed = _pack16(lib, w, cin, cout, k, 2, owner=G["weight"])
-                if below is not None and tuple(below[0].shape) == tuple(dx.shape):
-                    part, n_parts = _conv16_stats_launch(lib, dd, dz, packed, ones, zeros, dx, res1, 2, z=below[0], y=below[1],
-                                                         relu=below[2])
-                    if part is not None:
-                        if below[3] is not None:
-                            below[3].hand_over(part, n_parts, dx)
-                        else:
-                            pre = (part, n_parts)
+                below, link = (in_link.z, in_link.y, in_link.relu), in_link
+            if s != 1 and not (_bn_fuse_parts() & 16):  # the merged-phase launch of a stride-2 data gradient stays plain
+                below = None
+            dx, part, n_parts = _conv_dgrad(_F16, lib, a, w, G["weight"], dz, s, pad, res1=res1, below=below)
+            if part is not None:
+                if link is not None:
+                    link.hand_over(part, n_parts, dx)
                 else:
-                    _conv16_launch(lib, dd, dz, packed, ones, zeros, dx, "conv dgrad", res1=res1)
-            else:
-                if h != 2 * ho or wd != 2 * wo:
-                    raise NotImplementedError("stride-2 data gradient needs even input extents")
-                if res1 is not None:
-                    raise NotImplementedError("a residual chain starts with a stride-1 conv")
-                if k == 3:
-                    use = below if (below is not None and tuple(below[0].shape) == tuple(dx.shape) and (_bn_fuse_parts() & 16)) else None
-                    part, n_parts = _dgrad16_stride2(lib, w, G["weight"], dz, dx, n, cin, cout, h, wd, ho, wo, ones, zeros,
-                                                     below=use[:3] if use is not None else None)
-                    if part is not None:
-                        if use[3] is not None:
-                            use[3].hand_over(part, n_parts, dx)
-                        else:
-                            pre = (part, n_parts)
-                else:
-                    dx.zero_()
-                    dd = _desc(n, cout, ho, wo, cin, 1, 1, 0, 0, ho, wo, h, wd, out_mul=2)
-                    _conv16_launch(lib, dd, dz, _pack16(lib, w, cin, cout, 1, 2, owner=G["weight"]), ones, zeros, dx, "conv dgrad 1x1s2")
+                    pre = (part, n_parts)
         elif gi == 0 and dres is not None and res_is_input:
             dx = dres
         grads = [dw, dgamma, dbeta] + grads
