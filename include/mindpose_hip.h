@@ -601,6 +601,44 @@ int mp_bottomup_parse_nms_topk_flip(const mp_bottomup_stage* stages_host, const 
                                     int n, int k, int tag_per_joint, int nms_kernel, int max_num, float* heatmap_raw_dev,
                                     float* tagging_dev, void* workspace_dev, size_t workspace_bytes, mp_stream_t stream);
 
+/* mp_bottomup_parse_nms_topk_multi: the first decoder launch of the multi-scale test (this project's protocol; the
+ * reference ships none), over num_runs (1..4) runs of the network on the batch resized by one scale factor each.  runs_host is a
+ * HOST array; runs_host[r].stages [num_stages] (HOST) are run r's outputs and runs_host[r].flipped [num_stages] those of its
+ * horizontally mirrored input, NULL in every run = no flip test (then flip_index_host is NULL too).  Run base_run is the scale-1
+ * run: its last stage is the map (H, W), and the tags come from it alone, exactly as the plain / flip entry writes them (L slots,
+ * or 2L with the flip test); tag channels of the other runs are never read.  Every run has num_stages stages with the base run's
+ * c and has_tags per stage; its h, w are free (smaller or larger than the map: in / out > 1 is allowed).  With
+ *     t_{r,i}   = stages_i of run r, or with the flip test (stages_i[n,j,y,x] + flipped_i[n,flip_index[j],y,w_i-1-x]) * 0.5f,
+ *     R(.)      = ResizeBilinear to (H, W) without half-pixel centres, src = dst * (in / out); for the base run's last stage
+ *                 the direct read,
+ *     v_r       = R(t_{r,last}); v_r = v_r + R(t_{r,i}) for i = 0 .. num_stages - 2; v_r = v_r / (float)num_stages if > 1 stage,
+ *     total     = v_0 + v_1 + ... in array order; total = total / (float)num_runs if num_runs > 1 (a true division),
+ * heatmap_raw [n,k,H,W] = total, 0 where the nearest-resized mask is 0.  num_runs == 1 is mp_bottomup_parse_nms_topk (or _flip)
+ * operation for operation.  NMS, per-tile top-k, the workspace (mp_bottomup_workspace_bytes of the base map) and the
+ * mp_bottomup_gather that follows are unchanged.  Deterministic, no atomics.  The launch parameters (at most 16 stage records and
+ * the 64-entry joint permutation, under 1.5 KiB) travel BY VALUE in the kernel arguments: the entry writes no device table.
+ * Refusals, all before the launch: a NULL array or data pointer, or mirrored arrays without flip_index_host (or the reverse),
+ * MP_ERR_NULL; num_runs outside 1..4, base_run outside [0, num_runs), mirrored arrays in some runs only, a stage whose c or
+ * has_tags differs from the base run's, non-positive extents, a mirrored stage shaped unlike its plain one, a flip_index entry
+ * outside [0, k) MP_ERR_SHAPE; with the flip test tag_per_joint == 0, k > 64 or 2L > 4 MP_ERR_UNSUPPORTED; everything
+ * mp_bottomup_parse_nms_topk refuses, on the base run. */
+typedef struct mp_bottomup_run {
+    const mp_bottomup_stage* stages;  /* HOST [num_stages] */
+    const mp_bottomup_stage* flipped; /* HOST [num_stages], or NULL */
+} mp_bottomup_run;
+int mp_bottomup_parse_nms_topk_multi(const mp_bottomup_run* runs_host, int num_runs, int base_run, const int32_t* flip_index_host,
+                                     int num_stages, const uint8_t* mask_dev, int mask_h, int mask_w, int n, int k,
+                                     int tag_per_joint, int nms_kernel, int max_num, float* heatmap_raw_dev, float* tagging_dev,
+                                     void* workspace_dev, size_t workspace_bytes, mp_stream_t stream);
+
+/* mp_resize_bilinear_nchw: ops.ResizeBilinear((oh, ow)), align_corners=False, half_pixel_centers=False, of `planes` contiguous fp32
+ * planes [planes, ih, iw] -> [planes, oh, ow]: src = dst * ((float)in / (float)out), x0 = min(floor(src), in - 1),
+ * x1 = min(x0 + 1, in - 1), top = a + (b - a) * dx, bot = c + (d - c) * dx, out = top + (bot - top) * dy in fp32 without
+ * contraction - the decoder's own device function, so pixel q of the source lands on s * q of a map scaled by s and the decoder's
+ * resize reads exactly there.  16-byte stores when ow % 4 == 0 and out is 16-byte aligned, else 4-byte stores.  in and out must not
+ * overlap.  NULL -> MP_ERR_NULL; non-positive extents or a plane of 2^31 or more pixels -> MP_ERR_SHAPE. */
+int mp_resize_bilinear_nchw(const float* in_dev, float* out_dev, int planes, int ih, int iw, int oh, int ow, mp_stream_t stream);
+
 /* mp_bottomup_refine_missing (mindpose/engine/inferencer/bottomup_inferencer.py:189-250, refine_missing_joint): for every person p
  * of a batch's person list (image person_image[p], mean tag mean_tag [P, L] formed by the caller) and every joint, the first
  * arg-max in flat index over the joint's H x W map of  heatmap_raw - rint(sqrt(sum_l (tagging_l - mean_tag_l)^2))  in fp32 (tag

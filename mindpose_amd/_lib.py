@@ -51,6 +51,12 @@ class BottomUpStage(ctypes.Structure):
                 ("has_tags", ctypes.c_int32)]
 
 
+class BottomUpRun(ctypes.Structure):
+    """``mp_bottomup_run`` of include/mindpose_hip.h (one run of the multi-scale test: its stages and, under the flip test, those of
+    its mirrored input)."""
+    _fields_ = [("stages", ctypes.POINTER(BottomUpStage)), ("flipped", ctypes.POINTER(BottomUpStage))]
+
+
 class MindposeHipError(RuntimeError):
     pass
 
@@ -196,6 +202,9 @@ _PROTOTYPES = {
                                                                                                      ctypes.c_void_p]),
     "mp_bottomup_parse_nms_topk_flip": (c_int, [ctypes.POINTER(BottomUpStage)] * 2 + [ctypes.POINTER(ctypes.c_int32), c_int, c_f32p]
                                         + [c_int] * 7 + [c_f32p, c_f32p, c_f32p, c_size_t, ctypes.c_void_p]),
+    "mp_bottomup_parse_nms_topk_multi": (c_int, [ctypes.POINTER(BottomUpRun), c_int, c_int, ctypes.POINTER(ctypes.c_int32), c_int, c_f32p]
+                                         + [c_int] * 7 + [c_f32p, c_f32p, c_f32p, c_size_t, ctypes.c_void_p]),
+    "mp_resize_bilinear_nchw": (c_int, [c_f32p, c_f32p] + [c_int] * 5 + [ctypes.c_void_p]),
     "mp_bottomup_gather": (c_int, [c_f32p, c_f32p, c_f32p, c_size_t] + [c_int] * 8 + [c_f32p, c_f32p, c_f32p, ctypes.c_void_p]),
     "mp_bottomup_refine_missing": (c_int, [c_f32p] * 4 + [c_int] * 7 + [c_f32p, ctypes.c_void_p]),
     "mp_bottomup_match_supported": (c_int, [c_int] * 3),

@@ -31,6 +31,12 @@
 // do not commute), and the tags of the mirrored run, b[K + f[k]][y][ws - 1 - x], follow the plain ones on the last axis of
 // tagging (num_tags = 2 L).  The mirrored maps are never flipped, gathered, averaged or concatenated in memory.
 //
+// Multi-scale test (this project's protocol): bu_parse_multi_kernel is the same kernel body again, its heat map the
+// mean over up to four runs of the network on the batch resized by one scale factor each: per run the stage mean above with EVERY
+// stage resized to the scale-1 run's map (only that run's last stage is the map and is read directly), the runs summed in order and
+// divided by their count.  Tags come from the scale-1 run alone.  mp_resize_bilinear_nchw makes the scaled inputs with the same
+// resize_bilinear sample, so a source pixel q sits on s * q of the scaled image and the map resize reads exactly there.
+//
 // fp contraction is OFF in this file: the resize / mean arithmetic restates MindSpore's fp32 expressions and is compared
 // bit-for-bit with a CPU restatement on dyadic inputs.
 #include "common.h"
@@ -53,6 +59,7 @@ constexpr int kBuMergeKeys = 4096;
 constexpr int kBuMergeThreads = 512;
 constexpr int kBuMaxTags = 4;
 constexpr int kBuFlipMaxJoints = 64;  // the flip form carries the joint permutation by value in its kernel parameters
+constexpr int kBuMaxRuns = 4;         // scale factors of the multi-scale test
 
 struct BuStage {
     const float* data;  // [N, C, Hs, Ws]
@@ -77,6 +84,14 @@ struct BuParseParams {
 struct BuFlip {
     const float* data[kBuMaxStages];
     int index[kBuFlipMaxJoints];  // joint k reads channel index[k] of the mirrored run; every entry validated on the host
+};
+
+// the runs of the multi-scale test, the scale-1 run (base) among them: heat-map stages only (tag_slot unused), sy / sx towards the
+// base run's map; flipped = the mirrored partners under the flip test.  By value in the kernel parameters (648 bytes).
+struct BuRuns {
+    BuStage st[kBuMaxRuns][kBuMaxStages];
+    const float* flipped[kBuMaxRuns][kBuMaxStages];
+    int num_runs, base;
 };
 
 // One pixel of a stage plane as the resize sees it.  kTapPlain: the plane itself.  kTapMean: the flip test's heat map, the mean of
@@ -130,19 +145,47 @@ __device__ __forceinline__ BuTap<TAP> stage_tap(const BuStage& s, const float* f
     return BuTap<TAP>{s.data + ((size_t)n * s.c + c) * hw, TAP == kTapPlain ? nullptr : flipped + ((size_t)n * s.c + cf) * hw, s.w};
 }
 
-// masked stage mean at (n, k, y, x), inside the map; FLIP: of the flip test's averaged heat maps, kf = the mirrored run's channel
-template <bool FLIP>
-__device__ __forceinline__ float aggregate(const BuParseParams& p, const BuFlip* fl, int n, int k, int kf, int y, int x) {
+// stage mean of one run at map pixel (y, x) of (n, k): the last stage first - read at (y, x) when it IS the map (AT_MAP: the
+// scale-1 run), else resized like the others - then the lower stages in order.  FLIP: of the flip test's averaged heat maps, kf =
+// the mirrored run's channel, flipped[i] = its stage i.
+template <bool FLIP, bool AT_MAP>
+__device__ __forceinline__ float stage_mean(const BuStage* st, const float* const* flipped, int ns, int n, int k, int kf, int y, int x) {
     constexpr int kTap = FLIP ? kTapMean : kTapPlain;
-    const BuStage& full = p.st[p.ns - 1];
-    float v = stage_tap<kTap>(full, FLIP ? fl->data[p.ns - 1] : nullptr, n, k, kf)(y, x);
-    for (int i = 0; i < p.ns - 1; ++i) {
-        const BuStage& s = p.st[i];
-        v = v + resize_bilinear(stage_tap<kTap>(s, FLIP ? fl->data[i] : nullptr, n, k, kf), s.h, s.w, s.sy, s.sx, y, x);
+    const BuStage& full = st[ns - 1];
+    const BuTap<kTap> last = stage_tap<kTap>(full, FLIP ? flipped[ns - 1] : nullptr, n, k, kf);
+    float v = AT_MAP ? last(y, x) : resize_bilinear(last, full.h, full.w, full.sy, full.sx, y, x);
+    for (int i = 0; i < ns - 1; ++i) {
+        const BuStage& s = st[i];
+        v = v + resize_bilinear(stage_tap<kTap>(s, FLIP ? flipped[i] : nullptr, n, k, kf), s.h, s.w, s.sy, s.sx, y, x);
     }
-    if (p.ns > 1) v = v / (float)p.ns;
+    if (ns > 1) v = v / (float)ns;
+    return v;
+}
+
+// v where the nearest-resized mask of image n keeps map pixel (y, x), else 0
+__device__ __forceinline__ float masked(const BuParseParams& p, float v, int n, int y, int x) {
     const int my = min((int)floorf((float)y * p.msy), p.mh - 1), mx = min((int)floorf((float)x * p.msx), p.mw - 1);
     return p.mask[((size_t)n * p.mh + my) * p.mw + mx] ? v : 0.0f;
+}
+
+// masked stage mean at (n, k, y, x), inside the map
+template <bool FLIP>
+__device__ __forceinline__ float aggregate(const BuParseParams& p, const BuFlip* fl, int n, int k, int kf, int y, int x) {
+    return masked(p, stage_mean<FLIP, true>(p.st, FLIP ? fl->data : nullptr, p.ns, n, k, kf, y, x), n, y, x);
+}
+
+// the multi-scale test: the stage means of all runs summed in run order and divided by their count, then masked.  The scale-1 run
+// (base; its stages are p.st too) is read as aggregate() reads it, so one run gives aggregate()'s value operation for operation.
+template <bool FLIP>
+__device__ __forceinline__ float aggregate_runs(const BuParseParams& p, const BuRuns& rs, int n, int k, int kf, int y, int x) {
+    float total = 0.0f;
+    for (int r = 0; r < rs.num_runs; ++r) {
+        const float v = r == rs.base ? stage_mean<FLIP, true>(rs.st[r], rs.flipped[r], p.ns, n, k, kf, y, x)
+                                     : stage_mean<FLIP, false>(rs.st[r], rs.flipped[r], p.ns, n, k, kf, y, x);
+        total = r == 0 ? v : total + v;
+    }
+    if (rs.num_runs > 1) total = total / (float)rs.num_runs;
+    return masked(p, total, n, y, x);
 }
 
 // descending bitonic sort of P keys in LDS by NT threads (P a power of two, P / 2 a multiple of NT)
@@ -167,9 +210,10 @@ __device__ __forceinline__ void bitonic_sort_desc(unsigned long long* s) {
     }
 }
 
-// the body of both parse kernels; FLIP folds the mirrored run in (fl, else unused).  tag_per_joint is set under FLIP.
-template <bool FLIP>
-__device__ __forceinline__ void bu_parse_body(const BuParseParams& p, const BuFlip* fl) {
+// the body of every parse kernel; FLIP folds the mirrored run in (fl, else unused).  tag_per_joint is set under FLIP.  MULTI: the heat
+// map is the mean over the runs rs (else unused); p and fl describe the scale-1 run, the only one whose tags are read.
+template <bool FLIP, bool MULTI>
+__device__ __forceinline__ void bu_parse_body(const BuParseParams& p, const BuFlip* fl, const BuRuns* rs) {
     __shared__ float halo[kBuHaloPix];
     __shared__ unsigned long long keys[kBuTilePix];
     const int tile = blockIdx.x, k = blockIdx.y, n = blockIdx.z;
@@ -179,7 +223,9 @@ __device__ __forceinline__ void bu_parse_body(const BuParseParams& p, const BuFl
 
     for (int i = threadIdx.x; i < hh * hw; i += kBuThreads) {
         const int y = ty0 + i / hw - r, x = tx0 + i % hw - r;
-        halo[i] = (y >= 0 && y < p.h && x >= 0 && x < p.w) ? aggregate<FLIP>(p, fl, n, k, kf, y, x) : -INFINITY;
+        float v = -INFINITY;
+        if (y >= 0 && y < p.h && x >= 0 && x < p.w) v = MULTI ? aggregate_runs<FLIP>(p, *rs, n, k, kf, y, x) : aggregate<FLIP>(p, fl, n, k, kf, y, x);
+        halo[i] = v;
     }
     __syncthreads();
 
@@ -221,9 +267,36 @@ __device__ __forceinline__ void bu_parse_body(const BuParseParams& p, const BuFl
     for (int i = threadIdx.x; i < p.m; i += kBuThreads) out[i] = keys[i];
 }
 
-__global__ __launch_bounds__(kBuThreads) void bu_parse_kernel(BuParseParams p) { bu_parse_body<false>(p, nullptr); }
+__global__ __launch_bounds__(kBuThreads) void bu_parse_kernel(BuParseParams p) { bu_parse_body<false, false>(p, nullptr, nullptr); }
 
-__global__ __launch_bounds__(kBuThreads) void bu_parse_flip_kernel(BuParseParams p, BuFlip fl) { bu_parse_body<true>(p, &fl); }
+__global__ __launch_bounds__(kBuThreads) void bu_parse_flip_kernel(BuParseParams p, BuFlip fl) {
+    bu_parse_body<true, false>(p, &fl, nullptr);
+}
+
+template <bool FLIP>
+__global__ __launch_bounds__(kBuThreads) void bu_parse_multi_kernel(BuParseParams p, BuFlip fl, BuRuns rs) {
+    bu_parse_body<FLIP, true>(p, &fl, &rs);
+}
+
+// ResizeBilinear of whole planes with the decoder's own sample: V consecutive output pixels of a row per thread, one V * 4-byte store
+template <int V>
+__global__ __launch_bounds__(256) void resize_bilinear_kernel(const float* __restrict__ in, float* __restrict__ out, size_t total,
+                                                              int ih, int iw, int oh, int ow, float sy, float sx) {
+    const unsigned per_row = (unsigned)(ow / V);
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+        const size_t row = i / per_row, plane = row / (unsigned)oh;
+        const int x = (int)(i - row * per_row) * V, y = (int)(row - plane * (unsigned)oh);
+        const BuTap<kTapPlain> tap{in + plane * ((size_t)ih * iw), nullptr, iw};
+        float v[V];
+#pragma unroll
+        for (int j = 0; j < V; ++j) v[j] = resize_bilinear(tap, ih, iw, sy, sx, y, x + j);
+        float* dst = out + row * (unsigned)ow + x;
+        if constexpr (V == 4)
+            *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
+        else
+            dst[0] = v[0];
+    }
+}
 
 struct BuGatherParams {
     const float* raw;
@@ -472,6 +545,75 @@ int mp_bottomup_parse_nms_topk_flip(const mp_bottomup_stage* stages, const mp_bo
     }
     hipLaunchKernelGGL(bu_parse_flip_kernel, dim3((unsigned)p.tiles, (unsigned)k, (unsigned)n), dim3(kBuThreads), 0, as_stream(stream),
                        p, fl);
+    return check_launch();
+}
+
+int mp_bottomup_parse_nms_topk_multi(const mp_bottomup_run* runs_host, int num_runs, int base_run, const int32_t* flip_index_host,
+                                     int num_stages, const uint8_t* mask_dev, int mask_h, int mask_w, int n, int k,
+                                     int tag_per_joint, int nms_kernel, int max_num, float* heatmap_raw_dev, float* tagging_dev,
+                                     void* workspace_dev, size_t workspace_bytes, mp_stream_t stream) {
+    if (!runs_host) return MP_ERR_NULL;
+    if (num_runs < 1 || num_runs > kBuMaxRuns || base_run < 0 || base_run >= num_runs) return MP_ERR_SHAPE;
+    const bool flip = runs_host[0].flipped != nullptr;
+    for (int r = 0; r < num_runs; ++r) {
+        if (!runs_host[r].stages) return MP_ERR_NULL;
+        if ((runs_host[r].flipped != nullptr) != flip) return MP_ERR_SHAPE;  // the flip test covers every run or none
+    }
+    if (flip != (flip_index_host != nullptr)) return MP_ERR_NULL;
+    BuFlip fl{};
+    if (flip) {
+        if (k <= 0) return MP_ERR_SHAPE;
+        if (!tag_per_joint || k > kBuFlipMaxJoints) return MP_ERR_UNSUPPORTED;
+        for (int j = 0; j < k; ++j) {  // the kernel indexes the mirrored stages with these: none may leave [0, k)
+            if (flip_index_host[j] < 0 || flip_index_host[j] >= k) return MP_ERR_SHAPE;
+            fl.index[j] = flip_index_host[j];
+        }
+    }
+    const mp_bottomup_stage* base = runs_host[base_run].stages;
+    BuParseParams p{};
+    const int rc = bu_parse_params(base, num_stages, mask_dev, mask_h, mask_w, n, k, tag_per_joint, nms_kernel, max_num,
+                                   heatmap_raw_dev, tagging_dev, workspace_dev, workspace_bytes, flip ? 2 : 1, p);
+    if (rc != MP_OK) return rc;
+    BuRuns rs{};
+    rs.num_runs = num_runs;
+    rs.base = base_run;
+    for (int r = 0; r < num_runs; ++r)
+        for (int i = 0; i < num_stages; ++i) {
+            const mp_bottomup_stage& s = runs_host[r].stages[i];
+            if (!s.data_dev) return MP_ERR_NULL;
+            if (s.h <= 0 || s.w <= 0 || (size_t)s.h * s.w > 0x7fffffffu) return MP_ERR_SHAPE;
+            if (s.c != base[i].c || (s.has_tags != 0) != (base[i].has_tags != 0)) return MP_ERR_SHAPE;
+            rs.st[r][i] = BuStage{s.data_dev, s.c, s.h, s.w, -1, (float)s.h / (float)p.h, (float)s.w / (float)p.w};
+            if (!flip) continue;
+            const mp_bottomup_stage& f = runs_host[r].flipped[i];
+            if (!f.data_dev) return MP_ERR_NULL;
+            if (f.c != s.c || f.h != s.h || f.w != s.w || (f.has_tags != 0) != (s.has_tags != 0)) return MP_ERR_SHAPE;
+            rs.flipped[r][i] = f.data_dev;
+            if (r == base_run) fl.data[i] = f.data_dev;
+        }
+    const dim3 grid((unsigned)p.tiles, (unsigned)k, (unsigned)n);
+    if (flip)
+        hipLaunchKernelGGL(bu_parse_multi_kernel<true>, grid, dim3(kBuThreads), 0, as_stream(stream), p, fl, rs);
+    else
+        hipLaunchKernelGGL(bu_parse_multi_kernel<false>, grid, dim3(kBuThreads), 0, as_stream(stream), p, fl, rs);
+    return check_launch();
+}
+
+int mp_resize_bilinear_nchw(const float* in_dev, float* out_dev, int planes, int ih, int iw, int oh, int ow, mp_stream_t stream) {
+    if (!in_dev || !out_dev) return MP_ERR_NULL;
+    if (planes <= 0 || ih <= 0 || iw <= 0 || oh <= 0 || ow <= 0) return MP_ERR_SHAPE;
+    if ((size_t)ih * iw > 0x7fffffffu || (size_t)oh * ow > 0x7fffffffu) return MP_ERR_SHAPE;
+    const float sy = (float)ih / (float)oh, sx = (float)iw / (float)ow;
+    const bool wide = ow % 4 == 0 && (uintptr_t)out_dev % 16 == 0;
+    const size_t total = (size_t)planes * oh * (wide ? ow / 4 : ow);
+    size_t blocks = (total + 255) / 256;
+    if (blocks > 16384) blocks = 16384;
+    if (wide)
+        hipLaunchKernelGGL(resize_bilinear_kernel<4>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), in_dev, out_dev, total, ih,
+                           iw, oh, ow, sy, sx);
+    else
+        hipLaunchKernelGGL(resize_bilinear_kernel<1>, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), in_dev, out_dev, total, ih,
+                           iw, oh, ow, sy, sx);
     return check_launch();
 }
 

@@ -11,9 +11,13 @@ m-th smallest selected flat index, not of its own pixel.  The drop-in contract i
 
 ``decode_flip_aggregated`` is the flip test (the reference's ``_MultiRunNet``, engine/inferencer/bottomup_inferencer.py:252-297):
 the same two launches, the first reading the mirrored run's outputs beside the plain ones (``mp_bottomup_parse_nms_topk_flip``).
+
+``decode_multi_scale`` is the multi-scale test (this project's protocol; the reference ships none): the same two
+launches again, the first averaging the heat maps of up to four runs at different input scales
+(``mp_bottomup_parse_nms_topk_multi``); ``resize_bilinear`` makes the scaled inputs with the decoder's own resize.
 """
 import ctypes
-from typing import List, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -26,6 +30,31 @@ _MAX_NUM_LIMIT = 64  # csrc/bottomup_ops.hip kBuMaxM
 _MAX_LOWER_STAGES = 3
 _FLIP_MAX_JOINTS = 64  # csrc/bottomup_ops.hip kBuFlipMaxJoints
 _MAX_TAGS = 4  # csrc/bottomup_ops.hip kBuMaxTags
+_MAX_RUNS = 4  # csrc/bottomup_ops.hip kBuMaxRuns
+
+
+def resize_bilinear(x: torch.Tensor, size: Sequence[int], out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``ops.ResizeBilinear(size)`` with ``align_corners=False, half_pixel_centers=False`` of a CUDA fp32 [N, C, H, W] tensor, one
+    launch (``mp_resize_bilinear_nchw``): ``src = dst * (in / out)`` and the fp32 lerp of the decoder's stage resize, not
+    ``F.interpolate``, whose ``align_corners=False`` uses half-pixel centres.  ``out``: a contiguous CUDA fp32 [N, C, oh, ow] tensor
+    to write into (a plan's ``input_buffer``), which must not overlap ``x``."""
+    x = _lib.require_cuda_f32(x, "x")
+    if x.dim() != 4:
+        raise ValueError(f"x must be [N, C, H, W], got {tuple(x.shape)}")
+    oh, ow = (int(v) for v in size)
+    n, c, h, w = x.shape
+    if oh <= 0 or ow <= 0 or n * c == 0 or h * w == 0:
+        raise ValueError(f"cannot resize {tuple(x.shape)} to {(oh, ow)}")
+    if out is None:
+        out = torch.empty(n, c, oh, ow, device=x.device, dtype=torch.float32)
+    elif not torch.is_tensor(out) or out.dtype != torch.float32 or out.device != x.device or tuple(out.shape) != (n, c, oh, ow) \
+            or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous fp32 tensor of shape {(n, c, oh, ow)} on {x.device}")
+    elif out.data_ptr() == x.data_ptr():
+        raise ValueError("out must not be x")
+    _lib.check(_lib.load().mp_resize_bilinear_nchw(_lib.ptr(x), _lib.ptr(out), n * c, h, w, oh, ow, _lib.stream()),
+               "mp_resize_bilinear_nchw")
+    return out
 
 
 @register("decoder", extra_name="bottomup_heatmap_ae")
@@ -109,6 +138,45 @@ class BottomUpHeatMapAEDecoder(Decoder):
                 raise ValueError(f"stage {i} of the mirrored run is {tuple(b.shape)}, of the plain run {tuple(a.shape)}")
         return self._launch(stages, mask, flipped, index)
 
+    def decode_multi_scale(self, runs: Sequence[Sequence[torch.Tensor]], mask: torch.Tensor, base: int,
+                           flipped_runs: Optional[Sequence[Sequence[torch.Tensor]]] = None,
+                           flip_index: Optional[Sequence[int]] = None) -> Tuple[torch.Tensor, ...]:
+        """The multi-scale test's aggregation and decode in the decoder's two launches.  ``runs[r]`` are the raw stage outputs of
+        the network on the batch resized by scale factor r (``resize_bilinear``), ``runs[base]`` those of the batch itself;
+        ``flipped_runs[r]`` / ``flip_index`` add the flip test, run by run, as ``decode_flip_aggregated`` defines it.  Returns
+        ``decode``'s five tensors at the map size of ``runs[base]``.
+
+        With t_{r,i} stage i of run r at stage resolution (under the flip test the mean with the mirrored run,
+        ``(A + B[f][..., ::-1]) * 0.5``) and R the ``ops.ResizeBilinear`` to the base map (no half-pixel centres; the direct read for
+        the base run's last stage)::
+
+            v_r   = R(t_{r,last});  v_r = v_r + R(t_{r,i}) for i = 0 .. num_stages - 2;  v_r = v_r / num_stages  (more than one stage)
+            total = v_0 + v_1 + ...  in list order;  total = total / len(runs)  (more than one run)
+
+        ``total`` is masked and decoded as ``decode`` does its stage mean.  The tags are the base run's alone - L slots, 2L under
+        the flip test, the plain ones first - and the tag channels of the other runs are never read.  One run is ``decode`` (or
+        ``decode_flip_aggregated``) operation for operation.  A stage of another run may be smaller or larger than the map."""
+        if not 1 <= len(runs) <= _MAX_RUNS:
+            raise ValueError(f"the multi-scale test takes 1 to {_MAX_RUNS} runs, got {len(runs)}")
+        if not isinstance(base, int) or not 0 <= base < len(runs):
+            raise ValueError(f"base must index one of the {len(runs)} runs, got {base!r}")
+        if (flipped_runs is None) != (flip_index is None):
+            raise ValueError("flipped_runs and flip_index go together")
+        index = None if flip_index is None else self.check_flip_index(flip_index)
+        if flipped_runs is not None and len(flipped_runs) != len(runs):
+            raise ValueError(f"{len(flipped_runs)} mirrored runs beside {len(runs)} runs")
+        plain = [self._stages(*self.decouple_output(o)) for o in runs]
+        mirrored = None if flipped_runs is None else [self._stages(*self.decouple_output(o)) for o in flipped_runs]
+        dev, n = plain[base][-1][0].device, plain[base][-1][0].shape[0]
+        for r, stages in enumerate(plain):
+            for i, (a, _) in enumerate(stages):
+                if a.shape[0] != n or a.device != dev:
+                    raise ValueError(f"stage {i} of run {r} is {tuple(a.shape)} on {a.device}, the base run has batch {n} on {dev}")
+                if mirrored is not None and (mirrored[r][i][0].shape != a.shape or mirrored[r][i][0].device != dev):
+                    raise ValueError(f"stage {i} of mirrored run {r} is {tuple(mirrored[r][i][0].shape)}, of the plain run "
+                                     f"{tuple(a.shape)}")
+        return self._launch(plain[base], mask, None if mirrored is None else mirrored[base], index, runs=(plain, mirrored, base))
+
     def check_flip_index(self, flip_index) -> np.ndarray:
         """``flip_index`` as int32 [num_joints], after the checks of the flip test: ``ValueError`` unless it is a permutation of
         ``range(num_joints)`` and the decoder has one tag channel per joint, two tag slots per tag stage and a joint count the
@@ -125,8 +193,10 @@ class BottomUpHeatMapAEDecoder(Decoder):
             raise ValueError(f"flip TTA doubles the tags: at most {_MAX_TAGS // 2} stages may carry them")
         return np.ascontiguousarray(index, dtype=np.int32)
 
-    def _launch(self, stages, mask, flipped=None, flip_index=None):
-        """The two launches on ``stages`` (``_stages``); with ``flipped`` / ``flip_index`` the first one is the flip form."""
+    def _launch(self, stages, mask, flipped=None, flip_index=None, runs=None):
+        """The two launches on ``stages`` (``_stages``); with ``flipped`` / ``flip_index`` the first one is the flip form.  ``runs`` =
+        (the ``_stages`` of every run, those of their mirrored partners or None, the base run's position) makes it the multi-scale
+        form, ``stages`` / ``flipped`` being the base run's."""
         full = stages[-1][0]
         dev = full.device
         n, k, h, w = full.shape[0], self.num_joints, full.shape[2], full.shape[3]
@@ -160,10 +230,15 @@ class BottomUpHeatMapAEDecoder(Decoder):
         nms = self.nms_kernel if self.use_nms else 1
         tail = (len(stages), _lib.ptr(mask), mask.shape[1], mask.shape[2], n, k, int(self.tag_per_joint), nms, m,
                 _lib.ptr(heatmap_raw), _lib.ptr(tagging), _lib.ptr(ws), ws_bytes, stream)
-        if flipped is None:
+        index = None if flip_index is None else flip_index.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+        if runs is not None:
+            plain, mirrored, base = runs
+            arrays = [(describe(p), None if mirrored is None else describe(mirrored[r])) for r, p in enumerate(plain)]  # kept alive
+            table = (_lib.BottomUpRun * len(arrays))(*[_lib.BottomUpRun(stages=a, flipped=b) for a, b in arrays])
+            _lib.check(lib.mp_bottomup_parse_nms_topk_multi(table, len(arrays), base, index, *tail), "mp_bottomup_parse_nms_topk_multi")
+        elif flipped is None:
             _lib.check(lib.mp_bottomup_parse_nms_topk(describe(stages), *tail), "mp_bottomup_parse_nms_topk")
         else:
-            index = flip_index.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
             _lib.check(lib.mp_bottomup_parse_nms_topk_flip(describe(stages), describe(flipped), index, *tail),
                        "mp_bottomup_parse_nms_topk_flip")
         _lib.check(lib.mp_bottomup_gather(_lib.ptr(heatmap_raw), _lib.ptr(tagging), _lib.ptr(ws), ws_bytes, n, k, h, w,

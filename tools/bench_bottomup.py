@@ -30,6 +30,16 @@
   downloads and the per-image copies), wall milliseconds per batch in alternated rounds (median and min - max), the persons found,
   and the ``mp_bottomup_match_by_tag`` launch alone on prepared buffers in device microseconds.  Both paths are compared bit for
   bit first.
+- multi_scale: the multi-scale test at base 512 x 832, N = 1, scale factors (0.5, 1, 2), NMS 3, max_num 30, without and with the flip
+  test.  The ONE ``mp_bottomup_parse_nms_topk_multi`` launch on prepared arguments against the same aggregation composed in the same
+  run from what existed before it: one single-run parse launch per scale (each run's stage mean at its own map size), torch ops on
+  their ``heatmap_raw`` (``F.interpolate`` of the other scales' maps to the base map, the sum, the division) and one more parse
+  launch over the averaged map for the NMS and the per-tile top-k; alternated rounds of device-event timings (median, min - max).
+  The composition resizes in two steps and with half-pixel centres, so its bits differ: it stands for the work, not the values.
+  Fraction of 8 TB/s of the fused launch on its algorithmic bytes (every heat-map plane of every run read once, the base run's tag
+  planes once, ``heatmap_raw`` and ``tagging`` written).  ``mp_resize_bilinear_nchw`` of the input to the two other scales in device
+  microseconds.  Then one forward per scale 0.5 / 1 / 1.5 / 2 of both recipe sizes in fp32 and amp O2 (``MINDPOSE_AUTOTUNE`` as the
+  environment sets it, reported); a scale whose plan cannot be recorded reports the plan's own error instead of a time.
 Forward sizes are the recipe's eval images: 512 x 512 (N = 1 and 32) and 512 x 832 (N = 1).
 
 ``--only NAME`` runs one section in this process; without it every section runs in a child process of its own under a time limit
@@ -340,6 +350,100 @@ def match(steps, rounds=5, k=17, m=30, num_tags=1):
     return out
 
 
+def multi_scale(steps, rounds=5):
+    import torch.nn.functional as F
+    from mindpose_amd.models.decoders import resize_bilinear
+    lib = _lib.load()
+    n, k, m, bh, bw, scales, base = 1, 17, 30, 512, 832, (0.5, 1.0, 2.0), 1
+    h, w = bh // 2, bw // 2
+    g = torch.Generator().manual_seed(0)
+
+    def run_outputs(s):
+        hs, ws_ = int(bh * s), int(bw * s)
+        return [torch.rand(n, 2 * k, hs // 4, ws_ // 4, generator=g).to(DEV), torch.rand(n, k, hs // 2, ws_ // 2, generator=g).to(DEV)]
+
+    def describe(run):
+        return (_lib.BottomUpStage * 2)(*[_lib.BottomUpStage(data=t.data_ptr(), c=t.shape[1], h=t.shape[2], w=t.shape[3], has_tags=int(i == 0))
+                                          for i, t in enumerate(run)])
+
+    plain, mirrored = [run_outputs(s) for s in scales], [run_outputs(s) for s in scales]
+    pd, md = [describe(r) for r in plain], [describe(r) for r in mirrored]
+    index = (ctypes.c_int32 * k)(0, 2, 1, 4, 3, 6, 5, 8, 7, 10, 9, 12, 11, 14, 13, 16, 15)
+    mask = torch.ones(n, bh, bw, dtype=torch.uint8, device=DEV)
+    raw, tagging = torch.empty(n, k, h, w, device=DEV), torch.empty(n, k, h, w, 2, device=DEV)
+    ws_bytes = lib.mp_bottomup_workspace_bytes(n, k, h, w, m)
+    ws = torch.empty(ws_bytes // 8, device=DEV, dtype=torch.int64)
+    # the composition's buffers: every run's own map, its own workspace and tags; the averaged map beside unused tag channels
+    own = []
+    for r, s in enumerate(scales):
+        hs, ws_ = plain[r][1].shape[2:]
+        nb = lib.mp_bottomup_workspace_bytes(n, k, hs, ws_, m)
+        own.append(dict(raw=torch.empty(n, k, hs, ws_, device=DEV), tagging=torch.empty(n, k, hs, ws_, 2, device=DEV),
+                        ws=torch.empty(nb // 8, device=DEV, dtype=torch.int64), ws_bytes=nb, h=hs, w=ws_))
+    averaged = torch.zeros(n, 2 * k, h, w, device=DEV)
+    averaged_desc = describe([averaged])
+
+    def tail(raw_t, tagging_t, ws_t, nbytes, stages=2):
+        return (stages, _lib.ptr(mask), bh, bw, n, k, 1, 3, m, _lib.ptr(raw_t), _lib.ptr(tagging_t), _lib.ptr(ws_t), nbytes, _lib.stream())
+
+    def fused(flip):
+        table = (_lib.BottomUpRun * len(scales))(*[_lib.BottomUpRun(stages=a, flipped=b if flip else None) for a, b in zip(pd, md)])
+        args = (table, len(scales), base, index if flip else None) + tail(raw, tagging, ws, ws_bytes)
+        return lambda: _lib.check(lib.mp_bottomup_parse_nms_topk_multi(*args), "mp_bottomup_parse_nms_topk_multi")
+
+    def composed(flip):
+        def fn():
+            for r, o in enumerate(own):
+                t = tail(o["raw"], o["tagging"], o["ws"], o["ws_bytes"])
+                if flip:
+                    _lib.check(lib.mp_bottomup_parse_nms_topk_flip(pd[r], md[r], index, *t), "mp_bottomup_parse_nms_topk_flip")
+                else:
+                    _lib.check(lib.mp_bottomup_parse_nms_topk(pd[r], *t), "mp_bottomup_parse_nms_topk")
+            total = own[0]["raw"] if base == 0 else F.interpolate(own[0]["raw"], size=(h, w), mode="bilinear", align_corners=False)
+            for r in range(1, len(own)):
+                total = total + (own[r]["raw"] if r == base else F.interpolate(own[r]["raw"], size=(h, w), mode="bilinear", align_corners=False))
+            averaged[:, :k] = total / len(own)
+            _lib.check(lib.mp_bottomup_parse_nms_topk(averaged_desc, *tail(raw, own[base]["tagging"], ws, ws_bytes, stages=1)),
+                       "mp_bottomup_parse_nms_topk")
+        return fn
+
+    res = dict(base=[bh, bw], scales=list(scales), map=[h, w], autotune=os.environ.get("MINDPOSE_AUTOTUNE", "1"), parse_launch_us={})
+    heat = 4 * n * k * sum(t.shape[2] * t.shape[3] for r in plain for t in r)
+    tags = 4 * n * k * plain[base][0].shape[2] * plain[base][0].shape[3]
+    for flip in (False, True):
+        f, c = fused(flip), composed(flip)
+        times = dict(fused=[], composed=[])
+        for _ in range(rounds):  # alternated: a drift of the machine meets both alike
+            times["fused"].append(_time(f, steps) * 1000)
+            times["composed"].append(_time(c, steps) * 1000)
+        nbytes = (2 if flip else 1) * (heat + tags) + 4 * n * k * h * w * (3 if flip else 2)
+        fu, co = _spread(times["fused"]), _spread(times["composed"])
+        res["parse_launch_us"]["flip" if flip else "plain"] = dict(
+            fused=fu, composed=co, ratio=round(co["median"] / fu["median"], 2), mb=round(nbytes / 1e6, 2),
+            hbm_fraction=round(nbytes / (fu["median"] * 1e-6) / HBM, 4))
+
+    image = torch.randn(n, 3, bh, bw, generator=g).to(DEV)
+    res["resize_input_us"] = {}
+    for s in scales:
+        if s != 1.0:
+            out = torch.empty(n, 3, int(bh * s), int(bw * s), device=DEV)
+            res["resize_input_us"][str(s)] = round(_time(lambda: resize_bilinear(image, out.shape[2:], out=out), steps) * 1000, 2)
+
+    res["forward"] = []
+    for fh, fw in ((512, 512), (512, 832)):
+        for amp in ("O0", "O2"):
+            for s in (0.5, 1.0, 1.5, 2.0):
+                try:
+                    res["forward"].append(dict(forward(amp, n, int(fh * s), int(fw * s), max(3, steps // 4)), base=[fh, fw], scale=s))
+                except Exception as e:  # the plan's own error is the answer for this scale; a failed launch or HIP call ends the run
+                    if "hipError" in str(e) or "HIP error" in str(e):
+                        raise
+                    res["forward"].append(dict(amp=amp, n=n, h=int(fh * s), w=int(fw * s), base=[fh, fw], scale=s,
+                                               error=f"{type(e).__name__}: {str(e)[:200]}"))
+                torch.cuda.empty_cache()
+    return res
+
+
 SECTIONS = {
     "forward": lambda steps: [forward(a, n, h, w, steps) for a in ("O0", "O2") for n, h, w in ((1, 512, 512), (32, 512, 512), (1, 512, 832))],
     "decoder": lambda steps: [decoder(1, 256, 416, steps), decoder(32, 256, 256, steps)],
@@ -348,6 +452,7 @@ SECTIONS = {
     "train_augment": train_augment,
     "flip_tta": flip_tta,
     "match": match,
+    "multi_scale": multi_scale,
 }
 
 
