@@ -554,6 +554,44 @@ int mp_bottomup_train_augment(const uint8_t* src_dev, const long long* src_offse
                               int out_h, int out_w, int hmax, int wmax, const float mean[3], const float stddev[3],
                               mp_stream_t stream);
 
+/* mp_bottomup_train_augment with one source mask plane PER STAGE (the training mask under `expand_mask: True`, whose planes differ
+ * by the erosion radius): stage i of image j reads the [H, W] plane at mask_src + mask_offsets[j] + i * mask_stage_stride[j].
+ *   mask_stage_stride  [n] int64 (device), bytes; 0 for an image whose single plane serves every stage.  NULL = all zero, which
+ *                      IS mp_bottomup_train_augment (that entry calls this one with NULL: same kernel, same bits).
+ * Everything else, the validation included, as mp_bottomup_train_augment. */
+int mp_bottomup_train_augment_stages(const uint8_t* src_dev, const long long* src_offsets_dev, const int* src_hw_dev,
+                                     const uint8_t* mask_src_dev, const long long* mask_offsets_dev,
+                                     const long long* mask_stage_stride_dev, const double* trans_dev, const int* flip_dev,
+                                     const int* stage_wh_host, float* image_dev, uint8_t* mask_dev, int n, int s, int out_h, int out_w,
+                                     int hmax, int wmax, const float mean[3], const float stddev[3], mp_stream_t stream);
+
+/* Bottom-up training masks of a batch, rasterised and eroded on the device (mindpose/data/dataset/coco_bottomup.py:146-189
+ * _get_encoded_mask, there a start-up pass over the whole training set through pycocotools and cv2.erode).  TWO launches per batch.
+ * A region is one COCO run-length encoding: counts alternate zeros / ones starting with zeros over the column-major pixel index
+ * x * H + y and sum to H * W.  A pixel is invalid when any region of its image covers it; stage i of the uint8 [s, H, W] result is 1
+ * where no invalid pixel lies under the disc of radius radii[i] centred on the pixel (pixels outside the image count as valid:
+ * cv2.erode's default border).  The disc arrives as per-row half widths, so its raster is the caller's definition.
+ *   prefix        uint32 [T]: the INCLUSIVE prefix sums of every region's counts, regions back to back (the last of a region = H * W)
+ *   region_ptr    int32 [R + 1]: region r owns prefix[region_ptr[r] .. region_ptr[r + 1])
+ *   image_tab     int32 [n][4]: (H, W, first region, number of regions) - 0 regions: the image's planes are all ones
+ *   offsets       int64 [n][2]: byte offset of the image's [s, H, W] block in out, of its [H, W] row-clearance plane in workspace
+ *                 (an image without regions has no clearance plane: its second offset is not looked at)
+ *   the four tables are given twice, a HOST copy (validated here, before any HIP call) and the DEVICE copy the kernels read
+ *   radii_host    int32 [s], half_widths_host uint8 [s][128]: half_widths[i][d] is the half width of disc i's row at distance d from
+ *                 its centre row, 0 <= d <= radii[i] (the table is symmetric in the sign of d); both travel in the kernel arguments
+ *   out / workspace  uint8 device buffers of out_bytes / workspace_bytes; workspace holds clear(y, x) = min(255, distance to the
+ *                 nearest invalid pixel of row y), stage i is valid iff clear(y + d, x) > half_widths[i][|d|] for every in-image row
+ * Launch 1 finds, per pixel and region, the parity of the run that holds x * H + y by binary search (a gather: no scatter, no
+ * memset, no atomics) and writes the clearance of the row; launch 2 writes every byte of every stage once.  Integer throughout.
+ * Validation: NULL -> MP_ERR_NULL; s outside 1..8 or a radius outside 0..127 -> MP_ERR_UNSUPPORTED; n outside 1..65535, an extent
+ * outside 1..16384, a region table that is not ascending, a region whose counts do not sum to H * W, or a block that leaves out /
+ * workspace -> MP_ERR_SHAPE. */
+int mp_bottomup_train_masks(const uint32_t* prefix_host, const int* region_ptr_host, const int* image_tab_host,
+                            const long long* offsets_host, const uint32_t* prefix_dev, const int* region_ptr_dev,
+                            const int* image_tab_dev, const long long* offsets_dev, const int* radii_host,
+                            const uint8_t* half_widths_host, uint8_t* out_dev, size_t out_bytes, uint8_t* workspace_dev,
+                            size_t workspace_bytes, int n, int s, mp_stream_t stream);
+
 /* ---- bottom-up (associative-embedding) decoder, BottomUpHeatMapAEDecoder -------------------------------------------------
  * Replaces mindpose/models/decoders/bottom_up_decoder.py:81-203 (the ~10 MindSpore ops of decode()) with two launches.
  * stages[0 .. num_stages-1]: the model outputs in the reference's order, stages[num_stages-1] the full-resolution one (its h, w

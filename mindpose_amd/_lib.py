@@ -215,6 +215,13 @@ _PROTOTYPES = {
                                 + [ctypes.POINTER(ctypes.c_float)] * 2 + [ctypes.c_void_p]),
     "mp_bottomup_train_augment": (c_int, [c_f32p] * 7 + [ctypes.POINTER(ctypes.c_int)] + [c_f32p] * 2 + [c_int] * 6
                                   + [ctypes.POINTER(ctypes.c_float)] * 2 + [ctypes.c_void_p]),
+    "mp_bottomup_train_augment_stages": (c_int, [c_f32p] * 8 + [ctypes.POINTER(ctypes.c_int)] + [c_f32p] * 2 + [c_int] * 6
+                                         + [ctypes.POINTER(ctypes.c_float)] * 2 + [ctypes.c_void_p]),
+    # bottom-up training masks (bottomup_mask_ops.hip): four host tables, their device copies, radii and disc half widths (host)
+    "mp_bottomup_train_masks": (c_int, [ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
+                                        ctypes.POINTER(ctypes.c_longlong)] + [c_f32p] * 4
+                                + [ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_uint8), c_f32p, c_size_t, c_f32p, c_size_t,
+                                   c_int, c_int, ctypes.c_void_p]),
     # bottom-up training ends (bottomup_train_ops.hip): strided masked MSE, AE loss, batched target generation
     "mp_joints_mse_mask_workspace_bytes": (c_size_t, [c_int, c_int]),
     "mp_joints_mse_mask_fwd": (c_int, [c_f32p] + [c_i64] * 3 + [c_f32p] + [c_i64] * 3 + [c_f32p, c_int] + [c_i64] * 2

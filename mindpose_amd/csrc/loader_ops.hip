@@ -308,7 +308,8 @@ extern "C" int mp_resize_pad_normalize(const uint8_t* src, const long long* src_
 // matrix is formed once per workgroup and the plane kind never diverges inside a wave.
 //   image: sample_linear + normalize_store, i.e. mp_warp_affine's planes to the bit
 //   mask:  cv2.warpAffine(mask, M, (W_i, H_i), flags=INTER_NEAREST), written into the [:H_i, :W_i] corner of the stage's
-//          [hmax, wmax] plane, 0 in the padding.
+//          [hmax, wmax] plane, 0 in the padding.  The source plane of stage i is the image's one [H, W] mask, or - with a per-image
+//          stage stride (mp_bottomup_train_augment_stages) - plane i of its [S, H, W] mask.
 // The flip follows the warp (the reference's order): the value computed for column x is stored at column W - 1 - x.  It cannot be
 // folded into the matrix bit-exactly, because the fixed-point column terms are rounded per destination column - so the thread that
 // stores columns [4g, 4g + 4) computes the mirrored columns and the 16-byte vector leaves in reversed order.  (warp_affine_kernel's
@@ -325,6 +326,7 @@ struct AugParams {
     const int* src_hw;
     const uint8_t* msrc;
     const long long* msrc_off;
+    const long long* msrc_stage;  // NULL, or per image the byte stride from one stage's source plane to the next
     const double* trans;  // [n, s + 1, 6]: stages first, the image last
     const int* flip;
     float* image;   // [n, 3, out_h, out_w]
@@ -399,16 +401,17 @@ __global__ __launch_bounds__(256) void bottomup_train_augment_kernel(AugParams p
     const bool mirror = p.flip && p.flip[n] != 0;
     const int g = tile * 256 + threadIdx.x;
     if (is_image) augment_image_group<VI>(p, inv, p.src + p.src_off[n], H, W, mirror, n, g);
-    else augment_mask_group<VM>(p, inv, p.msrc + p.msrc_off[n], H, W, mirror, n, stage, g);
+    else augment_mask_group<VM>(p, inv, p.msrc + p.msrc_off[n] + (p.msrc_stage ? p.msrc_stage[n] * stage : 0), H, W, mirror, n, stage, g);
 }
 
 }  // namespace
 }  // namespace mp
 
-extern "C" int mp_bottomup_train_augment(const uint8_t* src, const long long* src_offsets, const int* src_hw, const uint8_t* mask_src,
-                                         const long long* mask_offsets, const double* trans, const int* flip, const int* stage_wh_host,
-                                         float* image, uint8_t* mask, int n, int s, int out_h, int out_w, int hmax, int wmax,
-                                         const float mean[3], const float stddev[3], mp_stream_t stream) {
+extern "C" int mp_bottomup_train_augment_stages(const uint8_t* src, const long long* src_offsets, const int* src_hw, const uint8_t* mask_src,
+                                                const long long* mask_offsets, const long long* mask_stage_stride, const double* trans,
+                                                const int* flip, const int* stage_wh_host, float* image, uint8_t* mask, int n, int s,
+                                                int out_h, int out_w, int hmax, int wmax, const float mean[3], const float stddev[3],
+                                                mp_stream_t stream) {
     if (!src || !src_offsets || !src_hw || !mask_src || !mask_offsets || !trans || !stage_wh_host || !image || !mask || !mean || !stddev)
         return MP_ERR_NULL;
     if (s < 1 || s > mp::kAugMaxStages) return MP_ERR_UNSUPPORTED;
@@ -423,7 +426,7 @@ extern "C" int mp_bottomup_train_augment(const uint8_t* src, const long long* sr
     if ((long long)out_h * out_w > (1LL << 30) || (long long)hmax * wmax > (1LL << 30)) return MP_ERR_SHAPE;  // group indices are int
     const bool wide_i = mp::wide_stores(out_w, image, 4), wide_m = mp::wide_stores(wmax, mask, 1);
     p.src = src; p.src_off = src_offsets; p.src_hw = src_hw;
-    p.msrc = mask_src; p.msrc_off = mask_offsets;
+    p.msrc = mask_src; p.msrc_off = mask_offsets; p.msrc_stage = mask_stage_stride;
     p.trans = trans; p.flip = flip;
     p.image = image; p.mask = mask;
     p.s = s; p.out_h = out_h; p.out_w = out_w; p.hmax = hmax; p.wmax = wmax;
@@ -436,4 +439,13 @@ extern "C" int mp_bottomup_train_augment(const uint8_t* src, const long long* sr
                                : (wide_m ? mp::bottomup_train_augment_kernel<1, 4> : mp::bottomup_train_augment_kernel<1, 1>);
     hipLaunchKernelGGL(kernel, dim3((unsigned)tiles, (unsigned)n), dim3(256), 0, mp::as_stream(stream), p);
     return mp::check_launch();
+}
+
+// one source mask plane per image, tiled over the stages: the stride-0 case
+extern "C" int mp_bottomup_train_augment(const uint8_t* src, const long long* src_offsets, const int* src_hw, const uint8_t* mask_src,
+                                         const long long* mask_offsets, const double* trans, const int* flip, const int* stage_wh_host,
+                                         float* image, uint8_t* mask, int n, int s, int out_h, int out_w, int hmax, int wmax,
+                                         const float mean[3], const float stddev[3], mp_stream_t stream) {
+    return mp_bottomup_train_augment_stages(src, src_offsets, src_hw, mask_src, mask_offsets, nullptr, trans, flip, stage_wh_host, image, mask,
+                                            n, s, out_h, out_w, hmax, wmax, mean, stddev, stream);
 }

@@ -18,8 +18,9 @@ forms: ``transform`` is the host path - the reference's random draws through the
 key-point arithmetic, the mask through ``warp_affine_nearest_u8`` (``cv2.warpAffine(..., INTER_NEAREST)`` restated [cv2-knowledge],
 parity with cv2 itself unpinned) - and ``bottomup_augment_batch`` draws per image exactly as the two ``transform`` s would, computes
 the key points on the host with the same functions and does the pixel work of the batch - the image warp, every stage's mask warp,
-the flip, Normalize and HWC2CHW - in ONE ``mp_bottomup_train_augment`` launch.  Its result is what ``generate_batch`` and
-``AEMultiLoss`` take.  No pipeline runs in train mode yet.
+the flip, Normalize and HWC2CHW - in ONE ``mp_bottomup_train_augment`` launch (``mp_bottomup_train_augment_stages`` when a mask
+comes as [S, H, W], one source plane per stage, as ``bottomup_masks_batch`` of bottomup_mask.py makes them).  Its result is what
+``generate_batch`` and ``AEMultiLoss`` take.  No pipeline runs in train mode yet.
 """
 import ctypes
 from typing import Any, Dict, List, Optional, Sequence, Tuple
@@ -409,8 +410,9 @@ def bottomup_augment_batch(affine: BottomUpRandomAffine, flip: Optional[BottomUp
                            normalize_std=NORMALIZE_STD, out: Optional[torch.Tensor] = None) -> Dict[str, Any]:
     """The two augmentations, Normalize and HWC2CHW for a batch: the device path.
 
-    ``images[i]`` is a contiguous CUDA uint8 [H, W, 3] tensor, ``masks[i]`` the contiguous CUDA uint8 [H, W] mask of the same image
-    (the plane the reference dataset tiles over the stages), ``keypoints[i]`` a host float32 [M_i, K, 3] array in source pixels.
+    ``images[i]`` is a contiguous CUDA uint8 [H, W, 3] tensor, ``masks[i]`` the contiguous CUDA uint8 mask of the same image -
+    [H, W], one plane tiled over the stages (the reference dataset without ``expand_mask``), or [S, H, W], one plane per stage (what
+    ``bottomup_masks_batch`` returns; stage i is warped from plane i) -, ``keypoints[i]`` a host float32 [M_i, K, 3] array in source pixels.
     Per image, in batch order, ``affine.draw`` and then ``flip.draw()`` consume the global ``np.random`` exactly as the two
     ``transform`` s run sample by sample would; the S stage key-point sets come from the very functions ``transform`` uses, padded
     to M = max(M_i); matrices and flags are uploaded and ONE ``mp_bottomup_train_augment`` launch does the pixel work.
@@ -421,14 +423,17 @@ def bottomup_augment_batch(affine: BottomUpRandomAffine, flip: Optional[BottomUp
     n = len(images)
     if n == 0 or len(masks) != n or len(keypoints) != n:
         raise ValueError("one mask and one key-point array per image, at least one image")
-    base, offs, hw, dev = source_batch(images, layout_error=ValueError)
-    mbase, moffs, _, _ = source_batch(masks, pixel=(), layout_error=ValueError)
-    if any(tuple(mk.shape) != tuple(im.shape[:2]) for im, mk in zip(images, masks)):
-        raise ValueError("every mask must be a contiguous uint8 [H, W] tensor of its image's size")
-    lib = _lib.load()
     cfg = affine._transform_cfg
     sizes = np.asarray(cfg["heatmap_sizes"]).reshape(-1, 2)
     s = len(sizes)
+    base, offs, hw, dev = source_batch(images, layout_error=ValueError)
+    # [S, H, W]: S planes of H * W bytes, back to back (a 3-d tensor that is not contiguous stays 3-d and is refused as a layout)
+    per_stage = [torch.is_tensor(mk) and mk.dim() == 3 and mk.is_contiguous() for mk in masks]
+    mbase, moffs, _, _ = source_batch([mk.view(-1, mk.shape[2]) if st else mk for mk, st in zip(masks, per_stage)], pixel=(),
+                                      layout_error=ValueError)
+    if any(tuple(mk.shape) != ((s,) if st else ()) + tuple(im.shape[:2]) for im, mk, st in zip(images, masks, per_stage)):
+        raise ValueError("every mask must be a contiguous uint8 [H, W] or [S, H, W] tensor of its image's size")
+    lib = _lib.load()
     out_w, out_h = (int(v) for v in cfg["image_size"])
     wmax, hmax = int(sizes[:, 0].max()), int(sizes[:, 1].max())
     mats, flags, stage_kps = [], [], []
@@ -461,9 +466,15 @@ def bottomup_augment_batch(affine: BottomUpRandomAffine, flip: Optional[BottomUp
     mask_out = torch.empty(n, s, hmax, wmax, device=dev, dtype=torch.uint8)
     wh = (ctypes.c_int * (2 * s))(*[int(v) for v in sizes.reshape(-1)])
     m3, s3 = norm255(normalize_mean, normalize_std)
-    _lib.check(lib.mp_bottomup_train_augment(base, _lib.ptr(offs), _lib.ptr(hw), mbase, _lib.ptr(moffs), _lib.ptr(trans), _lib.ptr(fl), wh,
-                                             _lib.ptr(out), _lib.ptr(mask_out), n, s, out_h, out_w, hmax, wmax, m3, s3, _lib.stream()),
-               "mp_bottomup_train_augment")
+    if any(per_stage):  # the byte stride from one stage's source plane to the next; 0 where one plane serves every stage
+        stride = torch.tensor([im.shape[0] * im.shape[1] if st else 0 for im, st in zip(images, per_stage)], dtype=torch.int64, device=dev)
+        _lib.check(lib.mp_bottomup_train_augment_stages(base, _lib.ptr(offs), _lib.ptr(hw), mbase, _lib.ptr(moffs), _lib.ptr(stride),
+                                                        _lib.ptr(trans), _lib.ptr(fl), wh, _lib.ptr(out), _lib.ptr(mask_out), n, s, out_h,
+                                                        out_w, hmax, wmax, m3, s3, _lib.stream()), "mp_bottomup_train_augment_stages")
+    else:
+        _lib.check(lib.mp_bottomup_train_augment(base, _lib.ptr(offs), _lib.ptr(hw), mbase, _lib.ptr(moffs), _lib.ptr(trans), _lib.ptr(fl),
+                                                 wh, _lib.ptr(out), _lib.ptr(mask_out), n, s, out_h, out_w, hmax, wmax, m3, s3,
+                                                 _lib.stream()), "mp_bottomup_train_augment")
     return dict(image=out, mask=mask_out, keypoints=torch.from_numpy(kp_all).to(dev), num_persons=num_persons)
 
 

@@ -19,6 +19,11 @@
   of the flipped half (the other half copied), and the masks by torch indexing (fixed-point coordinates, gather, ``where``, mirror,
   pad) from matrices already inverted and uploaded; the two results are compared bit for bit first.  Fraction of 8 TB/s on the
   algorithmic bytes (read: the uint8 sources and masks; written: three fp32 planes and the padded uint8 mask stages).
+- train_masks: the training masks of a batch, N = 32 images of 480 x 640 with two polygon regions each, radii [24, 12] (the recipe's
+  sigma 2 on two levels): the two launches of ``mp_bottomup_train_masks`` on prepared, uploaded tables in device microseconds
+  (alternated rounds, median and min - max), the whole ``bottomup_masks_batch`` call (packing, one upload, the launches) and the
+  same batch through ``decode_mask_info`` on the host in wall milliseconds; both results are compared bit for bit first.  Fraction
+  of 8 TB/s on the algorithmic bytes (written: the uint8 clearance plane and the S stage planes; read: the clearance plane once).
 - flip_tta: the flip test.  The parse launch alone at the recipe shape (N = 1, stages 128 x 128 with 34 channels and 256 x 256 with 17,
   NMS 3, max_num 30): ``mp_bottomup_parse_nms_topk_flip`` beside the plain ``mp_bottomup_parse_nms_topk``, alternated in rounds of
   device-event timings (median and min - max over the rounds) with the algorithmic bytes of each (flip: both runs' stages read,
@@ -240,6 +245,63 @@ def train_augment(steps, n=32, src_w=640, src_h=480):
                 hbm_fraction=round(nbytes / (fused_ms * 1e-3) / HBM, 4))
 
 
+def train_masks(steps, rounds=5, n=32, h=480, w=640, radii=(24, 12)):
+    from mindpose_amd.data.transform import bottomup_mask as bm
+    rng = np.random.RandomState(0)
+    infos = []
+    for _ in range(n):
+        x0, y0, x1, y1 = rng.randint(0, w // 2), rng.randint(0, h // 2), rng.randint(w // 2, w), rng.randint(h // 2, h)
+        box = [x0, y0, x0 + (x1 - x0) // 3, y0, x0 + (x1 - x0) // 3, y0 + (y1 - y0) // 3, x0, y0 + (y1 - y0) // 3]
+        blob = [float(v) for v in np.stack([rng.uniform(x0, x1, 3), rng.uniform(y0, y1, 3)], axis=1).reshape(-1)]
+        infos.append(dict(regions=[bm.rle_from_polygon(box, h, w), bm.rle_from_polygon(blob, h, w)], shape=(len(radii), h, w), radii=list(radii)))
+    t0 = time.perf_counter()
+    want = [bm.decode_mask_info(info) for info in infos]
+    host_ms = (time.perf_counter() - t0) * 1000
+    got = mp.bottomup_masks_batch(infos, DEV)
+    if any(not np.array_equal(g.cpu().numpy(), w_) for g, w_ in zip(got, want)):
+        raise RuntimeError("the device masks and the host decode disagree")
+    s, size = len(radii), len(radii) * h * w
+    tabs = bm.pack_mask_tables(infos, [i * size for i in range(n)])
+    tables = torch.from_numpy(tabs["blob"]).to(DEV)
+    out = torch.empty(n * size, dtype=torch.uint8, device=DEV)
+    ws = torch.empty(tabs["clear_bytes"], dtype=torch.uint8, device=DEV)
+    base, starts = tables.data_ptr(), tabs["starts"]
+    as_p = lambda a, c: a.ctypes.data_as(ctypes.POINTER(c))  # noqa: E731
+    args = (as_p(tabs["prefix"], ctypes.c_uint32), as_p(tabs["region_ptr"], ctypes.c_int), as_p(tabs["image_tab"], ctypes.c_int),
+            as_p(tabs["offsets"], ctypes.c_longlong), base + starts[3], base + starts[2], base + starts[1], base + starts[0],
+            (ctypes.c_int * s)(*radii), as_p(tabs["half"], ctypes.c_uint8), out.data_ptr(), out.numel(), ws.data_ptr(), ws.numel(), n, s)
+    lib = _lib.load()
+
+    def launches():
+        _lib.check(lib.mp_bottomup_train_masks(*args, _lib.stream()), "mp_bottomup_train_masks")
+
+    def call():
+        mp.bottomup_masks_batch(infos, DEV)
+
+    def wall(fn, reps):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(reps):
+            fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1000 / reps
+
+    launches()
+    torch.cuda.synchronize()
+    if any(not np.array_equal(out[i * size:(i + 1) * size].view(s, h, w).cpu().numpy(), want[i]) for i in range(n)):
+        raise RuntimeError("the prepared launch and the host decode disagree")
+    times, calls = [], []
+    for _ in range(rounds):
+        times.append(_time(launches, steps) * 1000)
+        calls.append(wall(call, max(2, steps // 4)))
+    nbytes = n * h * w * (s + 2)
+    us = _spread(times)
+    return dict(n=n, image=[w, h], regions=2, runs=[int(min(len(r) for i in infos for r in i["regions"])), int(max(len(r) for i in infos for r in i["regions"]))],
+                radii=list(radii), launches_us=us, call_ms=_spread(calls), host_decode_ms=round(host_ms, 1),
+                ratio_host_over_call=round(host_ms / _spread(calls)["median"], 1), mb=round(nbytes / 1e6, 2),
+                hbm_fraction=round(nbytes / (us["median"] * 1e-6) / HBM, 4), valid_fraction=[round(float(np.mean([m[i].mean() for m in want])), 3) for i in range(s)])
+
+
 def _spread(values):
     v = sorted(values)
     return dict(median=round(v[len(v) // 2], 3), min=round(v[0], 3), max=round(v[-1], 3))
@@ -450,6 +512,7 @@ SECTIONS = {
     "resize_pad_normalize": resize_pad_normalize,
     "refine": lambda steps: [refine(p, steps) for p in (1, 10, 30)],
     "train_augment": train_augment,
+    "train_masks": train_masks,
     "flip_tta": flip_tta,
     "match": match,
     "multi_scale": multi_scale,
