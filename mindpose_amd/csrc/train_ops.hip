@@ -26,6 +26,59 @@ __device__ __forceinline__ double block_sum_256(double v, double* sm) {
     return r;
 }
 
+// ---- the pieces every BatchNorm form shares: each formula, and each per-channel publication, is written here once -------------------
+// one lane of one element
+__device__ __forceinline__ float bn_xhat(float z, float mu, float is) { return (z - mu) * is; }
+// dz = gamma*invstd * (g - dbeta/M - xhat*dgamma/M):  k = gamma * invstd, mb = dbeta / M, mg = dgamma / M
+__device__ __forceinline__ float bn_dz(float k, float g, float mb, float xh, float mg) { return k * (g - mb - xh * mg); }
+
+// Batch statistics of a channel from its fp64 sums, the fp64 divide / sqrt flavour (the fp32 kernels and the reducing fp16 forms; the
+// apply-only forms have their own, bn16_fwd_coeffs, which rounds differently - the tests that compare forms allow for exactly that).
+// mindspore.nn.BatchNorm2d(momentum=0.9): moving = 0.9 * moving + 0.1 * batch; the moving variance takes the UNBIASED batch
+// variance (cuDNN / PyTorch convention) [MS-knowledge, unverifiable here - affects only the moving statistics, never the
+// training-mode output or any gradient].
+struct BnStats {
+    double mean, var, count;
+    float invstd;
+    __device__ __forceinline__ float var_unbiased() const { return (float)(count > 1.0 ? var * count / (count - 1.0) : var); }
+};
+__device__ __forceinline__ BnStats bn_stats(double s0, double s1, double count, float eps) {
+    BnStats o;
+    o.count = count;
+    o.mean = s0 / count;
+    o.var = s1 / count - o.mean * o.mean;
+    if (o.var < 0.0) o.var = 0.0;
+    o.invstd = (float)(1.0 / sqrt(o.var + (double)eps));
+    return o;
+}
+
+// what a direction leaves per channel.  The apply-only argument records carry these; the reducing kernels build them from their own
+// __restrict__ parameters (as struct members the pointers lose it, and bn16_coop_kernel<false> an occupancy step with it).
+// The *_acc pair is both or neither (bn_grad_out).
+struct BnStatOut { float *save_mean, *save_invstd, *moving_mean, *moving_var; float momentum; };
+struct BnGradOut { float *dgamma, *dbeta, *dgamma_acc, *dbeta_acc; };
+// per-channel inputs (mean / invstd: backward only; beta in the backward: only where the ReLU mask is re-derived from z)
+struct BnChannels { const float *gamma, *beta, *mean, *invstd; };
+
+// saved statistics + moving averages of channel ch; the moving variance takes the unbiased variance ALREADY rounded to fp32
+__device__ __forceinline__ void bn_fwd_publish(int ch, float mean, float invstd, float var_unbiased, const BnStatOut& o) {
+    o.save_mean[ch] = mean;
+    o.save_invstd[ch] = invstd;
+    if (o.moving_mean) {
+        o.moving_mean[ch] = o.momentum * o.moving_mean[ch] + (1.f - o.momentum) * mean;
+        o.moving_var[ch] = o.momentum * o.moving_var[ch] + (1.f - o.momentum) * var_unbiased;
+    }
+}
+// dbeta / dgamma of channel ch, + straight into the caller's gradient buffers (no separate add launch)
+__device__ __forceinline__ void bn_bwd_publish(int ch, float db, float dg, const BnGradOut& o) {
+    o.dbeta[ch] = db;
+    o.dgamma[ch] = dg;
+    if (o.dgamma_acc) {
+        o.dbeta_acc[ch] += db;
+        o.dgamma_acc[ch] += dg;
+    }
+}
+
 // stage 1: grid (C, kBnSplit); block (c, s) reduces images n = s, s + kBnSplit, ... of channel c.
 // out: part[(c * kBnSplit + s) * 2 + {0,1}] = (sum a, sum a*b) in fp64, where
 //   forward  a = z,            b = z            -> sum z, sum z^2
@@ -38,6 +91,9 @@ __global__ __launch_bounds__(256) void bn_reduce_kernel(const float* __restrict_
     const int ch = blockIdx.x, sp = blockIdx.y;
     double s0 = 0.0, s1 = 0.0;
     const float mu = BWD ? mean[ch] : 0.f, is = BWD ? invstd[ch] : 0.f;
+    // Both widths stay spelled out, here and in the two apply kernels: which product the compiler contracts into an fma (today: lane
+    // x of the backward float4 body, no other) depends on the shape of the source; a shared per-element body moved that choice and
+    // with it the last bit of the partial sums, so of the saved statistics of every fp32 BatchNorm.
     for (int img = sp; img < n; img += kBnSplit) {
         const size_t base = ((size_t)img * c + ch) * hw;
         float f0 = 0.f, f1 = 0.f;  // fp32 per-thread partial over <= hw/256 elements, then fp64
@@ -92,10 +148,8 @@ __global__ __launch_bounds__(256) void bn_reduce_kernel(const float* __restrict_
     }
 }
 
-// stage 2 (folded into the apply kernels below): per channel mean / biased variance -> scale/shift, saved stats, moving-average
-// update.  mindspore.nn.BatchNorm2d(momentum=0.9): moving = 0.9 * moving + 0.1 * batch; the moving variance takes the UNBIASED batch
-// variance (cuDNN / PyTorch convention) [MS-knowledge, unverifiable here - affects only the moving statistics, never the
-// training-mode output or any gradient].
+// stage 2 is folded into the apply kernels below: per channel mean / biased variance -> scale/shift, saved stats, moving-average
+// update (bn_stats, bn_fwd_publish), or dgamma / dbeta (bn_bwd_publish).
 // totals of one channel from its kBnSplit partials: the first wave of the block, lane l = split l, fixed-order shuffle tree
 __device__ __forceinline__ void bn_channel_sums(const double* __restrict__ part, int ch, double& s0, double& s1) {
     s0 = 0.0;
@@ -111,15 +165,16 @@ __device__ __forceinline__ void bn_channel_sums(const double* __restrict__ part,
     }
 }
 
-// y = act(z * scale[c] + shift[c] (+ res)) - block per (n, c) plane, 16 B per lane when hw % 4 == 0.  Stage 2 is folded in: every
-// block reduces its channel's 32 partials itself (same values, same order in every block); the block of image 0 also writes the
-// saved statistics and the moving averages - one launch less per BatchNorm and direction.
+// y = act(z * scale[c] + shift[c] (+ res)) - block per (n, c) plane.  Stage 2 is folded in: every block reduces its channel's 32
+// partials itself (same values, same order in every block); the block of image 0 also writes the saved statistics and the moving
+// averages - one launch less per BatchNorm and direction.
 __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__ z, const double* __restrict__ part,
                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
                                                        float* __restrict__ save_mean, float* __restrict__ save_invstd,
                                                        float* __restrict__ moving_mean, float* __restrict__ moving_var,
                                                        const float* __restrict__ res, float* __restrict__ y, int c, int hw, int relu,
                                                        double count, float eps, float momentum) {
+    const BnStatOut out = {save_mean, save_invstd, moving_mean, moving_var, momentum};
     const size_t plane = blockIdx.x;
     const int ch = (int)(plane % c);
     __shared__ float s_sc, s_sh;
@@ -127,22 +182,11 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
         double s0, s1;
         bn_channel_sums(part, ch, s0, s1);
         if (threadIdx.x == 0) {
-            const double mean = s0 / count;
-            double var = s1 / count - mean * mean;
-            if (var < 0.0) var = 0.0;
-            const float invstd = (float)(1.0 / sqrt(var + (double)eps));
-            const float a = gamma[ch] * invstd;
+            const BnStats st = bn_stats(s0, s1, count, eps);
+            const float a = gamma[ch] * st.invstd;
             s_sc = a;
-            s_sh = beta[ch] - (float)mean * a;
-            if (plane < (size_t)c) {  // image 0
-                save_mean[ch] = (float)mean;
-                save_invstd[ch] = invstd;
-                if (moving_mean) {
-                    const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-                    moving_mean[ch] = momentum * moving_mean[ch] + (1.f - momentum) * (float)mean;
-                    moving_var[ch] = momentum * moving_var[ch] + (1.f - momentum) * (float)unbiased;
-                }
-            }
+            s_sh = beta[ch] - (float)st.mean * a;
+            if (plane < (size_t)c) bn_fwd_publish(ch, (float)st.mean, st.invstd, st.var_unbiased(), out);  // image 0
         }
     }
     __syncthreads();
@@ -166,8 +210,8 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
     }
 }
 
-// dz = gamma*invstd * (g - dbeta/M - xhat*dgamma/M), dres = g  (g = dy masked by the ReLU of the forward output); stage 2 folded
-// in like the forward (the block of image 0 writes dgamma / dbeta and adds them into the caller's gradient buffers)
+// dz = bn_dz, dres = g  (g = dy masked by the ReLU of the forward output); stage 2 folded in like the forward (the block of image 0
+// writes dgamma / dbeta and adds them into the caller's gradient buffers)
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restrict__ dy, const float* __restrict__ z,
                                                            const float* __restrict__ y, const double* __restrict__ part,
                                                            const float* __restrict__ gamma, const float* __restrict__ mean,
@@ -175,6 +219,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
                                                            float* __restrict__ dbeta, float* __restrict__ dgamma_acc,
                                                            float* __restrict__ dbeta_acc, float* __restrict__ dz,
                                                            float* __restrict__ dres, int c, int hw, int relu, float inv_count) {
+    const BnGradOut out = {dgamma, dbeta, dgamma_acc, dbeta_acc};
     const size_t plane = blockIdx.x;
     const int ch = (int)(plane % c);
     __shared__ float s_mb, s_mg;
@@ -185,14 +230,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
             const float db = (float)s0, dg = (float)s1;
             s_mb = db * inv_count;
             s_mg = dg * inv_count;
-            if (plane < (size_t)c) {  // image 0
-                dbeta[ch] = db;
-                dgamma[ch] = dg;
-                if (dgamma_acc && dbeta_acc) {  // + straight into the caller's gradient buffers (no separate add launch)
-                    dbeta_acc[ch] += db;
-                    dgamma_acc[ch] += dg;
-                }
-            }
+            if (plane < (size_t)c) bn_bwd_publish(ch, db, dg, out);  // image 0
         }
     }
     __syncthreads();
@@ -229,10 +267,9 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
     }
 }
 
-// backward of out = act(base + sum_k up_{s_k}(t_k)):  g = dy * (out > 0);  dbase = g;  dt_k = s_k x s_k block sums of g
+// backward of out = act(base + sum_k up_{s_k}(t_k)):  g = dy * (out > 0);  dt_k = s_k x s_k block sums of g
 __global__ __launch_bounds__(256) void fuse_sum_bwd_kernel(const float* __restrict__ dy, const float* __restrict__ out,
-                                                           float* __restrict__ dbase, float* __restrict__ dt, int planes,
-                                                           int h, int w, int sh, int relu) {
+                                                           float* __restrict__ dt, int planes, int h, int w, int sh, int relu) {
     // one thread per element of the LOW-resolution grid of this term (sh = log2 scale); sh == 0 covers dbase-like terms
     const int lh = h >> sh, lw = w >> sh, s = 1 << sh;
     const size_t total = (size_t)planes * lh * lw;
@@ -248,7 +285,6 @@ __global__ __launch_bounds__(256) void fuse_sum_bwd_kernel(const float* __restri
                 float g = dy[o + (size_t)a * w + b];
                 if (relu && !(out[o + (size_t)a * w + b] > 0.f)) g = 0.f;
                 acc += g;
-                if (dbase && sh == 0) dbase[o] = g;
             }
         if (dt) dt[i] = acc;
     }
@@ -351,6 +387,131 @@ __device__ __forceinline__ void block_sum16_256(double (&v)[16], double (*sm)[16
     __syncthreads();
 }
 
+// The flat (image, pixel) element range [e0, e1) that chunk `chunk` of `chunks` owns in channel block blk of an [N][C8][HW] tensor of
+// 16-byte elements: 32-bit index arithmetic, image = multiply-high division by hw (64-bit divisions per element cost more than the
+// element's memory traffic).  len = ceil: trailing chunks may be empty (e0 >= e1).
+struct Bn16Span {
+    unsigned e0, e1, magic_hw;
+    int hw;
+    bool exact;  // the multiply-high division is exact on [0, n * hw)
+    size_t blk_off, img_extra;
+    __device__ __forceinline__ Bn16Span(int n, int hw_, int c8, int blk, unsigned chunk, unsigned chunks) : hw(hw_) {
+        const unsigned per_blk = (unsigned)n * (unsigned)hw;
+        const unsigned len = (per_blk + chunks - 1) / chunks;
+        e0 = chunk * len;
+        e1 = e0 + len < per_blk ? e0 + len : per_blk;
+        magic_hw = hw > 1 ? (unsigned)(0x100000000ULL / (unsigned)hw) + 1u : 0u;
+        exact = (unsigned long long)per_blk * (unsigned)hw < 0x100000000ULL;
+        blk_off = (size_t)blk * hw;
+        img_extra = (size_t)(c8 - 1) * hw;
+    }
+    __device__ __forceinline__ size_t index_of(unsigned e) const {
+        const unsigned img = hw <= 1 ? e : (exact ? __umulhi(e, magic_hw) : e / (unsigned)hw);
+        return (size_t)e + (size_t)img * img_extra + blk_off;
+    }
+};
+
+// ---- the fp16 element formulas, over the 8 channels (lanes) of one 16-byte element -----------------------------------------------
+// per-lane constants of a backward pass: xhat = (z - mu) * is; msc / msh = forward scale / shift for the re-derived ReLU mask (relu 2)
+struct Bn16GradLanes { float mu[8], is[8], msc[8], msh[8]; };
+struct Bn16DzLanes { float k[8], mb[8], mg[8]; };  // bn_dz's per-channel factors
+template <bool BWD>
+__device__ __forceinline__ Bn16GradLanes bn16_grad_lanes(int blk, int c, int relu, const BnChannels& p) {
+    Bn16GradLanes L;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int ch = blk * 8 + j;
+        L.mu[j] = (BWD && ch < c) ? p.mean[ch] : 0.f;
+        L.is[j] = (BWD && ch < c) ? p.invstd[ch] : 0.f;
+        L.msc[j] = (BWD && relu == 2 && ch < c) ? p.gamma[ch] * L.is[j] : 0.f;
+        L.msh[j] = (BWD && relu == 2 && ch < c) ? bn16_shift(p.beta[ch], L.mu[j], L.msc[j]) : 0.f;
+    }
+    return L;
+}
+
+// one element of a pass: z; in the backward also the incoming gradient, and y where the mask is read from it (relu 1).
+// (No __restrict__ on bn16_load's pointers: the kernels' own parameters carry it.  With a second, nested scope here the compiler
+// emitted other code for the backward kernels - bn16_coop_kernel<true> 3110 instead of 3473 instructions, fewer and later waits.)
+struct Bn16Elem { h16x8 z, g, y; };
+template <bool BWD>
+__device__ __forceinline__ Bn16Elem bn16_load(const u32x4_t* z, const u32x4_t* dy, const u32x4_t* y, size_t i, int relu) {
+    Bn16Elem e;
+    e.z = __builtin_bit_cast(h16x8, z[i]);
+    e.g = e.z;
+    e.y = e.z;
+    if (BWD) {
+        e.g = __builtin_bit_cast(h16x8, dy[i]);
+        if (relu == 1) e.y = __builtin_bit_cast(h16x8, y[i]);
+    }
+    return e;
+}
+// the masked gradient of lane j: relu 0 dy itself, 1 masked by the stored y, 2 by the mask re-derived from z
+__device__ __forceinline__ float bn16_masked(const Bn16Elem& e, int j, int relu, const Bn16GradLanes& L) {
+    float g = (float)e.g[j];
+    if (relu == 1 && !((float)e.y[j] > 0.f)) g = 0.f;
+    if (relu == 2 && !bn16_relu_open((float)e.z[j], L.msc[j], L.msh[j])) g = 0.f;
+    return g;
+}
+// pass 1: f[2j] += a, f[2j + 1] += a * b with (a, b) = (z, z) forward, (masked g, xhat) backward
+template <bool BWD>
+__device__ __forceinline__ void bn16_accumulate(float (&f)[16], const Bn16Elem& e, int relu, const Bn16GradLanes& L) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        if (BWD) {
+            const float g = bn16_masked(e, j, relu, L);
+            const float xh = bn_xhat((float)e.z[j], L.mu[j], L.is[j]);
+            f[2 * j] += g;
+            f[2 * j + 1] += g * xh;
+        } else {
+            const float v = (float)e.z[j];
+            f[2 * j] += v;
+            f[2 * j + 1] += v * v;
+        }
+    }
+}
+// the fp64 tail of pass 1: the block's 16 totals; thread t < 16 returns total t = (channel t >> 1, sum t & 1)
+__device__ __forceinline__ double bn16_accumulated(const float (&f)[16]) {
+    double acc[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) acc[j] = (double)f[j];
+    __shared__ double sm[4][16];
+    block_sum16_256(acc, sm);
+    return acc[0];
+}
+// pass 2 forward: y = act(z * sc + sh (+ res)); padding channels leave as zeros
+__device__ __forceinline__ u32x4_t bn16_fwd_elem(h16x8 zv, h16x8 rv, bool has_res, int relu, int blk, int c, const float (&sc)[8],
+                                                 const float (&sh)[8]) {
+    h16x8 o;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        float v = 0.f;
+        if (blk * 8 + j < c) {
+            v = bn16_affine((float)zv[j], sc[j], sh[j]);
+            if (has_res) v += (float)rv[j];
+            if (relu) v = fmaxf(v, 0.f);
+        }
+        o[j] = (_Float16)v;
+    }
+    return __builtin_bit_cast(u32x4_t, o);
+}
+// pass 2 backward: dz = bn_dz, dres = the masked gradient; padding channels leave as zeros
+__device__ __forceinline__ void bn16_bwd_elem(const Bn16Elem& e, int relu, int blk, int c, const Bn16GradLanes& L, const Bn16DzLanes& D,
+                                              u32x4_t& dz, u32x4_t& dres) {
+    h16x8 oz, og;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        float g = 0.f, d = 0.f;
+        if (blk * 8 + j < c) {
+            g = bn16_masked(e, j, relu, L);
+            d = bn_dz(D.k[j], g, D.mb[j], bn_xhat((float)e.z[j], L.mu[j], L.is[j]), D.mg[j]);
+        }
+        oz[j] = (_Float16)d;
+        og[j] = (_Float16)g;
+    }
+    dz = __builtin_bit_cast(u32x4_t, oz);
+    dres = __builtin_bit_cast(u32x4_t, og);
+}
+
 // grid (C8, kBnSplit): block (blk, sp) reduces images sp, sp + kBnSplit, ... of the 8 channels of block blk; partials in the
 // fp32 kernels' layout part[(ch * kBnSplit + sp) * 2 + {0,1}] so that the finalize kernels are shared
 template <bool BWD>
@@ -363,19 +524,11 @@ __global__ __launch_bounds__(256) void bn16_reduce_kernel(const u32x4_t* __restr
     const int blk = blockIdx.x, sp = blockIdx.y, nsplit = gi * gp;
     const int ig = sp % gi, pc = sp / gi;
     const int chunk = (hw + gp - 1) / gp, p0 = pc * chunk, p1 = min(p0 + chunk, hw);
-    float mu[8], is[8], msc[8], msh[8];  // msc / msh: forward scale / shift, for the recomputed ReLU mask (relu == 2)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int ch = blk * 8 + j;
-        mu[j] = (BWD && ch < c) ? mean[ch] : 0.f;
-        is[j] = (BWD && ch < c) ? invstd[ch] : 0.f;
-        msc[j] = (BWD && relu == 2 && ch < c) ? gamma[ch] * is[j] : 0.f;
-        msh[j] = (BWD && relu == 2 && ch < c) ? bn16_shift(beta[ch], mu[j], msc[j]) : 0.f;
-    }
+    const BnChannels chan = {gamma, beta, mean, invstd};
+    const Bn16GradLanes L = bn16_grad_lanes<BWD>(blk, c, relu, chan);
     // The block's elements are {images ig, ig + gi, ...} x {pixels p0 .. p1}: walked as ONE flat index space (the small maps give a
     // block only 1-2 elements per thread and image; an image loop around a pixel loop kept a single load in flight per thread and
     // made these passes latency-bound), 32-bit index arithmetic with a multiply-high division by the chunk length.
-    double acc[16];
     float f[16];
 #pragma unroll
     for (int j = 0; j < 16; ++j) f[j] = 0.f;
@@ -389,36 +542,12 @@ __global__ __launch_bounds__(256) void bn16_reduce_kernel(const u32x4_t* __restr
     for (unsigned e = threadIdx.x; e < cnt; e += 256) {
         const unsigned a = len <= 1 ? e : (exact ? __umulhi(e, magic) : e / len);
         const size_t i = ((size_t)(ig + a * gi)) * img_stride + (size_t)blk * hw + p0 + (e - a * len);
-        const h16x8 zv = __builtin_bit_cast(h16x8, z[i]);
-        if (BWD) {
-            const h16x8 gv = __builtin_bit_cast(h16x8, a_in[i]);
-            h16x8 yv = zv;
-            if (relu == 1) yv = __builtin_bit_cast(h16x8, y[i]);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                float g = (float)gv[j];
-                if (relu == 1 && !((float)yv[j] > 0.f)) g = 0.f;
-                if (relu == 2 && !bn16_relu_open((float)zv[j], msc[j], msh[j])) g = 0.f;
-                const float xh = ((float)zv[j] - mu[j]) * is[j];
-                f[2 * j] += g;
-                f[2 * j + 1] += g * xh;
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float v = (float)zv[j];
-                f[2 * j] += v;
-                f[2 * j + 1] += v * v;
-            }
-        }
+        bn16_accumulate<BWD>(f, bn16_load<BWD>(z, a_in, y, i, relu), relu, L);
     }
-#pragma unroll
-    for (int j = 0; j < 16; ++j) acc[j] = (double)f[j];
-    __shared__ double sm[4][16];
-    block_sum16_256(acc, sm);
+    const double total = bn16_accumulated(f);
     if (threadIdx.x < 16) {
         const int ch = blk * 8 + (threadIdx.x >> 1);
-        if (ch < c) part[((size_t)ch * nsplit + sp) * 2 + (threadIdx.x & 1)] = acc[0];
+        if (ch < c) part[((size_t)ch * nsplit + sp) * 2 + (threadIdx.x & 1)] = total;
     }
 }
 
@@ -464,6 +593,7 @@ __global__ __launch_bounds__(256) void bn16_apply_kernel(const u32x4_t* __restri
                                                          const u32x4_t* __restrict__ res, u32x4_t* __restrict__ y, int n, int c,
                                                          int c8, int hw, int nsplit, double count, float eps, float momentum,
                                                          int relu) {
+    const BnStatOut out = {save_mean, save_invstd, moving_mean, moving_var, momentum};
     const int blk = blockIdx.x;
     __shared__ float s_scale[8], s_shift[8];
     {
@@ -473,21 +603,10 @@ __global__ __launch_bounds__(256) void bn16_apply_kernel(const u32x4_t* __restri
         if ((threadIdx.x & 31) == 0) {
             float sc = 0.f, sh = 0.f;
             if (ch < c) {
-                const double mean = s0 / count;
-                double var = s1 / count - mean * mean;
-                if (var < 0.0) var = 0.0;
-                const float invstd = (float)(1.0 / sqrt(var + (double)eps));
-                sc = gamma[ch] * invstd;
-                sh = bn16_shift(beta[ch], (float)mean, sc);
-                if (blockIdx.y == 0) {
-                    save_mean[ch] = (float)mean;
-                    save_invstd[ch] = invstd;
-                    if (moving_mean) {
-                        const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-                        moving_mean[ch] = momentum * moving_mean[ch] + (1.f - momentum) * (float)mean;
-                        moving_var[ch] = momentum * moving_var[ch] + (1.f - momentum) * (float)unbiased;
-                    }
-                }
+                const BnStats st = bn_stats(s0, s1, count, eps);
+                sc = gamma[ch] * st.invstd;
+                sh = bn16_shift(beta[ch], (float)st.mean, sc);
+                if (blockIdx.y == 0) bn_fwd_publish(ch, (float)st.mean, st.invstd, st.var_unbiased(), out);
             }
             s_scale[j] = sc;
             s_shift[j] = sh;
@@ -497,33 +616,14 @@ __global__ __launch_bounds__(256) void bn16_apply_kernel(const u32x4_t* __restri
     float sc[8], sh[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) { sc[j] = s_scale[j]; sh[j] = s_shift[j]; }
-    // elements of this channel block: (image, pixel) flat, 32-bit, image = multiply-high division by hw (64-bit divisions per
-    // element cost more than the element's memory traffic)
-    const unsigned per_blk = (unsigned)n * (unsigned)hw;
-    const unsigned len = (per_blk + gridDim.y - 1) / gridDim.y;
-    const unsigned e0 = blockIdx.y * len, e1 = e0 + len < per_blk ? e0 + len : per_blk;
-    const unsigned magic_hw = hw > 1 ? (unsigned)(0x100000000ULL / (unsigned)hw) + 1u : 0u;
-    const bool exact = (unsigned long long)per_blk * (unsigned)hw < 0x100000000ULL;
-    const size_t blk_off = (size_t)blk * hw, img_extra = (size_t)(c8 - 1) * hw;
+    const Bn16Span span(n, hw, c8, blk, blockIdx.y, gridDim.y);
 #pragma unroll 4
-    for (unsigned e = e0 + threadIdx.x; e < e1; e += 256) {
-        const unsigned img = hw <= 1 ? e : (exact ? __umulhi(e, magic_hw) : e / (unsigned)hw);
-        const size_t i = (size_t)e + (size_t)img * img_extra + blk_off;
+    for (unsigned e = span.e0 + threadIdx.x; e < span.e1; e += 256) {
+        const size_t i = span.index_of(e);
         const h16x8 zv = __builtin_bit_cast(h16x8, z[i]);
         h16x8 rv = zv;
         if (res) rv = __builtin_bit_cast(h16x8, res[i]);
-        h16x8 o;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            float v = 0.f;
-            if (blk * 8 + j < c) {
-                v = bn16_affine((float)zv[j], sc[j], sh[j]);
-                if (res) v += (float)rv[j];
-                if (relu) v = fmaxf(v, 0.f);
-            }
-            o[j] = (_Float16)v;
-        }
-        y[i] = __builtin_bit_cast(u32x4_t, o);
+        y[i] = bn16_fwd_elem(zv, rv, res != nullptr, relu, blk, c, sc, sh);
     }
 }
 
@@ -535,6 +635,7 @@ __global__ __launch_bounds__(256) void bn16_bwd_apply_kernel(const u32x4_t* __re
                                                              float* __restrict__ dbeta_acc, u32x4_t* __restrict__ dz,
                                                              u32x4_t* __restrict__ dres, int n, int c, int c8, int hw, int nsplit,
                                                              int relu, float inv_count, const float* __restrict__ beta) {
+    const BnGradOut out = {dgamma, dbeta, dgamma_acc, dbeta_acc};
     const int blk = blockIdx.x;
     __shared__ float s_k[8], s_mu[8], s_is[8], s_mb[8], s_mg[8], s_sh[8];
     {
@@ -550,53 +651,27 @@ __global__ __launch_bounds__(256) void bn16_bwd_apply_kernel(const u32x4_t* __re
                 k = gamma[ch] * is;
                 mb = db * inv_count;
                 mg = dg * inv_count;
-                if (blockIdx.y == 0) {
-                    dbeta[ch] = db;
-                    dgamma[ch] = dg;
-                    if (dgamma_acc && dbeta_acc) {  // + straight into the caller's gradient buffers (no separate add launch)
-                        dbeta_acc[ch] += db;
-                        dgamma_acc[ch] += dg;
-                    }
-                }
+                if (blockIdx.y == 0) bn_bwd_publish(ch, db, dg, out);
             }
             s_k[j] = k; s_mu[j] = mu; s_is[j] = is; s_mb[j] = mb; s_mg[j] = mg;
             s_sh[j] = (relu == 2 && ch < c) ? bn16_shift(beta[ch], mu, k) : 0.f;  // k = gamma * invstd = the forward scale
         }
     }
     __syncthreads();
-    float k[8], mu[8], is[8], mb[8], mg[8], msh[8];
+    Bn16GradLanes L;
+    Bn16DzLanes D;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { k[j] = s_k[j]; mu[j] = s_mu[j]; is[j] = s_is[j]; mb[j] = s_mb[j]; mg[j] = s_mg[j]; msh[j] = s_sh[j]; }
-    const unsigned per_blk = (unsigned)n * (unsigned)hw;
-    const unsigned len = (per_blk + gridDim.y - 1) / gridDim.y;
-    const unsigned e0 = blockIdx.y * len, e1 = e0 + len < per_blk ? e0 + len : per_blk;
-    const unsigned magic_hw = hw > 1 ? (unsigned)(0x100000000ULL / (unsigned)hw) + 1u : 0u;
-    const bool exact = (unsigned long long)per_blk * (unsigned)hw < 0x100000000ULL;
-    const size_t blk_off = (size_t)blk * hw, img_extra = (size_t)(c8 - 1) * hw;
+    for (int j = 0; j < 8; ++j) {
+        D.k[j] = L.msc[j] = s_k[j]; L.mu[j] = s_mu[j]; L.is[j] = s_is[j]; D.mb[j] = s_mb[j]; D.mg[j] = s_mg[j]; L.msh[j] = s_sh[j];
+    }
+    const Bn16Span span(n, hw, c8, blk, blockIdx.y, gridDim.y);
 #pragma unroll 4
-    for (unsigned e = e0 + threadIdx.x; e < e1; e += 256) {
-        const unsigned img = hw <= 1 ? e : (exact ? __umulhi(e, magic_hw) : e / (unsigned)hw);
-        const size_t i = (size_t)e + (size_t)img * img_extra + blk_off;
-        const h16x8 gv = __builtin_bit_cast(h16x8, dy[i]);
-        const h16x8 zv = __builtin_bit_cast(h16x8, z[i]);
-        h16x8 yv = zv;
-        if (relu == 1) yv = __builtin_bit_cast(h16x8, y[i]);
-        h16x8 oz, og;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            float g = 0.f, d = 0.f;
-            if (blk * 8 + j < c) {
-                g = (float)gv[j];
-                if (relu == 1 && !((float)yv[j] > 0.f)) g = 0.f;
-                if (relu == 2 && !bn16_relu_open((float)zv[j], k[j], msh[j])) g = 0.f;
-                const float xh = ((float)zv[j] - mu[j]) * is[j];
-                d = k[j] * (g - mb[j] - xh * mg[j]);
-            }
-            oz[j] = (_Float16)d;
-            og[j] = (_Float16)g;
-        }
-        dz[i] = __builtin_bit_cast(u32x4_t, oz);
-        if (dres) dres[i] = __builtin_bit_cast(u32x4_t, og);
+    for (unsigned e = span.e0 + threadIdx.x; e < span.e1; e += 256) {
+        const size_t i = span.index_of(e);
+        u32x4_t oz, og;
+        bn16_bwd_elem(bn16_load<true>(z, dy, y, i, relu), relu, blk, c, L, D, oz, og);
+        dz[i] = oz;
+        if (dres) dres[i] = og;
     }
 }
 
@@ -607,6 +682,24 @@ __global__ __launch_bounds__(256) void bn16_bwd_apply_kernel(const u32x4_t* __re
 // order, every block the same values), kMaxFoldParts slots at most - above that bn16_fold_kernel reduces them to one slot first.
 constexpr int kMaxFoldParts = 512;
 constexpr int kFoldSplit = 8;  // slot ranges of the fold launch (more than kMaxFoldParts slots)
+
+// the tail of a slot fold: thread (q = t & 3, r = t >> 2) holds the fp64 sums a[4] of float4 q over its slot rows r, r + 64, ...;
+// xor tree over the 16 slot rows of the wave (q fixed), then the four waves through LDS.  Thread t < 16 returns total t of
+// {sum0, sumsq0, sum1, ...}; one barrier inside.
+__device__ __forceinline__ double bn16_fold_tail(double (&a)[4], double (*sm)[16]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        for (int off = 4; off <= 32; off <<= 1) a[i] += __shfl_xor(a[i], off, 64);
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (lane < 4) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) sm[wave][lane * 4 + i] = a[i];
+    }
+    __syncthreads();
+    double total = 0.0;
+    if (threadIdx.x < 16) total = ((sm[0][threadIdx.x] + sm[1][threadIdx.x]) + sm[2][threadIdx.x]) + sm[3][threadIdx.x];
+    return total;
+}
 
 // totals of the 8 channels of block blk -> tot[16] = {sum0, sumsq0, sum1, ...} (fp64, LDS); ends with a barrier
 __device__ __forceinline__ void bn16_fold_parts(const float* __restrict__ pre, int blk, int n_parts, double* tot, double (*sm)[16]) {
@@ -623,16 +716,8 @@ __device__ __forceinline__ void bn16_fold_parts(const float* __restrict__ pre, i
     for (int k = 0; k < kMaxFoldParts / 64; ++k) {
         a[0] += (double)v[k].x; a[1] += (double)v[k].y; a[2] += (double)v[k].z; a[3] += (double)v[k].w;
     }
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-        for (int off = 4; off <= 32; off <<= 1) a[i] += __shfl_xor(a[i], off, 64);  // over the 16 slot rows of the wave, q fixed
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (lane < 4) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) sm[wave][lane * 4 + i] = a[i];
-    }
-    __syncthreads();
-    if (threadIdx.x < 16) tot[threadIdx.x] = ((sm[0][threadIdx.x] + sm[1][threadIdx.x]) + sm[2][threadIdx.x]) + sm[3][threadIdx.x];
+    const double total = bn16_fold_tail(a, sm);
+    if (threadIdx.x < 16) tot[threadIdx.x] = total;
     __syncthreads();
 }
 
@@ -648,26 +733,40 @@ __global__ __launch_bounds__(256) void bn16_fold_kernel(const float* __restrict_
         const float4 v = src[(size_t)slot * 4 + q];
         a[0] += (double)v.x; a[1] += (double)v.y; a[2] += (double)v.z; a[3] += (double)v.w;
     }
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-        for (int off = 4; off <= 32; off <<= 1) a[i] += __shfl_xor(a[i], off, 64);
     __shared__ double sm[4][16];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (lane < 4) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) sm[wave][lane * 4 + i] = a[i];
-    }
-    __syncthreads();
+    const double total = bn16_fold_tail(a, sm);
     // fp32 slots: a range total (|sum| < 2^24 x its mean term) keeps 24 bits - the precision the conv's slots themselves have
-    if (threadIdx.x < 16)
-        out[((size_t)blk * kFoldSplit + f) * 16 + threadIdx.x] =
-            (float)(((sm[0][threadIdx.x] + sm[1][threadIdx.x]) + sm[2][threadIdx.x]) + sm[3][threadIdx.x]);
+    if (threadIdx.x < 16) out[((size_t)blk * kFoldSplit + f) * 16 + threadIdx.x] = (float)total;
 }
+
+// One typed argument record per direction of the apply-only passes: by value to the one-layer kernels, as a table of kBnJobs to the
+// grouped ones.  The host fills it in ONE place (bn16_fwd_fill / bn16_bwd_fill), which is also where an entry's arguments are checked.
+struct Bn16FwdArgs {
+    const u32x4_t *z, *res;
+    u32x4_t* y;
+    const float* pre;  // partial slots [c8][n_parts][8][2] (folded to kFoldSplit slots when there were more than a block folds)
+    BnChannels chan;
+    BnStatOut out;
+    double inv_count, unbias;
+    float eps;
+    int n_parts, n, c, c8, hw, relu;
+    unsigned chunks, first;  // chunks per channel block; first block of the job in a grouped grid (0xFFFFFFFF: no such job)
+};
+struct Bn16BwdArgs {
+    const u32x4_t *g, *z, *y;  // y: the reducing forms' mask (relu 1); the apply-only passes take g pre-masked
+    u32x4_t *dz, *dres;
+    const float* pre;
+    BnChannels chan;
+    BnGradOut out;
+    float inv_count;
+    int n_parts, n, c, c8, hw, relu;
+    unsigned chunks, first;
+};
 
 // channel j of block blk: batch mean / variance from the folded sums -> the forward scale / shift (0 / 0 on a padding channel).
 // gamma_v / beta_v were requested at the top of the kernel (their latency runs under the fold's); the saved statistics and the
-// moving averages are written by `bn16_fwd_publish` AFTER the caller has released scale / shift to the other threads - the
-// read-modify-write of the moving averages is a memory round trip nobody should wait for
+// moving averages are published AFTER the caller has released scale / shift to the other threads - the read-modify-write of the
+// moving averages is a memory round trip nobody should wait for
 struct Bn16Coeffs { float sc, sh, mean, invstd, var_unbiased; };
 __device__ __forceinline__ Bn16Coeffs bn16_fwd_coeffs(int j, int blk, int c, const double* s_tot, float gamma_v, float beta_v, double inv_count,
                                                       double unbias, float eps) {
@@ -688,294 +787,187 @@ __device__ __forceinline__ Bn16Coeffs bn16_fwd_coeffs(int j, int blk, int c, con
     }
     return o;
 }
-__device__ __forceinline__ void bn16_fwd_publish(int j, int blk, int c, const Bn16Coeffs& o, float* __restrict__ save_mean,
-                                                 float* __restrict__ save_invstd, float* __restrict__ moving_mean,
-                                                 float* __restrict__ moving_var, float momentum) {
-    const int ch = blk * 8 + j;
-    if (ch < c) {
-        save_mean[ch] = o.mean;
-        save_invstd[ch] = o.invstd;
-        if (moving_mean) {
-            moving_mean[ch] = momentum * moving_mean[ch] + (1.f - momentum) * o.mean;
-            moving_var[ch] = momentum * moving_var[ch] + (1.f - momentum) * o.var_unbiased;
-        }
-    }
-}
 
 // The prologue of the apply pass as a launch of its own, grid (C8): the statistics of a mode-1 conv launch -> the folded scale /
 // shift its CONSUMER applies on its own operand (conv_f16_wreg.hip, PRE) - same fold, same arithmetic, same saved statistics
-__global__ __launch_bounds__(256) void bn16_finalize_kernel(const float* __restrict__ pre, int n_parts, const float* __restrict__ gamma,
-                                                            const float* __restrict__ beta, float* __restrict__ save_mean,
-                                                            float* __restrict__ save_invstd, float* __restrict__ moving_mean,
-                                                            float* __restrict__ moving_var, float* __restrict__ scale,
-                                                            float* __restrict__ shift, int c, double inv_count, double unbias, float eps,
-                                                            float momentum) {
+__global__ __launch_bounds__(256) void bn16_finalize_kernel(const Bn16FwdArgs a, float* __restrict__ scale, float* __restrict__ shift) {
     __shared__ double s_tot[16];
     __shared__ double s_sm[4][16];
-    const int blk = blockIdx.x;
-    const bool coef = threadIdx.x < 8 && blk * 8 + (int)threadIdx.x < c;
-    const float gamma_v = coef ? gamma[blk * 8 + threadIdx.x] : 0.f, beta_v = coef ? beta[blk * 8 + threadIdx.x] : 0.f;
-    bn16_fold_parts(pre, blk, n_parts, s_tot, s_sm);
+    const int blk = blockIdx.x, ch = blk * 8 + (int)threadIdx.x;
+    const bool coef = threadIdx.x < 8 && ch < a.c;
+    const float gamma_v = coef ? a.chan.gamma[ch] : 0.f, beta_v = coef ? a.chan.beta[ch] : 0.f;
+    bn16_fold_parts(a.pre, blk, a.n_parts, s_tot, s_sm);
     if (threadIdx.x < 8) {
-        const Bn16Coeffs o = bn16_fwd_coeffs(threadIdx.x, blk, c, s_tot, gamma_v, beta_v, inv_count, unbias, eps);
-        scale[blk * 8 + threadIdx.x] = o.sc;
-        shift[blk * 8 + threadIdx.x] = o.sh;
-        bn16_fwd_publish(threadIdx.x, blk, c, o, save_mean, save_invstd, moving_mean, moving_var, momentum);
+        const Bn16Coeffs o = bn16_fwd_coeffs(threadIdx.x, blk, a.c, s_tot, gamma_v, beta_v, a.inv_count, a.unbias, a.eps);
+        scale[ch] = o.sc;
+        shift[ch] = o.sh;
+        if (coef) bn_fwd_publish(ch, o.mean, o.invstd, o.var_unbiased, a.out);
+    }
+}
+
+// The streaming loop of the apply-only passes over [span.e0, span.e1), two source tensors a and b (b only if has_b: zeros otherwise).
+// Batches of kBnBatch elements per thread: all loads of a batch are issued back to back, and the NEXT batch is requested before
+// this one is transformed (a loop of load / wait / transform / store per element keeps one load per tensor in flight and ran
+// the large maps at ~2 TB/s).  The first batch goes out BEFORE prologue() - the statistics prologue (partial slots -> totals ->
+// scale / shift: three dependent round trips) then runs under its latency - on the small maps that batch is all a thread has.
+// apply(a element, b element, index) transforms and stores one element.
+constexpr int kBnBatch = 4;
+template <class Prologue, class Apply>
+__device__ __forceinline__ void bn16_stream(const Bn16Span& span, const u32x4_t* __restrict__ a, const u32x4_t* __restrict__ b, bool has_b,
+                                            Prologue prologue, Apply apply) {
+    const u32x4_t zero4 = (u32x4_t){0u, 0u, 0u, 0u};
+    u32x4_t ca[kBnBatch], cb[kBnBatch];
+    size_t ci[kBnBatch];
+    auto request = [&](unsigned base, u32x4_t (&qa)[kBnBatch], u32x4_t (&qb)[kBnBatch], size_t (&qi)[kBnBatch]) {
+#pragma unroll
+        for (int k = 0; k < kBnBatch; ++k) {
+            const unsigned e = base + threadIdx.x + 256u * k;
+            const bool ok = e < span.e1;
+            qi[k] = span.index_of(ok ? e : span.e0);
+            qa[k] = ok ? a[qi[k]] : zero4;
+            qb[k] = (ok && has_b) ? b[qi[k]] : zero4;
+        }
+    };
+    request(span.e0, ca, cb, ci);
+    prologue();
+    for (unsigned base = span.e0; base < span.e1; base += 256u * kBnBatch) {
+        u32x4_t na[kBnBatch], nb[kBnBatch];
+        size_t ni[kBnBatch];
+        const bool more = base + 256u * kBnBatch < span.e1;  // uniform
+        if (more) request(base + 256u * kBnBatch, na, nb, ni);
+#pragma unroll
+        for (int k = 0; k < kBnBatch; ++k)
+            if (base + threadIdx.x + 256u * k < span.e1) apply(ca[k], cb[k], ci[k]);
+        if (more) {
+#pragma unroll
+            for (int k = 0; k < kBnBatch; ++k) { ca[k] = na[k]; cb[k] = nb[k]; ci[k] = ni[k]; }
+        }
     }
 }
 
 // forward apply with the statistics folded from the conv's partials: y = act(z * scale + shift (+ res))
-// (a __device__ body: the one-layer kernel passes blockIdx, the grouped kernel below the block's place inside its job)
-__device__ __forceinline__ void bn16_apply_pre_body(const u32x4_t* __restrict__ z, const float* __restrict__ pre, int n_parts,
-                                                    const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                    float* __restrict__ save_mean, float* __restrict__ save_invstd,
-                                                    float* __restrict__ moving_mean, float* __restrict__ moving_var,
-                                                    const u32x4_t* __restrict__ res, u32x4_t* __restrict__ y, int n, int c, int c8, int hw,
-                                                    double inv_count, double unbias, float eps, float momentum, int relu, int blk,
-                                                    unsigned chunk, unsigned chunks) {
+// (a __device__ body: the one-layer kernel passes blockIdx, the grouped kernel below the block's place inside its job).
+// Branch-free per element on purpose (floor_v, the keep mask, zeros for a missing residual): measured against the `ch < c` form.
+__device__ __forceinline__ void bn16_apply_pre_body(const Bn16FwdArgs& a, int blk, unsigned chunk) {
     __shared__ double s_tot[16];
     __shared__ double s_sm[4][16];
     __shared__ float s_scale[8], s_shift[8];
-    const unsigned per_blk = (unsigned)n * (unsigned)hw;
-    const unsigned len = (per_blk + chunks - 1) / chunks;
-    const unsigned e0 = chunk * len, e1 = e0 + len < per_blk ? e0 + len : per_blk;
-    const unsigned magic_hw = hw > 1 ? (unsigned)(0x100000000ULL / (unsigned)hw) + 1u : 0u;
-    const bool exact = (unsigned long long)per_blk * (unsigned)hw < 0x100000000ULL;
-    const size_t blk_off = (size_t)blk * hw, img_extra = (size_t)(c8 - 1) * hw;
-    auto index_of = [&](unsigned e) {
-        const unsigned img = hw <= 1 ? e : (exact ? __umulhi(e, magic_hw) : e / (unsigned)hw);
-        return (size_t)e + (size_t)img * img_extra + blk_off;
-    };
-    // Batches of kBatch elements per thread: all loads of a batch are issued back to back, and the NEXT batch is requested before
-    // this one is transformed (a loop of load / wait / transform / store per element keeps one load per tensor in flight and ran
-    // the large maps at ~2 TB/s).  The first batch goes out BEFORE the fold: the statistics prologue (partial slots -> totals ->
-    // scale / shift: three dependent round trips) then runs under its latency - on the small maps that batch is all a thread has.
-    constexpr int kBatch = 4;
-    const bool has_res = res != nullptr;
-    const u32x4_t zero4 = (u32x4_t){0u, 0u, 0u, 0u};
-    u32x4_t cz[kBatch], cr[kBatch];
-    size_t ci[kBatch];
-    auto request = [&](unsigned base, u32x4_t (&qz)[kBatch], u32x4_t (&qr)[kBatch], size_t (&qi)[kBatch]) {
-#pragma unroll
-        for (int k = 0; k < kBatch; ++k) {
-            const unsigned e = base + threadIdx.x + 256u * k;
-            const bool ok = e < e1;
-            qi[k] = index_of(ok ? e : e0);
-            qz[k] = ok ? z[qi[k]] : zero4;
-            qr[k] = (ok && has_res) ? res[qi[k]] : zero4;
-        }
-    };
-    const bool coef = threadIdx.x < 8 && blk * 8 + (int)threadIdx.x < c;
-    const float gamma_v = coef ? gamma[blk * 8 + threadIdx.x] : 0.f, beta_v = coef ? beta[blk * 8 + threadIdx.x] : 0.f;
-    request(e0, cz, cr, ci);
-    bn16_fold_parts(pre, blk, n_parts, s_tot, s_sm);
-    Bn16Coeffs co = {0.f, 0.f, 0.f, 0.f, 0.f};
-    if (threadIdx.x < 8) {
-        co = bn16_fwd_coeffs(threadIdx.x, blk, c, s_tot, gamma_v, beta_v, inv_count, unbias, eps);
-        s_scale[threadIdx.x] = co.sc;
-        s_shift[threadIdx.x] = co.sh;
-    }
-    __syncthreads();
-    if (threadIdx.x < 8 && chunk == 0) bn16_fwd_publish(threadIdx.x, blk, c, co, save_mean, save_invstd, moving_mean, moving_var, momentum);
+    const Bn16Span span(a.n, a.hw, a.c8, blk, chunk, a.chunks);
+    const int ch = blk * 8 + (int)threadIdx.x;
+    const bool coef = threadIdx.x < 8 && ch < a.c;
+    const float gamma_v = coef ? a.chan.gamma[ch] : 0.f, beta_v = coef ? a.chan.beta[ch] : 0.f;
     float sc[8], sh[8];
+    const float floor_v = a.relu ? 0.f : -__builtin_inff();
+    const u32x4_t keep = bn16_channel_mask(blk, a.c);  // padding channels leave as zeros whatever the operands hold there
+    u32x4_t* __restrict__ y = a.y;
+    bn16_stream(
+        span, a.z, a.res, a.res != nullptr,
+        [&] {
+            bn16_fold_parts(a.pre, blk, a.n_parts, s_tot, s_sm);
+            Bn16Coeffs co = {0.f, 0.f, 0.f, 0.f, 0.f};
+            if (threadIdx.x < 8) {
+                co = bn16_fwd_coeffs(threadIdx.x, blk, a.c, s_tot, gamma_v, beta_v, a.inv_count, a.unbias, a.eps);
+                s_scale[threadIdx.x] = co.sc;
+                s_shift[threadIdx.x] = co.sh;
+            }
+            __syncthreads();
+            if (coef && chunk == 0) bn_fwd_publish(ch, co.mean, co.invstd, co.var_unbiased, a.out);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { sc[j] = s_scale[j]; sh[j] = s_shift[j]; }  // 0 / 0 on the padding channels: they stay zero
-    const float floor_v = relu ? 0.f : -__builtin_inff();
-    const u32x4_t keep = bn16_channel_mask(blk, c);  // padding channels leave as zeros whatever the operands hold there
-    auto apply = [&](const u32x4_t zq, const u32x4_t rq, size_t i) {
-        const h16x8 zv = __builtin_bit_cast(h16x8, zq), rv = __builtin_bit_cast(h16x8, rq);
-        h16x8 o;
+            for (int j = 0; j < 8; ++j) { sc[j] = s_scale[j]; sh[j] = s_shift[j]; }  // 0 / 0 on the padding channels: they stay zero
+        },
+        [&](const u32x4_t zq, const u32x4_t rq, size_t i) {
+            const h16x8 zv = __builtin_bit_cast(h16x8, zq), rv = __builtin_bit_cast(h16x8, rq);
+            h16x8 o;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            float v = bn16_affine((float)zv[j], sc[j], sh[j]);
-            v += (float)rv[j];  // zeros without a residual: exact
-            o[j] = (_Float16)fmaxf(v, floor_v);
-        }
-        y[i] = __builtin_bit_cast(u32x4_t, o) & keep;
-    };
-    for (unsigned base = e0; base < e1; base += 256u * kBatch) {
-        u32x4_t nz[kBatch], nr[kBatch];
-        size_t ni[kBatch];
-        const bool more = base + 256u * kBatch < e1;  // uniform
-        if (more) request(base + 256u * kBatch, nz, nr, ni);
-#pragma unroll
-        for (int k = 0; k < kBatch; ++k)
-            if (base + threadIdx.x + 256u * k < e1) apply(cz[k], cr[k], ci[k]);
-        if (more) {
-#pragma unroll
-            for (int k = 0; k < kBatch; ++k) { cz[k] = nz[k]; cr[k] = nr[k]; ci[k] = ni[k]; }
-        }
-    }
+            for (int j = 0; j < 8; ++j) {
+                float v = bn16_affine((float)zv[j], sc[j], sh[j]);
+                v += (float)rv[j];  // zeros without a residual: exact
+                o[j] = (_Float16)fmaxf(v, floor_v);
+            }
+            y[i] = __builtin_bit_cast(u32x4_t, o) & keep;
+        });
 }
 
-__global__ __launch_bounds__(256) void bn16_apply_pre_kernel(const u32x4_t* __restrict__ z, const float* __restrict__ pre, int n_parts,
-                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                             float* __restrict__ save_mean, float* __restrict__ save_invstd,
-                                                             float* __restrict__ moving_mean, float* __restrict__ moving_var,
-                                                             const u32x4_t* __restrict__ res, u32x4_t* __restrict__ y, int n, int c,
-                                                             int c8, int hw, double inv_count, double unbias, float eps, float momentum,
-                                                             int relu) {
-    bn16_apply_pre_body(z, pre, n_parts, gamma, beta, save_mean, save_invstd, moving_mean, moving_var, res, y, n, c, c8, hw, inv_count,
-                        unbias, eps, momentum, relu, (int)blockIdx.x, blockIdx.y, gridDim.y);
-}
+__global__ __launch_bounds__(256) void bn16_apply_pre_kernel(const Bn16FwdArgs a) { bn16_apply_pre_body(a, (int)blockIdx.x, blockIdx.y); }
 
 // ---- grouped apply passes: up to four BatchNorms of ONE step of parallel chains (the k-th BatchNorm of every branch of an HRModule,
 // hrnet.py:202-241) as one launch.  On the 32x24 ... 8x6 maps an apply pass is ~9 - 14 us of launch, fold and tail around 1 - 3 us of
 // streaming; the branches' passes are independent, so a flat grid of [job 0's blocks | job 1's | ...] runs them under the largest
-// one.  The job table travels by value; a block picks its job with compares on constant indices (no dynamic index into the
+// one.  The job table travels by value; a block picks its whole record with compares on constant indices (no dynamic index into the
 // argument struct - that would put it in scratch).
 constexpr int kBnJobs = 4;
-struct Bn16FwdJobs {
-    const u32x4_t* z[kBnJobs]; const float* pre[kBnJobs]; const float* gamma[kBnJobs]; const float* beta[kBnJobs];
-    float* save_mean[kBnJobs]; float* save_invstd[kBnJobs]; float* moving_mean[kBnJobs]; float* moving_var[kBnJobs];
-    const u32x4_t* res[kBnJobs]; u32x4_t* y[kBnJobs];
-    double inv_count[kBnJobs], unbias[kBnJobs];
-    int n_parts[kBnJobs], n[kBnJobs], c[kBnJobs], c8[kBnJobs], hw[kBnJobs], relu[kBnJobs];
-    unsigned chunks[kBnJobs], first[kBnJobs];  // first block of the job in the flat grid (0xFFFFFFFF: no such job)
-    float eps, momentum;
-};
-#define MP_BN_PICK(t, a, j) ((j) == 0 ? (t).a[0] : (j) == 1 ? (t).a[1] : (j) == 2 ? (t).a[2] : (t).a[3])
-
-__global__ __launch_bounds__(256) void bn16_apply_pre_grouped_kernel(const Bn16FwdJobs t) {
+template <class Args> struct Bn16Jobs { Args job[kBnJobs]; };
+// the job of this block: the last one whose first block is not behind it
+__device__ __forceinline__ int bn16_job_of_block(unsigned first1, unsigned first2, unsigned first3) {
     const unsigned b = blockIdx.x;
-    const int j = (b >= t.first[1] ? 1 : 0) + (b >= t.first[2] ? 1 : 0) + (b >= t.first[3] ? 1 : 0);
-    const unsigned local = b - MP_BN_PICK(t, first, j);
-    const int c8 = MP_BN_PICK(t, c8, j);
-    bn16_apply_pre_body(MP_BN_PICK(t, z, j), MP_BN_PICK(t, pre, j), MP_BN_PICK(t, n_parts, j), MP_BN_PICK(t, gamma, j),
-                        MP_BN_PICK(t, beta, j), MP_BN_PICK(t, save_mean, j), MP_BN_PICK(t, save_invstd, j), MP_BN_PICK(t, moving_mean, j),
-                        MP_BN_PICK(t, moving_var, j), MP_BN_PICK(t, res, j), MP_BN_PICK(t, y, j), MP_BN_PICK(t, n, j), MP_BN_PICK(t, c, j), c8,
-                        MP_BN_PICK(t, hw, j), MP_BN_PICK(t, inv_count, j), MP_BN_PICK(t, unbias, j), t.eps, t.momentum,
-                        MP_BN_PICK(t, relu, j), (int)(local % (unsigned)c8), local / (unsigned)c8, MP_BN_PICK(t, chunks, j));
+    return (b >= first1 ? 1 : 0) + (b >= first2 ? 1 : 0) + (b >= first3 ? 1 : 0);
+}
+
+__global__ __launch_bounds__(256) void bn16_apply_pre_grouped_kernel(const Bn16Jobs<Bn16FwdArgs> t) {
+    const int j = bn16_job_of_block(t.job[1].first, t.job[2].first, t.job[3].first);
+    // picked on the kernel argument itself: through a reference to the table the compiler copies the table to scratch
+    const Bn16FwdArgs a = j == 0 ? t.job[0] : j == 1 ? t.job[1] : j == 2 ? t.job[2] : t.job[3];
+    const unsigned local = blockIdx.x - a.first;
+    bn16_apply_pre_body(a, (int)(local % (unsigned)a.c8), local / (unsigned)a.c8);
 }
 
 // backward apply on a PRE-MASKED gradient g with sum g, sum g * z folded from the data-gradient conv's partials:
 // dz = gamma * invstd * (g - mean(g) - xhat * mean(g * xhat)); the residual branch's gradient is g itself (nothing to write)
-__device__ __forceinline__ void bn16_bwd_apply_pre_body(const u32x4_t* __restrict__ g_in, const u32x4_t* __restrict__ z,
-                                                        const float* __restrict__ pre, int n_parts, const float* __restrict__ gamma,
-                                                        const float* __restrict__ mean, const float* __restrict__ invstd,
-                                                        float* __restrict__ dgamma, float* __restrict__ dbeta,
-                                                        float* __restrict__ dgamma_acc, float* __restrict__ dbeta_acc,
-                                                        u32x4_t* __restrict__ dz, int n, int c, int c8, int hw, float inv_count, int blk,
-                                                        unsigned chunk, unsigned chunks) {
+__device__ __forceinline__ void bn16_bwd_apply_pre_body(const Bn16BwdArgs& a, int blk, unsigned chunk) {
     __shared__ double s_tot[16];
     __shared__ double s_sm[4][16];
     __shared__ float s_k[8], s_mu[8], s_is[8], s_mb[8], s_mg[8];
-    const unsigned per_blk = (unsigned)n * (unsigned)hw;
-    const unsigned len = (per_blk + chunks - 1) / chunks;
-    const unsigned e0 = chunk * len, e1 = e0 + len < per_blk ? e0 + len : per_blk;
-    const unsigned magic_hw = hw > 1 ? (unsigned)(0x100000000ULL / (unsigned)hw) + 1u : 0u;
-    const bool exact = (unsigned long long)per_blk * (unsigned)hw < 0x100000000ULL;
-    const size_t blk_off = (size_t)blk * hw, img_extra = (size_t)(c8 - 1) * hw;
-    auto index_of = [&](unsigned e) {
-        const unsigned img = hw <= 1 ? e : (exact ? __umulhi(e, magic_hw) : e / (unsigned)hw);
-        return (size_t)e + (size_t)img * img_extra + blk_off;
-    };
-    constexpr int kBatch = 4;  // batched requests, the first batch before the fold (see bn16_apply_pre_kernel)
-    const u32x4_t zero4 = (u32x4_t){0u, 0u, 0u, 0u};
-    u32x4_t cg[kBatch], cz[kBatch];
-    size_t ci[kBatch];
-    auto request = [&](unsigned base, u32x4_t (&qg)[kBatch], u32x4_t (&qz)[kBatch], size_t (&qi)[kBatch]) {
-#pragma unroll
-        for (int k = 0; k < kBatch; ++k) {
-            const unsigned e = base + threadIdx.x + 256u * k;
-            const bool ok = e < e1;
-            qi[k] = index_of(ok ? e : e0);
-            qg[k] = ok ? g_in[qi[k]] : zero4;
-            qz[k] = ok ? z[qi[k]] : zero4;
-        }
-    };
+    const Bn16Span span(a.n, a.hw, a.c8, blk, chunk, a.chunks);
     // the per-channel parameters are requested first: their latency runs under the fold's (they used to be a second, dependent
     // round trip behind it)
-    const bool coef = threadIdx.x < 8 && blk * 8 + (int)threadIdx.x < c;
-    const float mean_v = coef ? mean[blk * 8 + threadIdx.x] : 0.f, invstd_v = coef ? invstd[blk * 8 + threadIdx.x] : 0.f;
-    const float gamma_v = coef ? gamma[blk * 8 + threadIdx.x] : 0.f;
-    request(e0, cg, cz, ci);
-    bn16_fold_parts(pre, blk, n_parts, s_tot, s_sm);
-    float db = 0.f, dg = 0.f;
-    if (threadIdx.x < 8) {
-        const int j = threadIdx.x;
-        float k = 0.f, mu = 0.f, is = 0.f, mb = 0.f, mg = 0.f;
-        if (coef) {
-            mu = mean_v;
-            is = invstd_v;
-            // the conv epilogue summed g and g * z (raw z): sum g * xhat = invstd * (sum g z - mean * sum g), in fp64
-            db = (float)s_tot[2 * j];
-            dg = (float)((s_tot[2 * j + 1] - (double)mu * s_tot[2 * j]) * (double)is);
-            k = gamma_v * is;
-            mb = db * inv_count;
-            mg = dg * inv_count;
-        }
-        s_k[j] = k; s_mu[j] = mu; s_is[j] = is; s_mb[j] = mb; s_mg[j] = mg;
-    }
-    __syncthreads();
-    if (coef && chunk == 0) {  // parameter gradients: published behind the barrier (the accumulating form reads the arena first)
-        const int ch = blk * 8 + threadIdx.x;
-        dbeta[ch] = db;
-        dgamma[ch] = dg;
-        if (dgamma_acc && dbeta_acc) {
-            dbeta_acc[ch] += db;
-            dgamma_acc[ch] += dg;
-        }
-    }
+    const int ch = blk * 8 + (int)threadIdx.x;
+    const bool coef = threadIdx.x < 8 && ch < a.c;
+    const float mean_v = coef ? a.chan.mean[ch] : 0.f, invstd_v = coef ? a.chan.invstd[ch] : 0.f;
+    const float gamma_v = coef ? a.chan.gamma[ch] : 0.f;
     float k[8], mu[8], is[8], mb[8], mg[8];
+    const u32x4_t keep = bn16_channel_mask(blk, a.c);  // padding channels leave as zeros whatever the operands hold there
+    u32x4_t* __restrict__ dz = a.dz;
+    bn16_stream(
+        span, a.g, a.z, true,
+        [&] {
+            bn16_fold_parts(a.pre, blk, a.n_parts, s_tot, s_sm);
+            float db = 0.f, dg = 0.f;
+            if (threadIdx.x < 8) {
+                const int j = threadIdx.x;
+                float k_v = 0.f, mb_v = 0.f, mg_v = 0.f;  // mean_v / invstd_v are zero on a padding channel already
+                if (coef) {
+                    // the conv epilogue summed g and g * z (raw z): sum g * xhat = invstd * (sum g z - mean * sum g), in fp64
+                    db = (float)s_tot[2 * j];
+                    dg = (float)((s_tot[2 * j + 1] - (double)mean_v * s_tot[2 * j]) * (double)invstd_v);
+                    k_v = gamma_v * invstd_v;
+                    mb_v = db * a.inv_count;
+                    mg_v = dg * a.inv_count;
+                }
+                s_k[j] = k_v; s_mu[j] = mean_v; s_is[j] = invstd_v; s_mb[j] = mb_v; s_mg[j] = mg_v;
+            }
+            __syncthreads();
+            // parameter gradients: published behind the barrier (the accumulating form reads the arena first)
+            if (coef && chunk == 0) bn_bwd_publish(ch, db, dg, a.out);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { k[j] = s_k[j]; mu[j] = s_mu[j]; is[j] = s_is[j]; mb[j] = s_mb[j]; mg[j] = s_mg[j]; }  // zeros on padding channels
-    const u32x4_t keep = bn16_channel_mask(blk, c);  // padding channels leave as zeros whatever the operands hold there
-    auto apply = [&](const u32x4_t gq, const u32x4_t zq, size_t i) {
-        const h16x8 gv = __builtin_bit_cast(h16x8, gq), zv = __builtin_bit_cast(h16x8, zq);
-        h16x8 oz;
+            for (int j = 0; j < 8; ++j) { k[j] = s_k[j]; mu[j] = s_mu[j]; is[j] = s_is[j]; mb[j] = s_mb[j]; mg[j] = s_mg[j]; }  // zeros on padding channels
+        },
+        [&](const u32x4_t gq, const u32x4_t zq, size_t i) {
+            const h16x8 gv = __builtin_bit_cast(h16x8, gq), zv = __builtin_bit_cast(h16x8, zq);
+            h16x8 oz;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const float xh = ((float)zv[j] - mu[j]) * is[j];
-            oz[j] = (_Float16)(k[j] * ((float)gv[j] - mb[j] - xh * mg[j]));
-        }
-        dz[i] = __builtin_bit_cast(u32x4_t, oz) & keep;
-    };
-    for (unsigned base = e0; base < e1; base += 256u * kBatch) {
-        u32x4_t ng[kBatch], nz[kBatch];
-        size_t ni[kBatch];
-        const bool more = base + 256u * kBatch < e1;  // uniform
-        if (more) request(base + 256u * kBatch, ng, nz, ni);
-#pragma unroll
-        for (int q = 0; q < kBatch; ++q)
-            if (base + threadIdx.x + 256u * q < e1) apply(cg[q], cz[q], ci[q]);
-        if (more) {
-#pragma unroll
-            for (int q = 0; q < kBatch; ++q) { cg[q] = ng[q]; cz[q] = nz[q]; ci[q] = ni[q]; }
-        }
-    }
+            for (int j = 0; j < 8; ++j) oz[j] = (_Float16)bn_dz(k[j], (float)gv[j], mb[j], bn_xhat((float)zv[j], mu[j], is[j]), mg[j]);
+            dz[i] = __builtin_bit_cast(u32x4_t, oz) & keep;
+        });
 }
 
-__global__ __launch_bounds__(256) void bn16_bwd_apply_pre_kernel(const u32x4_t* __restrict__ g_in, const u32x4_t* __restrict__ z,
-                                                                 const float* __restrict__ pre, int n_parts,
-                                                                 const float* __restrict__ gamma, const float* __restrict__ mean,
-                                                                 const float* __restrict__ invstd, float* __restrict__ dgamma,
-                                                                 float* __restrict__ dbeta, float* __restrict__ dgamma_acc,
-                                                                 float* __restrict__ dbeta_acc, u32x4_t* __restrict__ dz, int n, int c,
-                                                                 int c8, int hw, float inv_count) {
-    bn16_bwd_apply_pre_body(g_in, z, pre, n_parts, gamma, mean, invstd, dgamma, dbeta, dgamma_acc, dbeta_acc, dz, n, c, c8, hw, inv_count,
-                            (int)blockIdx.x, blockIdx.y, gridDim.y);
-}
+__global__ __launch_bounds__(256) void bn16_bwd_apply_pre_kernel(const Bn16BwdArgs a) { bn16_bwd_apply_pre_body(a, (int)blockIdx.x, blockIdx.y); }
 
-struct Bn16BwdJobs {
-    const u32x4_t* g[kBnJobs]; const u32x4_t* z[kBnJobs]; const float* pre[kBnJobs]; const float* gamma[kBnJobs];
-    const float* mean[kBnJobs]; const float* invstd[kBnJobs]; float* dgamma[kBnJobs]; float* dbeta[kBnJobs];
-    float* dgamma_acc[kBnJobs]; float* dbeta_acc[kBnJobs]; u32x4_t* dz[kBnJobs];
-    float inv_count[kBnJobs];
-    int n_parts[kBnJobs], n[kBnJobs], c[kBnJobs], c8[kBnJobs], hw[kBnJobs];
-    unsigned chunks[kBnJobs], first[kBnJobs];
-};
-
-__global__ __launch_bounds__(256) void bn16_bwd_apply_pre_grouped_kernel(const Bn16BwdJobs t) {
-    const unsigned b = blockIdx.x;
-    const int j = (b >= t.first[1] ? 1 : 0) + (b >= t.first[2] ? 1 : 0) + (b >= t.first[3] ? 1 : 0);
-    const unsigned local = b - MP_BN_PICK(t, first, j);
-    const int c8 = MP_BN_PICK(t, c8, j);
-    bn16_bwd_apply_pre_body(MP_BN_PICK(t, g, j), MP_BN_PICK(t, z, j), MP_BN_PICK(t, pre, j), MP_BN_PICK(t, n_parts, j),
-                            MP_BN_PICK(t, gamma, j), MP_BN_PICK(t, mean, j), MP_BN_PICK(t, invstd, j), MP_BN_PICK(t, dgamma, j),
-                            MP_BN_PICK(t, dbeta, j), MP_BN_PICK(t, dgamma_acc, j), MP_BN_PICK(t, dbeta_acc, j), MP_BN_PICK(t, dz, j),
-                            MP_BN_PICK(t, n, j), MP_BN_PICK(t, c, j), c8, MP_BN_PICK(t, hw, j), MP_BN_PICK(t, inv_count, j),
-                            (int)(local % (unsigned)c8), local / (unsigned)c8, MP_BN_PICK(t, chunks, j));
+__global__ __launch_bounds__(256) void bn16_bwd_apply_pre_grouped_kernel(const Bn16Jobs<Bn16BwdArgs> t) {
+    const int j = bn16_job_of_block(t.job[1].first, t.job[2].first, t.job[3].first);
+    // picked on the kernel argument itself: through a reference to the table the compiler copies the table to scratch
+    const Bn16BwdArgs a = j == 0 ? t.job[0] : j == 1 ? t.job[1] : j == 2 ? t.job[2] : t.job[3];
+    const unsigned local = blockIdx.x - a.first;
+    bn16_bwd_apply_pre_body(a, (int)(local % (unsigned)a.c8), local / (unsigned)a.c8);
 }
 
 // ---- small maps: both passes of a BatchNorm direction in ONE launch --------------------------------------------------------------
@@ -1041,7 +1033,8 @@ __device__ __forceinline__ void coop_channel_sums(const double* part, int ch, in
     }
 }
 
-// grid (C8, S): block (blk, sp) owns elements [e0, e1) of the flat (image, pixel) space of channel block blk
+// grid (C8, S): block (blk, sp) owns elements [e0, e1) of the flat (image, pixel) space of channel block blk.
+// mean_io / invstd_io: published by the forward, read by the backward; yres: the residual (forward) or y (backward, relu 1)
 template <bool BWD>
 __global__ __launch_bounds__(256) void bn16_coop_kernel(const u32x4_t* __restrict__ dy, const u32x4_t* __restrict__ z,
                                                         const u32x4_t* __restrict__ yres, const float* __restrict__ gamma,
@@ -1054,67 +1047,27 @@ __global__ __launch_bounds__(256) void bn16_coop_kernel(const u32x4_t* __restric
                                                         unsigned long long* __restrict__ counter, int n, int c, int c8, int hw, int relu,
                                                         float eps, float momentum) {
     const int blk = blockIdx.x, sp = blockIdx.y, nsplit = gridDim.y;
-    const unsigned per_blk = (unsigned)n * (unsigned)hw;
-    const unsigned len = (per_blk + nsplit - 1) / nsplit;
-    const unsigned e0 = sp * len, e1 = e0 + len < per_blk ? e0 + len : per_blk;
-    const unsigned magic_hw = hw > 1 ? (unsigned)(0x100000000ULL / (unsigned)hw) + 1u : 0u;
-    const bool exact = (unsigned long long)per_blk * (unsigned)hw < 0x100000000ULL;
-    const size_t blk_off = (size_t)blk * hw, img_extra = (size_t)(c8 - 1) * hw;
-    auto index_of = [&](unsigned e) {
-        const unsigned img = hw <= 1 ? e : (exact ? __umulhi(e, magic_hw) : e / (unsigned)hw);
-        return (size_t)e + (size_t)img * img_extra + blk_off;
-    };
-    float mu[8], is[8], msc[8], msh[8];  // msc / msh: forward scale / shift for the recomputed ReLU mask (relu == 2)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int ch = blk * 8 + j;
-        mu[j] = (BWD && ch < c) ? mean_io[ch] : 0.f;
-        is[j] = (BWD && ch < c) ? invstd_io[ch] : 0.f;
-        msc[j] = (BWD && relu == 2 && ch < c) ? gamma[ch] * is[j] : 0.f;
-        msh[j] = (BWD && relu == 2 && ch < c) ? bn16_shift(beta[ch], mu[j], msc[j]) : 0.f;
-    }
+    const Bn16Span span(n, hw, c8, blk, sp, nsplit);
+    const BnChannels chan = {gamma, beta, mean_io, invstd_io};
+    const BnStatOut stats = {mean_io, invstd_io, moving_mean, moving_var, momentum};
+    const BnGradOut grads = {dgamma, dbeta, dgamma_acc, dbeta_acc};
+    const Bn16GradLanes L = bn16_grad_lanes<BWD>(blk, c, relu, chan);
     // ---- pass 1: partial sums of this slice
     float f[16];
 #pragma unroll
     for (int j = 0; j < 16; ++j) f[j] = 0.f;
 #pragma unroll 4
-    for (unsigned e = e0 + threadIdx.x; e < e1; e += 256) {
-        const size_t i = index_of(e);
-        const h16x8 zv = __builtin_bit_cast(h16x8, z[i]);
-        if (BWD) {
-            const h16x8 gv = __builtin_bit_cast(h16x8, dy[i]);
-            h16x8 yv = zv;
-            if (relu == 1) yv = __builtin_bit_cast(h16x8, yres[i]);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                float g = (float)gv[j];
-                if (relu == 1 && !((float)yv[j] > 0.f)) g = 0.f;
-                if (relu == 2 && !bn16_relu_open((float)zv[j], msc[j], msh[j])) g = 0.f;
-                f[2 * j] += g;
-                f[2 * j + 1] += g * (((float)zv[j] - mu[j]) * is[j]);
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float v = (float)zv[j];
-                f[2 * j] += v;
-                f[2 * j + 1] += v * v;
-            }
-        }
-    }
-    double acc[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) acc[j] = (double)f[j];
-    __shared__ double sm[4][16];
-    block_sum16_256(acc, sm);
+    for (unsigned e = span.e0 + threadIdx.x; e < span.e1; e += 256)
+        bn16_accumulate<BWD>(f, bn16_load<BWD>(z, dy, yres, span.index_of(e), relu), relu, L);
+    const double total = bn16_accumulated(f);
     if (threadIdx.x < 16) {
         const int ch = blk * 8 + (threadIdx.x >> 1);
-        if (ch < c) __hip_atomic_store(part + ((size_t)ch * nsplit + sp) * 2 + (threadIdx.x & 1), acc[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (ch < c) __hip_atomic_store(part + ((size_t)ch * nsplit + sp) * 2 + (threadIdx.x & 1), total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     // only the workgroups of ONE channel block depend on each other: one barrier slot per channel block, gridDim.y arrivals each
     // (an arrival is a cross-XCD atomic, ~70 ns serialised per address: 128 arrivals on one slot cost ~9 us)
     const bool ok = grid_barrier(counter + (size_t)blk * 16, gridDim.y);
-    // ---- totals of the 8 channels, per-channel constants
+    // ---- totals of the 8 channels, per-channel constants: (scale, shift, -) forward, bn_dz's (k, mb, mg) backward
     __shared__ float s_a[8], s_b[8], s_c[8];
     {
         const int j = threadIdx.x >> 5, ch = blk * 8 + j;
@@ -1125,33 +1078,15 @@ __global__ __launch_bounds__(256) void bn16_coop_kernel(const u32x4_t* __restric
             if (ch < c) {
                 if (BWD) {
                     const float db = (float)s0, dg = (float)s1, inv_count = (float)(1.0 / ((double)n * hw));
-                    a = gamma[ch] * is[j];   // k
-                    b = db * inv_count;      // mean of g
-                    cc = dg * inv_count;     // mean of g * xhat
-                    if (sp == 0) {
-                        dbeta[ch] = db;
-                        dgamma[ch] = dg;
-                        if (dgamma_acc && dbeta_acc) {
-                            dbeta_acc[ch] += db;
-                            dgamma_acc[ch] += dg;
-                        }
-                    }
+                    a = chan.gamma[ch] * chan.invstd[ch];
+                    b = db * inv_count;
+                    cc = dg * inv_count;
+                    if (sp == 0) bn_bwd_publish(ch, db, dg, grads);
                 } else {
-                    const double count = (double)n * hw, mean = s0 / count;
-                    double var = s1 / count - mean * mean;
-                    if (var < 0.0) var = 0.0;
-                    const float invstd = (float)(1.0 / sqrt(var + (double)eps));
-                    a = gamma[ch] * invstd;
-                    b = bn16_shift(beta[ch], (float)mean, a);
-                    if (sp == 0) {
-                        mean_io[ch] = (float)mean;
-                        invstd_io[ch] = invstd;
-                        if (moving_mean) {
-                            const double unbiased = count > 1.0 ? var * count / (count - 1.0) : var;
-                            moving_mean[ch] = momentum * moving_mean[ch] + (1.f - momentum) * (float)mean;
-                            moving_var[ch] = momentum * moving_var[ch] + (1.f - momentum) * (float)unbiased;
-                        }
-                    }
+                    const BnStats st = bn_stats(s0, s1, (double)n * hw, eps);
+                    a = chan.gamma[ch] * st.invstd;
+                    b = bn16_shift(chan.beta[ch], (float)st.mean, a);
+                    if (sp == 0) bn_fwd_publish(ch, (float)st.mean, st.invstd, st.var_unbiased(), stats);
                 }
                 if (!ok) a = b = cc = __builtin_nanf("");  // barrier timed out: poison, never hang
             }
@@ -1159,48 +1094,23 @@ __global__ __launch_bounds__(256) void bn16_coop_kernel(const u32x4_t* __restric
         }
     }
     __syncthreads();
-    float ka[8], kb[8], kc[8];
+    Bn16DzLanes D;  // forward: k = scale, mb = shift
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { ka[j] = s_a[j]; kb[j] = s_b[j]; kc[j] = s_c[j]; }
+    for (int j = 0; j < 8; ++j) { D.k[j] = s_a[j]; D.mb[j] = s_b[j]; D.mg[j] = s_c[j]; }
     // ---- pass 2 over the same slice (L2-resident)
 #pragma unroll 4
-    for (unsigned e = e0 + threadIdx.x; e < e1; e += 256) {
-        const size_t i = index_of(e);
-        const h16x8 zv = __builtin_bit_cast(h16x8, z[i]);
-        h16x8 o, og;
+    for (unsigned e = span.e0 + threadIdx.x; e < span.e1; e += 256) {
+        const size_t i = span.index_of(e);
         if (BWD) {
-            const h16x8 gv = __builtin_bit_cast(h16x8, dy[i]);
-            h16x8 yv = zv;
-            if (relu == 1) yv = __builtin_bit_cast(h16x8, yres[i]);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                float g = 0.f, d = 0.f;
-                if (blk * 8 + j < c) {
-                    g = (float)gv[j];
-                    if (relu == 1 && !((float)yv[j] > 0.f)) g = 0.f;
-                if (relu == 2 && !bn16_relu_open((float)zv[j], msc[j], msh[j])) g = 0.f;
-                    const float xh = ((float)zv[j] - mu[j]) * is[j];
-                    d = ka[j] * (g - kb[j] - xh * kc[j]);
-                }
-                o[j] = (_Float16)d;
-                og[j] = (_Float16)g;
-            }
-            out[i] = __builtin_bit_cast(u32x4_t, o);
-            if (dres) dres[i] = __builtin_bit_cast(u32x4_t, og);
+            u32x4_t oz, og;
+            bn16_bwd_elem(bn16_load<true>(z, dy, yres, i, relu), relu, blk, c, L, D, oz, og);
+            out[i] = oz;
+            if (dres) dres[i] = og;
         } else {
+            const h16x8 zv = __builtin_bit_cast(h16x8, z[i]);
             h16x8 rv = zv;
             if (yres) rv = __builtin_bit_cast(h16x8, yres[i]);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                float v = 0.f;
-                if (blk * 8 + j < c) {
-                    v = bn16_affine((float)zv[j], ka[j], kb[j]);
-                    if (yres) v += (float)rv[j];
-                    if (relu) v = fmaxf(v, 0.f);
-                }
-                o[j] = (_Float16)v;
-            }
-            out[i] = __builtin_bit_cast(u32x4_t, o);
+            out[i] = bn16_fwd_elem(zv, rv, yres != nullptr, relu, blk, c, D.k, D.mb);
         }
     }
 }
@@ -1325,12 +1235,8 @@ __global__ __launch_bounds__(256) void sum_tensors_kernel(const u32x4_t* __restr
 // g = value * [y > 0] stored, partial sums of g and g * z per (channel block, chunk) in the conv epilogue's layout
 // [C8][chunks][8][2] fp32.  Fixed partition, fixed order: bit-reproducible.
 __device__ __forceinline__ void ew_stats_tail(float (&f)[16], float* __restrict__ part, int blk, int chunk, int n_parts) {
-    double acc[16];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) acc[j] = (double)f[j];
-    __shared__ double sm[4][16];
-    block_sum16_256(acc, sm);
-    if (threadIdx.x < 16) part[((size_t)blk * n_parts + chunk) * 16 + threadIdx.x] = (float)acc[0];
+    const double total = bn16_accumulated(f);
+    if (threadIdx.x < 16) part[((size_t)blk * n_parts + chunk) * 16 + threadIdx.x] = (float)total;
 }
 
 // out = fp16(((a + b) + c) + d) * [y > 0]  (mp_sum_tensors' arithmetic, then the mask)
@@ -1340,19 +1246,13 @@ __global__ __launch_bounds__(256) void sum_tensors16_stats_kernel(const u32x4_t*
                                                                   u32x4_t* __restrict__ out, float* __restrict__ part, int n, int c8,
                                                                   int hw, int relu) {
     const int blk = blockIdx.x;
-    const unsigned per_blk = (unsigned)n * (unsigned)hw;
-    const unsigned len = (per_blk + gridDim.y - 1) / gridDim.y;
-    const unsigned e0 = blockIdx.y * len, e1 = e0 + len < per_blk ? e0 + len : per_blk;
-    const unsigned magic_hw = hw > 1 ? (unsigned)(0x100000000ULL / (unsigned)hw) + 1u : 0u;
-    const bool exact = (unsigned long long)per_blk * (unsigned)hw < 0x100000000ULL;
-    const size_t blk_off = (size_t)blk * hw, img_extra = (size_t)(c8 - 1) * hw;
+    const Bn16Span span(n, hw, c8, blk, blockIdx.y, gridDim.y);
     float f[16];
 #pragma unroll
     for (int j = 0; j < 16; ++j) f[j] = 0.f;
 #pragma unroll 2
-    for (unsigned e = e0 + threadIdx.x; e < e1; e += 256) {
-        const unsigned img = hw <= 1 ? e : (exact ? __umulhi(e, magic_hw) : e / (unsigned)hw);
-        const size_t i = (size_t)e + (size_t)img * img_extra + blk_off;
+    for (unsigned e = span.e0 + threadIdx.x; e < span.e1; e += 256) {
+        const size_t i = span.index_of(e);
         const h16x8 ha = __builtin_bit_cast(h16x8, a[i]), hb = __builtin_bit_cast(h16x8, b[i]);
         h16x8 hc = ha, hd = ha;
         if (c) hc = __builtin_bit_cast(h16x8, c[i]);
@@ -1464,6 +1364,107 @@ static int log2_exact_t(int v) {
     return -1;
 }
 
+// pixel-range chunks per channel block of the statistics-free apply kernels.  These passes are bound by the bytes they keep in
+// flight (a thread has 4 x 16 B per operand tensor outstanding), not by the n_parts x 64 bytes of partials every block folds first:
+// ~1024 blocks (four per CU) of >= 1024 elements measured best on every map size of the HRNet step - 512 fatter blocks ran the
+// 64x48 maps at 2.2 TB/s, 1024 at 3.3 TB/s; 2048 and more lose again to the redundant folds (round 3 sweep with MP_BN_PRE_BLOCKS / MP_BN_PRE_MIN, tools/ab_train.sh).
+static unsigned bn16_pre_chunks(int n, int c8, int hw) {
+    size_t total = 1024, floor_elems = 1024;
+    if (const char* e = knob("MP_BN_PRE_BLOCKS")) total = (size_t)atoi(e);
+    if (const char* e = knob("MP_BN_PRE_MIN")) floor_elems = (size_t)atoi(e);
+    size_t chunks = (total + c8 - 1) / c8;
+    const size_t per_blk = (size_t)n * hw;
+    while (chunks > 1 && per_blk / chunks < floor_elems) --chunks;
+    return (unsigned)chunks;
+}
+
+// more slots than a consumer block folds: reduce them to one per channel block (into the workspace)
+static int bn16_prefold(const float*& pre, int& n_parts, int c8, void* workspace, hipStream_t s) {
+    int above = kMaxFoldParts;
+    if (const char* e = knob("MP_BN_PREFOLD_ABOVE")) above = atoi(e);
+    if (n_parts <= above) return MP_OK;
+    float* folded = reinterpret_cast<float*>(workspace);
+    hipLaunchKernelGGL(bn16_fold_kernel, dim3(c8, kFoldSplit), dim3(256), 0, s, pre, folded, n_parts);
+    pre = folded;
+    n_parts = kFoldSplit;
+    return check_launch();
+}
+
+// the accumulating pair is taken only when both are given
+static BnGradOut bn_grad_out(float* dgamma, float* dbeta, float* dgamma_acc, float* dbeta_acc) {
+    const bool acc = dgamma_acc && dbeta_acc;
+    return {dgamma, dbeta, acc ? dgamma_acc : nullptr, acc ? dbeta_acc : nullptr};
+}
+
+// What an fp16 BatchNorm entry checks, in the order it checks it, and the argument record its kernels take - one function per
+// direction, for the one-layer entries and for every job of the grouped ones (an entry's arguments travel in the job's form).
+// An apply-only entry also folds its partial slots when a block would not (bn16_prefold) - at fold_off of the workspace, which
+// jobs of one grouped call may share (chains on one stream): job j folds into its own region behind those of the jobs before it.
+enum Bn16Entry { kBn16Reducing, kBn16ApplyOnly, kBn16Finalize };
+// the apply-only part of either direction: the partial slots (folded first when a block would not), the chunks of the grid
+template <class Args, class Job> static int bn16_fill_pre(Args& a, const Job& q, size_t fold_off, hipStream_t s) {
+    if (q.workspace_bytes < fold_off + (size_t)a.c8 * kFoldSplit * 16 * sizeof(float)) return MP_ERR_WORKSPACE;
+    a.pre = q.partials_dev;
+    a.n_parts = q.n_parts;
+    a.chunks = bn16_pre_chunks(q.n, a.c8, q.hw);
+    return bn16_prefold(a.pre, a.n_parts, a.c8, reinterpret_cast<char*>(q.workspace_dev) + fold_off, s);
+}
+static int bn16_fwd_fill(Bn16FwdArgs& a, const mp_f16_bn_fwd_job& q, Bn16Entry kind, float eps, float momentum, size_t fold_off, hipStream_t s) {
+    const bool pre = kind != kBn16Reducing;
+    if ((kind != kBn16Finalize && (!q.z_dev || !q.y_dev)) || !q.gamma_dev || !q.beta_dev || !q.save_mean_dev || !q.save_invstd_dev ||
+        (pre && !q.partials_dev))
+        return MP_ERR_NULL;
+    if ((q.moving_mean_dev == nullptr) != (q.moving_var_dev == nullptr)) return MP_ERR_NULL;
+    if (q.n <= 0 || q.c <= 0 || q.hw <= 0 || (pre && q.n_parts <= 0)) return MP_ERR_SHAPE;
+    if (!q.workspace_dev || q.workspace_bytes < mp_bn_workspace_bytes(q.c)) return MP_ERR_WORKSPACE;
+    a = Bn16FwdArgs{};
+    a.z = reinterpret_cast<const u32x4_t*>(q.z_dev);
+    a.res = reinterpret_cast<const u32x4_t*>(q.res_dev);
+    a.y = reinterpret_cast<u32x4_t*>(q.y_dev);
+    a.chan = {q.gamma_dev, q.beta_dev, nullptr, nullptr};
+    a.out = {q.save_mean_dev, q.save_invstd_dev, q.moving_mean_dev, q.moving_var_dev, momentum};
+    a.eps = eps;
+    a.n = q.n, a.c = q.c, a.c8 = (q.c + 7) / 8, a.hw = q.hw, a.relu = q.relu ? 1 : 0;
+    const double cnt = (double)q.n * q.hw;
+    a.inv_count = 1.0 / cnt;
+    a.unbias = cnt > 1.0 ? cnt / (cnt - 1.0) : 1.0;
+    return pre ? bn16_fill_pre(a, q, fold_off, s) : MP_OK;
+}
+
+// y / beta / dres / relu: the reducing entry's (an apply-only entry takes its gradient pre-masked: relu 0)
+static int bn16_bwd_fill(Bn16BwdArgs& a, const mp_f16_bn_bwd_job& q, const void* y, const float* beta, void* dres, int relu, bool pre,
+                         size_t fold_off, hipStream_t s) {
+    if (!q.g_dev || !q.z_dev || !q.gamma_dev || !q.save_mean_dev || !q.save_invstd_dev || !q.dz_dev || !q.dgamma_dev || !q.dbeta_dev ||
+        (pre && !q.partials_dev))
+        return MP_ERR_NULL;
+    // ReLU mask: from the stored output y - or, for a layer without residual input, re-derived from z with the forward arithmetic
+    // (y == NULL, beta given): y is then not read at all
+    if (relu && !y && (!beta || dres)) return MP_ERR_NULL;
+    if (q.n <= 0 || q.c <= 0 || q.hw <= 0 || (pre && q.n_parts <= 0)) return MP_ERR_SHAPE;
+    if (!q.workspace_dev || q.workspace_bytes < mp_bn_workspace_bytes(q.c)) return MP_ERR_WORKSPACE;
+    a = Bn16BwdArgs{};
+    a.g = reinterpret_cast<const u32x4_t*>(q.g_dev);
+    a.z = reinterpret_cast<const u32x4_t*>(q.z_dev);
+    a.y = reinterpret_cast<const u32x4_t*>(y);
+    a.dz = reinterpret_cast<u32x4_t*>(q.dz_dev);
+    a.dres = reinterpret_cast<u32x4_t*>(dres);
+    a.chan = {q.gamma_dev, beta, q.save_mean_dev, q.save_invstd_dev};
+    a.out = bn_grad_out(q.dgamma_dev, q.dbeta_dev, q.dgamma_acc_dev, q.dbeta_acc_dev);
+    a.inv_count = (float)(1.0 / ((double)q.n * q.hw));
+    a.n = q.n, a.c = q.c, a.c8 = (q.c + 7) / 8, a.hw = q.hw, a.relu = relu ? (y ? 1 : 2) : 0;
+    return pre ? bn16_fill_pre(a, q, fold_off, s) : MP_OK;
+}
+
+// the flat grid of a grouped launch: job j's blocks start at `first`; table entries behind the last job are never picked
+template <class Args> static unsigned bn16_place_jobs(Bn16Jobs<Args>& t, int n_jobs) {
+    unsigned total = 0;
+    for (int j = 0; j < kBnJobs; ++j) {
+        t.job[j].first = j < n_jobs ? total : 0xFFFFFFFFu;
+        if (j < n_jobs) total += (unsigned)t.job[j].c8 * t.job[j].chunks;
+    }
+    return total;
+}
+
 }  // namespace mp
 
 using namespace mp;
@@ -1515,10 +1516,9 @@ int mp_bn_train_bwd_acc(const float* dy, const float* z, const float* y, const f
                        hw, relu ? 1 : 0);
     int rc = check_launch();
     if (rc != MP_OK) return rc;
-    const bool acc = dgamma_acc && dbeta_acc;
+    const BnGradOut acc = bn_grad_out(dgamma, dbeta, dgamma_acc, dbeta_acc);
     hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(n * c), dim3(256), 0, s, dy, z, y, part, gamma, save_mean, save_invstd, dgamma, dbeta,
-                       acc ? dgamma_acc : nullptr, acc ? dbeta_acc : nullptr, dz, dres, c, hw, relu ? 1 : 0,
-                       (float)(1.0 / ((double)n * hw)));
+                       acc.dgamma_acc, acc.dbeta_acc, dz, dres, c, hw, relu ? 1 : 0, (float)(1.0 / ((double)n * hw)));
     return check_launch();
 }
 
@@ -1536,8 +1536,7 @@ int mp_fuse_upsample_sum_bwd(const float* dy, const float* out, float* dbase, fl
         const size_t total = (size_t)n * c * (h >> sh) * (w >> sh);
         size_t blocks = (total + 255) / 256;
         if (blocks > 256 * 32) blocks = 256 * 32;
-        hipLaunchKernelGGL(fuse_sum_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, s, dy, out, nullptr, dts[k], n * c, h, w, sh,
-                           relu ? 1 : 0);
+        hipLaunchKernelGGL(fuse_sum_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, s, dy, out, dts[k], n * c, h, w, sh, relu ? 1 : 0);
         int rc = check_launch();
         if (rc != MP_OK) return rc;
     }
@@ -1576,195 +1575,129 @@ int mp_optimizer_step(int kind, float* param, const float* grad, float* state1, 
     return check_launch();
 }
 
-int mp_f16_bn_train_fwd(const void* z, const float* gamma, const float* beta, const void* res, void* y, float* save_mean,
-                        float* save_invstd, float* moving_mean, float* moving_var, int n, int c, int hw, float eps, float momentum,
-                        int relu, void* workspace, size_t workspace_bytes, mp_stream_t stream) {
-    if (!z || !gamma || !beta || !y || !save_mean || !save_invstd) return MP_ERR_NULL;
-    if ((moving_mean == nullptr) != (moving_var == nullptr)) return MP_ERR_NULL;
-    if (n <= 0 || c <= 0 || hw <= 0) return MP_ERR_SHAPE;
-    if (!workspace || workspace_bytes < mp_bn_workspace_bytes(c)) return MP_ERR_WORKSPACE;
-    double* part = reinterpret_cast<double*>(workspace);
-    const int c8 = (c + 7) / 8;
-    hipStream_t s = as_stream(stream);
+// The reducing forms of a validated record (bn16_fwd_fill / bn16_bwd_fill): every kernel argument comes from the record, none from the
+// entry's own parameters.  Small map: both passes in one launch; otherwise reduce, then apply.
+static int bn16_fwd_reducing(const Bn16FwdArgs& a, double* part, hipStream_t s) {
+    const BnChannels& ch = a.chan;
+    const BnStatOut& o = a.out;
     int coop_split;
-    if (unsigned long long* counter = bn16_coop_plan(n, c8, hw, s, coop_split)) {  // small map: both passes in one launch
-        hipLaunchKernelGGL(bn16_coop_kernel<false>, dim3(c8, coop_split), dim3(256), 0, s, nullptr, reinterpret_cast<const u32x4_t*>(z),
-                           reinterpret_cast<const u32x4_t*>(res), gamma, beta, save_mean, save_invstd, moving_mean, moving_var, nullptr,
-                           nullptr, nullptr, nullptr, reinterpret_cast<u32x4_t*>(y), nullptr, part, counter, n, c, c8, hw, relu ? 1 : 0,
-                           eps, momentum);
+    if (unsigned long long* counter = bn16_coop_plan(a.n, a.c8, a.hw, s, coop_split)) {
+        hipLaunchKernelGGL(bn16_coop_kernel<false>, dim3(a.c8, coop_split), dim3(256), 0, s, nullptr, a.z, a.res, ch.gamma, ch.beta, o.save_mean,
+                           o.save_invstd, o.moving_mean, o.moving_var, nullptr, nullptr, nullptr, nullptr, a.y, nullptr, part, counter, a.n, a.c,
+                           a.c8, a.hw, a.relu, a.eps, o.momentum);
         return check_launch();
     }
     int gi, gp;
-    bn16_split(n, c8, hw, gi, gp);
-    float* scale = reinterpret_cast<float*>(part + (size_t)c * kBn16MaxSplit * 2);
-    float* shift = scale + c;
-    hipLaunchKernelGGL(bn16_reduce_kernel<false>, dim3(c8, gi * gp), dim3(256), 0, s, nullptr, reinterpret_cast<const u32x4_t*>(z),
-                       nullptr, nullptr, nullptr, nullptr, nullptr, part, n, c, c8, hw, 0, gi, gp);
-    int rc = check_launch();
+    bn16_split(a.n, a.c8, a.hw, gi, gp);
+    hipLaunchKernelGGL(bn16_reduce_kernel<false>, dim3(a.c8, gi * gp), dim3(256), 0, s, nullptr, a.z, nullptr, nullptr, nullptr, nullptr,
+                       nullptr, part, a.n, a.c, a.c8, a.hw, 0, gi, gp);
+    const int rc = check_launch();
     if (rc != MP_OK) return rc;
-    (void)scale; (void)shift;
-    hipLaunchKernelGGL(bn16_apply_kernel, dim3(c8, bn16_apply_chunks(n, c8, hw)), dim3(256), 0, s, reinterpret_cast<const u32x4_t*>(z),
-                       part, gamma, beta, save_mean, save_invstd, moving_mean, moving_var, reinterpret_cast<const u32x4_t*>(res),
-                       reinterpret_cast<u32x4_t*>(y), n, c, c8, hw, gi * gp, (double)n * hw, eps, momentum, relu ? 1 : 0);
+    hipLaunchKernelGGL(bn16_apply_kernel, dim3(a.c8, bn16_apply_chunks(a.n, a.c8, a.hw)), dim3(256), 0, s, a.z, part, ch.gamma, ch.beta,
+                       o.save_mean, o.save_invstd, o.moving_mean, o.moving_var, a.res, a.y, a.n, a.c, a.c8, a.hw, gi * gp,
+                       (double)a.n * a.hw, a.eps, o.momentum, a.relu);
     return check_launch();
+}
+
+static int bn16_bwd_reducing(const Bn16BwdArgs& a, double* part, hipStream_t s) {
+    const BnChannels& ch = a.chan;
+    const BnGradOut& o = a.out;
+    int coop_split;
+    if (unsigned long long* counter = bn16_coop_plan(a.n, a.c8, a.hw, s, coop_split)) {
+        hipLaunchKernelGGL(bn16_coop_kernel<true>, dim3(a.c8, coop_split), dim3(256), 0, s, a.g, a.z, a.y, ch.gamma, ch.beta,
+                           const_cast<float*>(ch.mean), const_cast<float*>(ch.invstd), nullptr, nullptr, o.dgamma, o.dbeta, o.dgamma_acc,
+                           o.dbeta_acc, a.dz, a.dres, part, counter, a.n, a.c, a.c8, a.hw, a.relu, 0.f, 0.f);
+        return check_launch();
+    }
+    int gi, gp;
+    bn16_split(a.n, a.c8, a.hw, gi, gp);
+    hipLaunchKernelGGL(bn16_reduce_kernel<true>, dim3(a.c8, gi * gp), dim3(256), 0, s, a.g, a.z, a.y, ch.mean, ch.invstd, ch.gamma, ch.beta,
+                       part, a.n, a.c, a.c8, a.hw, a.relu, gi, gp);
+    const int rc = check_launch();
+    if (rc != MP_OK) return rc;
+    hipLaunchKernelGGL(bn16_bwd_apply_kernel, dim3(a.c8, bn16_apply_chunks(a.n, a.c8, a.hw)), dim3(256), 0, s, a.g, a.z, a.y, part, ch.gamma,
+                       ch.mean, ch.invstd, o.dgamma, o.dbeta, o.dgamma_acc, o.dbeta_acc, a.dz, a.dres, a.n, a.c, a.c8, a.hw, gi * gp, a.relu,
+                       a.inv_count, ch.beta);
+    return check_launch();
+}
+
+int mp_f16_bn_train_fwd(const void* z, const float* gamma, const float* beta, const void* res, void* y, float* save_mean,
+                        float* save_invstd, float* moving_mean, float* moving_var, int n, int c, int hw, float eps, float momentum,
+                        int relu, void* workspace, size_t workspace_bytes, mp_stream_t stream) {
+    const mp_f16_bn_fwd_job q = {z, gamma, beta, res, y, save_mean, save_invstd, moving_mean, moving_var, nullptr, workspace, workspace_bytes,
+                                 n, c, hw, relu, 0, 0};
+    hipStream_t s = as_stream(stream);
+    Bn16FwdArgs a;
+    const int rc = bn16_fwd_fill(a, q, kBn16Reducing, eps, momentum, 0, s);
+    return rc != MP_OK ? rc : bn16_fwd_reducing(a, reinterpret_cast<double*>(workspace), s);
 }
 
 int mp_f16_bn_train_bwd(const void* dy, const void* z, const void* y, const float* gamma, const float* beta, const float* save_mean,
                         const float* save_invstd, void* dz, void* dres, float* dgamma, float* dbeta, float* dgamma_acc, float* dbeta_acc,
                         int n, int c, int hw, int relu, void* workspace, size_t workspace_bytes, mp_stream_t stream) {
-    if (!dy || !z || !gamma || !save_mean || !save_invstd || !dz || !dgamma || !dbeta) return MP_ERR_NULL;
-    // ReLU mask: from the stored output y - or, for a layer without residual input, re-derived from z with the forward arithmetic
-    // (y == NULL, beta given): y is then not read at all
-    if (relu && !y && (!beta || dres)) return MP_ERR_NULL;
-    relu = relu ? (y ? 1 : 2) : 0;
-    if (n <= 0 || c <= 0 || hw <= 0) return MP_ERR_SHAPE;
-    if (!workspace || workspace_bytes < mp_bn_workspace_bytes(c)) return MP_ERR_WORKSPACE;
-    double* part = reinterpret_cast<double*>(workspace);
-    const int c8 = (c + 7) / 8;
+    const mp_f16_bn_bwd_job q = {dy, z, gamma, save_mean, save_invstd, dz, dgamma, dbeta, dgamma_acc, dbeta_acc, nullptr, workspace,
+                                 workspace_bytes, n, c, hw, 0};
     hipStream_t s = as_stream(stream);
-    int coop_split;
-    if (unsigned long long* counter = bn16_coop_plan(n, c8, hw, s, coop_split)) {  // small map: both passes in one launch
-        const bool acc2 = dgamma_acc && dbeta_acc;
-        hipLaunchKernelGGL(bn16_coop_kernel<true>, dim3(c8, coop_split), dim3(256), 0, s, reinterpret_cast<const u32x4_t*>(dy),
-                           reinterpret_cast<const u32x4_t*>(z), reinterpret_cast<const u32x4_t*>(y), gamma, beta,
-                           const_cast<float*>(save_mean), const_cast<float*>(save_invstd), nullptr, nullptr, dgamma, dbeta,
-                           acc2 ? dgamma_acc : nullptr, acc2 ? dbeta_acc : nullptr, reinterpret_cast<u32x4_t*>(dz),
-                           reinterpret_cast<u32x4_t*>(dres), part, counter, n, c, c8, hw, relu, 0.f, 0.f);
-        return check_launch();
-    }
-    int gi, gp;
-    bn16_split(n, c8, hw, gi, gp);
-    hipLaunchKernelGGL(bn16_reduce_kernel<true>, dim3(c8, gi * gp), dim3(256), 0, s, reinterpret_cast<const u32x4_t*>(dy),
-                       reinterpret_cast<const u32x4_t*>(z), reinterpret_cast<const u32x4_t*>(y), save_mean, save_invstd, gamma, beta,
-                       part, n, c, c8, hw, relu, gi, gp);
-    int rc = check_launch();
-    if (rc != MP_OK) return rc;
-    const bool acc = dgamma_acc && dbeta_acc;
-    hipLaunchKernelGGL(bn16_bwd_apply_kernel, dim3(c8, bn16_apply_chunks(n, c8, hw)), dim3(256), 0, s,
-                       reinterpret_cast<const u32x4_t*>(dy), reinterpret_cast<const u32x4_t*>(z), reinterpret_cast<const u32x4_t*>(y),
-                       part, gamma, save_mean, save_invstd, dgamma, dbeta, acc ? dgamma_acc : nullptr, acc ? dbeta_acc : nullptr,
-                       reinterpret_cast<u32x4_t*>(dz), reinterpret_cast<u32x4_t*>(dres), n, c, c8, hw, gi * gp, relu,
-                       (float)(1.0 / ((double)n * hw)), beta);
-    return check_launch();
-}
-
-// pixel-range chunks per channel block of the statistics-free apply kernels.  These passes are bound by the bytes they keep in
-// flight (a thread has 4 x 16 B per operand tensor outstanding), not by the n_parts x 64 bytes of partials every block folds first:
-// ~1024 blocks (four per CU) of >= 1024 elements measured best on every map size of the HRNet step - 512 fatter blocks ran the
-// 64x48 maps at 2.2 TB/s, 1024 at 3.3 TB/s; 2048 and more lose again to the redundant folds (round 3 sweep with MP_BN_PRE_BLOCKS / MP_BN_PRE_MIN, tools/ab_train.sh).
-static unsigned bn16_pre_chunks(int n, int c8, int hw, int n_parts) {
-    (void)n_parts;
-    size_t total = 1024, floor_elems = 1024;
-    if (const char* e = knob("MP_BN_PRE_BLOCKS")) total = (size_t)atoi(e);
-    if (const char* e = knob("MP_BN_PRE_MIN")) floor_elems = (size_t)atoi(e);
-    size_t chunks = (total + c8 - 1) / c8;
-    const size_t per_blk = (size_t)n * hw;
-    while (chunks > 1 && per_blk / chunks < floor_elems) --chunks;
-    return (unsigned)chunks;
-}
-
-// more slots than a consumer block folds: reduce them to one per channel block (into the workspace)
-static int bn16_prefold(const float*& pre, int& n_parts, int c8, void* workspace, hipStream_t s) {
-    int above = kMaxFoldParts;
-    if (const char* e = knob("MP_BN_PREFOLD_ABOVE")) above = atoi(e);
-    if (n_parts <= above) return MP_OK;
-    float* folded = reinterpret_cast<float*>(workspace);
-    hipLaunchKernelGGL(bn16_fold_kernel, dim3(c8, kFoldSplit), dim3(256), 0, s, pre, folded, n_parts);
-    pre = folded;
-    n_parts = kFoldSplit;
-    return check_launch();
+    Bn16BwdArgs a;
+    const int rc = bn16_bwd_fill(a, q, y, beta, dres, relu, false, 0, s);
+    return rc != MP_OK ? rc : bn16_bwd_reducing(a, reinterpret_cast<double*>(workspace), s);
 }
 
 int mp_f16_bn_train_fwd_stats(const void* z, const float* gamma, const float* beta, const void* res, void* y, float* save_mean,
                               float* save_invstd, float* moving_mean, float* moving_var, int n, int c, int hw, float eps,
                               float momentum, int relu, const float* partials, int n_parts, void* workspace, size_t workspace_bytes,
                               mp_stream_t stream) {
-    if (!z || !gamma || !beta || !y || !save_mean || !save_invstd || !partials) return MP_ERR_NULL;
-    if ((moving_mean == nullptr) != (moving_var == nullptr)) return MP_ERR_NULL;
-    if (n <= 0 || c <= 0 || hw <= 0 || n_parts <= 0) return MP_ERR_SHAPE;
-    if (!workspace || workspace_bytes < mp_bn_workspace_bytes(c)) return MP_ERR_WORKSPACE;
-    const int c8 = (c + 7) / 8;
+    const mp_f16_bn_fwd_job q = {z, gamma, beta, res, y, save_mean, save_invstd, moving_mean, moving_var, partials, workspace, workspace_bytes,
+                                 n, c, hw, relu, n_parts, 0};
     hipStream_t s = as_stream(stream);
-    int rc = bn16_prefold(partials, n_parts, c8, workspace, s);
+    Bn16FwdArgs a;
+    const int rc = bn16_fwd_fill(a, q, kBn16ApplyOnly, eps, momentum, 0, s);
     if (rc != MP_OK) return rc;
-    hipLaunchKernelGGL(bn16_apply_pre_kernel, dim3(c8, bn16_pre_chunks(n, c8, hw, n_parts)), dim3(256), 0, s, reinterpret_cast<const u32x4_t*>(z),
-                       partials, n_parts, gamma, beta, save_mean, save_invstd, moving_mean, moving_var,
-                       reinterpret_cast<const u32x4_t*>(res), reinterpret_cast<u32x4_t*>(y), n, c, c8, hw, 1.0 / ((double)n * hw),
-                       (double)n * hw > 1.0 ? ((double)n * hw) / ((double)n * hw - 1.0) : 1.0, eps, momentum, relu ? 1 : 0);
+    hipLaunchKernelGGL(bn16_apply_pre_kernel, dim3(a.c8, a.chunks), dim3(256), 0, s, a);
     return check_launch();
 }
 
 int mp_f16_bn_train_finalize(const float* gamma, const float* beta, float* save_mean, float* save_invstd, float* moving_mean,
                              float* moving_var, int n, int c, int hw, float eps, float momentum, const float* partials, int n_parts,
                              float* scale, float* shift, void* workspace, size_t workspace_bytes, mp_stream_t stream) {
-    if (!gamma || !beta || !save_mean || !save_invstd || !partials || !scale || !shift) return MP_ERR_NULL;
-    if ((moving_mean == nullptr) != (moving_var == nullptr)) return MP_ERR_NULL;
-    if (n <= 0 || c <= 0 || hw <= 0 || n_parts <= 0) return MP_ERR_SHAPE;
-    if (!workspace || workspace_bytes < mp_bn_workspace_bytes(c)) return MP_ERR_WORKSPACE;
-    const int c8 = (c + 7) / 8;
+    if (!scale || !shift) return MP_ERR_NULL;
+    const mp_f16_bn_fwd_job q = {nullptr, gamma, beta, nullptr, nullptr, save_mean, save_invstd, moving_mean, moving_var, partials, workspace,
+                                 workspace_bytes, n, c, hw, 0, n_parts, 0};
     hipStream_t s = as_stream(stream);
-    int rc = bn16_prefold(partials, n_parts, c8, workspace, s);
+    Bn16FwdArgs a;
+    const int rc = bn16_fwd_fill(a, q, kBn16Finalize, eps, momentum, 0, s);
     if (rc != MP_OK) return rc;
-    hipLaunchKernelGGL(bn16_finalize_kernel, dim3(c8), dim3(256), 0, s, partials, n_parts, gamma, beta, save_mean, save_invstd, moving_mean,
-                       moving_var, scale, shift, c, 1.0 / ((double)n * hw),
-                       (double)n * hw > 1.0 ? ((double)n * hw) / ((double)n * hw - 1.0) : 1.0, eps, momentum);
+    hipLaunchKernelGGL(bn16_finalize_kernel, dim3(a.c8), dim3(256), 0, s, a, scale, shift);
     return check_launch();
 }
 
 int mp_f16_bn_train_bwd_stats(const void* g, const void* z, const float* gamma, const float* save_mean, const float* save_invstd,
                               void* dz, float* dgamma, float* dbeta, float* dgamma_acc, float* dbeta_acc, int n, int c, int hw,
                               const float* partials, int n_parts, void* workspace, size_t workspace_bytes, mp_stream_t stream) {
-    if (!g || !z || !gamma || !save_mean || !save_invstd || !dz || !dgamma || !dbeta || !partials) return MP_ERR_NULL;
-    if (n <= 0 || c <= 0 || hw <= 0 || n_parts <= 0) return MP_ERR_SHAPE;
-    if (!workspace || workspace_bytes < mp_bn_workspace_bytes(c)) return MP_ERR_WORKSPACE;
-    const int c8 = (c + 7) / 8;
+    const mp_f16_bn_bwd_job q = {g, z, gamma, save_mean, save_invstd, dz, dgamma, dbeta, dgamma_acc, dbeta_acc, partials, workspace,
+                                 workspace_bytes, n, c, hw, n_parts};
     hipStream_t s = as_stream(stream);
-    int rc = bn16_prefold(partials, n_parts, c8, workspace, s);
+    Bn16BwdArgs a;
+    const int rc = bn16_bwd_fill(a, q, nullptr, nullptr, nullptr, 0, true, 0, s);
     if (rc != MP_OK) return rc;
-    const bool acc = dgamma_acc && dbeta_acc;
-    hipLaunchKernelGGL(bn16_bwd_apply_pre_kernel, dim3(c8, bn16_pre_chunks(n, c8, hw, n_parts)), dim3(256), 0, s,
-                       reinterpret_cast<const u32x4_t*>(g), reinterpret_cast<const u32x4_t*>(z), partials, n_parts, gamma, save_mean,
-                       save_invstd, dgamma, dbeta, acc ? dgamma_acc : nullptr, acc ? dbeta_acc : nullptr, reinterpret_cast<u32x4_t*>(dz),
-                       n, c, c8, hw, (float)(1.0 / ((double)n * hw)));
+    hipLaunchKernelGGL(bn16_bwd_apply_pre_kernel, dim3(a.c8, a.chunks), dim3(256), 0, s, a);
     return check_launch();
 }
 
 // Grouped apply passes (kernels above): job j must satisfy what the one-layer entries check; a job with more than kMaxFoldParts
-// partial slots is folded by its own bn16_fold_kernel launch first (its workspace).
+// partial slots is folded by its own bn16_fold_kernel launch first (its region of the workspace).
 int mp_f16_bn_train_fwd_stats_grouped(const mp_f16_bn_fwd_job* jobs, int n_jobs, float eps, float momentum, mp_stream_t stream) {
     if (!jobs) return MP_ERR_NULL;
     if (n_jobs < 1 || n_jobs > kBnJobs) return MP_ERR_SHAPE;
     hipStream_t s = as_stream(stream);
-    Bn16FwdJobs t{};
-    unsigned total = 0;
+    Bn16Jobs<Bn16FwdArgs> t{};
     size_t fold_off = 0;
-    for (int j = 0; j < kBnJobs; ++j) t.first[j] = 0xFFFFFFFFu;
     for (int j = 0; j < n_jobs; ++j) {
-        const mp_f16_bn_fwd_job& q = jobs[j];
-        if (!q.z_dev || !q.gamma_dev || !q.beta_dev || !q.y_dev || !q.save_mean_dev || !q.save_invstd_dev || !q.partials_dev) return MP_ERR_NULL;
-        if ((q.moving_mean_dev == nullptr) != (q.moving_var_dev == nullptr)) return MP_ERR_NULL;
-        if (q.n <= 0 || q.c <= 0 || q.hw <= 0 || q.n_parts <= 0) return MP_ERR_SHAPE;
-        if (!q.workspace_dev || q.workspace_bytes < mp_bn_workspace_bytes(q.c)) return MP_ERR_WORKSPACE;
-        const int c8 = (q.c + 7) / 8;
-        const float* pre = q.partials_dev;
-        int n_parts = q.n_parts;
-        // jobs may share one workspace (chains on one stream): job j folds into its own region behind those of the jobs before it
-        if (q.workspace_bytes < fold_off + (size_t)c8 * kFoldSplit * 16 * sizeof(float)) return MP_ERR_WORKSPACE;
-        const int rc = bn16_prefold(pre, n_parts, c8, reinterpret_cast<char*>(q.workspace_dev) + fold_off, s);
+        const int rc = bn16_fwd_fill(t.job[j], jobs[j], kBn16ApplyOnly, eps, momentum, fold_off, s);
         if (rc != MP_OK) return rc;
-        fold_off += ((size_t)c8 * kFoldSplit * 16 * sizeof(float) + 255) / 256 * 256;
-        const double cnt = (double)q.n * q.hw;
-        t.z[j] = reinterpret_cast<const u32x4_t*>(q.z_dev); t.pre[j] = pre; t.gamma[j] = q.gamma_dev; t.beta[j] = q.beta_dev;
-        t.save_mean[j] = q.save_mean_dev; t.save_invstd[j] = q.save_invstd_dev; t.moving_mean[j] = q.moving_mean_dev;
-        t.moving_var[j] = q.moving_var_dev; t.res[j] = reinterpret_cast<const u32x4_t*>(q.res_dev); t.y[j] = reinterpret_cast<u32x4_t*>(q.y_dev);
-        t.inv_count[j] = 1.0 / cnt; t.unbias[j] = cnt > 1.0 ? cnt / (cnt - 1.0) : 1.0;
-        t.n_parts[j] = n_parts; t.n[j] = q.n; t.c[j] = q.c; t.c8[j] = c8; t.hw[j] = q.hw; t.relu[j] = q.relu ? 1 : 0;
-        t.chunks[j] = bn16_pre_chunks(q.n, c8, q.hw, n_parts);
-        t.first[j] = total;
-        total += (unsigned)c8 * t.chunks[j];
+        fold_off += ((size_t)t.job[j].c8 * kFoldSplit * 16 * sizeof(float) + 255) / 256 * 256;
     }
-    for (int j = n_jobs; j < kBnJobs; ++j) { t.c8[j] = 1; t.chunks[j] = 1; }
-    t.eps = eps; t.momentum = momentum;
+    const unsigned total = bn16_place_jobs(t, n_jobs);
     hipLaunchKernelGGL(bn16_apply_pre_grouped_kernel, dim3(total), dim3(256), 0, s, t);
     return check_launch();
 }
@@ -1773,36 +1706,14 @@ int mp_f16_bn_train_bwd_stats_grouped(const mp_f16_bn_bwd_job* jobs, int n_jobs,
     if (!jobs) return MP_ERR_NULL;
     if (n_jobs < 1 || n_jobs > kBnJobs) return MP_ERR_SHAPE;
     hipStream_t s = as_stream(stream);
-    Bn16BwdJobs t{};
-    unsigned total = 0;
+    Bn16Jobs<Bn16BwdArgs> t{};
     size_t fold_off = 0;
-    for (int j = 0; j < kBnJobs; ++j) t.first[j] = 0xFFFFFFFFu;
     for (int j = 0; j < n_jobs; ++j) {
-        const mp_f16_bn_bwd_job& q = jobs[j];
-        if (!q.g_dev || !q.z_dev || !q.gamma_dev || !q.save_mean_dev || !q.save_invstd_dev || !q.dz_dev || !q.dgamma_dev || !q.dbeta_dev ||
-            !q.partials_dev)
-            return MP_ERR_NULL;
-        if (q.n <= 0 || q.c <= 0 || q.hw <= 0 || q.n_parts <= 0) return MP_ERR_SHAPE;
-        if (!q.workspace_dev || q.workspace_bytes < mp_bn_workspace_bytes(q.c)) return MP_ERR_WORKSPACE;
-        const int c8 = (q.c + 7) / 8;
-        const float* pre = q.partials_dev;
-        int n_parts = q.n_parts;
-        if (q.workspace_bytes < fold_off + (size_t)c8 * kFoldSplit * 16 * sizeof(float)) return MP_ERR_WORKSPACE;
-        const int rc = bn16_prefold(pre, n_parts, c8, reinterpret_cast<char*>(q.workspace_dev) + fold_off, s);
+        const int rc = bn16_bwd_fill(t.job[j], jobs[j], nullptr, nullptr, nullptr, 0, true, fold_off, s);
         if (rc != MP_OK) return rc;
-        fold_off += ((size_t)c8 * kFoldSplit * 16 * sizeof(float) + 255) / 256 * 256;
-        const bool acc = q.dgamma_acc_dev && q.dbeta_acc_dev;
-        t.g[j] = reinterpret_cast<const u32x4_t*>(q.g_dev); t.z[j] = reinterpret_cast<const u32x4_t*>(q.z_dev); t.pre[j] = pre;
-        t.gamma[j] = q.gamma_dev; t.mean[j] = q.save_mean_dev; t.invstd[j] = q.save_invstd_dev; t.dgamma[j] = q.dgamma_dev;
-        t.dbeta[j] = q.dbeta_dev; t.dgamma_acc[j] = acc ? q.dgamma_acc_dev : nullptr; t.dbeta_acc[j] = acc ? q.dbeta_acc_dev : nullptr;
-        t.dz[j] = reinterpret_cast<u32x4_t*>(q.dz_dev);
-        t.inv_count[j] = (float)(1.0 / ((double)q.n * q.hw));
-        t.n_parts[j] = n_parts; t.n[j] = q.n; t.c[j] = q.c; t.c8[j] = c8; t.hw[j] = q.hw;
-        t.chunks[j] = bn16_pre_chunks(q.n, c8, q.hw, n_parts);
-        t.first[j] = total;
-        total += (unsigned)c8 * t.chunks[j];
+        fold_off += ((size_t)t.job[j].c8 * kFoldSplit * 16 * sizeof(float) + 255) / 256 * 256;
     }
-    for (int j = n_jobs; j < kBnJobs; ++j) { t.c8[j] = 1; t.chunks[j] = 1; }
+    const unsigned total = bn16_place_jobs(t, n_jobs);
     hipLaunchKernelGGL(bn16_bwd_apply_pre_grouped_kernel, dim3(total), dim3(256), 0, s, t);
     return check_launch();
 }
