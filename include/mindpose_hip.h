@@ -707,6 +707,35 @@ int mp_bottomup_match_by_tag(const float* val_k_dev, const float* tag_k_dev, con
                              float* people_dev, int* counts_dev, int* status_dev, void* workspace_dev, size_t workspace_bytes,
                              mp_stream_t stream);
 
+/* mp_bottomup_finish_people (bottomup_ops.hip; the tail of mindpose/engine/inferencer/bottomup_inferencer.py:120-150 and :189-250 for a
+ * batch): per-person score, mean tag and the missing-joint refinement of the persons mp_bottomup_match_by_tag left in device
+ * memory, with no host value that depends on how many there are.  people [n, k * m, k, 3 + L], counts [n] and status [n] are that
+ * entry's outputs, untouched; heatmap_raw [n, k, h, w] and tagging [n, ktag, h, w, L] the decoder's (ktag = k with tag_per_joint,
+ * else 1).  Both grids are sized from the capacity k * m; every workgroup reads counts[i], clamped to [0, k * m], and status[i]
+ * itself and exits for p >= counts[i] or status[i] != 0: rows of people beyond counts[i] are never read, and nothing of an image
+ * that was handed over (status != 0) is read or written.
+ *   Launch A, one wave64 per (person, image): scores [n, k * m] = np.mean of the person's value column (person[:, 2], k values)
+ *     and, in the workspace, the mean tag [n, k * m, L] over the joints with value > 0 in joint order, followed by the number of
+ *     those joints [n, k * m] (int32).  The tag of joint j is read at column (int)x, row (int)y of the person's row j - truncated
+ *     toward zero, then clamped to the map, a NaN coordinate reading column / row 0 - from tag channel j (channel 0 without
+ *     tag_per_joint).  Both means are numpy's float32 ones (rule (b) of bottomup_match.hip): a 1-D view - the score and the mean
+ *     tag with L == 1 - sums sequentially from 0 below eight values and with eight accumulators over whole blocks of eight, combined
+ *     ((r0+r1)+(r2+r3)) + ((r4+r5)+(r6+r7)), the tail added in order, from eight on; L >= 2 sums sequentially in joint order from
+ *     the first tag; then one float32 division by the number of values.
+ *   Launch B, with refine != 0 only, behind A in stream order, one workgroup per (joint, person, image): for the joints with
+ *     person[j, 2] == 0 of a person with at least one located joint, the arg-max of mp_bottomup_refine_missing (the same device
+ *     function) against the person's mean tag; when the winner's heat-map value is > 0, person[j, 0:3] = (x, y, value) in place.
+ *     Every other workgroup exits after reading counts, status and one value.  Each (joint, person) scans its own map: (1 + L) * h * w
+ *     * 4 bytes per MISSING joint, none for a located one.
+ * Deterministic, no atomics.  workspace >= mp_bottomup_finish_workspace_bytes (0 outside the limits).
+ * Before any HIP call: n == 0 -> MP_OK without a launch; NULL -> MP_ERR_NULL; n < 0 or n > 65535, non-positive k, m, h, w or
+ * num_tags, or a map of 2^31 or more pixels -> MP_ERR_SHAPE; k > 64, m > 64, L > 4 or k * m > 1024 (the grouping entry's limits) ->
+ * MP_ERR_UNSUPPORTED; a missing or short workspace -> MP_ERR_WORKSPACE. */
+size_t mp_bottomup_finish_workspace_bytes(int n, int k, int m, int num_tags);
+int mp_bottomup_finish_people(float* people_dev, const int* counts_dev, const int* status_dev, const float* heatmap_raw_dev,
+                              const float* tagging_dev, int n, int k, int m, int h, int w, int tag_per_joint, int num_tags, int refine,
+                              float* scores_dev, void* workspace_dev, size_t workspace_bytes, mp_stream_t stream);
+
 /* ---- bottom-up training ends: masked heat-map MSE, associative-embedding loss, target generation (bottomup_train_ops.hip) -------
  * Every entry validates before any HIP call (NULL -> MP_ERR_NULL, bad extents / strides -> MP_ERR_SHAPE), fully writes its
  * outputs and is deterministic: no atomics, fixed-order reductions.

@@ -211,6 +211,8 @@ _PROTOTYPES = {
     "mp_bottomup_match_workspace_bytes": (c_size_t, [c_int] * 4),
     "mp_bottomup_match_by_tag": (c_int, [c_f32p] * 3 + [c_int] * 4 + [ctypes.POINTER(ctypes.c_int), ctypes.c_float, ctypes.c_float, c_int,
                                          c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_size_t, ctypes.c_void_p]),
+    "mp_bottomup_finish_workspace_bytes": (c_size_t, [c_int] * 4),
+    "mp_bottomup_finish_people": (c_int, [c_f32p] * 5 + [c_int] * 8 + [c_f32p, c_f32p, c_size_t, ctypes.c_void_p]),
     "mp_resize_pad_normalize": (c_int, [c_f32p] * 3 + [ctypes.POINTER(ctypes.c_int)] + [c_f32p] * 2 + [c_int] * 3
                                 + [ctypes.POINTER(ctypes.c_float)] * 2 + [ctypes.c_void_p]),
     "mp_bottomup_train_augment": (c_int, [c_f32p] * 7 + [ctypes.POINTER(ctypes.c_int)] + [c_f32p] * 2 + [c_int] * 6

@@ -37,6 +37,9 @@
 // divided by their count.  Tags come from the scale-1 run alone.  mp_resize_bilinear_nchw makes the scaled inputs with the same
 // resize_bilinear sample, so a source pixel q sits on s * q of the scaled image and the map resize reads exactly there.
 //
+// Behind the grouping (bottomup_match.hip) the file also holds the missing-joint refinement (bu_refine_kernel) and the tail of a
+// batch on the persons the grouping left in device memory (bu_finish_score_kernel, bu_finish_refine_kernel); see their own comments.
+//
 // fp contraction is OFF in this file: the resize / mean arithmetic restates MindSpore's fp32 expressions and is compared
 // bit-for-bit with a CPU restatement on dyadic inputs.
 #include "common.h"
@@ -398,20 +401,13 @@ struct BuRefineParams {
 
 __device__ __forceinline__ bool refine_better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
 
+// The arg-max of one (joint, person) by a whole workgroup of kBuRefineThreads: plane = the joint's H x W map, tags = its tag map
+// [H * W, L], mean = the person's mean tag.  True on thread 0 alone, with found = (x, y, value) of the winner.  Every thread of the
+// workgroup calls it (it holds a barrier); wave_v / wave_i are kBuRefineThreads / kWave LDS words each.
 template <int L>
-__global__ __launch_bounds__(kBuRefineThreads) void bu_refine_kernel(BuRefineParams p) {
-    __shared__ float wave_v[kBuRefineThreads / kWave];
-    __shared__ int wave_i[kBuRefineThreads / kWave];
-    const int k = blockIdx.x, person = blockIdx.y;
-    const int img = p.person_img[person];
-    if (img < 0 || img >= p.n) return;  // (uniform per workgroup) an index outside the batch reads nothing
-    const int hw = p.h * p.w;
-    const float* __restrict__ plane = p.raw + ((size_t)img * p.k + k) * hw;
-    const float* __restrict__ tags = p.tagging + ((size_t)img * p.ktag + (p.tag_per_joint ? k : 0)) * (size_t)hw * L;
-    float mean[L];
-#pragma unroll
-    for (int l = 0; l < L; ++l) mean[l] = p.mean_tag[(size_t)person * L + l];
-
+__device__ __forceinline__ bool bu_refine_argmax(const float* __restrict__ plane, const float* __restrict__ tags, const float (&mean)[L],
+                                                 int h, int w, float* wave_v, int* wave_i, float (&found)[3]) {
+    const int hw = h * w;
     float bv = -INFINITY;
     int bi = 0x7fffffff;
     for (int i = threadIdx.x; i < hw; i += kBuRefineThreads) {  // ascending per lane: '>' keeps the lane's first maximum
@@ -432,21 +428,163 @@ __global__ __launch_bounds__(kBuRefineThreads) void bu_refine_kernel(BuRefinePar
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
     if (lane == 0) { wave_v[wave] = bv; wave_i[wave] = bi; }
     __syncthreads();
-    if (threadIdx.x == 0) {
-        for (int q = 1; q < kBuRefineThreads / kWave; ++q)
-            if (refine_better(wave_v[q], wave_i[q], bv, bi)) { bv = wave_v[q]; bi = wave_i[q]; }
-        if (bi >= hw) bi = 0;  // no finite value anywhere (outside the contract): stay inside the map
-        const int y = bi / p.w, x = bi - y * p.w;
-        float xs = (float)x + 0.5f, ys = (float)y + 0.5f;
-        const float* row = plane + (size_t)y * p.w;
-        xs += row[min(x + 1, p.w - 1)] > row[max(x - 1, 0)] ? 0.25f : -0.25f;
-        ys += plane[(size_t)min(y + 1, p.h - 1) * p.w + x] > plane[(size_t)max(y - 1, 0) * p.w + x] ? 0.25f : -0.25f;
+    if (threadIdx.x != 0) return false;
+    for (int q = 1; q < kBuRefineThreads / kWave; ++q)
+        if (refine_better(wave_v[q], wave_i[q], bv, bi)) { bv = wave_v[q]; bi = wave_i[q]; }
+    if (bi >= hw) bi = 0;  // no finite value anywhere (outside the contract): stay inside the map
+    const int y = bi / w, x = bi - y * w;
+    float xs = (float)x + 0.5f, ys = (float)y + 0.5f;
+    const float* row = plane + (size_t)y * w;
+    xs += row[min(x + 1, w - 1)] > row[max(x - 1, 0)] ? 0.25f : -0.25f;
+    ys += plane[(size_t)min(y + 1, h - 1) * w + x] > plane[(size_t)max(y - 1, 0) * w + x] ? 0.25f : -0.25f;
+    found[0] = xs;
+    found[1] = ys;
+    found[2] = plane[bi];
+    return true;
+}
+
+template <int L>
+__global__ __launch_bounds__(kBuRefineThreads) void bu_refine_kernel(BuRefineParams p) {
+    __shared__ float wave_v[kBuRefineThreads / kWave];
+    __shared__ int wave_i[kBuRefineThreads / kWave];
+    const int k = blockIdx.x, person = blockIdx.y;
+    const int img = p.person_img[person];
+    if (img < 0 || img >= p.n) return;  // (uniform per workgroup) an index outside the batch reads nothing
+    const int hw = p.h * p.w;
+    const float* __restrict__ plane = p.raw + ((size_t)img * p.k + k) * hw;
+    const float* __restrict__ tags = p.tagging + ((size_t)img * p.ktag + (p.tag_per_joint ? k : 0)) * (size_t)hw * L;
+    float mean[L];
+#pragma unroll
+    for (int l = 0; l < L; ++l) mean[l] = p.mean_tag[(size_t)person * L + l];
+    float found[3];
+    if (bu_refine_argmax<L>(plane, tags, mean, p.h, p.w, wave_v, wave_i, found)) {
         float* out = p.found + ((size_t)person * p.k + k) * 3;
-        out[0] = xs;
-        out[1] = ys;
-        out[2] = plane[bi];
+        out[0] = found[0];
+        out[1] = found[1];
+        out[2] = found[2];
     }
 }
+
+// ---- the tail of a bottom-up batch on the persons the grouping kernel left in device memory (bottomup_inferencer.py:120-150 of the
+// reference: the per-person score, then refine_missing_joint): two launches whose grids are sized from the capacity K * M, so that
+// no host value depends on the person counts.  Every workgroup reads counts[img] (clamped to the capacity) and status[img] itself
+// and exits for a person that does not exist or an image that was handed to the host function.
+//
+//   bu_finish_score_kernel<L>   one wave64 per (person, image): lane j holds joint j (K <= 64).  score = np.mean(person[:, 2]); mean tag
+//                               = np.mean over the joints with value > 0 in joint order (a ballot compacts them into LDS) of the tag
+//                               at ((int)x, (int)y), truncated toward zero and clamped as _refine_on_device clamps.  Both are numpy's
+//                               float32 means, rule (b) of bottomup_match.hip: bu_numpy_sum below for a 1-D view (the value column; the
+//                               tags with L == 1), a sequential sum in joint order per component for L >= 2, one division.
+//   bu_finish_refine_kernel<L>  one workgroup per (joint, person, image), behind the first in stream order: the arg-max above, only
+//                               where person[j, 2] == 0 and the person has a located joint; the reference's fill rule (winner's value
+//                               > 0) writes person[j, 0:3] in place.  A (joint, person) pair is read and written by its own
+//                               workgroup alone.
+struct BuFinishParams {
+    float* people;         // [N, K * M, K, 3 + L]
+    const int* counts;     // [N]
+    const int* status;     // [N]
+    const float* raw;      // [N, K, H, W]
+    const float* tagging;  // [N, KTAG, H, W, L]
+    int k, groups, h, w, ktag, tag_per_joint;
+    float* scores;         // [N, K * M]
+    float* mean_tag;       // [N, K * M, L]
+    int* located;          // [N, K * M]: joints with value > 0
+};
+
+// persons of image img that exist on the device: none for an image handed over, else counts[img] inside the capacity
+__device__ __forceinline__ int bu_finish_count(const BuFinishParams& p, int img) {
+    return p.status[img] != 0 ? 0 : min(max(p.counts[img], 0), p.groups);
+}
+
+// numpy's float32 sum of the n <= 64 values a[0 .. n) in LDS by one wave (n uniform), valid on lane 0: n < 8 sequential from 0;
+// else lanes 0 .. 7 are the eight accumulators over the whole blocks of eight, combined pairwise by shuffles, the tail in order
+__device__ __forceinline__ float bu_numpy_sum(const float* a, int n, int lane) {
+    float res = 0.0f;
+    if (n < 8) {
+        for (int i = 0; i < n; ++i) res = res + a[i];
+        return res;
+    }
+    const int j = lane & 7;
+    float r = a[j];
+    for (int i = 8; i + 8 <= n; i += 8) r = r + a[i + j];
+    r = r + __shfl_down(r, 1, kWave);  // lanes 0, 2, 4, 6: r0 + r1, r2 + r3, r4 + r5, r6 + r7
+    r = r + __shfl_down(r, 2, kWave);  // lanes 0, 4
+    res = r + __shfl_down(r, 4, kWave);
+    for (int i = n & ~7; i < n; ++i) res = res + a[i];
+    return res;
+}
+
+// (int)v as numpy's astype(int32) truncates, clamped to [0, size - 1]; a NaN reads 0 and nothing leaves the map
+__device__ __forceinline__ int bu_map_coord(float v, int size) {
+    if (!(v == v)) return 0;
+    return min(max((int)fminf(fmaxf(v, -2.0f), (float)size), 0), size - 1);
+}
+
+template <int L>
+__global__ __launch_bounds__(kWave) void bu_finish_score_kernel(BuFinishParams p) {
+    __shared__ float vals[kWave];
+    __shared__ float tags[kWave][L];
+    constexpr int W = 3 + L;
+    const int person = blockIdx.x, img = blockIdx.y, lane = threadIdx.x;
+    if (person >= bu_finish_count(p, img)) return;  // (uniform per workgroup)
+    const size_t slot = (size_t)img * p.groups + person;
+    const float* __restrict__ row = p.people + (slot * p.k + lane) * W;
+    float x = 0.0f, y = 0.0f, v = 0.0f;
+    if (lane < p.k) { x = row[0]; y = row[1]; v = row[2]; }
+    vals[lane] = v;
+    const bool has = lane < p.k && v > 0.0f;
+    const unsigned long long mask = __ballot(has);
+    const int located = __popcll(mask);
+    if (has) {
+        const int pos = __popcll(mask & ((1ull << lane) - 1ull));  // joint order
+        const int xi = bu_map_coord(x, p.w), yi = bu_map_coord(y, p.h);
+        const float* __restrict__ t =
+            p.tagging + ((((size_t)img * p.ktag + (p.tag_per_joint ? lane : 0)) * p.h + yi) * p.w + xi) * L;
+#pragma unroll
+        for (int l = 0; l < L; ++l) tags[pos][l] = t[l];
+    }
+    __syncthreads();
+    const float total = bu_numpy_sum(vals, p.k, lane);
+    if (lane == 0) {
+        p.scores[slot] = total / (float)p.k;
+        p.located[slot] = located;
+    }
+    if (located == 0) return;  // (grouping builds a person from at least one detection) no mean tag: the refinement skips it
+    if (L == 1) {
+        const float sum = bu_numpy_sum(&tags[0][0], located, lane);
+        if (lane == 0) p.mean_tag[slot] = sum / (float)located;
+    } else if (lane < L) {
+        float sum = tags[0][lane];
+        for (int i = 1; i < located; ++i) sum = sum + tags[i][lane];
+        p.mean_tag[slot * L + lane] = sum / (float)located;
+    }
+}
+
+template <int L>
+__global__ __launch_bounds__(kBuRefineThreads) void bu_finish_refine_kernel(BuFinishParams p) {
+    __shared__ float wave_v[kBuRefineThreads / kWave];
+    __shared__ int wave_i[kBuRefineThreads / kWave];
+    const int k = blockIdx.x, person = blockIdx.y, img = blockIdx.z;
+    if (person >= bu_finish_count(p, img)) return;  // (every exit is uniform per workgroup)
+    const size_t slot = (size_t)img * p.groups + person;
+    float* joint = p.people + (slot * p.k + k) * (3 + L);
+    if (!(joint[2] == 0.0f) || p.located[slot] == 0) return;  // a located joint stays; a person without any has no mean tag
+    const int hw = p.h * p.w;
+    const float* __restrict__ plane = p.raw + ((size_t)img * p.k + k) * hw;
+    const float* __restrict__ tags = p.tagging + ((size_t)img * p.ktag + (p.tag_per_joint ? k : 0)) * (size_t)hw * L;
+    float mean[L];
+#pragma unroll
+    for (int l = 0; l < L; ++l) mean[l] = p.mean_tag[slot * L + l];
+    float found[3];
+    if (bu_refine_argmax<L>(plane, tags, mean, p.h, p.w, wave_v, wave_i, found) && found[2] > 0.0f) {
+        joint[0] = found[0];
+        joint[1] = found[1];
+        joint[2] = found[2];
+    }
+}
+
+// the grouping entry's limits (bottomup_match.hip): what people [N, K * M, K, 3 + L] can hold
+static bool bu_finish_in_limits(int k, int m, int num_tags) { return k <= 64 && m <= kBuMaxM && num_tags <= kBuMaxTags && k * m <= 1024; }
 
 static int bu_tiles_x(int w) { return (w + kBuTileW - 1) / kBuTileW; }
 static int bu_tiles(int h, int w) { return bu_tiles_x(w) * ((h + kBuTileH - 1) / kBuTileH); }
@@ -674,6 +812,53 @@ int mp_bottomup_refine_missing(const float* heatmap_raw_dev, const float* taggin
         case 2: hipLaunchKernelGGL(bu_refine_kernel<2>, grid, block, 0, as_stream(stream), p); break;
         case 3: hipLaunchKernelGGL(bu_refine_kernel<3>, grid, block, 0, as_stream(stream), p); break;
         default: hipLaunchKernelGGL(bu_refine_kernel<4>, grid, block, 0, as_stream(stream), p); break;
+    }
+    return check_launch();
+}
+
+size_t mp_bottomup_finish_workspace_bytes(int n, int k, int m, int num_tags) {
+    if (n <= 0 || k <= 0 || m <= 0 || num_tags <= 0 || !bu_finish_in_limits(k, m, num_tags)) return 0;
+    return (size_t)n * k * m * (num_tags + 1) * sizeof(float);  // the mean tags, then the located-joint counts
+}
+
+int mp_bottomup_finish_people(float* people_dev, const int* counts_dev, const int* status_dev, const float* heatmap_raw_dev,
+                              const float* tagging_dev, int n, int k, int m, int h, int w, int tag_per_joint, int num_tags, int refine,
+                              float* scores_dev, void* workspace_dev, size_t workspace_bytes, mp_stream_t stream) {
+    if (n == 0) return MP_OK;  // no image: no launch
+    if (!people_dev || !counts_dev || !status_dev || !heatmap_raw_dev || !tagging_dev || !scores_dev) return MP_ERR_NULL;
+    if (n < 0 || n > 65535 || k <= 0 || m <= 0 || h <= 0 || w <= 0 || num_tags <= 0 || (size_t)h * w > 0x7fffffffu) return MP_ERR_SHAPE;
+    if (!bu_finish_in_limits(k, m, num_tags)) return MP_ERR_UNSUPPORTED;
+    const size_t need = mp_bottomup_finish_workspace_bytes(n, k, m, num_tags);
+    if (!workspace_dev || workspace_bytes < need) return MP_ERR_WORKSPACE;
+    BuFinishParams p{};
+    p.people = people_dev;
+    p.counts = counts_dev;
+    p.status = status_dev;
+    p.raw = heatmap_raw_dev;
+    p.tagging = tagging_dev;
+    p.k = k;
+    p.groups = k * m;
+    p.h = h;
+    p.w = w;
+    p.ktag = tag_per_joint ? k : 1;
+    p.tag_per_joint = tag_per_joint ? 1 : 0;
+    p.scores = scores_dev;
+    p.mean_tag = reinterpret_cast<float*>(workspace_dev);
+    p.located = reinterpret_cast<int*>(p.mean_tag + (size_t)n * p.groups * num_tags);
+    const dim3 persons((unsigned)p.groups, (unsigned)n), pairs((unsigned)k, (unsigned)p.groups, (unsigned)n);
+    switch (num_tags) {
+        case 1: hipLaunchKernelGGL(bu_finish_score_kernel<1>, persons, dim3(kWave), 0, as_stream(stream), p); break;
+        case 2: hipLaunchKernelGGL(bu_finish_score_kernel<2>, persons, dim3(kWave), 0, as_stream(stream), p); break;
+        case 3: hipLaunchKernelGGL(bu_finish_score_kernel<3>, persons, dim3(kWave), 0, as_stream(stream), p); break;
+        default: hipLaunchKernelGGL(bu_finish_score_kernel<4>, persons, dim3(kWave), 0, as_stream(stream), p); break;
+    }
+    const int rc = check_launch();
+    if (rc != MP_OK || !refine) return rc;
+    switch (num_tags) {
+        case 1: hipLaunchKernelGGL(bu_finish_refine_kernel<1>, pairs, dim3(kBuRefineThreads), 0, as_stream(stream), p); break;
+        case 2: hipLaunchKernelGGL(bu_finish_refine_kernel<2>, pairs, dim3(kBuRefineThreads), 0, as_stream(stream), p); break;
+        case 3: hipLaunchKernelGGL(bu_finish_refine_kernel<3>, pairs, dim3(kBuRefineThreads), 0, as_stream(stream), p); break;
+        default: hipLaunchKernelGGL(bu_finish_refine_kernel<4>, pairs, dim3(kBuRefineThreads), 0, as_stream(stream), p); break;
     }
     return check_launch();
 }

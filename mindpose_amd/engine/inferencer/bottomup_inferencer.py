@@ -3,10 +3,12 @@
 The network and the decoder run on the HIP path (``EvalNet(net, BottomUpHeatMapAEDecoder)``), and so does the grouping: one
 ``mp_bottomup_match_by_tag`` launch per batch (``match_by_tag_batch``), bit-equal to the host ``match_by_tag``, which serves arrays
 that live on the CPU, extents outside the kernel's limits and ``MINDPOSE_MATCH_DEVICE=0``.  The back-projection is host numpy, as
-in the reference.  The optional missing-joint refinement runs on the device
-(``mp_bottomup_refine_missing``, one launch per batch): the full-resolution maps never travel to the host - only the located tags
-of the grouped persons ([J_total, L]) come down and their mean tags ([P, L]) go up.  Maps that already live on the CPU take the
-host function ``refine_missing_joint``.
+in the reference.  Behind the device grouping the rest of ``_parse`` stays on the device too (``finish_people_batch``: the
+per-person scores, the mean tags and the optional missing-joint refinement in the two launches of ``mp_bottomup_finish_people``,
+then two downloads; ``MINDPOSE_FINISH_DEVICE=0``: the host-driven tail below).  Without it the optional missing-joint refinement
+still runs on the device (``mp_bottomup_refine_missing``, one launch per batch): the full-resolution maps never travel to the
+host - only the located tags of the grouped persons ([J_total, L]) come down and their mean tags ([P, L]) go up.  Maps that
+already live on the CPU take the host function ``refine_missing_joint``.
 
 Flip TTA (``hflip_tta``, the reference's ``_MultiRunNet``, :252-297): the backbone and head run on the image and its mirror, and the
 decoder folds the mirrored run into its own first launch (``decode_flip_aggregated``); the two decodes the reference computes and
@@ -25,7 +27,11 @@ from ...models import EvalNet
 from ...models.decoders import BottomUpHeatMapAEDecoder
 from ...models.layers import flip_pair_batched
 from ...register import register
-from ...utils.match import match_by_tag, match_by_tag_batch, match_on_device_supported
+from ...utils.match import finish_people_batch, host_match_of, match_by_tag, match_by_tag_batch, match_on_device_supported
+
+
+# MINDPOSE_FINISH_DEVICE when the environment does not set it (DESIGN.md 4.13 holds the measurement that decided it)
+FINISH_DEVICE_DEFAULT = True
 
 
 class _MultiRunNet(nn.Module):
@@ -118,7 +124,16 @@ class BottomUpHeatMapAEInferencer:
         return outputs
 
     def _parse(self, val_k, tag_k, ind_k, heatmap, tagging_heatmap) -> Tuple[List[np.ndarray], List[List[float]]]:
-        """Grouping, per-person score (mean joint value) and the optional missing-joint refinement (:120-150)."""
+        """Grouping, per-person score (mean joint value) and the optional missing-joint refinement (:120-150).  With maps on the
+        device and everything ``_match`` asks of the device grouping, all three stay there (``MINDPOSE_FINISH_DEVICE=0``: never): the
+        grouping launch, the two launches of ``mp_bottomup_finish_people`` and two downloads (``finish_people_batch``) - the same
+        records."""
+        if heatmap.is_cuda and tagging_heatmap.is_cuda and _lib.env_on("MINDPOSE_FINISH_DEVICE", default=FINISH_DEVICE_DEFAULT) \
+                and self._match_on_device(val_k, tag_k, ind_k):
+            kwargs = self._match_kwargs()
+            people, counts, status = match_by_tag_batch(val_k, tag_k, ind_k, download=False, **kwargs)  # match_by_tag_device
+            return finish_people_batch(people, counts, status, heatmap, tagging_heatmap, self._inference_cfg["refine_missing_joint"],
+                                       host_match_of(val_k, tag_k, ind_k, **kwargs))
         keypoints = self._match(val_k, tag_k, ind_k)
         scores = [[person[:, 2].mean() for person in people] for people in keypoints]
         if self._inference_cfg["refine_missing_joint"]:
@@ -172,14 +187,21 @@ class BottomUpHeatMapAEInferencer:
             fill = (rows[:, 2] > 0) & (person[:, 2] == 0)
             person[fill, :3] = rows[fill]
 
+    def _match_kwargs(self) -> Dict[str, Any]:
+        cfg = self._inference_cfg
+        return dict(joint_order=cfg["joint_order"], vis_thr=cfg["vis_thr"], tag_thr=cfg["tag_thr"],
+                    ignore_too_much=cfg["ignore_too_much"], use_rounded_norm=cfg["use_rounded_norm"])
+
+    @staticmethod
+    def _match_on_device(val_k, tag_k, ind_k) -> bool:
+        return val_k.is_cuda and tag_k.is_cuda and ind_k.is_cuda and _lib.env_on("MINDPOSE_MATCH_DEVICE") \
+            and match_on_device_supported(val_k.shape[1], val_k.shape[2], tag_k.shape[3])
+
     def _match(self, val_k, tag_k, ind_k) -> List[np.ndarray]:
         """Grouping of the batch: one ``mp_bottomup_match_by_tag`` launch when the decoder's arrays live on the device and are inside
         the entry's limits (``MINDPOSE_MATCH_DEVICE=0``: never), else the host function image by image - the same arrays either way."""
-        cfg = self._inference_cfg
-        kwargs = dict(joint_order=cfg["joint_order"], vis_thr=cfg["vis_thr"], tag_thr=cfg["tag_thr"],
-                      ignore_too_much=cfg["ignore_too_much"], use_rounded_norm=cfg["use_rounded_norm"])
-        if val_k.is_cuda and tag_k.is_cuda and ind_k.is_cuda and _lib.env_on("MINDPOSE_MATCH_DEVICE") \
-                and match_on_device_supported(val_k.shape[1], val_k.shape[2], tag_k.shape[3]):
+        kwargs = self._match_kwargs()
+        if self._match_on_device(val_k, tag_k, ind_k):
             return match_by_tag_batch(val_k, tag_k, ind_k, **kwargs)
         return list(map(partial(match_by_tag, **kwargs), val_k.cpu().numpy(), tag_k.cpu().numpy(), ind_k.cpu().numpy()))
 

@@ -45,6 +45,15 @@
   planes once, ``heatmap_raw`` and ``tagging`` written).  ``mp_resize_bilinear_nchw`` of the input to the two other scales in device
   microseconds.  Then one forward per scale 0.5 / 1 / 1.5 / 2 of both recipe sizes in fp32 and amp O2 (``MINDPOSE_AUTOTUNE`` as the
   environment sets it, reported); a scale whose plan cannot be recorded reports the plan's own error instead of a time.
+- finish: the tail of a bottom-up batch behind the decoder - ``BottomUpHeatMapAEInferencer._parse`` (grouping, scores, missing-joint
+  refinement on) - with ``MINDPOSE_FINISH_DEVICE`` 0 (the grouping launch, then the host-driven tail: four downloads, one upload and
+  two Python loops over persons) and 1 (the grouping launch, ``mp_bottomup_finish_people``, two downloads): wall milliseconds per
+  batch in alternated rounds in one process (median and min - max) at K = 17, M = 30, L = 1, the 256 x 256 map, N = 1 and N = 32,
+  detections drawn around 5, 20 and 500 centres as in ``match``; the persons found and the share of their joints that grouping left
+  empty (the refinement's work) are printed, and both settings are compared bit for bit first.  Then the entry's two launches in
+  device microseconds (events around each call, the persons restored outside them; launch A alone is the call without refinement)
+  and the bytes launch B reads ((1 + L) * H * W * 4 per missing joint), beside ``mp_bottomup_refine_missing`` for the same persons
+  (every joint of every person).
 Forward sizes are the recipe's eval images: 512 x 512 (N = 1 and 32) and 512 x 832 (N = 1).
 
 ``--only NAME`` runs one section in this process; without it every section runs in a child process of its own under a time limit
@@ -412,6 +421,96 @@ def match(steps, rounds=5, k=17, m=30, num_tags=1):
     return out
 
 
+def _time_each(prepare, fn, steps, warmup=2):
+    """device milliseconds per call of ``fn``, ``prepare`` run before each call outside the timed events"""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    total = 0.0
+    for i in range(warmup + steps):
+        prepare()
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        if i >= warmup:
+            total += e0.elapsed_time(e1)
+    return total / steps
+
+
+def finish(steps, rounds=5, k=17, m=30, num_tags=1, h=256, w=256):
+    from mindpose_amd.utils.match import match_by_tag_device
+    lib = _lib.load()
+    cfg = dict(has_heatmap_output=True, hflip_tta=False, joint_order=JOINT_ORDER, vis_thr=0.1, ignore_too_much=False, use_rounded_norm=True,
+               tag_thr=1.0, pixel_std=200.0, downsample_scale=2, refine_missing_joint=True,
+               flip_pairs=[[1, 2], [3, 4], [5, 6], [7, 8], [9, 10], [11, 12], [13, 14], [15, 16]])
+    inf = BottomUpHeatMapAEInferencer(None, config=cfg)
+    out = []
+    for n in (1, 32):
+        g = torch.Generator().manual_seed(n)
+        heat = torch.rand(n, k, h, w, generator=g).to(DEV)
+        tagging = (torch.rand(n, k, h, w, num_tags, generator=g) * 8.0).to(DEV)
+        for centres in (5, 20, 500):
+            rng = np.random.RandomState(centres + n)
+            tag = (rng.randint(0, centres, (n, k, m, 1)) + 0.25 * rng.randn(n, k, m, num_tags)).astype(np.float32)
+            val, tag, ind = (torch.from_numpy(a).to(DEV) for a in (rng.rand(n, k, m).astype(np.float32), tag,
+                                                                   rng.randint(0, 256, (n, k, m, 2)).astype(np.float32)))
+
+            def parse(switch):
+                os.environ["MINDPOSE_FINISH_DEVICE"] = switch
+                return inf._parse(val, tag, ind, heat, tagging)
+
+            (kp0, sc0), (kp1, sc1) = parse("0"), parse("1")
+            if any(a.shape != b.shape or not np.array_equal(a.view(np.uint32), b.view(np.uint32)) for a, b in zip(kp0, kp1)) or sc0 != sc1:
+                raise RuntimeError("the device tail and the host-driven tail disagree")
+
+            def wall(switch, reps):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(reps):
+                    parse(switch)  # both end in downloads: synchronised
+                return (time.perf_counter() - t0) * 1000 / reps
+
+            reps = max(1, steps // (1 if n == 1 else 10))
+            times = {"0": [], "1": []}
+            for _ in range(rounds):  # alternated: a drift of the machine meets both alike
+                for switch in ("0", "1"):
+                    times[switch].append(wall(switch, reps))
+
+            # the launches alone, on the grouping's own buffers; the grouped persons are kept aside and restored before every call
+            people, counts, status = match_by_tag_device(val, tag, ind, JOINT_ORDER)
+            pristine = people.clone()
+            scores = torch.empty(n, k * m, device=DEV)
+            ws_bytes = lib.mp_bottomup_finish_workspace_bytes(n, k, m, num_tags)
+            ws = torch.empty(ws_bytes // 4, device=DEV)
+
+            def entry(refine):
+                return lambda: _lib.check(lib.mp_bottomup_finish_people(
+                    _lib.ptr(people), _lib.ptr(counts), _lib.ptr(status), _lib.ptr(heat), _lib.ptr(tagging), n, k, m, h, w, 1, num_tags, refine,
+                    _lib.ptr(scores), _lib.ptr(ws), ws_bytes, _lib.stream()), "mp_bottomup_finish_people")
+
+            restore = lambda: people.copy_(pristine)  # noqa: E731
+            a_us = _time_each(restore, entry(0), steps) * 1000
+            ab_us = _time_each(restore, entry(1), steps) * 1000
+            # mp_bottomup_refine_missing for the same persons with the mean tags launch A left in the workspace
+            count_host = counts.cpu().numpy()
+            persons = int(count_host.sum())
+            img = torch.from_numpy(np.repeat(np.arange(n), count_host).astype(np.int32)).to(DEV)
+            mean = torch.cat([ws[:n * k * m * num_tags].view(n, k * m, num_tags)[i, :count_host[i]] for i in range(n)]).contiguous()
+            found = torch.empty(persons, k, 3, device=DEV)
+            old_us = _time(lambda: lib.mp_bottomup_refine_missing(_lib.ptr(heat), _lib.ptr(tagging), _lib.ptr(mean), _lib.ptr(img), persons, n, k, h,
+                                                                  w, 1, num_tags, _lib.ptr(found), _lib.stream()), steps) * 1000
+            grouped = [p for p in match_by_tag_batch(val, tag, ind, JOINT_ORDER)]
+            missing = int(sum((p[:, :, 2] == 0).sum() for p in grouped if p.size))
+            plane_bytes = (1 + num_tags) * h * w * 4
+            off_ms, on_ms = _spread(times["0"]), _spread(times["1"])
+            out.append(dict(n=n, centres=centres, persons=[int(count_host.min()), int(count_host.max())],
+                            missing_share=round(missing / max(1, persons * k), 3), switch0_ms=off_ms, switch1_ms=on_ms,
+                            ratio=round(off_ms["median"] / on_ms["median"], 2), launch_a_us=round(a_us, 2),
+                            launch_b_us=round(ab_us - a_us, 2), launch_b_mb=round(missing * plane_bytes / 1e6, 1),
+                            refine_missing_us=round(old_us, 2), refine_missing_mb=round(persons * k * plane_bytes / 1e6, 1)))
+    os.environ.pop("MINDPOSE_FINISH_DEVICE", None)
+    return out
+
+
 def multi_scale(steps, rounds=5):
     import torch.nn.functional as F
     from mindpose_amd.models.decoders import resize_bilinear
@@ -515,6 +614,7 @@ SECTIONS = {
     "train_masks": train_masks,
     "flip_tta": flip_tta,
     "match": match,
+    "finish": finish,
     "multi_scale": multi_scale,
 }
 
