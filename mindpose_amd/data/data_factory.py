@@ -23,7 +23,7 @@ import subprocess
 import sys
 import threading
 import weakref
-from typing import Any, Dict, Iterator, List, Optional, Sequence, Union
+from typing import Any, Callable, Dict, Hashable, Iterable, Iterator, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
@@ -33,7 +33,8 @@ from .column_names import COLUMN_MAP, FINAL_COLUMN_MAP
 from .transform.bottomup_transform import BottomUpPad, BottomUpRescale, BottomUpResize, launch_resize_pad_normalize
 from .transform.topdown_transform import TopDownAffine, TopDownGenerateTarget, launch_warp_affine
 
-__all__ = ["create_dataset", "create_pipeline", "ShardedDataset", "TopDownPipeline", "BottomUpPipeline"]
+__all__ = ["create_dataset", "create_pipeline", "ShardedDataset", "TopDownPipeline", "BottomUpPipeline", "bucket_indices",
+           "bottomup_mode", "bottomup_input_size"]
 
 
 class ShardedDataset:
@@ -495,31 +496,117 @@ class TopDownPipeline(_BatchPipeline):
         return {k: out[k] for k in self.final_column_names}
 
 
+def bucket_indices(order: Iterable[int], size_of: Callable[[int], Tuple[int, int]], key_of: Callable[[int, int], Hashable],
+                   batch_size: int) -> Iterator[List[int]]:
+    """The indices of ``order`` grouped into lists of at most ``batch_size`` that share one key ``key_of(*size_of(idx))`` - host
+    arithmetic only, nothing is decoded.  ``order`` is walked once; every index joins the pending list of its key, and a list is
+    yielded the moment it holds ``batch_size`` indices.  At the end the partial lists follow, in the order of their first pending
+    index.  Nothing is dropped or repeated, two calls give the same lists, and ``batch_size`` 1 gives ``order`` itself."""
+    if batch_size < 1:
+        raise ValueError("batch_size must be >= 1")
+    pending: Dict[Hashable, List[int]] = {}  # insertion order = the order of each key's first pending index (a key is removed when it is emitted)
+    for idx in order:
+        idx = int(idx)
+        key = key_of(*size_of(idx))
+        pending.setdefault(key, []).append(idx)
+        if len(pending[key]) == batch_size:
+            yield pending.pop(key)
+    yield from pending.values()
+
+
+def bottomup_mode(transforms: Sequence[Any], normalize: bool = True, hwc_to_chw: bool = True) -> str:
+    """How `BottomUpPipeline` runs a transform list: "rescale_pad" / "resize" - the two lists whose pixel work is one launch per
+    batch and whose network input size follows from the source size alone - else "host"."""
+    kinds = [type(t) for t in transforms]
+    fused = normalize and hwc_to_chw
+    if fused and kinds == [BottomUpRescale, BottomUpPad]:
+        return "rescale_pad"
+    if fused and kinds == [BottomUpResize]:
+        return "resize"
+    return "host"
+
+
+def bottomup_input_size(transforms: Sequence[Any], mode: str, width: int, height: int) -> Tuple[int, int]:
+    """(width, height) of the network input the transform objects themselves give a ``width`` x ``height`` source: the bucket key.
+    It is NOT an orientation test - with ``max_image_size`` (832, 512) a 1279 x 1280 source is portrait, rescales to 512 x 512 and
+    pads to the landscape shape."""
+    if mode == "rescale_pad":
+        rescale, pad = transforms
+        return tuple(int(v) for v in pad.padded_size(*rescale.geometry(width, height)["image_shape"]))
+    if mode == "resize":
+        return tuple(int(v) for v in transforms[0].geometry(width, height)["image_shape"])
+    raise ValueError("the network input size of a `host` transform list is only known after the host chain ran")
+
+
+def _refuse_host_buckets(mode: str) -> None:
+    if mode == "host":
+        raise ValueError("bucket_by_shape needs the `bottomup_rescale` + `bottomup_pad` or the `bottomup_resize` transform list "
+                         "(with Normalize and HWC2CHW): the sizes of any other list are only known after its host chain ran")
+
+
 class BottomUpPipeline(_BatchPipeline):
     """The evaluation pipeline of the bottom-up path: one image per batch (landscape and portrait images pad to different shapes),
     ``image`` [1, 3, H, W] fp32 normalised and ``mask`` [1, H, W] uint8 CUDA tensors, ``center`` / ``scale`` / ``image_shape`` numpy,
     ``image_file`` a list - what ``BottomUpHeatMapAEInferencer.infer`` consumes.
+
+    ``bucket_by_shape=True``: batches of up to ``batch_size`` images that share one network input size (`bucket_indices` over the
+    dataset's ``image_size``, keyed by `bottomup_input_size`: no image is decoded to plan an epoch) - ``image`` [N, 3, H, W],
+    ``mask`` [N, H, W], ``center`` / ``scale`` / ``image_shape`` [N, 2], ``image_file`` a list of N; the last batch of a shape may
+    be partial.  The batches - and so the inferencer's records - come in BATCH order, not dataset order (the evaluator keys on
+    ``image_path``), and ``len`` is the exact number of batches of the coming epoch.  Each decoded image is checked against the
+    size its record declared: a wrong entry would have put it into the wrong bucket.
 
     The pixel transforms are recognised in the list; per sample only their geometry runs on the host, the pixels of a batch are ONE
     launch: ``bottomup_rescale`` + ``bottomup_pad`` -> ``mp_resize_pad_normalize`` (resize, pad, Normalize, HWC2CHW and the mask),
     ``bottomup_resize`` -> ``mp_warp_affine`` with the transform's matrix and an all-ones mask.  Any other list (rescale without
     pad, no Normalize ...) runs the transforms' host ``transform`` chain and finishes with tensor operations."""
 
-    def __init__(self, *args: Any, **kwargs: Any) -> None:
+    def __init__(self, *args: Any, bucket_by_shape: bool = False, **kwargs: Any) -> None:
         super().__init__(*args, **kwargs)
-        kinds = [type(t) for t in self.transforms]
-        fused = self.normalize and self.hwc_to_chw
-        if fused and kinds == [BottomUpRescale, BottomUpPad]:
-            self.mode = "rescale_pad"
-        elif fused and kinds == [BottomUpResize]:
-            self.mode = "resize"
-        else:
-            self.mode = "host"
+        self.mode = bottomup_mode(self.transforms, self.normalize, self.hwc_to_chw)
+        self.bucket_by_shape = bool(bucket_by_shape)
+        self._plan: Optional[Tuple[int, List[List[int]]]] = None  # (epoch, its buckets)
+        if self.bucket_by_shape:
+            _refuse_host_buckets(self.mode)
+            if not hasattr(self.dataset.source, "image_size"):
+                raise ValueError("bucket_by_shape needs a dataset with `image_size(idx)`")
+
+    def input_size(self, width: int, height: int) -> Tuple[int, int]:
+        """The network input size (width, height) of a ``width`` x ``height`` source: the bucket key."""
+        return bottomup_input_size(self.transforms, self.mode, width, height)
+
+    def buckets(self) -> List[List[int]]:
+        """The index lists of the coming epoch's batches, from the declared sizes alone."""
+        if self._plan is None or self._plan[0] != self.dataset.epoch:
+            source = self.dataset.source
+            self._plan = (self.dataset.epoch, list(bucket_indices(self.dataset.indices(), source.image_size, self.input_size, self.batch_size)))
+        return self._plan[1]
+
+    def __len__(self) -> int:
+        return len(self.buckets()) if self.bucket_by_shape else super().__len__()
+
+    def _groups(self) -> Iterator[List[Dict[str, Any]]]:
+        if not self.bucket_by_shape:
+            yield from super()._groups()
+            return
+        source, names = self.dataset.source, self.dataset.column_names
+        for bucket in self.buckets():
+            group = []
+            for i in bucket:
+                state = dict(zip(names, source[i]))
+                state["_declared_size"] = tuple(source.image_size(i))
+                group.append(state)
+            yield group
+        self.dataset.epoch += 1  # (as ShardedDataset.__iter__)
 
     def _run_sample(self, state: Dict[str, Any]) -> Dict[str, Any]:
         if not (isinstance(state["image"], np.ndarray) and state["image"].ndim == 3):
             state["image"] = _decode(state["image"])
         height, width = state["image"].shape[:2]
+        declared = state.pop("_declared_size", None)
+        if declared is not None and (width, height) != tuple(declared):
+            raise ValueError(f"{state['image_file']}: the dataset declares {declared[0]} x {declared[1]} (width x height), the decoded "
+                             f"image is {width} x {height}")
         if self.mode == "rescale_pad":  # geometry now, pixels with the batch
             rescale, pad = self.transforms
             state.update(rescale.geometry(width, height))
@@ -568,25 +655,39 @@ class BottomUpPipeline(_BatchPipeline):
 def create_pipeline(dataset: ShardedDataset, transforms: List[Union[str, Dict[str, Any]]], method: str = "topdown", batch_size: int = 1,
                     is_train: bool = True, normalize: bool = True, normalize_mean: List[float] = [0.485, 0.456, 0.406],
                     normalize_std: List[float] = [0.229, 0.224, 0.255], hwc_to_chw: bool = True, num_workers: int = 1,
-                    config: Optional[Dict[str, Any]] = None, prefetch: Optional[int] = None) -> Union[TopDownPipeline, BottomUpPipeline]:
+                    config: Optional[Dict[str, Any]] = None, prefetch: Optional[int] = None,
+                    bucket_by_shape: bool = False) -> Union[TopDownPipeline, BottomUpPipeline]:
     """Signature of data_factory.py:71-151 (the reference's ``normalize_std`` really ends in 0.255: checkpoints were trained with it)
-    plus ``prefetch`` (batches prepared ahead on a side stream, `_BatchPipeline`; MindSpore's dataset engine prefetches by itself).
-    ``method`` "bottomup" / "imagefolder_bottomup" is evaluation only and gives a `BottomUpPipeline` of one image per batch."""
+    plus ``prefetch`` (batches prepared ahead on a side stream, `_BatchPipeline`; MindSpore's dataset engine prefetches by itself)
+    and ``bucket_by_shape``.
+    ``method`` "bottomup" / "imagefolder_bottomup" is evaluation only and gives a `BottomUpPipeline`: of one image per batch,
+    whatever ``batch_size`` says, as in the reference (its images pad to different shapes) - unless ``bucket_by_shape=True``, which
+    honours ``batch_size`` by batching images that share one network input size (`BottomUpPipeline`: the recipe's rescale + pad
+    list has exactly two).  The batches then come in batch order, not dataset order, the last batch of a shape may be partial, and
+    ``len`` of the pipeline is the exact number of batches.  It is a ``ValueError`` for any other method, and for a transform list
+    whose sizes are only known after its host chain ran (anything but ``bottomup_rescale`` + ``bottomup_pad`` or
+    ``bottomup_resize`` with Normalize and HWC2CHW)."""
     if method not in FINAL_COLUMN_MAP:
         raise ValueError(f"method `{method}` is not supported (supported: {sorted(FINAL_COLUMN_MAP)})")
     bottomup = method in ("bottomup", "imagefolder_bottomup")
     if bottomup and is_train:
         raise ValueError("bottom-up training data is not implemented")
+    if bucket_by_shape and not bottomup:
+        raise ValueError(f"bucket_by_shape is for the bottom-up evaluation methods, not `{method}` (its batches already share one shape)")
     key = "train" if is_train else "val"
     column_names, final_column_names = COLUMN_MAP[method][key], FINAL_COLUMN_MAP[method][key]
     transform_funcs = _convert_names_to_transform(transforms, is_train=is_train, config=config)
-    if bottomup:
+    extra: Dict[str, Any] = {}
+    if bottomup and bucket_by_shape:
+        _refuse_host_buckets(bottomup_mode(transform_funcs, normalize, hwc_to_chw))  # (before the pipeline, which opens the device, is built)
+        extra["bucket_by_shape"] = True
+    elif bottomup:
         logging.info(f"Set batch_size = 1 for `{method}` evaluation method.")
         batch_size = 1
     logging.info(f"pipeline: {[type(t).__name__ for t in transform_funcs]}, batch {batch_size}")
     pipeline = BottomUpPipeline if bottomup else TopDownPipeline
     return pipeline(dataset, transform_funcs, column_names, final_column_names, batch_size, is_train, normalize, normalize_mean,
-                           normalize_std, hwc_to_chw, num_workers, prefetch=prefetch)
+                           normalize_std, hwc_to_chw, num_workers, prefetch=prefetch, **extra)
 
 
 def _convert_names_to_transform(names_with_args: List[Union[str, Dict[str, Any]]], is_train: bool = True,

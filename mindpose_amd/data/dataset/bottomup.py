@@ -5,7 +5,7 @@ Contract kept: the constructor, the two hooks of a format class (``load_dataset_
 crowd mask) is not built: ``is_train=True`` raises ``ValueError``.  The ``image`` column follows the lazy-path convention of
 ``dataset/topdown.py``: a pipeline whose codec runs in worker processes sets ``lazy_image`` and only the path travels."""
 import logging
-from typing import Any, Callable, Dict, List, Optional
+from typing import Any, Callable, Dict, List, Optional, Tuple
 
 import numpy as np
 
@@ -44,6 +44,12 @@ class BottomUpDataset:
 
     def __len__(self) -> int:
         return len(self._dataset)
+
+    def image_size(self, idx: int) -> Tuple[int, int]:
+        """(width, height) of record ``idx`` WITHOUT decoding its pixels: what a pipeline that buckets its batches by network input
+        shape (``create_pipeline(bucket_by_shape=True)``) asks before any image exists.  A format class answers from what it
+        holds - the annotation file, the file's header."""
+        raise NotImplementedError("Child class must implement this method.")
 
     def _column_sources(self, idx: int) -> Dict[str, Callable[[], Any]]:
         image_file = self._dataset[idx]["image_file"]

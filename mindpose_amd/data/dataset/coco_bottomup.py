@@ -32,6 +32,11 @@ class COCOBottomUpDataset(BottomUpDataset):
         self.img_ids = self.coco.get_img_ids()
         return [{"image_file": os.path.join(self.image_root, self.id2name[img_id])} for img_id in self.img_ids]
 
+    def image_size(self, idx: int) -> Tuple[int, int]:
+        """The annotation file's ``width`` / ``height`` of record ``idx`` (the pipeline checks the decoded image against them)."""
+        info = self.coco.load_img(self.img_ids[idx])
+        return int(info["width"]), int(info["height"])
+
     @staticmethod
     def _get_mapping_id_name(imgs: Dict[int, Dict[str, Any]]) -> Tuple[Dict[int, str], Dict[str, int]]:
         id2name = {image_id: image["file_name"] for image_id, image in imgs.items()}

@@ -54,6 +54,14 @@
   device microseconds (events around each call, the persons restored outside them; launch A alone is the call without refinement)
   and the bytes launch B reads ((1 + L) * H * W * 4 per missing joint), beside ``mp_bottomup_refine_missing`` for the same persons
   (every joint of every person).
+- eval_batched: the evaluation chain dataset -> pipeline -> inferencer end to end on a synthetic folder of 96 JPEG files of COCO's
+  usual sizes (64 of 640 x 480, 32 of 480 x 640, interleaved) with the synthetic weights, NMS 3, max_num 30, refinement on, no flip
+  test, four codec workers and a prefetch of 2: ``create_pipeline(bucket_by_shape=False)`` (one image per batch, what the parent
+  commit did) against ``bucket_by_shape=True`` at batch sizes 4, 8 and 16, in fp32 and amp O2.  Wall milliseconds per image over a
+  whole epoch, alternated rounds in one process after one pass per setting that records its plans (median and min - max), the
+  speed-up over the unbucketed median of the same run, the pipeline alone (every batch waited for, no network) and the persons
+  per image.  The synthetic weights find far more persons per image than a trained network would: the share of grouping and
+  finish is overstated.  ``MINDPOSE_AUTOTUNE`` is as the environment sets it and is reported.
 Forward sizes are the recipe's eval images: 512 x 512 (N = 1 and 32) and 512 x 832 (N = 1).
 
 ``--only NAME`` runs one section in this process; without it every section runs in a child process of its own under a time limit
@@ -605,6 +613,85 @@ def multi_scale(steps, rounds=5):
     return res
 
 
+def eval_batched(steps, rounds=5, landscape=64, portrait=32):
+    """(``steps`` is not used: a pass is one epoch over the folder.)"""
+    import shutil
+    import tempfile
+    from PIL import Image
+    root = tempfile.mkdtemp(prefix="mindpose_eval_batched_")
+    try:
+        # COCO's usual sizes, both orientations interleaved 2 : 1; smooth content with mild noise, so that the JPEG codec has real work
+        rng = np.random.RandomState(0)
+        kinds = (["land", "land", "port"] * max(landscape, portrait))
+        left = dict(land=landscape, port=portrait)
+        count = 0
+        for kind in kinds:
+            if left[kind] == 0:
+                continue
+            left[kind] -= 1
+            w, h = (640, 480) if kind == "land" else (480, 640)
+            yy, xx = np.mgrid[0:h, 0:w]
+            base = np.stack([(xx * 255 // w), (yy * 255 // h), ((xx + yy) * 255 // (w + h))], axis=2).astype(np.float32)
+            pixels = np.clip(base + rng.normal(0, 6, (h, w, 3)), 0, 255).astype(np.uint8)
+            Image.fromarray(pixels).save(os.path.join(root, f"{count:04d}_{kind}.jpg"), quality=90)
+            count += 1
+        cfg = dict(image_size=[512, 512], max_image_size=[832, 512], heatmap_sizes=[[128, 128], [256, 256]], pixel_std=200.0, tag_per_joint=True,
+                   flip_pairs=[[1, 2], [3, 4], [5, 6], [7, 8], [9, 10], [11, 12], [13, 14], [15, 16]])
+        infer_cfg = dict(has_heatmap_output=True, hflip_tta=False, joint_order=JOINT_ORDER, vis_thr=0.1, ignore_too_much=False,
+                         use_rounded_norm=True, tag_thr=1.0, pixel_std=200.0, downsample_scale=2, refine_missing_joint=True,
+                         flip_pairs=cfg["flip_pairs"])
+        ds = mp.create_dataset(root, None, dataset_format="imagefolder_bottomup", is_train=False)
+        settings = [("unbucketed", dict(batch_size=1))] + [(f"bucketed_{n}", dict(batch_size=n, bucket_by_shape=True)) for n in (4, 8, 16)]
+        res = dict(images=count, landscape=landscape, portrait=portrait, rounds=rounds, num_workers=4, prefetch=2,
+                   autotune=os.environ.get("MINDPOSE_AUTOTUNE", "unset"), rows=[])
+        for amp in ("O0", "O2"):
+            net = mp.init_synthetic(mp.create_network("hrnet_w32", "higher_hrnet_head"), seed=0).to(DEV).eval()
+            if amp != "O0":
+                mp.models.auto_mixed_precision(net, amp)
+            dec = mp.create_decoder("bottomup_heatmap_ae", use_nms=True, nms_kernel=3, max_num=30)
+            inf = mp.create_inferencer(mp.create_eval_network(net, dec), "bottomup_heatmap_ae", config=infer_cfg, decoder=dec)
+            pipes = {name: mp.create_pipeline(ds, ["bottomup_rescale", "bottomup_pad"], method="imagefolder_bottomup", is_train=False, config=cfg,
+                                              num_workers=4, prefetch=2, **kw) for name, kw in settings}
+
+            def chain(pipe):  # dataset -> pipeline -> inferencer: ends in the downloads of the last batch, synchronised
+                t0 = time.perf_counter()
+                records = inf(pipe)
+                return (time.perf_counter() - t0) * 1000 / count, records
+
+            def loader(pipe):  # the pipeline alone, every batch waited for
+                t0 = time.perf_counter()
+                for batch in pipe:
+                    pass
+                torch.cuda.synchronize()
+                return (time.perf_counter() - t0) * 1000 / count
+
+            try:
+                persons = {}
+                for name, pipe in pipes.items():  # the first pass records the plans of this setting's batch sizes
+                    _, records = chain(pipe)
+                    assert len(records) == count
+                    persons[name] = round(sum(len(r["pred"]) for r in records) / count, 1)
+                times = {name: [] for name in pipes}
+                loads = {name: [] for name in pipes}
+                for _ in range(rounds):  # alternated: a drift of the machine meets every setting alike
+                    for name, pipe in pipes.items():
+                        times[name].append(chain(pipe)[0])
+                        loads[name].append(loader(pipe))
+            finally:
+                for pipe in pipes.values():
+                    pipe.close()
+            base = _spread(times["unbucketed"])["median"]
+            for name in pipes:
+                t = _spread(times[name])
+                res["rows"].append(dict(amp=amp, setting=name, batches=len(pipes[name]), ms_per_image=t, pipeline_alone_ms_per_image=_spread(loads[name]),
+                                        speedup_over_unbucketed=round(base / t["median"], 2), persons_per_image=persons[name]))
+            del inf, net
+            torch.cuda.empty_cache()
+        return res
+    finally:
+        shutil.rmtree(root, ignore_errors=True)
+
+
 SECTIONS = {
     "forward": lambda steps: [forward(a, n, h, w, steps) for a in ("O0", "O2") for n, h, w in ((1, 512, 512), (32, 512, 512), (1, 512, 832))],
     "decoder": lambda steps: [decoder(1, 256, 416, steps), decoder(32, 256, 256, steps)],
@@ -616,6 +703,7 @@ SECTIONS = {
     "match": match,
     "finish": finish,
     "multi_scale": multi_scale,
+    "eval_batched": eval_batched,
 }
 
 
