@@ -1195,11 +1195,11 @@ __global__ __launch_bounds__(256) void fuse_sum16_bwd_kernel(const u32x4_t* __re
 
 // out = a + b (+ c) (+ d): the gradients that reach one tensor from its consumers (the exchange unit feeds every branch output to
 // every row) summed in ONE pass with fp32 arithmetic - autograd would add them pairwise, k - 1 launches of 3 tensors each.
-// fp16: 16-byte units of 8 halves, one rounding at the end.
+// fp16: 16-byte units of 8 halves, one rounding at the end.  `out` may alias an input (include/mindpose_hip.h; a running sum
+// accumulated in place): every thread reads unit i of all operands before it stores unit i, so no pointer carries __restrict__.
 template <bool HALF>
-__global__ __launch_bounds__(256) void sum_tensors_kernel(const u32x4_t* __restrict__ a, const u32x4_t* __restrict__ b,
-                                                          const u32x4_t* __restrict__ c, const u32x4_t* __restrict__ d,
-                                                          u32x4_t* __restrict__ out, size_t units) {
+__global__ __launch_bounds__(256) void sum_tensors_kernel(const u32x4_t* a, const u32x4_t* b, const u32x4_t* c, const u32x4_t* d,
+                                                          u32x4_t* out, size_t units) {
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < units; i += (size_t)gridDim.x * 256) {
         const u32x4_t va = a[i], vb = b[i];
         u32x4_t vc = va, vd = va;

@@ -36,31 +36,39 @@ from tests.test_gpu_bands import _assert_untouched, _window  # noqa: E402
 DEV = torch.device("cuda:0")
 LIB = _lib.load()
 NAN32 = 0x7FC00000  # the sentinel bit pattern (a quiet NaN) of guard bands and unwritten outputs
-GUARD = 1024        # floats on either side of every operand (a multiple of 16 bytes: the operands keep their alignment)
+NAN16 = 0x7E00      # ... of fp16 tensors
+GUARD = 1024        # elements on either side of every operand (a multiple of 16 bytes: the operands keep their alignment)
 BAR = 2e-5          # single-layer bound of tests/test_gpu_conv.py, relative to the reference's max abs
 
 
 class Guarded:
-    """A contiguous fp32 tensor between two NaN guard bands of one allocation."""
+    """A contiguous tensor between two NaN guard bands of one allocation: fp32 (the default) or, for the channel-blocked fp16
+    activations, fp16 - every element of the bands, and of a tensor made without a value, holds the quiet-NaN sentinel of its type."""
 
-    def __init__(self, shape, value=None):
+    def __init__(self, shape, value=None, dtype=torch.float32):
         self.numel = int(np.prod(shape))
-        self.buf = torch.empty(self.numel + 2 * GUARD, device=DEV)
-        self.buf.view(torch.int32).fill_(NAN32)
+        self.itype, self.sentinel = {torch.float32: (torch.int32, NAN32), torch.float16: (torch.int16, NAN16)}[dtype]
+        self.buf = torch.empty(self.numel + 2 * GUARD, device=DEV, dtype=dtype)
+        self.buf.view(self.itype).fill_(self.sentinel)
         self.t = self.buf[GUARD:GUARD + self.numel].view(shape)
         if value is not None:
             self.t.copy_(value)
-        self.start = self.buf.view(torch.int32).clone()
+        self.start = self.buf.view(self.itype).clone()
 
     def bits(self):
-        return self.buf.view(torch.int32)
+        return self.buf.view(self.itype)
 
     def assert_guards(self, what):
         b = self.bits()
-        assert bool((b[:GUARD] == NAN32).all()) and bool((b[GUARD + self.numel:] == NAN32).all()), f"{what}: wrote into a guard band"
+        assert bool((b[:GUARD] == self.sentinel).all()) and bool((b[GUARD + self.numel:] == self.sentinel).all()), \
+            f"{what}: wrote into a guard band"
 
     def assert_unchanged(self, what):
         assert torch.equal(self.bits(), self.start), f"{what} was written to"
+
+    def assert_written(self, what):
+        left = self.bits()[GUARD:GUARD + self.numel] == self.sentinel
+        assert not bool(left.any()), f"{what}: {int(left.sum())} elements were never written, first at flat index {int(torch.nonzero(left)[0])}"
 
 
 @functools.lru_cache(maxsize=4)
