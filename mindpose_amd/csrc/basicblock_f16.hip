@@ -41,11 +41,7 @@ __global__ __launch_bounds__(256, 2) void basicblock_f16_kernel(const BlockF16Pa
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int lq = lane >> 4, lr = lane & 15;
 
-    int b = blockIdx.x;  // XCD-aware workgroup id: every XCD walks a contiguous run of tiles
-    {
-        const int nb = p.total_blocks, q8 = nb >> 3, r8 = nb & 7, xcd = b & 7, j = b >> 3;
-        b = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + j;
-    }
+    int b = xcd_contiguous(blockIdx.x, p.total_blocks);  // every XCD walks a contiguous run of tiles
     const int t_begin = b * p.tiles_per_wg, t_end = min(t_begin + p.tiles_per_wg, p.tiles_total);
     const int HW = p.H * p.W;
 
@@ -275,14 +271,7 @@ __global__ __launch_bounds__(256, 2) void basicblock_f16_kernel(const BlockF16Pa
 
 template <int PS1, int PS2>
 int launch_block(const BlockF16Params& p, size_t lds_bytes, hipStream_t s) {
-    auto kern = basicblock_f16_kernel<PS1, PS2>;
-    static AttrOnce attr_set_once;
-    if (attr_set_once.need()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipGetLastError();
-    }
-    hipLaunchKernelGGL(kern, dim3(p.total_blocks), dim3(256), lds_bytes, s, p);
-    return check_launch();
+    return launch_lds<basicblock_f16_kernel<PS1, PS2>>(dim3(p.total_blocks), dim3(256), lds_bytes, s, p);
 }
 
 }  // namespace

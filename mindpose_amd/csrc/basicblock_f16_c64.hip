@@ -47,7 +47,7 @@ __global__ __launch_bounds__(128 * NQ, NQ == 2 ? 2 : 1) void basicblock_f16_c64_
     const int lq = lane >> 4, lr = lane & 15;
 
     int b = blockIdx.x;
-    {
+    {   // xcd_contiguous (common.h) written out: through the helper the compiler orders and allocates this kernel's epilogues differently
         const int nb = p.total_blocks, q8 = nb >> 3, r8 = nb & 7, xcd = b & 7, j = b >> 3;
         b = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + j;
     }
@@ -227,14 +227,7 @@ __global__ __launch_bounds__(128 * NQ, NQ == 2 ? 2 : 1) void basicblock_f16_c64_
 
 template <int NQ, int PS1, int PS2>
 int launch_c64(const BlockF16Params& p, size_t lds_bytes, hipStream_t s) {
-    auto kern = basicblock_f16_c64_kernel<NQ, PS1, PS2>;
-    static AttrOnce attr_set_once;
-    if (attr_set_once.need()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipGetLastError();
-    }
-    hipLaunchKernelGGL(kern, dim3(p.total_blocks), dim3(128 * NQ), lds_bytes, s, p);
-    return check_launch();
+    return launch_lds<basicblock_f16_c64_kernel<NQ, PS1, PS2>>(dim3(p.total_blocks), dim3(128 * NQ), lds_bytes, s, p);
 }
 
 }  // namespace

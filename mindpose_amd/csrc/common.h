@@ -40,6 +40,43 @@ struct AttrOnce {
     }
 };
 
+// Launch of a kernel that takes dynamic LDS: raises the kernel's limit to the 160 KB of a gfx950 workgroup on its first launch on
+// each device (the error of a refused raise is dropped: the launch itself reports what it cannot have), launches, and returns
+// check_launch().  One launcher per kernel instantiation - the kernel is the TEMPLATE argument: the dynamic-LDS attribute is a
+// property of the instantiation, so the once-per-device flag must be too (a flag shared through the common function-pointer type,
+// as a static in a generic lambda or in a function that takes the kernel as a value would be, reaches only the first kernel a
+// process launches through it).
+template <auto Kern, typename... Args>
+int launch_lds(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t s, const Args&... args) {
+    static AttrOnce once;
+    if (once.need()) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipGetLastError();
+    }
+    hipLaunchKernelGGL(Kern, grid, block, lds_bytes, s, args...);
+    return check_launch();
+}
+
+// XCD-aware workgroup id.  Workgroups are dealt round-robin over the 8 XCDs (blocks b, b+8, ... share an XCD and its L2): this maps
+// block b of nb to the id it takes when every XCD walks one contiguous run of ids instead, so neighbouring ids share an L2.
+__device__ __forceinline__ int xcd_contiguous(int b, int nb) {
+    const int q8 = nb >> 3, r8 = nb & 7, xcd = b & 7, j = b >> 3;
+    return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + j;
+}
+
+// Raw buffer access: the hardware range check makes invalid lanes free - an offset >= num_records loads 0 /
+// drops the store - so masked staging and epilogue traffic needs no branches (and no s_waitcnt between loads).
+constexpr unsigned kOob = 0x80000000u;  // every descriptor spans < 2 GiB
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, size_t bytes) {
+    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)(bytes < 0x7FFFFFF0u ? bytes : 0x7FFFFFF0u), 0x00020000);
+}
+
+// Division by a launch-constant d: magic = magic_of(d) = floor(2^32 / d) + 1; exact while e * d < 2^32
+inline unsigned magic_of(unsigned d) { return d <= 1 ? 0u : (unsigned)(0x100000000ULL / d) + 1u; }
+__device__ __forceinline__ unsigned fastdiv(unsigned e, unsigned d, unsigned magic) { return d == 1 ? e : __umulhi(e, magic); }
+
+inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
+
 // Experiment knobs (MP_* environment variables: tile counts, forced forms - used by tests/ and tools/ to reach code paths small
 // problems would not take).  A production process never looks at them: whether they are honoured at all is decided ONCE per
 // process by MINDPOSE_EXPERIMENT_KNOBS=1 (tests/conftest.py and the tools set it), so the configure functions - called per conv

@@ -18,9 +18,6 @@
 
 namespace mp {
 
-static inline unsigned magic_of(unsigned d) { return d <= 1 ? 0u : (unsigned)(0x100000000ULL / d) + 1u; }
-static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
-
 // [Cout,Cin,kh,kw] (or the (py,px) 2x2 phase of a [Cin,Cout,4,4] transposed-conv weight)
 //   -> [Cin_pad4/4][T][4][Cout_pad16], zero padded.
 // source value of packed element (cout co, cin ci, tap t); callers have checked co < cout && ci < cin

@@ -41,11 +41,7 @@ __device__ __forceinline__ void conv_f16_body(const ConvF16Params& p, const int 
     const int lq = lane >> 4, lr = lane & 15;
 
     // XCD-aware tile id (blocks b, b+8, ... share an XCD): every XCD walks a contiguous run of tiles
-    int b = block_x;
-    {
-        const int nb = p.total_blocks, q8 = nb >> 3, r8 = nb & 7, xcd = b & 7, j = b >> 3;
-        b = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + j;
-    }
+    int b = xcd_contiguous(block_x, p.total_blocks);
     const int ct = b % p.n_ct;
     b /= p.n_ct;
     // pixel tile (of its phase, MP_CONV_PHASES4) = partial-sum slot of the epilogue statistics
@@ -374,15 +370,9 @@ constexpr bool f16_has_stats(int ks) { return ks == 1 || ks == 3; }
 template <int KS, int S, int PS, int CS, int WAVES_P, int WAVES_C, bool LIGHT, bool ONE_CHUNK, int STATS>
 int launch_f16_kernel(const ConvF16Params& p, size_t lds_bytes, hipStream_t s) {
     if (g_dry_launch) return MP_OK;  // mp_f16_conv_supported: the dispatch alone
-    auto kern = conv_f16_kernel<KS, S, PS, CS, WAVES_P, WAVES_C, f16_ni(KS, LIGHT), f16_nw(KS, LIGHT), ONE_CHUNK ? 2 : f16_occ(LIGHT),
-                                ONE_CHUNK, STATS>;
-    static AttrOnce attr_set_once;
-    if (attr_set_once.need()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipGetLastError();
-    }
-    hipLaunchKernelGGL(kern, dim3(p.total_blocks, p.phases > 1 ? p.phases : 1), dim3(256), lds_bytes, s, p);
-    return check_launch();
+    constexpr auto kern = conv_f16_kernel<KS, S, PS, CS, WAVES_P, WAVES_C, f16_ni(KS, LIGHT), f16_nw(KS, LIGHT),
+                                          ONE_CHUNK ? 2 : f16_occ(LIGHT), ONE_CHUNK, STATS>;
+    return launch_lds<kern>(dim3(p.total_blocks, p.phases > 1 ? p.phases : 1), dim3(256), lds_bytes, s, p);
 }
 
 template <int KS, int S, int PS, int CS, int WAVES_P, int WAVES_C, bool LIGHT, bool ONE_CHUNK = false>

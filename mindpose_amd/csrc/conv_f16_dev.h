@@ -13,16 +13,10 @@ typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
-constexpr unsigned kOob = 0x80000000u;
 // "masked" marker for the two ADDENDS of an output offset (cout part + pixel part): marker + marker, marker + any valid part
 // and a valid sum are all told apart by the buffer range check alone as long as the tensor is smaller than the marker, so the
 // epilogue adds the parts without a select per store (tensors >= 1.5 GB are refused at plan time)
 constexpr unsigned kInv = 0x60000000u;
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, size_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)(bytes < 0x7FFFFFF0u ? bytes : 0x7FFFFFF0u), 0x00020000);
-}
-__device__ __forceinline__ unsigned fastdiv(unsigned e, unsigned d, unsigned magic) { return d == 1 ? e : __umulhi(e, magic); }
 
 // Cout-tile PAIRING: the 16x16 accumulator of v_mfma_f32_16x16x32_f16 gives a lane 4 consecutive MFMA rows of one pixel.  If rows
 // map to couts in order, that is 4 couts = HALF a 16-byte channel block -> 8-byte stores (0.54-0.70 of the 16-byte rate, twice the
@@ -164,10 +158,6 @@ __device__ __forceinline__ void f16_stats_flush(f32x4 (&sa)[CS], f32x4 (&sb)[CS]
         }
     }
 }
-
-inline unsigned magic_of(unsigned d) { return d <= 1 ? 0u : (unsigned)(0x100000000ULL / d) + 1u; }
-inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
-
 
 }  // namespace
 }  // namespace mp

@@ -24,11 +24,7 @@ __global__ __launch_bounds__(256, OCC) void conv_f16_mt_kernel(const ConvF16Para
     const int wp_i = wave % WAVES_P, wc_i = wave / WAVES_P;
     const int lq = lane >> 4, lr = lane & 15;
 
-    int b = blockIdx.x;
-    {
-        const int nb = p.total_blocks, q8 = nb >> 3, r8 = nb & 7, xcd = b & 7, j = b >> 3;
-        b = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + j;
-    }
+    int b = xcd_contiguous(blockIdx.x, p.total_blocks);
     const int ct = b % p.n_ct;
     const int grp = b / p.n_ct;
     const int t_begin = grp * p.tiles_per_wg;
@@ -326,14 +322,8 @@ constexpr int mt_ni(int occ) { return occ == 1 ? 12 : 8; }
 template <int KS, int S, int PS, int CS, int WAVES_P, int WAVES_C, int OCC, int STATS>
 int launch_mt_kernel(const ConvF16Params& p, size_t lds_bytes, hipStream_t s) {
     if (g_dry_launch) return MP_OK;  // mp_f16_conv_supported: the dispatch alone
-    auto kern = conv_f16_mt_kernel<KS, S, PS, CS, WAVES_P, WAVES_C, mt_ni(OCC), OCC, STATS>;
-    static AttrOnce attr_set_once;
-    if (attr_set_once.need()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipGetLastError();
-    }
-    hipLaunchKernelGGL(kern, dim3(p.total_blocks, p.phases > 1 ? p.phases : 1), dim3(256), lds_bytes, s, p);
-    return check_launch();
+    constexpr auto kern = conv_f16_mt_kernel<KS, S, PS, CS, WAVES_P, WAVES_C, mt_ni(OCC), OCC, STATS>;
+    return launch_lds<kern>(dim3(p.total_blocks, p.phases > 1 ? p.phases : 1), dim3(256), lds_bytes, s, p);
 }
 
 template <int KS, int S, int PS, int CS, int WAVES_P, int WAVES_C, int OCC>

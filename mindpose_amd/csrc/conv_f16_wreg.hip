@@ -76,11 +76,7 @@ __global__ __launch_bounds__(256, OCC) void conv_f16_wreg_kernel(const ConvF16Pa
     const int lq = lane >> 4, lr = lane & 15;
     WREG_STAMP(0);
 
-    int b = blockIdx.x;
-    {
-        const int nb = p.total_blocks, q8 = nb >> 3, r8 = nb & 7, xcd = b & 7, j = b >> 3;
-        b = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + j;
-    }
+    int b = xcd_contiguous(blockIdx.x, p.total_blocks);
     const int ct = b % p.n_ct;
     b /= p.n_ct;
     const int part_idx = b;  // pixel tile = partial-sum slot of the epilogue statistics
@@ -388,19 +384,13 @@ __global__ __launch_bounds__(256, OCC) void conv_f16_wreg_kernel(const ConvF16Pa
 template <int KS, int S, int PS, int CSW, int WAVES_P, int OCC, int STATS, bool PRE = false>
 int launch_wreg_kernel(const ConvF16Params& p, size_t lds_bytes, hipStream_t s) {
     if (g_dry_launch) return MP_OK;  // mp_f16_conv_supported: the dispatch alone
-    auto kern = conv_f16_wreg_kernel<KS, S, PS, CSW, WAVES_P, OCC, STATS, PRE>;
-    static AttrOnce attr_set_once;
-    if (attr_set_once.need()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipGetLastError();
-    }
+    constexpr auto kern = conv_f16_wreg_kernel<KS, S, PS, CSW, WAVES_P, OCC, STATS, PRE>;
 #if MP_WS_STAMPS
-    hipLaunchKernelGGL(kern, dim3(p.total_blocks), dim3(256), lds_bytes, s, p,
-                       (g_ws_stamp_buf && (size_t)p.total_blocks * 64 * 8 <= g_ws_stamp_bytes) ? g_ws_stamp_buf : nullptr);
+    return launch_lds<kern>(dim3(p.total_blocks), dim3(256), lds_bytes, s, p,
+                            (g_ws_stamp_buf && (size_t)p.total_blocks * 64 * 8 <= g_ws_stamp_bytes) ? g_ws_stamp_buf : nullptr);
 #else
-    hipLaunchKernelGGL(kern, dim3(p.total_blocks), dim3(256), lds_bytes, s, p);
+    return launch_lds<kern>(dim3(p.total_blocks), dim3(256), lds_bytes, s, p);
 #endif
-    return check_launch();
 }
 
 template <int KS, int S, int PS, int CSW, int WAVES_P, int OCC>

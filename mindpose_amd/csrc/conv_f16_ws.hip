@@ -118,11 +118,7 @@ __global__ __launch_bounds__(256, OCC) void conv_f16_ws_kernel(const ConvF16Para
     const int lq = lane >> 4, lr = lane & 15;
     WS_STAMP(0);
 
-    int b = blockIdx.x;
-    {
-        const int nb = p.total_blocks, q8 = nb >> 3, r8 = nb & 7, xcd = b & 7, j = b >> 3;
-        b = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + j;
-    }
+    int b = xcd_contiguous(blockIdx.x, p.total_blocks);
     const int ct = b % p.n_ct;  // the cout slices of one tile run sit next to each other: they share the input through one L2
     const int grp = b / p.n_ct;
     const int t_begin = grp * p.tiles_per_wg, t_end = min(t_begin + p.tiles_per_wg, p.tiles_total);
@@ -547,19 +543,13 @@ int launch_ws_kernel(const ConvF16Params& p, size_t lds_bytes, hipStream_t s) {
     if constexpr (!ws_build_fits<NQ, CSW, WAVES_P, PS, OCC, STATS, RES>()) return MP_ERR_UNSUPPORTED;
     else {
     if (g_dry_launch) return MP_OK;  // mp_f16_conv_supported: the dispatch alone
-    auto kern = conv_f16_ws_kernel<NQ, CSW, WAVES_P, PS, OCC, STATS, RES>;
-    static AttrOnce attr_set_once;
-    if (attr_set_once.need()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipGetLastError();
-    }
+    constexpr auto kern = conv_f16_ws_kernel<NQ, CSW, WAVES_P, PS, OCC, STATS, RES>;
 #if MP_WS_STAMPS
-    hipLaunchKernelGGL(kern, dim3(p.total_blocks), dim3(256), lds_bytes, s, p,
-                       (g_ws_stamp_buf && (size_t)p.total_blocks * 64 * 8 <= g_ws_stamp_bytes) ? g_ws_stamp_buf : nullptr);
+    return launch_lds<kern>(dim3(p.total_blocks), dim3(256), lds_bytes, s, p,
+                            (g_ws_stamp_buf && (size_t)p.total_blocks * 64 * 8 <= g_ws_stamp_bytes) ? g_ws_stamp_buf : nullptr);
 #else
-    hipLaunchKernelGGL(kern, dim3(p.total_blocks), dim3(256), lds_bytes, s, p);
+    return launch_lds<kern>(dim3(p.total_blocks), dim3(256), lds_bytes, s, p);
 #endif
-    return check_launch();
     }
 }
 

@@ -63,11 +63,7 @@ __global__ __launch_bounds__(256, 2) void conv1x1_f32_gemm_kernel(const GemmPara
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1, l31 = lane & 31, lh = lane >> 5;
 
-    int wg = blockIdx.x;
-    {   // XCD-aware workgroup id (blocks b, b+8, ... share an XCD): the cout tiles of one column tile share an L2
-        const int nb = gridDim.x, q8 = nb >> 3, r8 = nb & 7, xcd = wg & 7, j = wg >> 3;
-        wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + j;
-    }
+    const int wg = xcd_contiguous(blockIdx.x, gridDim.x);  // the cout tiles of one column tile share an L2
     const int ct = wg % p.n_ct, co0 = ct * TM, col0 = (wg / p.n_ct) * TN;
     // p.phases == 4: the four sub-pixel phases of a transposed convolution in ONE launch, phase (py, px) = blockIdx.y - its own
     // packed weights (four equal slices of one buffer), padding 1 - p on the top / left, output pixels (2 y + py, 2 x + px)

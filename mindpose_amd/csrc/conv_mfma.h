@@ -38,12 +38,7 @@ namespace mp {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
-// Raw buffer access: the hardware range check makes invalid lanes free - an offset >= num_records loads 0 /
-// drops the store - so masked staging and epilogue traffic needs no branches (and no s_waitcnt between loads).
-constexpr unsigned kOob = 0x80000000u;  // every descriptor below spans < 2 GiB
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* base, size_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)(bytes < 0x7FFFFFF0u ? bytes : 0x7FFFFFF0u), 0x00020000);
-}
+// Raw buffer access (descriptors: make_rsrc, masked lanes: kOob - common.h)
 __device__ __forceinline__ f32x4 buf_load4(__amdgpu_buffer_rsrc_t r, unsigned off) {
     return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
 }
@@ -90,11 +85,6 @@ struct ConvKParams {
     unsigned long long* dbg;  // diagnostic builds (MP_CONV_STAMPS) only: 8 x u64 per workgroup
 };
 
-__device__ __forceinline__ unsigned fastdiv(unsigned e, unsigned d, unsigned magic) {
-    // magic = floor(2^32 / d) + 1; exact while e * d < 2^32 (all uses here: e, d < 2^16)
-    return d == 1 ? e : __umulhi(e, magic);
-}
-
 // Software-pipelined workgroup:
 //   prologue   zero both input buffers (halo), build the per-thread staging tables, stage chunk 0
 //   per chunk  issue the global loads of chunk c+1 into registers  ->  MFMA over chunk c (operand
@@ -121,11 +111,7 @@ __global__ __launch_bounds__(256, OCC) void conv_mfma_kernel(const ConvKParams p
 
     // XCD-aware tile id: blocks b and b+8 share an XCD (round-robin dispatch), so give every XCD a
     // contiguous run of tiles; cout tiles of one pixel tile (same input) then share one L2.
-    int b = blockIdx.x;
-    {
-        const int nb = p.total_blocks, q8 = nb >> 3, r8 = nb & 7, xcd = b & 7, j = b >> 3;
-        b = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + j;
-    }
+    int b = xcd_contiguous(blockIdx.x, p.total_blocks);
     const int ct = b % p.n_ct;
     b /= p.n_ct;
     const int ty = b % p.tiles_y, tn = b / p.tiles_y;
@@ -554,14 +540,8 @@ constexpr int stage_occ(bool light) { return light ? 3 : 2; }
 
 template <int KS, int S, int PS, int CS, int WAVES_P, int WAVES_C, bool VEC, bool LIGHT>
 int launch_variant(const ConvKParams& p, size_t lds_bytes, hipStream_t s) {
-    auto kern = conv_mfma_kernel<KS, S, PS, CS, WAVES_P, WAVES_C, stage_ni(KS, LIGHT, VEC), stage_nw(KS, LIGHT), VEC, stage_occ(LIGHT)>;
-    static AttrOnce attr_set_once;
-    if (attr_set_once.need()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipGetLastError();
-    }
-    hipLaunchKernelGGL(kern, dim3(p.total_blocks), dim3(256), lds_bytes, s, p);
-    return check_launch();
+    constexpr auto kern = conv_mfma_kernel<KS, S, PS, CS, WAVES_P, WAVES_C, stage_ni(KS, LIGHT, VEC), stage_nw(KS, LIGHT), VEC, stage_occ(LIGHT)>;
+    return launch_lds<kern>(dim3(p.total_blocks), dim3(256), lds_bytes, s, p);
 }
 
 template <int KS, int S, bool VEC>

@@ -22,7 +22,6 @@ namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-static inline unsigned magic_of(unsigned d) { return d <= 1 ? 0u : (unsigned)(0x100000000ULL / d) + 1u; }
 __device__ __forceinline__ unsigned fdiv(unsigned e, unsigned d, unsigned magic) { return d == 1 ? e : __umulhi(e, magic); }
 
 // weight k-steps in flight per wave = four cin quads x the taps (3x3: 36 dwords per lane, 9 KB per wave - the k loop is a weight
@@ -244,13 +243,7 @@ int small_configure(const mp_conv_desc* d, SmallLaunch& L, int wide) {
 
 template <int KS, int S, int PT>
 static int small_launch_ks(const SmallLaunch& L, hipStream_t s) {
-    static AttrOnce attr_set_once;
-    if (attr_set_once.need()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv_small_f32_kernel<KS, S, PT>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipGetLastError();
-    }
-    hipLaunchKernelGGL((conv_small_f32_kernel<KS, S, PT>), dim3(L.grid), dim3(64 * kWaves), L.lds_bytes, s, L.p);
-    return check_launch();
+    return launch_lds<conv_small_f32_kernel<KS, S, PT>>(dim3(L.grid), dim3(64 * kWaves), L.lds_bytes, s, L.p);
 }
 
 template <int KS, int S>

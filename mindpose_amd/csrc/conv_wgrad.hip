@@ -404,41 +404,18 @@ int mp_conv_wgrad(const mp_conv_desc* desc, const float* x, const float* dz, flo
     p.x = x; p.dz = dz; p.slabs = reinterpret_cast<float*>(workspace);
     hipStream_t s = as_stream(stream);
     dim3 grid(((p.Cout + 31) / 32) * p.ci_tiles, p.splits), block(256);
-#define MP_WGRAD_LAUNCH(KS_, S_)                                                                                        \
-    do {                                                                                                                \
-        auto kern = conv_wgrad_kernel<KS_, S_>;                                                                         \
-        static AttrOnce attr_once;                                                                                       \
-        if (attr_once.need()) {                                                                                                    \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-            (void)hipGetLastError();                                                                                    \
-        }                                                                                                               \
-        hipLaunchKernelGGL(kern, grid, block, lds, s, p);                                                               \
-    } while (0)
-#define MP_WGRAD_LAUNCH_PIPE(KS_, S_)                                                                                   \
-    do {                                                                                                                \
-        auto kern = conv_wgrad_pipe_kernel<KS_, S_, 6, 9>;                                                              \
-        static AttrOnce attr_once;                                                                                       \
-        if (attr_once.need()) {                                                                                                    \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-            (void)hipGetLastError();                                                                                    \
-        }                                                                                                               \
-        hipLaunchKernelGGL(kern, grid, block, lds, s, p);                                                               \
-    } while (0)
     if (p.vec) {
-        if (desc->kh == 3 && desc->stride == 1) MP_WGRAD_LAUNCH_PIPE(3, 1);
-        else if (desc->kh == 3 && desc->stride == 2) MP_WGRAD_LAUNCH_PIPE(3, 2);
-        else if (desc->kh == 1 && desc->stride == 1) MP_WGRAD_LAUNCH_PIPE(1, 1);
-        else MP_WGRAD_LAUNCH_PIPE(1, 2);
+        if (desc->kh == 3 && desc->stride == 1) rc = launch_lds<conv_wgrad_pipe_kernel<3, 1, 6, 9>>(grid, block, lds, s, p);
+        else if (desc->kh == 3 && desc->stride == 2) rc = launch_lds<conv_wgrad_pipe_kernel<3, 2, 6, 9>>(grid, block, lds, s, p);
+        else if (desc->kh == 1 && desc->stride == 1) rc = launch_lds<conv_wgrad_pipe_kernel<1, 1, 6, 9>>(grid, block, lds, s, p);
+        else rc = launch_lds<conv_wgrad_pipe_kernel<1, 2, 6, 9>>(grid, block, lds, s, p);
     } else {
-        if (desc->kh == 4) MP_WGRAD_LAUNCH(4, 2);
-        else if (desc->kh == 3 && desc->stride == 1) MP_WGRAD_LAUNCH(3, 1);
-        else if (desc->kh == 3 && desc->stride == 2) MP_WGRAD_LAUNCH(3, 2);
-        else if (desc->kh == 1 && desc->stride == 1) MP_WGRAD_LAUNCH(1, 1);
-        else MP_WGRAD_LAUNCH(1, 2);
+        if (desc->kh == 4) rc = launch_lds<conv_wgrad_kernel<4, 2>>(grid, block, lds, s, p);
+        else if (desc->kh == 3 && desc->stride == 1) rc = launch_lds<conv_wgrad_kernel<3, 1>>(grid, block, lds, s, p);
+        else if (desc->kh == 3 && desc->stride == 2) rc = launch_lds<conv_wgrad_kernel<3, 2>>(grid, block, lds, s, p);
+        else if (desc->kh == 1 && desc->stride == 1) rc = launch_lds<conv_wgrad_kernel<1, 1>>(grid, block, lds, s, p);
+        else rc = launch_lds<conv_wgrad_kernel<1, 2>>(grid, block, lds, s, p);
     }
-#undef MP_WGRAD_LAUNCH_PIPE
-#undef MP_WGRAD_LAUNCH
-    rc = check_launch();
     if (rc != MP_OK) return rc;
     if (count <= 18432 && p.splits >= 64) {
         hipLaunchKernelGGL(wgrad_reduce_grouped_kernel<16>, dim3((unsigned)((count + 15) / 16)), dim3(256), 0, s, p.slabs, dw, count,

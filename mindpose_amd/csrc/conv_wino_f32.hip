@@ -104,11 +104,7 @@ __global__ __launch_bounds__(WIDE ? 256 : 256 * TEAMS, TEAMS == 1 ? 2 : 1) void 
 
     // A workgroup walks p.tiles_per_wg consecutive tiles (same staging tables, one zero fill; the raw rows of the next tile are
     // requested before the epilogue of the current one, so only the first tile of a workgroup sees the HBM latency).
-    int wg = blockIdx.x;
-    {   // XCD-aware workgroup id (blocks b, b+8, ... share an XCD): neighbouring tiles (cout tiles of one band) share an L2
-        const int nb = gridDim.x, q8 = nb >> 3, r8 = nb & 7, xcd = wg & 7, j = wg >> 3;
-        wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + j;
-    }
+    const int wg = xcd_contiguous(blockIdx.x, gridDim.x);  // neighbouring tiles (cout tiles of one band) share an L2
     const int HW = p.H * p.W;
     int ct, n, y0, n_img;  // coordinates of the tile whose INPUT side is being worked on
     auto tile_coords = [&](int tile) {
@@ -713,19 +709,9 @@ __global__ __launch_bounds__(256) void pack_weight_wino_kernel(const float* __re
     }
 }
 
-inline unsigned magic_of(unsigned d) { return d <= 1 ? 0u : (unsigned)(0x100000000ULL / d) + 1u; }
-
-// One launcher per kernel instantiation: the dynamic-LDS attribute is a property of the instantiation, so the once-per-device
-// flag must be too (a flag shared through the common function-pointer type would reach only the first kernel a process launches).
 template <auto Kern>
 int wino_go(const WinoLaunch& L, hipStream_t s) {
-    static AttrOnce attr_once;
-    if (attr_once.need()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipGetLastError();
-    }
-    hipLaunchKernelGGL(Kern, dim3((L.p.total_blocks + L.p.tiles_per_wg - 1) / L.p.tiles_per_wg), dim3(L.wide ? 256 : 256 * L.teams), L.lds_bytes, s, L.p);
-    return check_launch();
+    return launch_lds<Kern>(dim3((L.p.total_blocks + L.p.tiles_per_wg - 1) / L.p.tiles_per_wg), dim3(L.wide ? 256 : 256 * L.teams), L.lds_bytes, s, L.p);
 }
 
 }  // namespace

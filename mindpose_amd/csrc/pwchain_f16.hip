@@ -50,11 +50,7 @@ __global__ __launch_bounds__(256, DS ? 2 : 3) void expand_reduce_f16_kernel(cons
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lq = lane >> 4, lr = lane & 15;
 
-    int b = blockIdx.x;
-    {
-        const int nb = p.total_blocks, q8 = nb >> 3, r8 = nb & 7, xcd = b & 7, j = b >> 3;
-        b = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + j;
-    }
+    int b = xcd_contiguous(blockIdx.x, p.total_blocks);
     const unsigned n = (unsigned)b / (unsigned)p.tiles_per_img;
     const unsigned p0 = ((unsigned)b - n * (unsigned)p.tiles_per_img) * kPT;
     const unsigned HW = (unsigned)p.HW;

@@ -565,29 +565,16 @@ int pwchain32_build(const float* mid, const float* res, const float* x0, const f
 
 int pwchain32_launch(const PwChainF32Launch& L, hipStream_t s) {
     if (g_dry_launch) return MP_OK;
-    auto go = [&](auto kern) {
-        static AttrOnce attr_once;  // (one per instantiation of this lambda)
-        if (attr_once.need()) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipGetLastError();
-        }
-        hipLaunchKernelGGL(kern, dim3(L.grid), dim3(256), L.lds_bytes, s, L.p);
-        return check_launch();
-    };
-    auto go8 = [&](auto kern, int threads) {
-        static AttrOnce attr_once;
-        if (attr_once.need()) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipGetLastError();
-        }
-        hipLaunchKernelGGL(kern, dim3(L.grid), dim3(threads), L.lds_bytes, s, L.p);
-        return check_launch();
-    };
-    if (L.ds) return go(expand_reduce_f32_kernel<true, true>);
-    if (L.form == 8) return L.red ? go8(expand_reduce_f32_w8_kernel<true, 2>, 512) : go8(expand_reduce_f32_w8_kernel<false, 2>, 512);
-    if (L.form == 2) return L.red ? go8(expand_reduce_f32_w8_kernel<true, 1>, 256) : go8(expand_reduce_f32_w8_kernel<false, 1>, 256);
-    if (L.red) return go(expand_reduce_f32_kernel<false, true>);
-    return go(expand_reduce_f32_kernel<false, false>);
+    const dim3 grid(L.grid), b256(256), b512(512);
+    if (L.ds) return launch_lds<expand_reduce_f32_kernel<true, true>>(grid, b256, L.lds_bytes, s, L.p);
+    if (L.form == 8)
+        return L.red ? launch_lds<expand_reduce_f32_w8_kernel<true, 2>>(grid, b512, L.lds_bytes, s, L.p)
+                     : launch_lds<expand_reduce_f32_w8_kernel<false, 2>>(grid, b512, L.lds_bytes, s, L.p);
+    if (L.form == 2)
+        return L.red ? launch_lds<expand_reduce_f32_w8_kernel<true, 1>>(grid, b256, L.lds_bytes, s, L.p)
+                     : launch_lds<expand_reduce_f32_w8_kernel<false, 1>>(grid, b256, L.lds_bytes, s, L.p);
+    if (L.red) return launch_lds<expand_reduce_f32_kernel<false, true>>(grid, b256, L.lds_bytes, s, L.p);
+    return launch_lds<expand_reduce_f32_kernel<false, false>>(grid, b256, L.lds_bytes, s, L.p);
 }
 
 }  // namespace mp

@@ -31,11 +31,7 @@ __global__ __launch_bounds__(256) void stem_conv_f16_kernel(const StemF16Params 
     const int lq = lane >> 4, lr = lane & 15;
     constexpr int RIN = 2 * kStemR + 1, CS = 4;
     const int pitch = p.pitch;
-    int b = blockIdx.x;
-    {
-        const int nb = p.total_blocks, q8 = nb >> 3, r8 = nb & 7, xcd = b & 7, j = b >> 3;
-        b = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + j;
-    }
+    int b = xcd_contiguous(blockIdx.x, p.total_blocks);
     const int n = b / p.tiles_y, y0 = (b - n * p.tiles_y) * kStemR;
 
     // ---- this lane's k positions: k = 8 lq + j -> (tap, channel) = (k / 3, k % 3) -> element offset in the tile; k >= 27: the zero slot

@@ -26,11 +26,7 @@ __global__ __launch_bounds__(256) void stem_conv_f32_kernel(const StemF32Params 
     const int lq = lane >> 4, lr = lane & 15;
     constexpr int RIN = 2 * kR + 1, KQ = 7, CB = 4;
     const int pitch = p.pitch;
-    int b = blockIdx.x;
-    {
-        const int nb = p.total_blocks, q8 = nb >> 3, r8 = nb & 7, xcd = b & 7, j = b >> 3;
-        b = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + j;
-    }
+    int b = xcd_contiguous(blockIdx.x, p.total_blocks);
     const int n = b / p.tiles_y, y0 = (b - n * p.tiles_y) * kR;
 
     // ---- this lane's k positions (A operand: row = pixel lr, k = 4 q + lq): (tap, channel) = (k / 3, k % 3) -> offset in the tile

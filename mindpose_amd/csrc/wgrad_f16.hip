@@ -724,41 +724,26 @@ int geometry(const mp_conv_desc* d, Wgrad16Params& p, size_t& lds_bytes, int n_j
 
 template <int KS, int S>
 int launch_wgrad16_dma(const Wgrad16Params& p, size_t lds, hipStream_t s) {
-    auto kern = KS == 4 ? conv_wgrad_f16_dma_k4s2
-                        : KS == 3 ? (S == 1 ? conv_wgrad_f16_dma_k3s1 : conv_wgrad_f16_dma_k3s2)
-                                  : (S == 1 ? conv_wgrad_f16_dma_k1s1 : conv_wgrad_f16_dma_k1s2);
-    auto kern_k = KS == 3 ? (S == 1 ? conv_wgrad_f16_dmak_k3s1 : conv_wgrad_f16_dmak_k3s2)
-                          : (S == 1 ? conv_wgrad_f16_dmak_k1s1 : conv_wgrad_f16_dmak_k1s2);
-    static AttrOnce attr_once;
-    if (attr_once.need()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern_k), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipGetLastError();
+    const dim3 grid(p.co_tiles * p.ci_tiles, p.splits, p.n_jobs ? p.n_jobs : 1), block(256);
+    if constexpr (KS == 3) {  // 16-channel input side
+        constexpr auto kern_n = S == 1 ? conv_wgrad_f16_dman_k3s1 : conv_wgrad_f16_dman_k3s2;
+        if (p.wide == 2) return launch_lds<kern_n>(grid, block, lds, s, p);
     }
-    if (p.wide == 1 && KS <= 3) kern = kern_k;
-    if (p.wide == 2 && KS == 3) {
-        kern = S == 1 ? conv_wgrad_f16_dman_k3s1 : conv_wgrad_f16_dman_k3s2;
-        static AttrOnce attr_n;
-        if (attr_n.need()) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            (void)hipGetLastError();
-        }
+    if constexpr (KS <= 3) {  // 64 x 64 tile
+        constexpr auto kern_k = KS == 3 ? (S == 1 ? conv_wgrad_f16_dmak_k3s1 : conv_wgrad_f16_dmak_k3s2)
+                                        : (S == 1 ? conv_wgrad_f16_dmak_k1s1 : conv_wgrad_f16_dmak_k1s2);
+        if (p.wide == 1) return launch_lds<kern_k>(grid, block, lds, s, p);
     }
-    hipLaunchKernelGGL(kern, dim3(p.co_tiles * p.ci_tiles, p.splits, p.n_jobs ? p.n_jobs : 1), dim3(256), lds, s, p);
-    return check_launch();
+    constexpr auto kern = KS == 4 ? conv_wgrad_f16_dma_k4s2
+                                  : KS == 3 ? (S == 1 ? conv_wgrad_f16_dma_k3s1 : conv_wgrad_f16_dma_k3s2)
+                                            : (S == 1 ? conv_wgrad_f16_dma_k1s1 : conv_wgrad_f16_dma_k1s2);
+    return launch_lds<kern>(grid, block, lds, s, p);
 }
 
 template <int KS, int S>
 int launch_wgrad16(const Wgrad16Params& p, size_t lds, hipStream_t s) {
     if (p.pieces > 0) return launch_wgrad16_dma<KS, S>(p, lds, s);
-    auto kern = conv_wgrad_f16_kernel<KS, S, kNZ, kNX>;
-    static AttrOnce attr_once;
-    if (attr_once.need()) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipGetLastError();
-    }
-    hipLaunchKernelGGL(kern, dim3(p.co_tiles * p.ci_tiles, p.splits, p.n_jobs ? p.n_jobs : 1), dim3(256), lds, s, p);
-    return check_launch();
+    return launch_lds<conv_wgrad_f16_kernel<KS, S, kNZ, kNX>>(dim3(p.co_tiles * p.ci_tiles, p.splits, p.n_jobs ? p.n_jobs : 1), dim3(256), lds, s, p);
 }
 
 // launches + fixed-order slab reduction of 1 .. kWgradJobs layers of one shape
