@@ -338,6 +338,40 @@ int mp_reduce_scatter_allgather_grads(void* comm, float* arena_dev, size_t count
 int mp_optimizer_step(int kind, float* param_dev, const float* grad_dev, float* state1_dev, float* state2_dev, size_t count,
                       float lr, float grad_scale, float weight_decay, const float hyper[5], mp_stream_t stream);
 
+/* ---- device-resident step tail (train_tail.hip): the host queues training steps without reading one back --------------------
+ * The loss-scale state machine of mindspore.amp.DynamicLossScaleManager (tools/train.py:170-181), the skip decision and the
+ * learning-rate lookup run on the device; the update launches read their step-dependent arguments from device memory. */
+typedef struct mp_train_tail_state {   /* device memory, owned by the caller */
+    double loss_scale;
+    int64_t cur_iter, last_overflow_iter, skipped_steps, applied_steps;
+} mp_train_tail_state;
+typedef struct mp_step_args {          /* device memory, written by mp_train_tail_advance, read by the *_resident launches */
+    int32_t skip;                      /* 1: this step overflowed, the update launches leave everything untouched */
+    float grad_scale;                  /* (float)(mean_scale / loss_scale before the update / static_loss_scale) */
+    float lr;                          /* lr_table[min(applied_steps, lr_len - 1)] */
+    float aux0, aux1;                  /* aux_table[min(applied_steps, aux_len - 1)][0..1] (Adam: beta1^t, beta2^t), 0 without a table */
+    float first_step;                  /* applied_steps == 0 */
+} mp_step_args;
+/* One launch of one workgroup.  overflow_flag_dev: the flag mp_grad_finite_check filled; NULL = no loss scaling, never overflow
+ * (loss_scale is then neither read into a decision nor changed).  Fills *step_args_dev from the state BEFORE the update, then
+ * advances the state as DynamicLossScaleManager.update_loss_scale does, in double: on overflow loss_scale = max(loss_scale /
+ * scale_factor, 1), last_overflow_iter = cur_iter, ++skipped_steps; otherwise loss_scale *= scale_factor when (cur_iter -
+ * last_overflow_iter) % scale_window == 0, ++applied_steps; always ++cur_iter.  Finally *loss_scale_out_dev (may be NULL) =
+ * (float)loss_scale: the scalar a captured step multiplies its loss by.  lr_table_dev: lr_len >= 1 fp32 values; aux_table_dev
+ * (may be NULL): aux_len pairs. */
+int mp_train_tail_advance(const int* overflow_flag_dev, mp_train_tail_state* state_dev, double scale_factor, int64_t scale_window,
+                          double mean_scale, double static_loss_scale, const float* lr_table_dev, int64_t lr_len,
+                          const float* aux_table_dev, int64_t aux_len, mp_step_args* step_args_dev, float* loss_scale_out_dev,
+                          mp_stream_t stream);
+/* mp_adamw_step_scaled / mp_optimizer_step with lr, grad_scale and skip - and, kind 1, hyper[3..4] = aux0, aux1; kind 2, hyper[3]
+ * = first_step - read from *step_args_dev instead of the launch's arguments: the same per-element arithmetic, operation for
+ * operation.  A set skip leaves parameters and states untouched. */
+int mp_adamw_step_resident(float* param_dev, const float* grad_dev, float* exp_avg_dev, float* exp_avg_sq_dev, size_t count,
+                           float beta1, float beta2, float eps, float weight_decay, const mp_step_args* step_args_dev,
+                           mp_stream_t stream);
+int mp_optimizer_step_resident(int kind, float* param_dev, const float* grad_dev, float* state1_dev, float* state2_dev, size_t count,
+                               float weight_decay, const float hyper[5], const mp_step_args* step_args_dev, mp_stream_t stream);
+
 /* Conv2d weight gradient (training backward of every conv of hrnet.py): dW[co,ci,ky,kx] = sum_{n,y,x}
  * dz[n,co,y,x] * x[n,ci,y*s+ky-p,x*s+kx-p] for k in {1,3}, s in {1,2}, p = k/2 (desc as for the forward conv; its
  * output-mapping fields are ignored).  fp32 MFMA, pixel axis split over workgroups into slabs that are summed in a

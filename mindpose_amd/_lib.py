@@ -173,6 +173,12 @@ _PROTOTYPES = {
     "mp_f16_fuse_sum_bwd_term_stats": (c_int, [c_f32p] * 3 + [c_int] * 6 + [c_f32p, c_f32p, c_int, c_f32p, c_size_t, ctypes.c_void_p]),
     "mp_optimizer_step": (c_int, [c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_size_t, ctypes.c_float,
                                   ctypes.c_float, ctypes.c_float, ctypes.POINTER(ctypes.c_float * 5), ctypes.c_void_p]),
+    # device-resident step tail (train_tail.hip): state block, step-arguments block, tables and flags travel as device pointers
+    "mp_train_tail_advance": (c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, c_i64, ctypes.c_double, ctypes.c_double,
+                                      ctypes.c_void_p, c_i64, ctypes.c_void_p, c_i64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "mp_adamw_step_resident": (c_int, [c_f32p] * 4 + [c_size_t] + [ctypes.c_float] * 4 + [ctypes.c_void_p, ctypes.c_void_p]),
+    "mp_optimizer_step_resident": (c_int, [c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_size_t,
+                                           ctypes.c_float, ctypes.POINTER(ctypes.c_float * 5), ctypes.c_void_p, ctypes.c_void_p]),
     "mp_f16_basicblock_fwd": (c_int, [c_f32p] * 8 + [c_int] * 5 + [ctypes.c_void_p]),
     "mp_f16_basicblock_supported": (c_int, [c_int] * 4),
     "mp_stem_conv_fwd": (c_int, [c_f32p] * 4 + [c_int, c_f32p] + [c_int] * 3 + [ctypes.c_void_p]),

@@ -9,6 +9,7 @@
 #include <dlfcn.h>
 
 #include "common.h"
+#include "optim_update.h"
 
 namespace mp {
 struct Id128 {  // ncclUniqueId: 128 opaque bytes passed BY VALUE to ncclCommInitRank
@@ -38,16 +39,8 @@ __global__ __launch_bounds__(256) void adamw_scaled_kernel(float* __restrict__ p
                                                            float* __restrict__ v, size_t n, float lr, float b1, float b2, float eps,
                                                            float wd, float grad_scale, const int* __restrict__ skip) {
     if (skip != nullptr && *skip != 0) return;  // overflow step: parameters and moments untouched (uniform over the grid)
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const float gi = g[i] * grad_scale;
-        const float mi = b1 * m[i] + (1.f - b1) * gi;
-        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-        m[i] = mi;
-        v[i] = vi;
-        float upd = mi / (sqrtf(vi) + eps);
-        upd += wd * p[i];
-        p[i] = p[i] - lr * upd;
-    }
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+        adamw_update(p, m, v, i, g[i] * grad_scale, lr, b1, b2, eps, wd);
 }
 
 // ---- RCCL, bound lazily ------------------------------------------------------------------------------------------------------

@@ -2,6 +2,7 @@
 // backward), the backward of the exchange-unit sum, and the AdamWeightDecay update.  All reductions are
 // two-stage with a fixed partition and a fixed combine order, so results are bit-reproducible run to run.
 #include "common.h"
+#include "optim_update.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -290,64 +291,22 @@ __global__ __launch_bounds__(256) void fuse_sum_bwd_kernel(const float* __restri
     }
 }
 
-// mindspore.nn.AdamWeightDecay: Adam WITHOUT bias correction, decoupled weight decay, eps added to sqrt(v)
-// (mindpose/optim/optim_factory.py:69-72 selects it for "adamw")
+// mindspore.nn.AdamWeightDecay (update rule: adamw_update of optim_update.h)
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                     float* __restrict__ v, size_t n, float lr, float b1, float b2, float eps,
                                                     float wd) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const float gi = g[i];
-        const float mi = b1 * m[i] + (1.f - b1) * gi;
-        const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
-        m[i] = mi;
-        v[i] = vi;
-        float upd = mi / (sqrtf(vi) + eps);
-        upd += wd * p[i];
-        p[i] = p[i] - lr * upd;
-    }
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+        adamw_update(p, m, v, i, g[i], lr, b1, b2, eps, wd);
 }
 
-// The other optimizers the reference registers (mindpose/optim/optim_factory.py:9-14), same flat-arena form.  Update rules as
-// documented for mindspore.nn.{Adam, SGD, Momentum, Adagrad} [MS-knowledge: no reference test pins them]; the gradient is
-// first divided by the static loss scale and given the L2 term (g = g * grad_scale + wd * p), as those optimizers do.
-//   kind 1 Adam:     m = b1 m + (1-b1) g; v = b2 v + (1-b2) g^2; p -= lr sqrt(1-b2^t)/(1-b1^t) * m / (sqrt(v) + eps)
-//        (h: b1, b2, eps, b1^t, b2^t)
-//   kind 2 SGD:      buf = g on the first step, else mom buf + (1-damp) g; d = nesterov ? g + mom buf : buf (d = g when
-//        mom == 0); p -= lr d      (h: mom, damp, nesterov, first_step)
-//   kind 3 Momentum: acc = mom acc + g; p -= lr (nesterov ? g + mom acc : acc)      (h: mom, nesterov)
-//   kind 4 Adagrad:  acc += g^2; p -= lr g / sqrt(acc)      (accumulator initialised by the caller, 0.1 in MindSpore)
+// The other optimizers the reference registers (mindpose/optim/optim_factory.py:9-14), same flat-arena form: kinds 1 ... 4 of
+// optimizer_update (optim_update.h), hyper-parameters as kernel arguments.
 template <int KIND>
 __global__ __launch_bounds__(256) void optimizer_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ s1,
                                                         float* __restrict__ s2, size_t n, float lr, float grad_scale, float wd,
                                                         float h0, float h1, float h2, float h3, float h4) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const float w = p[i];
-        const float gi = g[i] * grad_scale + wd * w;
-        if (KIND == 1) {
-            const float mi = h0 * s1[i] + (1.f - h0) * gi;
-            const float vi = h1 * s2[i] + (1.f - h1) * gi * gi;
-            s1[i] = mi;
-            s2[i] = vi;
-            const float lr_t = lr * sqrtf(1.f - h4) / (1.f - h3);
-            p[i] = w - lr_t * mi / (sqrtf(vi) + h2);
-        } else if (KIND == 2) {
-            float d = gi;
-            if (h0 != 0.f) {
-                const float buf = h3 != 0.f ? gi : h0 * s1[i] + (1.f - h1) * gi;
-                s1[i] = buf;
-                d = h2 != 0.f ? gi + h0 * buf : buf;
-            }
-            p[i] = w - lr * d;
-        } else if (KIND == 3) {
-            const float acc = h0 * s1[i] + gi;
-            s1[i] = acc;
-            p[i] = w - lr * (h1 != 0.f ? gi + h0 * acc : acc);
-        } else {
-            const float acc = s1[i] + gi * gi;
-            s1[i] = acc;
-            p[i] = w - lr * gi / sqrtf(acc);
-        }
-    }
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+        optimizer_update<KIND>(p, s1, s2, i, g[i], lr, grad_scale, wd, h0, h1, h2, h3, h4);
 }
 
 // ---- fp16 (amp O2) training: the same BatchNorm passes over channel-blocked fp16 activations [N][C8][HW][8] ------------

@@ -126,6 +126,13 @@ class AdamWeightDecay(_ArenaOptimizer):
                                             float(self.lr), float(self.beta1), float(self.beta2), float(self.eps), wd,
                                             float(self.grad_scale), None, stream), "mp_adamw_step_scaled")
 
+    def _update_resident(self, lib, start, count, wd, step_args, stream):
+        """``_update`` with lr / gradient scale / skip read from the device step-arguments block (utils/step_tail.py)."""
+        _lib.check(lib.mp_adamw_step_resident(self.flat[start:].data_ptr(), self._grad_flat[start:].data_ptr(),
+                                              self.exp_avg[start:].data_ptr(), self.exp_avg_sq[start:].data_ptr(), count,
+                                              float(self.beta1), float(self.beta2), float(self.eps), wd, step_args, stream),
+                   "mp_adamw_step_resident")
+
 
 class _KernelOptimizer(_ArenaOptimizer):
     """The reference's other registered optimizers (optim_factory.py:9-14) through ``mp_optimizer_step``.  ``loss_scale`` is
@@ -147,6 +154,15 @@ class _KernelOptimizer(_ArenaOptimizer):
         _lib.check(lib.mp_optimizer_step(self.kind, self.flat[start:].data_ptr(), self._grad_flat[start:].data_ptr(), st[0], st[1],
                                          count, float(self.lr), float(self.grad_scale) / float(self.loss_scale), wd, ctypes.byref(hyper), stream),
                    "mp_optimizer_step")
+
+    def _update_resident(self, lib, start, count, wd, step_args, stream):
+        """``_update`` with lr / gradient scale / skip - and the step-dependent entries of ``_hyper()``: Adam's beta^t, SGD's
+        first_step - read from the device step-arguments block (utils/step_tail.py)."""
+        import ctypes
+        hyper = (ctypes.c_float * 5)(*[float(v) for v in self._hyper()])
+        st = [s_[start:].data_ptr() for s_ in self.states] + [None, None]
+        _lib.check(lib.mp_optimizer_step_resident(self.kind, self.flat[start:].data_ptr(), self._grad_flat[start:].data_ptr(), st[0], st[1],
+                                                  count, wd, ctypes.byref(hyper), step_args, stream), "mp_optimizer_step_resident")
 
 
 class Adam(_KernelOptimizer):

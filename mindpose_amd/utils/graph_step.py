@@ -64,13 +64,17 @@ def run_segments(grads, runners, schedule, exchange: bool = True) -> float:
 
 class GraphedTrainStep:
     def __init__(self, net_with_loss: torch.nn.Module, optimizer, example_inputs: Sequence[torch.Tensor],
-                 loss_scale_manager=None, warmup: int = 3, segments: Optional[int] = None) -> None:
+                 loss_scale_manager=None, warmup: int = 3, segments: Optional[int] = None, resident: bool = False,
+                 total_steps: int = 1) -> None:
         """``optimizer``: an ``AdamWeightDecay`` built with ``overlap=False`` (its gradient arena is what the graph writes);
         ``example_inputs``: CUDA tensors with the step's static shapes (data, label, extra inputs of ``NetWithLoss``).
         The ``warmup`` eager forward/backward passes that precede the capture (autotuner, kernel attributes, allocator) do
         not update parameters, only the BatchNorm moving statistics.
         ``segments``: None = 4 when the gradient all-reduce is active (several ranks) and the backbone offers ``train_segments()``,
-        else 1 (one graph, every bucket reduced after it); an explicit value is honoured where the backbone allows it."""
+        else 1 (one graph, every bucket reduced after it); an explicit value is honoured where the backbone allows it.
+        ``resident``: the step tail runs from device state (utils/step_tail.py ``ResidentStepTail``, its tables ``total_steps``
+        long): ``__call__`` reads nothing back, ``updated`` is None and the manager / ``optimizer.global_step`` are current only
+        after ``sync()``.  The captured graphs are the same either way; the tail's launches follow the replay on its stream."""
         if optimizer.grads.overlap:
             raise ValueError("build the optimizer with overlap=False for a graphed step: the bucket all-reduces are issued between "
                              "the captured segments / after the replay")
@@ -92,6 +96,10 @@ class GraphedTrainStep:
             self._warm_up_and_capture(net_with_loss, optimizer, backbone, groups, dev, warmup)
         set_branch_streams(prev_branch_streams)
         self._planned = [m for m in net_with_loss.modules() if hasattr(m, "_plans")]  # walked once, not per step
+        self.tail = None
+        if resident:
+            from .step_tail import ResidentStepTail
+            self.tail = ResidentStepTail(optimizer, loss_scale_manager, total_steps, scale_out=self.scale_t)
 
     def _warm_up_and_capture(self, net_with_loss, optimizer, backbone, groups, dev, warmup) -> None:
         from ..models.train_ops import flush_wgrad_jobs
@@ -213,6 +221,8 @@ class GraphedTrainStep:
         for dst, src in zip(self.static_in, inputs):
             if dst.data_ptr() != src.data_ptr():
                 dst.copy_(src)
+        if self.tail is not None:
+            return self._call_resident()
         if self.mgr is not None:
             self.scale_t.fill_(self.mgr.loss_scale)
         self.replay()  # under DP opt.step() waits for the bucket all-reduces (and launches those no segment boundary released)
@@ -224,3 +234,22 @@ class GraphedTrainStep:
             for m in self._planned:
                 m._plans.clear()
         return self.static_loss
+
+    def _call_resident(self) -> torch.Tensor:
+        """The step with the tail on the device: ``scale_t`` already holds the loss scale (the previous advance launch wrote it),
+        whether the update applies is the device's decision - so packs and recorded plans are dropped every step."""
+        from ..models.train_ops import flush_wgrad_jobs, invalidate_packs
+        self.replay()
+        flush_wgrad_jobs()  # as _ArenaOptimizer.step: queued weight gradients land before anything reads the arena
+        self.opt.grads.finish()
+        self.tail.launch()
+        invalidate_packs()
+        for m in self._planned:
+            m._plans.clear()
+        self.updated = None
+        return self.static_loss
+
+    def sync(self) -> None:
+        """Resident step: one download of the device counters into the manager and ``optimizer.global_step`` (no-op otherwise)."""
+        if self.tail is not None:
+            self.tail.sync()
