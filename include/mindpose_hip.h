@@ -372,6 +372,31 @@ int mp_adamw_step_resident(float* param_dev, const float* grad_dev, float* exp_a
 int mp_optimizer_step_resident(int kind, float* param_dev, const float* grad_dev, float* state1_dev, float* state2_dev, size_t count,
                                float weight_decay, const float hyper[5], const mp_step_args* step_args_dev, mp_stream_t stream);
 
+/* ---- training-time pose accuracy (pose_metric.hip): PCK of the output heat maps against the target heat maps ------------------
+ * The accuracy() of the HRNet training code (lib/core/evaluate.py), restated; the reference has no counterpart.  output_dev and
+ * target_dev: contiguous fp32 [N][K][H][W].  Per map the first (row-major) index of the maximum gives (x, y) = (idx % W, idx / W),
+ * or (0, 0) when the maximum is not > 0 or the map holds a NaN; +inf is an ordinary maximum.  A pair (n, k) is valid iff the
+ * target's x > 1 and y > 1; with dx, dy the integer differences output - target, a valid pair is a hit iff
+ * 100.0 * ((dx W)^2 + (dy H)^2) < thr * thr * (H W)^2, both sides in double in this order, strictly.  Per call acc_k =
+ * hits_k / valid_k over the joints with valid_k > 0, cnt = their number, avg_acc = their sum in joint order / cnt (0 without any).
+ * Two launches: one workgroup per map pair (at most 4096 workgroups, further pairs by a grid-stride loop) writes flags_dev[n * K + k]
+ * = valid | hit << 1; a single workgroup sums them per joint and advances *state_dev.  No atomics, no allocation, no
+ * synchronisation; capturable.  The state block is 48 + 16 K bytes of device memory owned by the caller, 8-byte aligned, zeroed by
+ * the caller to start an epoch: this header, then int64 hits[K], then int64 valid[K] (summed over the calls).
+ * Before any HIP call: NULL -> MP_ERR_NULL; a non-positive extent, N * K of 2^31 or more, thr not positive and finite ->
+ * MP_ERR_SHAPE; H or W above 4096 (the hit test's squares would no longer be exact in double), a map pointer off 4-byte
+ * or a state pointer off 8-byte alignment -> MP_ERR_UNSUPPORTED. */
+typedef struct mp_pose_pck_state {
+    int64_t steps;        /* calls accumulated */
+    int64_t sum_cnt;      /* running sum of cnt */
+    double sum_acc_cnt;   /* running sum of avg_acc * cnt: the epoch's accuracy is sum_acc_cnt / sum_cnt */
+    double last_avg_acc;  /* the last call's avg_acc */
+    int64_t last_cnt;     /* the last call's cnt */
+    int64_t pad;
+} mp_pose_pck_state;
+int mp_pose_pck_accuracy(const float* output_dev, const float* target_dev, int N, int K, int H, int W, double thr,
+                         unsigned char* flags_dev, void* state_dev, mp_stream_t stream);
+
 /* Conv2d weight gradient (training backward of every conv of hrnet.py): dW[co,ci,ky,kx] = sum_{n,y,x}
  * dz[n,co,y,x] * x[n,ci,y*s+ky-p,x*s+kx-p] for k in {1,3}, s in {1,2}, p = k/2 (desc as for the forward conv; its
  * output-mapping fields are ignored).  fp32 MFMA, pixel axis split over workgroups into slabs that are summed in a

@@ -179,6 +179,8 @@ _PROTOTYPES = {
     "mp_adamw_step_resident": (c_int, [c_f32p] * 4 + [c_size_t] + [ctypes.c_float] * 4 + [ctypes.c_void_p, ctypes.c_void_p]),
     "mp_optimizer_step_resident": (c_int, [c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_size_t,
                                            ctypes.c_float, ctypes.POINTER(ctypes.c_float * 5), ctypes.c_void_p, ctypes.c_void_p]),
+    # training-time pose accuracy (pose_metric.hip): output, target, N, K, H, W, thr, flags, state, stream
+    "mp_pose_pck_accuracy": (c_int, [c_f32p] * 2 + [c_int] * 4 + [ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "mp_f16_basicblock_fwd": (c_int, [c_f32p] * 8 + [c_int] * 5 + [ctypes.c_void_p]),
     "mp_f16_basicblock_supported": (c_int, [c_int] * 4),
     "mp_stem_conv_fwd": (c_int, [c_f32p] * 4 + [c_int, c_f32p] + [c_int] * 3 + [ctypes.c_void_p]),

@@ -5,16 +5,29 @@ meter, per-epoch log line, mean loss over the ranks, ``last.ckpt`` every epoch, 
 There is no ``mindspore.Model`` driving it here: the training loop calls ``on_train_step_end(loss)`` and
 ``on_train_epoch_end(cur_epoch, network, lr)`` itself (``tools/train_smoke.py`` style loops).  The scalar records the reference
 writes through ``SummaryRecord`` go to ``<summary_dir>/summary.jsonl`` (one JSON object per epoch: step, epoch, train/loss,
-train/lr, val/<metric>...)."""
+train/lr, val/<metric>...; with a training-time accuracy metric also train/acc, train/acc_count and train/acc_<k>)."""
 import json
 import logging
 import os
-from typing import Any, Dict, Optional
+from typing import Any, Dict, Optional, Sequence, Tuple
 
 import torch
 
 from ..utils.ckpt import save_checkpoint
 from ..utils.misc import Allreduce, AverageMeter
+
+
+def combine_train_accuracy(rank_sums: Sequence[Tuple[float, int, Sequence[int], Sequence[int]]]) -> Dict[str, Any]:
+    """The epoch accuracy from the raw sums of one or several ranks (``PoseAccuracy.sums()``: sum of avg_acc * cnt, sum of cnt,
+    per-joint hits and valid pairs): everything is added over the ranks first, then ``acc`` = sum_acc_cnt / sum_cnt (0 when nothing
+    counted) and ``joint_acc[k]`` = hits_k / valid_k for the joints with valid pairs (None otherwise)."""
+    sum_acc_cnt = float(sum(float(r[0]) for r in rank_sums))
+    count = int(sum(int(r[1]) for r in rank_sums))
+    k = max((len(r[2]) for r in rank_sums), default=0)
+    hits = [int(sum(int(r[2][j]) for r in rank_sums if len(r[2]) > j)) for j in range(k)]
+    valid = [int(sum(int(r[3][j]) for r in rank_sums if len(r[3]) > j)) for j in range(k)]
+    return dict(acc=sum_acc_cnt / count if count > 0 else 0.0, count=count, hits=hits, valid=valid,
+                joint_acc=[h / v if v > 0 else None for h, v in zip(hits, valid)])
 
 
 class EvalCallback:
@@ -60,14 +73,19 @@ class EvalCallback:
         self.cur_step += 1
         self.loss_meter.update(loss)
 
-    def on_train_epoch_end(self, cur_epoch: int, network, lr: float) -> Dict[str, Any]:
-        """Returns the evaluation output of this epoch ({} when none ran)."""
+    def on_train_epoch_end(self, cur_epoch: int, network, lr: float, train_metrics: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+        """Returns the evaluation output of this epoch ({} when none ran).  ``train_metrics``: this rank's
+        ``PoseAccuracy.compute()`` of the epoch, when the run has the metric."""
         avg = self.loss_meter.avg
-        logging.info(f"[rank = {self.rank_id}] epoch = {cur_epoch}, lr = {float(lr):.3e}, loss = {float(avg.sum()):.6f}")
+        line = f"[rank = {self.rank_id}] epoch = {cur_epoch}, lr = {float(lr):.3e}, loss = {float(avg.sum()):.6f}"
+        if train_metrics is not None:
+            line += f", acc = {float(train_metrics['acc']):.4f}"
+        logging.info(line)
         loss_avg = avg
         if self.all_reduce is not None:  # mean over the ranks of the per-rank epoch mean
             dev = next(network.parameters()).device if hasattr(network, "parameters") else torch.device("cpu")
             loss_avg = (self.all_reduce(avg.to(dev, torch.float32)) / self.device_num).to("cpu", torch.float64)
+        train_acc = self._train_accuracy(train_metrics, network) if train_metrics is not None else None
         self.loss_meter.reset()
         if self.rank_id == 0 and self.save_last:
             self._save(network, self.last_ckpt_path)
@@ -92,11 +110,28 @@ class EvalCallback:
             rec = {"step": self.cur_step, "epoch": cur_epoch, "train/lr": float(lr), "train/loss": float(loss_avg.sum())}
             if loss_avg.numel() > 1:
                 rec.update({f"train/loss_{i}": float(v) for i, v in enumerate(loss_avg.flatten())})
+            if train_acc is not None:
+                rec.update({"train/acc": train_acc["acc"], "train/acc_count": train_acc["count"]})
+                rec.update({f"train/acc_{k}": a for k, a in enumerate(train_acc["joint_acc"]) if a is not None})
             rec.update({"val/" + k: float(v) for k, v in output.items()})
             self._summary.write(json.dumps(rec) + "\n")
             self._summary.flush()
         self.last_epoch_loss = loss_avg
         return output
+
+    def _train_accuracy(self, train_metrics: Dict[str, Any], network) -> Dict[str, Any]:
+        """The epoch accuracy over all ranks: the raw sums travel through the all-reduce as one float64 vector (every entry an
+        integer below 2^53 or the one double numerator) and are divided afterwards."""
+        hits, valid = list(train_metrics["hits"]), list(train_metrics["valid"])
+        sum_acc_cnt = train_metrics.get("sum_acc_cnt", float(train_metrics["acc"]) * int(train_metrics["count"]))
+        sums = (float(sum_acc_cnt), int(train_metrics["count"]), hits, valid)
+        if self.all_reduce is not None:
+            dev = next(network.parameters()).device if hasattr(network, "parameters") else torch.device("cpu")
+            vec = torch.tensor([sums[0], float(sums[1])] + [float(v) for v in hits + valid], dtype=torch.float64, device=dev)
+            vec = self.all_reduce(vec).to("cpu").tolist()
+            k = len(hits)
+            sums = (vec[0], int(round(vec[1])), [int(round(v)) for v in vec[2:2 + k]], [int(round(v)) for v in vec[2 + k:2 + 2 * k]])
+        return combine_train_accuracy([sums])
 
     # -- checkpoints ----------------------------------------------------------------------------------------------------------
     @staticmethod

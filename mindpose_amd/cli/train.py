@@ -18,8 +18,8 @@ from ..callbacks import EvalCallback
 from ..data import create_dataset, create_pipeline
 from ..engine import Trainer, create_evaluator, create_inferencer
 from ..models.layers import Conv2d, Conv2dTranspose
-from ..models import (auto_mixed_precision, create_decoder, create_eval_network, create_loss, create_network,
-                      create_network_with_loss)
+from ..models import (NetWithLoss, PoseAccuracy, auto_mixed_precision, create_decoder, create_eval_network, create_loss,
+                      create_network, create_network_with_loss)
 from ..utils import DynamicLossScaleManager, create_lr_scheduler, create_optimizer, load_checkpoint, load_param_into_net
 from .config import parse_args
 
@@ -98,7 +98,21 @@ def evaluation(args: Namespace, net, dev, result_path: str, progress_bar: bool =
     return inferencer, evaluator
 
 
+def train_metric(args: Namespace) -> Optional[PoseAccuracy]:
+    """The training-time accuracy metric of a run: ``train_accuracy`` (``--cfg-options train_accuracy=True``; no recipe of the
+    reference has the key) asks for the PCK of the output heat maps against the target heat maps, logged per epoch.  It compares
+    one heat map per joint with its label, which is what the top-down pipeline trains on."""
+    if not getattr(args, "train_accuracy", False):
+        return None
+    method = getattr(args, "pipeline_method", None)
+    if method != "topdown":
+        raise ValueError(f"`train_accuracy` needs `pipeline_method: topdown` (one target heat map per output heat map), the recipe "
+                         f"has `{method}`")
+    return PoseAccuracy()
+
+
 def train(args: Namespace) -> None:
+    metric = train_metric(args)  # refused before anything is opened
     torch.manual_seed(0)
     np.random.seed(0)
     random.seed(0)
@@ -118,7 +132,10 @@ def train(args: Namespace) -> None:
         if args.amp_level != "O0":
             auto_mixed_precision(net, args.amp_level)  # before the optimizer: the arenas are built over the network as it trains
         loss = create_loss(args.loss, **(args.loss_setting or {}))
-        net_with_loss = create_network_with_loss(net, loss, has_extra_inputs=args.loss_with_extra_input).to(dev)
+        if metric is None:
+            net_with_loss = create_network_with_loss(net, loss, has_extra_inputs=args.loss_with_extra_input).to(dev)
+        else:  # (the factory keeps the reference's signature)
+            net_with_loss = NetWithLoss(net, loss, has_extra_inputs=args.loss_with_extra_input, metric=metric).to(dev)
         lr_scheduler = create_lr_scheduler(name=args.scheduler, lr=args.lr, total_epochs=args.num_epochs,
                                            steps_per_epoch=train_pipeline.get_dataset_size(), warmup=args.warmup,
                                            **(args.lr_scheduler_setting or {}))

@@ -60,8 +60,13 @@ class Trainer:
                 if self.step is not None:
                     self.step.sync()
                 lr = self.last_lr()
+                extra = {}
+                metric = getattr(self.nwl, "metric", None)
+                if metric is not None:  # the epoch's one read of the accuracy state; callbacks without the keyword see no change
+                    extra["train_metrics"] = metric.compute()
+                    metric.reset()
                 for cb in callbacks:
-                    cb.on_train_epoch_end(epoch, getattr(self.nwl, "net", self.nwl), lr)
+                    cb.on_train_epoch_end(epoch, getattr(self.nwl, "net", self.nwl), lr, **extra)
         finally:
             if hasattr(dataset, "close"):
                 dataset.close()

@@ -58,12 +58,19 @@ class EvalNet(nn.Module):
 
 class NetWithLoss(nn.Module):
     """Training wrapper (networks.py:79-106): ``loss(net(data), label[, *extra_inputs])``; the extra inputs (e.g. the
-    per-joint target weights of JointsMSELoss) are forwarded only when ``has_extra_inputs`` says the loss takes them."""
+    per-joint target weights of JointsMSELoss) are forwarded only when ``has_extra_inputs`` says the loss takes them.
+    ``metric`` (models/metrics.py ``PoseAccuracy``; the reference has none): in training mode its ``update`` sees the heat maps and
+    the label between the network and the loss - inside a captured step its launches are part of the graph."""
 
-    def __init__(self, net: Net, loss: Loss, has_extra_inputs: bool = False) -> None:
+    def __init__(self, net: Net, loss: Loss, has_extra_inputs: bool = False, metric=None) -> None:
         super().__init__()
         self.net, self.loss, self.has_extra_inputs = net, loss, has_extra_inputs
+        self.metric = metric
 
     def forward(self, data: torch.Tensor, label: torch.Tensor, *extra_inputs: torch.Tensor) -> torch.Tensor:
         loss_inputs = (label, *extra_inputs) if self.has_extra_inputs else (label,)
+        if self.metric is not None and self.training:
+            out = self.net(data)
+            self.metric.update(out.detach(), label)
+            return self.loss(out, *loss_inputs)
         return self.loss(self.net(data), *loss_inputs)

@@ -95,6 +95,9 @@ class GraphedTrainStep:
         with quiet_accumulate_grad_stream_warning():  # (only the warm-up passes and the capture run the autograd engine)
             self._warm_up_and_capture(net_with_loss, optimizer, backbone, groups, dev, warmup)
         set_branch_streams(prev_branch_streams)
+        metric = getattr(net_with_loss, "metric", None)
+        if metric is not None:
+            metric.reset()  # the warm-up passes ran eagerly and counted; only replays are steps
         self._planned = [m for m in net_with_loss.modules() if hasattr(m, "_plans")]  # walked once, not per step
         self.tail = None
         if resident:
