@@ -110,6 +110,31 @@ int mp_joints_mse_bwd(const float* pred_dev, const float* target_dev, const floa
                       const float* grad_out_dev, float* grad_pred_dev, int n, int k, int hw, mp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Loss: joint MSE with online hard keypoint mining (ohkm_loss.hip); the reference has no counterpart.
+ * pred, target: contiguous fp32 [N][K][HW]; weight_dev [N][K] or NULL (= 1); 1 <= topk <= K <= 1024.
+ *   S[n,k]   = sum_i ((pred_i - target_i)^2 * w[n,k]), fp32, the arithmetic of mp_joints_mse_fwd's row pass: a function of the
+ *              row's values and weight only (bit-identical rows give bit-identical sums).
+ *   sel[n,k] = 1 for the topk joints of sample n that come first in this total order, else 0: a NaN sum before every number,
+ *              then the larger sum, then (equal sums, -0 == +0, or two NaNs) the lower joint index.  ONE BYTE per (n, k).
+ *   L        = (float)(sum_n sum_{k selected, ascending} (double)S[n,k] / ((double)N * topk * HW)), sums in fp64 in a fixed
+ *              order; no atomics, bit-reproducible.  topk == K is the value of mp_joints_mse_fwd (up to the order of the sums).
+ *   bwd: grad_pred[n,k,i] = grad_out * sel[n,k] * w[n,k] * 2 (pred_i - target_i) / (N * topk * HW); grad_out_dev NULL means 1.0.
+ *        A row with sel == 0 is written as zeros and its pred / target are NOT read.
+ * fwd writes loss_dev [1], row_sum_dev [N*K] fp32 and sel_dev [N*K] bytes in three launches (rows; a workgroup per sample;
+ * one workgroup), bwd is one launch; all on `stream`, no synchronisation, capturable.  16-byte accesses when HW % 4 == 0 and
+ * the bases are 16-byte aligned, 4-byte ones otherwise.  workspace: mp_joints_ohkm_workspace_bytes(n, k) bytes (N doubles,
+ * 8-byte aligned).
+ * Before any launch: NULL (weight_dev and grad_out_dev excepted) -> MP_ERR_NULL; n, k or hw <= 0, topk < 1, topk > k, k > 1024
+ * or n * k of 2^31 or more -> MP_ERR_SHAPE; a missing, short or misaligned workspace -> MP_ERR_WORKSPACE.
+ * ------------------------------------------------------------------------------------------ */
+size_t mp_joints_ohkm_workspace_bytes(int n, int k);
+int mp_joints_ohkm_fwd(const float* pred_dev, const float* target_dev, const float* weight_dev, float* loss_dev, float* row_sum_dev,
+                       unsigned char* sel_dev, void* workspace_dev, size_t workspace_bytes, int n, int k, int hw, int topk,
+                       mp_stream_t stream);
+int mp_joints_ohkm_bwd(const float* pred_dev, const float* target_dev, const float* weight_dev, const unsigned char* sel_dev,
+                       const float* grad_out_dev, float* grad_pred_dev, int n, int k, int hw, int topk, mp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Convolution family (direct, im2col-free, LDS-tiled, fp32 MFMA v_mfma_f32_16x16x4_f32):
  *   nn.Conv2d + nn.BatchNorm2d(eval) + residual add + nn.ReLU of
  *     BasicBlock  mindpose/models/backbones/hrnet.py:66-83, Bottleneck :126-146,
