@@ -397,6 +397,57 @@ int mp_adamw_step_resident(float* param_dev, const float* grad_dev, float* exp_a
 int mp_optimizer_step_resident(int kind, float* param_dev, const float* grad_dev, float* state1_dev, float* state2_dev, size_t count,
                                float weight_decay, const float hyper[5], const mp_step_args* step_args_dev, mp_stream_t stream);
 
+/* ---- gradient clipping by global norm, decided on the device (grad_clip.hip, train_tail.hip) --------------------------------------
+ * mindspore.ops.clip_by_global_norm restated on the gradient arena; the reference trains without it.  The arena A holds the
+ * gradient sums over ranks, still multiplied by the loss scale.  With base = mean_scale / loss_scale / static_loss_scale (double,
+ * the expression of mp_step_args.grad_scale) and S = sum over the arena of (double)A[i] * (double)A[i]:
+ *   norm = sqrt(S) * base;   coef = clip_norm / norm when norm is finite and norm > clip_norm, else exactly 1.0;
+ *   grad_scale = (float)(base * coef)          - the coefficient multiplies last, one rounding to fp32.
+ * No epsilon: an unclipped step is bit-equal to the step without clipping.  clip_norm = +inf measures only.  No pass scales the
+ * gradients: the update launches already multiply every gradient by grad_scale while reading it. */
+typedef struct mp_grad_clip_state {    /* device memory, owned by the caller, zeroed by the caller to start a period */
+    double last_norm;                  /* norm of the last step that was not skipped */
+    double norm_sum;                   /* running sum of those norms: the mean is norm_sum / measured_steps */
+    double norm_max;                   /* their maximum (a NaN norm never becomes it) */
+    int64_t measured_steps;            /* steps that were not skipped */
+    int64_t clipped_steps;             /* of those, steps with norm > clip_norm */
+} mp_grad_clip_state;
+typedef struct mp_grad_clip_resolved { /* device memory, written by mp_grad_clip_resolve, downloaded by a host-driven step */
+    int32_t flag, pad;                 /* the overflow flag as the launch saw it (0 when it was given none) */
+    double norm, coef;                 /* as defined above; garbage-in norm and coef = 1.0 on an overflow step */
+} mp_grad_clip_resolved;
+/* Number of fp64 partial sums mp_grad_finite_norm writes for `count` values: the number of its workgroups, a function of count
+ * alone - ceil(count / 4 / 1024), one per 1024 quads, at least 1, at most 2048; 0 for count == 0. */
+int mp_grad_norm_partials(size_t count);
+/* mp_grad_finite_check and the sum of squares in ONE read of the arena.  The flag semantics are those of mp_grad_finite_check
+ * (*flag_dev |= 1 on any inf / nan, the caller zeroes it; grad_dev 16-byte aligned); partials_dev[b] = the sum of (double)x * x over
+ * the values workgroup b read, for b < mp_grad_norm_partials of count (plain stores, every entry written by every launch;
+ * 8-byte aligned).  Bit-reproducible and independent of occupancy: the grid depends on count alone; a trip of a workgroup is one
+ * contiguous run of 1024 quads, thread t reading quads t, t + 256, t + 512, t + 768 of it, trips a grid stride apart, then a last
+ * partial run and (workgroup 0) the scalar tail; a thread adds its values in index order into one fp64 accumulator (products of two
+ * fp32 values are exact in fp64: only the additions round, and no finite fp32 value overflows the sum - so the flag is "the sum is
+ * not finite"), a wave adds its lanes by shuffles down by 32, 16, 8, 4, 2, 1, thread 0 adds the four wave sums in wave order.  No
+ * floating-point atomics. */
+int mp_grad_finite_norm(const float* grad_dev, size_t count, int* flag_dev, double* partials_dev, mp_stream_t stream);
+/* mp_train_tail_advance with clipping: one launch of one workgroup, the same arguments, and partials_dev[0..n_partials) of
+ * mp_grad_finite_norm (n_partials <= 2048), clip_norm (positive or +inf) and *clip_state_dev.  Lane l of the 64 adds partials l,
+ * l + 64, ... in index order, the lanes are added by shuffles down by 32 ... 1: that is S.  grad_scale of the step-arguments block
+ * is (float)(base * coef); everything else of the block and of mp_train_tail_state is what mp_train_tail_advance makes it.  On a
+ * step that is not skipped the clip state advances: last_norm = norm, norm_sum += norm, norm_max = max, ++measured_steps,
+ * ++clipped_steps when norm > clip_norm; an overflow step leaves it untouched (its norm is garbage).  Without a flag
+ * (overflow_flag_dev NULL) a non-finite norm gives coef = 1 and is recorded as it is. */
+int mp_train_tail_advance_clip(const int* overflow_flag_dev, mp_train_tail_state* state_dev, double scale_factor, int64_t scale_window,
+                               double mean_scale, double static_loss_scale, const float* lr_table_dev, int64_t lr_len,
+                               const float* aux_table_dev, int64_t aux_len, mp_step_args* step_args_dev, float* loss_scale_out_dev,
+                               const double* partials_dev, int n_partials, double clip_norm, mp_grad_clip_state* clip_state_dev,
+                               mp_stream_t stream);
+/* The host-driven step's form of the same decision: one launch of one workgroup runs the same device code for S, norm and coef
+ * with loss_scale given by the host (1.0 without a manager), writes *resolved_dev and advances *clip_state_dev as above.  The host
+ * downloads the block where it would download the flag - one read-back per step - and multiplies coef in last. */
+int mp_grad_clip_resolve(const int* overflow_flag_dev, const double* partials_dev, int n_partials, double mean_scale, double loss_scale,
+                         double static_loss_scale, double clip_norm, mp_grad_clip_state* clip_state_dev,
+                         mp_grad_clip_resolved* resolved_dev, mp_stream_t stream);
+
 /* ---- training-time pose accuracy (pose_metric.hip): PCK of the output heat maps against the target heat maps ------------------
  * The accuracy() of the HRNet training code (lib/core/evaluate.py), restated; the reference has no counterpart.  output_dev and
  * target_dev: contiguous fp32 [N][K][H][W].  Per map the first (row-major) index of the maximum gives (x, y) = (idx % W, idx / W),

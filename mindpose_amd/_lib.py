@@ -184,6 +184,16 @@ _PROTOTYPES = {
     "mp_adamw_step_resident": (c_int, [c_f32p] * 4 + [c_size_t] + [ctypes.c_float] * 4 + [ctypes.c_void_p, ctypes.c_void_p]),
     "mp_optimizer_step_resident": (c_int, [c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_size_t,
                                            ctypes.c_float, ctypes.POINTER(ctypes.c_float * 5), ctypes.c_void_p, ctypes.c_void_p]),
+    # gradient clipping by global norm (grad_clip.hip, train_tail.hip): count -> partials / grad, count, flag, partials, stream /
+    # mp_train_tail_advance's arguments + partials, their number, clip_norm, clip state / flag, partials, their number, mean scale,
+    # loss scale, static loss scale, clip_norm, clip state, resolved block, stream
+    "mp_grad_norm_partials": (c_int, [c_size_t]),
+    "mp_grad_finite_norm": (c_int, [c_f32p, c_size_t, c_f32p, ctypes.c_void_p, ctypes.c_void_p]),
+    "mp_train_tail_advance_clip": (c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, c_i64, ctypes.c_double, ctypes.c_double,
+                                           ctypes.c_void_p, c_i64, ctypes.c_void_p, c_i64, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_void_p, c_int, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p]),
+    "mp_grad_clip_resolve": (c_int, [ctypes.c_void_p, ctypes.c_void_p, c_int] + [ctypes.c_double] * 4
+                             + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     # training-time pose accuracy (pose_metric.hip): output, target, N, K, H, W, thr, flags, state, stream
     "mp_pose_pck_accuracy": (c_int, [c_f32p] * 2 + [c_int] * 4 + [ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "mp_f16_basicblock_fwd": (c_int, [c_f32p] * 8 + [c_int] * 5 + [ctypes.c_void_p]),

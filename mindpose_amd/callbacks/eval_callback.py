@@ -73,13 +73,17 @@ class EvalCallback:
         self.cur_step += 1
         self.loss_meter.update(loss)
 
-    def on_train_epoch_end(self, cur_epoch: int, network, lr: float, train_metrics: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
+    def on_train_epoch_end(self, cur_epoch: int, network, lr: float, train_metrics: Optional[Dict[str, Any]] = None,
+                           grad_norm: Optional[Dict[str, Any]] = None) -> Dict[str, Any]:
         """Returns the evaluation output of this epoch ({} when none ran).  ``train_metrics``: this rank's
-        ``PoseAccuracy.compute()`` of the epoch, when the run has the metric."""
+        ``PoseAccuracy.compute()`` of the epoch, when the run has the metric; ``grad_norm``: the optimizer's
+        ``grad_clip_stats()`` of the epoch, when the run clips its gradients."""
         avg = self.loss_meter.avg
         line = f"[rank = {self.rank_id}] epoch = {cur_epoch}, lr = {float(lr):.3e}, loss = {float(avg.sum()):.6f}"
         if train_metrics is not None:
             line += f", acc = {float(train_metrics['acc']):.4f}"
+        if grad_norm is not None:
+            line += f", grad_norm = {float(grad_norm['mean_norm']):.4g}"
         logging.info(line)
         loss_avg = avg
         if self.all_reduce is not None:  # mean over the ranks of the per-rank epoch mean

@@ -21,6 +21,7 @@ from ..models.layers import Conv2d, Conv2dTranspose
 from ..models import (NetWithLoss, PoseAccuracy, auto_mixed_precision, create_decoder, create_eval_network, create_loss,
                       create_network, create_network_with_loss)
 from ..utils import DynamicLossScaleManager, create_lr_scheduler, create_optimizer, load_checkpoint, load_param_into_net
+from ..utils.adamw import check_clip_norm
 from .config import parse_args
 
 _logger = logging.getLogger(__name__)
@@ -111,8 +112,29 @@ def train_metric(args: Namespace) -> Optional[PoseAccuracy]:
     return PoseAccuracy()
 
 
+def grad_clip_norm(args: Namespace) -> Optional[float]:
+    """The optimizer's ``clip_norm`` of a run: ``clip_grad`` (bool, default False) switches clipping of the gradient by its global
+    norm on, ``clip_value`` (default 15.0) is the norm - the two keys of the sibling mindcv recipes; no recipe of the reference has
+    them, ``--cfg-options clip_grad=True clip_value=1.0`` sets them.  ``clip_value=inf`` measures and logs the norm and clips
+    nothing.  A value that is not a positive number is refused, also with ``clip_grad`` off."""
+    clip_grad = getattr(args, "clip_grad", False)
+    if not isinstance(clip_grad, bool):
+        raise ValueError(f"`clip_grad` is True or False, got {clip_grad!r}")
+    value = getattr(args, "clip_value", 15.0)
+    if isinstance(value, str) and value.strip().lower() in ("inf", "+inf", "infinity"):
+        value = math.inf  # (not a Python literal: --cfg-options hands the text on)
+    try:
+        value = check_clip_norm(value)
+    except ValueError as e:
+        raise ValueError(f"`clip_value`: {e}") from None
+    if value is None:
+        raise ValueError("`clip_value` must be a positive number or inf, got None")
+    return value if clip_grad else None
+
+
 def train(args: Namespace) -> None:
     metric = train_metric(args)  # refused before anything is opened
+    clip_norm = grad_clip_norm(args)  # likewise
     torch.manual_seed(0)
     np.random.seed(0)
     random.seed(0)
@@ -140,7 +162,8 @@ def train(args: Namespace) -> None:
                                            steps_per_epoch=train_pipeline.get_dataset_size(), warmup=args.warmup,
                                            **(args.lr_scheduler_setting or {}))
         optimizer = create_optimizer(net, name=args.optimizer, learning_rate=lr_scheduler, filter_bias_and_bn=args.filter_bias_and_bn,
-                                     weight_decay=args.weight_decay, overlap=False, **(args.optimizer_setting or {}))
+                                     weight_decay=args.weight_decay, overlap=False, clip_norm=clip_norm,
+                                     **(args.optimizer_setting or {}))
         if args.ckpt:
             _logger.info(f"Loading the checkpoint from {args.ckpt}")
             load_param_into_net(net, load_checkpoint(args.ckpt))  # (the arena's parameters are views: loaded in place)

@@ -8,25 +8,26 @@
 // arithmetic is utils/loss_scale.py + utils/adamw.py; every quantity here is that integer / double arithmetic restated, or the
 // same fp32 update body (optim_update.h).
 #include "common.h"
+#include "grad_clip.h"
 #include "optim_update.h"
 
 namespace mp {
 namespace {
 
-__global__ __launch_bounds__(64) void train_tail_advance_kernel(const int* __restrict__ overflow_flag, mp_train_tail_state* __restrict__ st,
-                                                                double factor, long long window, double mean_scale,
-                                                                double static_loss_scale, const float* __restrict__ lr_table,
-                                                                long long lr_len, const float* __restrict__ aux_table, long long aux_len,
-                                                                mp_step_args* __restrict__ args, float* __restrict__ loss_scale_out) {
-    if (threadIdx.x != 0) return;
+// The step tail of ONE thread: fills *args from the state before the update, then advances the state.  clip_coef multiplies the
+// gradient scale last (1.0 without clipping: the product is then the scale itself, bit for bit).  Returns whether the step is skipped.
+__device__ __forceinline__ bool tail_advance(const int* __restrict__ overflow_flag, mp_train_tail_state* __restrict__ st, double factor,
+                                             long long window, double grad_scale_base, double clip_coef,
+                                             const float* __restrict__ lr_table, long long lr_len, const float* __restrict__ aux_table,
+                                             long long aux_len, mp_step_args* __restrict__ args, float* __restrict__ loss_scale_out) {
     const bool scaling = overflow_flag != nullptr;
     const bool overflow = scaling && *overflow_flag != 0;
-    double loss_scale = st->loss_scale;
+    double loss_scale = st->loss_scale;  // (grad_scale_base was made from it by the caller)
     const long long cur = st->cur_iter, applied = st->applied_steps;
     // what the update launches of THIS step read
     const long long li = applied < lr_len - 1 ? applied : lr_len - 1;
     args->skip = overflow ? 1 : 0;
-    args->grad_scale = (float)(mean_scale / loss_scale / static_loss_scale);
+    args->grad_scale = (float)(grad_scale_base * clip_coef);
     args->lr = lr_table[li];
     float aux0 = 0.f, aux1 = 0.f;
     if (aux_table != nullptr) {
@@ -50,6 +51,36 @@ __global__ __launch_bounds__(64) void train_tail_advance_kernel(const int* __res
     st->loss_scale = loss_scale;
     st->cur_iter = cur + 1;
     if (loss_scale_out != nullptr) *loss_scale_out = (float)loss_scale;  // the next replay multiplies the loss by it
+    return overflow;
+}
+
+__global__ __launch_bounds__(64) void train_tail_advance_kernel(const int* __restrict__ overflow_flag, mp_train_tail_state* __restrict__ st,
+                                                                double factor, long long window, double mean_scale,
+                                                                double static_loss_scale, const float* __restrict__ lr_table,
+                                                                long long lr_len, const float* __restrict__ aux_table, long long aux_len,
+                                                                mp_step_args* __restrict__ args, float* __restrict__ loss_scale_out) {
+    if (threadIdx.x != 0) return;
+    tail_advance(overflow_flag, st, factor, window, mean_scale / st->loss_scale / static_loss_scale, 1.0, lr_table, lr_len, aux_table,
+                 aux_len, args, loss_scale_out);
+}
+
+// The same with gradient clipping by global norm (grad_clip.h): the 64 lanes sum the partials of mp_grad_finite_norm, lane 0 decides
+// the coefficient and records the norm of a step that is not skipped.
+__global__ __launch_bounds__(64) void train_tail_advance_clip_kernel(const int* __restrict__ overflow_flag,
+                                                                     mp_train_tail_state* __restrict__ st, double factor, long long window,
+                                                                     double mean_scale, double static_loss_scale,
+                                                                     const float* __restrict__ lr_table, long long lr_len,
+                                                                     const float* __restrict__ aux_table, long long aux_len,
+                                                                     mp_step_args* __restrict__ args, float* __restrict__ loss_scale_out,
+                                                                     const double* __restrict__ partials, int n_partials, double clip_norm,
+                                                                     mp_grad_clip_state* __restrict__ cs) {
+    const double sum_sq = clip_sum_partials(partials, n_partials);
+    if (threadIdx.x != 0) return;
+    const double base = mean_scale / st->loss_scale / static_loss_scale;
+    const ClipDecision d = clip_decide(sum_sq, base, clip_norm);
+    const bool skipped = tail_advance(overflow_flag, st, factor, window, base, d.coef, lr_table, lr_len, aux_table, aux_len, args,
+                                      loss_scale_out);
+    if (!skipped) clip_record(cs, d);
 }
 
 __global__ __launch_bounds__(256) void adamw_resident_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
@@ -94,6 +125,20 @@ int mp_train_tail_advance(const int* overflow_flag, mp_train_tail_state* state, 
     hipLaunchKernelGGL(train_tail_advance_kernel, dim3(1), dim3(64), 0, as_stream(stream), overflow_flag, state, scale_factor,
                        (long long)scale_window, mean_scale, static_loss_scale, lr_table, (long long)lr_len, aux_table, (long long)aux_len,
                        step_args, loss_scale_out);
+    return check_launch();
+}
+
+int mp_train_tail_advance_clip(const int* overflow_flag, mp_train_tail_state* state, double scale_factor, int64_t scale_window,
+                               double mean_scale, double static_loss_scale, const float* lr_table, int64_t lr_len, const float* aux_table,
+                               int64_t aux_len, mp_step_args* step_args, float* loss_scale_out, const double* partials, int n_partials,
+                               double clip_norm, mp_grad_clip_state* clip_state, mp_stream_t stream) {
+    if (!state || !lr_table || !step_args || !clip_state || (!partials && n_partials != 0)) return MP_ERR_NULL;
+    if (lr_len < 1 || (aux_table && aux_len < 1)) return MP_ERR_SHAPE;
+    if (overflow_flag && scale_window < 1) return MP_ERR_SHAPE;
+    if (n_partials < 0 || n_partials > kNormBlocksCap || !(clip_norm > 0.0)) return MP_ERR_SHAPE;
+    hipLaunchKernelGGL(train_tail_advance_clip_kernel, dim3(1), dim3(64), 0, as_stream(stream), overflow_flag, state, scale_factor,
+                       (long long)scale_window, mean_scale, static_loss_scale, lr_table, (long long)lr_len, aux_table, (long long)aux_len,
+                       step_args, loss_scale_out, partials, n_partials, clip_norm, clip_state);
     return check_launch();
 }
 

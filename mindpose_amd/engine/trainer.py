@@ -5,7 +5,12 @@
 With ``resident`` (the default, ``MINDPOSE_TRAIN_RESIDENT=0`` switches it off) the step tail runs from device state
 (``utils/step_tail.py``): the host reads nothing back per step and keeps at most two steps queued ahead of the device; the
 loss-scale manager and ``optimizer.global_step`` are brought up to date at each epoch end, before the callbacks look at them.
+
+With gradient clipping (the optimizer's ``clip_norm``) the epoch end also reads the device's gradient-norm statistics once, logs
+them and hands them to the callbacks whose ``on_train_epoch_end`` takes a ``grad_norm`` keyword.
 """
+import inspect
+import logging
 from typing import Iterable, Optional
 
 import torch
@@ -16,6 +21,13 @@ from ..utils.graph_step import GraphedTrainStep
 __all__ = ["Trainer"]
 
 QUEUED_STEPS = 2  # steps the host may run ahead of the device
+
+_logger = logging.getLogger(__name__)
+
+
+def _takes_keyword(fn, name: str) -> bool:
+    params = inspect.signature(fn).parameters
+    return name in params or any(p.kind is inspect.Parameter.VAR_KEYWORD for p in params.values())
 
 
 class Trainer:
@@ -65,8 +77,16 @@ class Trainer:
                 if metric is not None:  # the epoch's one read of the accuracy state; callbacks without the keyword see no change
                     extra["train_metrics"] = metric.compute()
                     metric.reset()
+                grad_norm = None
+                if getattr(self.opt, "clip_norm", None) is not None:  # the epoch's one read of the clip state, then a new period
+                    grad_norm = self.opt.grad_clip_stats()
+                    self.opt.reset_grad_clip_stats()
+                    _logger.info(f"epoch = {epoch}, gradient norm: mean = {grad_norm['mean_norm']:.6g}, max = {grad_norm['max_norm']:.6g}, "
+                                 f"clipped {grad_norm['clipped_steps']} of {grad_norm['measured_steps']} steps "
+                                 f"(clip_norm = {self.opt.clip_norm:g})")
                 for cb in callbacks:
-                    cb.on_train_epoch_end(epoch, getattr(self.nwl, "net", self.nwl), lr, **extra)
+                    more = {"grad_norm": grad_norm} if grad_norm is not None and _takes_keyword(cb.on_train_epoch_end, "grad_norm") else {}
+                    cb.on_train_epoch_end(epoch, getattr(self.nwl, "net", self.nwl), lr, **extra, **more)
         finally:
             if hasattr(dataset, "close"):
                 dataset.close()

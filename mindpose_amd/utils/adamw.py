@@ -7,9 +7,15 @@ weight decay, and - with ``filter_bias_and_bn`` - no decay for parameters whose 
 Natively the parameters, their gradients and the optimizer state are flat fp32 arenas ordered [decay | no-decay], so a step
 is two launches of one streaming kernel (``mp_adamw_step`` / ``mp_optimizer_step``) regardless of the number of tensors (878
 for HRNet-W32).
-"""
-from typing import Iterable, Tuple
 
+``clip_norm`` (off by default) clips the gradient by its global norm, MindSpore's ``clip_by_global_norm``: the sum of squares rides
+on the overflow check's one read of the arena (``mp_grad_finite_norm``), the coefficient is decided on the device and is one more
+factor of the gradient scale the update kernels apply while reading - no pass scales the gradients (include/mindpose_hip.h).
+"""
+import math
+from typing import Dict, Iterable, Optional, Tuple
+
+import numpy as np
 import torch
 
 from .. import _lib
@@ -28,6 +34,30 @@ def split_decay(named_params: Iterable[Tuple[str, torch.nn.Parameter]], filter_b
     return decay, no_decay
 
 
+CLIP_STATE_DTYPE = np.dtype([("last_norm", "<f8"), ("norm_sum", "<f8"), ("norm_max", "<f8"), ("measured_steps", "<i8"),
+                             ("clipped_steps", "<i8")])  # mp_grad_clip_state (include/mindpose_hip.h)
+CLIP_RESOLVED_DTYPE = np.dtype([("flag", "<i4"), ("pad", "<i4"), ("norm", "<f8"), ("coef", "<f8")])  # mp_grad_clip_resolved
+
+
+def check_clip_norm(clip_norm) -> Optional[float]:
+    """``None`` (clipping off) or the norm as a float: positive, ``inf`` = measure only.  NaN, zero, negative values and anything
+    that is not a number are refused."""
+    if clip_norm is None:
+        return None
+    if isinstance(clip_norm, bool) or not isinstance(clip_norm, (int, float, np.integer, np.floating)):
+        raise ValueError(f"clip_norm must be a positive number or inf, got {clip_norm!r}")
+    value = float(clip_norm)
+    if math.isnan(value) or value <= 0.0:
+        raise ValueError(f"clip_norm must be a positive number or inf, got {clip_norm!r}")
+    return value
+
+
+def clip_coefficient(norm: float, clip_norm: float) -> float:
+    """The definition in double, as the device states it: ``clip_norm / norm`` when the norm is finite and above ``clip_norm``,
+    else exactly 1.0 (no epsilon)."""
+    return clip_norm / norm if (math.isfinite(norm) and norm > clip_norm) else 1.0
+
+
 class _ArenaOptimizer:
     """Parameters, gradients and optimizer state as flat fp32 arenas ordered [decay | no-decay]; ``_update`` of a subclass
     launches its streaming kernel once per group.  ``step`` = gradient mean over ranks (RCCL, overlapped with backward),
@@ -37,7 +67,8 @@ class _ArenaOptimizer:
 
     def __init__(self, net: torch.nn.Module, lr: float, weight_decay: float = 0.0, filter_bias_and_bn: bool = True,
                  bucket_mb: float = 32.0, process_group=None, overlap: bool = True, state_init: float = 0.0,
-                 transport=None, force_collectives: bool = False) -> None:
+                 transport=None, force_collectives: bool = False, clip_norm: Optional[float] = None) -> None:
+        self.clip_norm = check_clip_norm(clip_norm)  # refused before anything is rearranged
         decay, no_decay = split_decay(net.named_parameters(), filter_bias_and_bn)
         self.params = decay + no_decay
         self.n_decay = sum(p.numel() for p in decay)
@@ -63,6 +94,32 @@ class _ArenaOptimizer:
         self._overflow = torch.zeros(1, device=dev, dtype=torch.int32)  # device flag of the loss-scale overflow check
         self.global_step = 0
         self.time_comm, self.comm_events = False, []
+        self.clip_coef = 1.0  # the last step's clip coefficient: the last factor of the gradient scale (exactly 1.0 = none)
+        if self.clip_norm is not None:
+            n_partials = _lib.load().mp_grad_norm_partials(self._grad_flat.numel())
+            self._clip_partials = torch.zeros(n_partials, device=dev, dtype=torch.float64)  # one per workgroup of the fused pass
+            self._clip_state = torch.zeros(CLIP_STATE_DTYPE.itemsize, device=dev, dtype=torch.uint8)
+            self._clip_resolved = torch.zeros(CLIP_RESOLVED_DTYPE.itemsize, device=dev, dtype=torch.uint8)
+
+    def launch_finite_norm(self, lib, stream) -> None:
+        """Clipping on: the overflow check and the sum of squares in one read of the arena (flag zeroed first)."""
+        self._overflow.zero_()
+        _lib.check(lib.mp_grad_finite_norm(self._grad_flat.data_ptr(), self._grad_flat.numel(), self._overflow.data_ptr(),
+                                           self._clip_partials.data_ptr(), stream), "mp_grad_finite_norm")
+
+    def grad_clip_stats(self) -> Dict[str, float]:
+        """One download of the clip-state block (synchronises): the gradient norms of the steps since the last reset that were
+        not skipped."""
+        if self.clip_norm is None:
+            raise ValueError("gradient clipping is off: build the optimizer with clip_norm (inf measures only)")
+        st = self._clip_state.cpu().numpy().view(CLIP_STATE_DTYPE)[0]
+        n = int(st["measured_steps"])
+        return {"last_norm": float(st["last_norm"]), "mean_norm": float(st["norm_sum"]) / n if n else 0.0,
+                "max_norm": float(st["norm_max"]), "measured_steps": n, "clipped_steps": int(st["clipped_steps"])}
+
+    def reset_grad_clip_stats(self) -> None:
+        if self.clip_norm is not None:
+            self._clip_state.zero_()
 
     def zero_grad(self) -> None:
         self.grads.begin_step()
@@ -76,7 +133,8 @@ class _ArenaOptimizer:
 
         With a ``DynamicLossScaleManager`` (amp O2, tools/train.py:170-181) the gradients are first divided by the loss
         scale and checked: on overflow (inf / nan anywhere) the update is skipped and the scale halves, exactly one
-        host read-back per step; returns whether the parameters were updated."""
+        host read-back per step; returns whether the parameters were updated.  With ``clip_norm`` the check also sums the
+        squares and a single-workgroup launch decides the clip coefficient: the read-back is its block instead of the flag."""
         lib = _lib.load()
         from ..models.train_ops import flush_wgrad_jobs
         flush_wgrad_jobs()  # queued (grouped) weight gradients land in the arena before anything reads it
@@ -92,7 +150,26 @@ class _ArenaOptimizer:
             self.grads.finish()
         # gradient scale the update kernels apply while reading the arena: 1 / loss_scale (amp O2) x 1 / world (gradient mean)
         self.grad_scale = self.grads.mean_scale
-        if loss_scale_manager is not None:
+        self.clip_coef = 1.0
+        if self.clip_norm is not None:
+            # the fused pass instead of the check, and one single-workgroup launch that decides the coefficient with the device
+            # code of the resident tail; its block is downloaded where the flag would be: still one read-back per step
+            mgr = loss_scale_manager
+            if mgr is not None:
+                self.grad_scale /= mgr.loss_scale
+            self.launch_finite_norm(lib, _lib.stream())
+            _lib.check(lib.mp_grad_clip_resolve(
+                self._overflow.data_ptr() if mgr is not None else None, self._clip_partials.data_ptr(), self._clip_partials.numel(),
+                float(self.grads.mean_scale), float(mgr.loss_scale) if mgr is not None else 1.0, float(getattr(self, "loss_scale", 1.0)),
+                self.clip_norm, self._clip_state.data_ptr(), self._clip_resolved.data_ptr(), _lib.stream()), "mp_grad_clip_resolve")
+            resolved = self._clip_resolved.cpu().numpy().view(CLIP_RESOLVED_DTYPE)[0]
+            self.clip_coef = float(resolved["coef"])  # multiplies last, in ``_update``
+            if mgr is not None:
+                finite = int(resolved["flag"]) == 0
+                mgr.update_loss_scale(not finite)
+                if not finite:
+                    return False
+        elif loss_scale_manager is not None:
             self.grad_scale /= loss_scale_manager.loss_scale
             # overflow check on the (still scaled) sums: inf / nan survive the scaling, so one read-only pass decides
             self._overflow.zero_()
@@ -124,7 +201,7 @@ class AdamWeightDecay(_ArenaOptimizer):
         _lib.check(lib.mp_adamw_step_scaled(self.flat[start:].data_ptr(), self._grad_flat[start:].data_ptr(),
                                             self.exp_avg[start:].data_ptr(), self.exp_avg_sq[start:].data_ptr(), count,
                                             float(self.lr), float(self.beta1), float(self.beta2), float(self.eps), wd,
-                                            float(self.grad_scale), None, stream), "mp_adamw_step_scaled")
+                                            float(self.grad_scale) * self.clip_coef, None, stream), "mp_adamw_step_scaled")
 
     def _update_resident(self, lib, start, count, wd, step_args, stream):
         """``_update`` with lr / gradient scale / skip read from the device step-arguments block (utils/step_tail.py)."""
@@ -152,7 +229,8 @@ class _KernelOptimizer(_ArenaOptimizer):
         hyper = (ctypes.c_float * 5)(*[float(v) for v in self._hyper()])
         st = [s_[start:].data_ptr() for s_ in self.states] + [None, None]
         _lib.check(lib.mp_optimizer_step(self.kind, self.flat[start:].data_ptr(), self._grad_flat[start:].data_ptr(), st[0], st[1],
-                                         count, float(self.lr), float(self.grad_scale) / float(self.loss_scale), wd, ctypes.byref(hyper), stream),
+                                         count, float(self.lr), float(self.grad_scale) / float(self.loss_scale) * self.clip_coef, wd,
+                                         ctypes.byref(hyper), stream),
                    "mp_optimizer_step")
 
     def _update_resident(self, lib, start, count, wd, step_args, stream):

@@ -69,21 +69,34 @@ class ResidentStepTail:
             self.scale_out.fill_(mgr.loss_scale)
 
     def launch(self) -> None:
-        """Finite check (with a manager), advance, one update launch per non-empty decay group; no host read."""
+        """Finite check (with a manager), advance, one update launch per non-empty decay group; no host read.  With the
+        optimizer's ``clip_norm`` the check also sums the squares and the advance launch decides the clip coefficient."""
         lib = _lib.load()
         opt, mgr, stream = self.opt, self.mgr, _lib.stream()
+
+        def tail_args(flag):
+            return (
+                flag, self.state_dev.data_ptr(), mgr.scale_factor if mgr is not None else 1.0, mgr.scale_window if mgr is not None else 1,
+                float(opt.grads.mean_scale), self.static_loss_scale, self.lr_dev.data_ptr(), self.lr_dev.numel(),
+                self.aux_dev.data_ptr() if self.aux_dev is not None else None, self.aux_dev.shape[0] if self.aux_dev is not None else 0,
+                self.args_dev.data_ptr(), self.scale_out.data_ptr() if (self.scale_out is not None and mgr is not None) else None)
+
         flag = None
-        if mgr is not None:
-            opt._overflow.zero_()
-            _lib.check(lib.mp_grad_finite_check(opt._grad_flat.data_ptr(), opt._grad_flat.numel(), opt._overflow.data_ptr(), stream),
-                       "mp_grad_finite_check")
-            flag = opt._overflow.data_ptr()
-        _lib.check(lib.mp_train_tail_advance(
-            flag, self.state_dev.data_ptr(), mgr.scale_factor if mgr is not None else 1.0, mgr.scale_window if mgr is not None else 1,
-            float(opt.grads.mean_scale), self.static_loss_scale, self.lr_dev.data_ptr(), self.lr_dev.numel(),
-            self.aux_dev.data_ptr() if self.aux_dev is not None else None, self.aux_dev.shape[0] if self.aux_dev is not None else 0,
-            self.args_dev.data_ptr(), self.scale_out.data_ptr() if (self.scale_out is not None and mgr is not None) else None, stream),
-            "mp_train_tail_advance")
+        if getattr(opt, "clip_norm", None) is not None:
+            # gradient clipping: the fused check + sum of squares and the tail that decides the coefficient, in place of the two
+            # launches below; without a manager the pass runs for the norm alone and its flag is not handed on (never skip)
+            opt.launch_finite_norm(lib, stream)
+            if mgr is not None:
+                flag = opt._overflow.data_ptr()
+            _lib.check(lib.mp_train_tail_advance_clip(*tail_args(flag), opt._clip_partials.data_ptr(), opt._clip_partials.numel(),
+                                                      opt.clip_norm, opt._clip_state.data_ptr(), stream), "mp_train_tail_advance_clip")
+        else:
+            if mgr is not None:
+                opt._overflow.zero_()
+                _lib.check(lib.mp_grad_finite_check(opt._grad_flat.data_ptr(), opt._grad_flat.numel(), opt._overflow.data_ptr(), stream),
+                           "mp_grad_finite_check")
+                flag = opt._overflow.data_ptr()
+            _lib.check(lib.mp_train_tail_advance(*tail_args(flag), stream), "mp_train_tail_advance")
         for start, count, wd in ((0, opt.n_decay, opt.weight_decay), (opt.n_decay, opt.flat.numel() - opt.n_decay, 0.0)):
             if count:
                 opt._update_resident(lib, start, count, float(wd), self.args_dev.data_ptr(), stream)
