@@ -363,7 +363,7 @@ int mp_reduce_scatter_allgather_grads(void* comm, float* arena_dev, size_t count
 int mp_optimizer_step(int kind, float* param_dev, const float* grad_dev, float* state1_dev, float* state2_dev, size_t count,
                       float lr, float grad_scale, float weight_decay, const float hyper[5], mp_stream_t stream);
 
-/* ---- device-resident step tail (train_tail.hip): the host queues training steps without reading one back --------------------
+/* ---- device-resident step tail (step_end.hip): the host queues training steps without reading one back ---------------------
  * The loss-scale state machine of mindspore.amp.DynamicLossScaleManager (tools/train.py:170-181), the skip decision and the
  * learning-rate lookup run on the device; the update launches read their step-dependent arguments from device memory. */
 typedef struct mp_train_tail_state {   /* device memory, owned by the caller */
@@ -397,7 +397,7 @@ int mp_adamw_step_resident(float* param_dev, const float* grad_dev, float* exp_a
 int mp_optimizer_step_resident(int kind, float* param_dev, const float* grad_dev, float* state1_dev, float* state2_dev, size_t count,
                                float weight_decay, const float hyper[5], const mp_step_args* step_args_dev, mp_stream_t stream);
 
-/* ---- gradient clipping by global norm, decided on the device (grad_clip.hip, train_tail.hip) --------------------------------------
+/* ---- gradient clipping by global norm, decided on the device (step_end.hip) ----------------------------------------------------
  * mindspore.ops.clip_by_global_norm restated on the gradient arena; the reference trains without it.  The arena A holds the
  * gradient sums over ranks, still multiplied by the loss scale.  With base = mean_scale / loss_scale / static_loss_scale (double,
  * the expression of mp_step_args.grad_scale) and S = sum over the arena of (double)A[i] * (double)A[i]:

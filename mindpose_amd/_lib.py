@@ -178,13 +178,13 @@ _PROTOTYPES = {
     "mp_f16_fuse_sum_bwd_term_stats": (c_int, [c_f32p] * 3 + [c_int] * 6 + [c_f32p, c_f32p, c_int, c_f32p, c_size_t, ctypes.c_void_p]),
     "mp_optimizer_step": (c_int, [c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_size_t, ctypes.c_float,
                                   ctypes.c_float, ctypes.c_float, ctypes.POINTER(ctypes.c_float * 5), ctypes.c_void_p]),
-    # device-resident step tail (train_tail.hip): state block, step-arguments block, tables and flags travel as device pointers
+    # device-resident step tail (step_end.hip): state block, step-arguments block, tables and flags travel as device pointers
     "mp_train_tail_advance": (c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, c_i64, ctypes.c_double, ctypes.c_double,
                                       ctypes.c_void_p, c_i64, ctypes.c_void_p, c_i64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "mp_adamw_step_resident": (c_int, [c_f32p] * 4 + [c_size_t] + [ctypes.c_float] * 4 + [ctypes.c_void_p, ctypes.c_void_p]),
     "mp_optimizer_step_resident": (c_int, [c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_size_t,
                                            ctypes.c_float, ctypes.POINTER(ctypes.c_float * 5), ctypes.c_void_p, ctypes.c_void_p]),
-    # gradient clipping by global norm (grad_clip.hip, train_tail.hip): count -> partials / grad, count, flag, partials, stream /
+    # gradient clipping by global norm (step_end.hip): count -> partials / grad, count, flag, partials, stream /
     # mp_train_tail_advance's arguments + partials, their number, clip_norm, clip state / flag, partials, their number, mean scale,
     # loss scale, static loss scale, clip_norm, clip state, resolved block, stream
     "mp_grad_norm_partials": (c_int, [c_size_t]),

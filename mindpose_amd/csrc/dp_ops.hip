@@ -1,47 +1,19 @@
-// Data-parallel step tail (SURVEY.md 8a row a17, 8b "mp_allreduce_grads"): the gradient mean over ranks on RCCL, the dynamic
-// loss-scale overflow check and the AdamWeightDecay update as streaming passes over the flat fp32 gradient arena.
+// Data-parallel gradient exchange (SURVEY.md 8a row a17, 8b "mp_allreduce_grads"): the gradient mean over ranks on RCCL, in place
+// on the flat fp32 gradient arena.  (The overflow check and the update that follow it are in step_end.hip.)
 //
-// Reference: tools/train.py:43-49 (data_parallel, gradients_mean=True: MindSpore all-reduces every gradient each step),
-// tools/train.py:170-181 (DynamicLossScaleManager: overflow check, skip + halve), optim/optim_factory.py:69-72 (AdamWeightDecay).
+// Reference: tools/train.py:43-49 (data_parallel, gradients_mean=True: MindSpore all-reduces every gradient each step).
 //
 // RCCL is bound at run time (the copy the process already holds - PyTorch ships its own librccl - found with RTLD_NOLOAD; the
 // system library only when none is loaded): the library has no link-time dependency on it and single-GPU users never load it.
 #include <dlfcn.h>
 
 #include "common.h"
-#include "optim_update.h"
 
 namespace mp {
 struct Id128 {  // ncclUniqueId: 128 opaque bytes passed BY VALUE to ncclCommInitRank
     char internal[128];
 };
 namespace {
-
-// ---- overflow check: one read of the arena, flag |= any(!isfinite) ----------------------------------------------------------
-__global__ __launch_bounds__(256) void finite_check_kernel(const float4* __restrict__ g4, const float* __restrict__ g, size_t n4,
-                                                           size_t n, int* __restrict__ flag) {
-    // a value is non-finite iff its exponent field is all ones
-    unsigned bad = 0;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
-        const float4 v = g4[i];
-        const unsigned e = 0x7f800000u;
-        bad |= (unsigned)((__float_as_uint(v.x) & e) == e) | (unsigned)((__float_as_uint(v.y) & e) == e) |
-               (unsigned)((__float_as_uint(v.z) & e) == e) | (unsigned)((__float_as_uint(v.w) & e) == e);
-    }
-    if (blockIdx.x == 0) {
-        for (size_t i = n4 * 4 + threadIdx.x; i < n; i += blockDim.x) bad |= (unsigned)((__float_as_uint(g[i]) & 0x7f800000u) == 0x7f800000u);
-    }
-    if (__ballot(bad != 0) != 0ull && (threadIdx.x & 63) == 0) atomicOr(flag, 1);
-}
-
-// ---- AdamWeightDecay with the gradient scale folded in (1 / (loss_scale * world)) and a device-side skip flag ----------------
-__global__ __launch_bounds__(256) void adamw_scaled_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                           float* __restrict__ v, size_t n, float lr, float b1, float b2, float eps,
-                                                           float wd, float grad_scale, const int* __restrict__ skip) {
-    if (skip != nullptr && *skip != 0) return;  // overflow step: parameters and moments untouched (uniform over the grid)
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-        adamw_update(p, m, v, i, g[i] * grad_scale, lr, b1, b2, eps, wd);
-}
 
 // ---- RCCL, bound lazily ------------------------------------------------------------------------------------------------------
 struct Rccl {
@@ -94,30 +66,6 @@ thread_local int g_last_rccl_error = 0;
 using namespace mp;
 
 extern "C" {
-
-int mp_grad_finite_check(const float* grad, size_t count, int* flag, mp_stream_t stream) {
-    if (!grad || !flag) return MP_ERR_NULL;
-    if (count == 0) return MP_OK;
-    if ((reinterpret_cast<uintptr_t>(grad) & 15) != 0) return MP_ERR_UNSUPPORTED;  // arena slices are 16-byte aligned by the caller
-    const size_t n4 = count / 4;
-    size_t blocks = (n4 + 255) / 256;
-    if (blocks > 256 * 8) blocks = 256 * 8;
-    if (blocks == 0) blocks = 1;
-    hipLaunchKernelGGL(finite_check_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream),
-                       reinterpret_cast<const float4*>(grad), grad, n4, count, flag);
-    return check_launch();
-}
-
-int mp_adamw_step_scaled(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t count, float lr, float beta1,
-                         float beta2, float eps, float weight_decay, float grad_scale, const int* skip_flag, mp_stream_t stream) {
-    if (!param || !grad || !exp_avg || !exp_avg_sq) return MP_ERR_NULL;
-    if (count == 0) return MP_OK;
-    size_t blocks = (count + 255) / 256;
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    hipLaunchKernelGGL(adamw_scaled_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), param, grad, exp_avg, exp_avg_sq,
-                       count, lr, beta1, beta2, eps, weight_decay, grad_scale, skip_flag);
-    return check_launch();
-}
 
 int mp_comm_available(void) { return rccl().ok ? 1 : 0; }
 

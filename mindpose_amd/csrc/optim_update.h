@@ -1,6 +1,5 @@
-// The per-element update rules of the arena optimizers, each stated once: the host-argument kernels (adamw_kernel of train_ops.hip,
-// adamw_scaled_kernel of dp_ops.hip, optimizer_kernel of train_ops.hip) and the device-resident ones of train_tail.hip, which read
-// lr / gradient scale / skip from the step-arguments block, run these bodies.
+// The per-element update rules of the arena optimizers, each stated once: step_update_kernel of step_end.hip runs these bodies, with
+// lr / gradient scale / skip from the host or from the device's step-arguments block.
 #pragma once
 #include "common.h"
 

@@ -1,8 +1,7 @@
 // Training-side HBM-bound kernels (gfx950): BatchNorm2d in training mode (batch statistics, forward and
-// backward), the backward of the exchange-unit sum, and the AdamWeightDecay update.  All reductions are
+// backward) and the backward of the exchange-unit sum (the optimizer updates are in step_end.hip).  All reductions are
 // two-stage with a fixed partition and a fixed combine order, so results are bit-reproducible run to run.
 #include "common.h"
-#include "optim_update.h"
 
 #include <math.h>
 #include <stdlib.h>
@@ -289,24 +288,6 @@ __global__ __launch_bounds__(256) void fuse_sum_bwd_kernel(const float* __restri
             }
         if (dt) dt[i] = acc;
     }
-}
-
-// mindspore.nn.AdamWeightDecay (update rule: adamw_update of optim_update.h)
-__global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                    float* __restrict__ v, size_t n, float lr, float b1, float b2, float eps,
-                                                    float wd) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-        adamw_update(p, m, v, i, g[i], lr, b1, b2, eps, wd);
-}
-
-// The other optimizers the reference registers (mindpose/optim/optim_factory.py:9-14), same flat-arena form: kinds 1 ... 4 of
-// optimizer_update (optim_update.h), hyper-parameters as kernel arguments.
-template <int KIND>
-__global__ __launch_bounds__(256) void optimizer_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ s1,
-                                                        float* __restrict__ s2, size_t n, float lr, float grad_scale, float wd,
-                                                        float h0, float h1, float h2, float h3, float h4) {
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-        optimizer_update<KIND>(p, s1, s2, i, g[i], lr, grad_scale, wd, h0, h1, h2, h3, h4);
 }
 
 // ---- fp16 (amp O2) training: the same BatchNorm passes over channel-blocked fp16 activations [N][C8][HW][8] ------------
@@ -1500,38 +1481,6 @@ int mp_fuse_upsample_sum_bwd(const float* dy, const float* out, float* dbase, fl
         if (rc != MP_OK) return rc;
     }
     return MP_OK;
-}
-
-int mp_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, size_t count, float lr, float beta1,
-                  float beta2, float eps, float weight_decay, mp_stream_t stream) {
-    if (!param || !grad || !exp_avg || !exp_avg_sq) return MP_ERR_NULL;
-    if (count == 0) return MP_OK;
-    size_t blocks = (count + 255) / 256;
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), param, grad, exp_avg, exp_avg_sq,
-                       count, lr, beta1, beta2, eps, weight_decay);
-    return check_launch();
-}
-
-int mp_optimizer_step(int kind, float* param, const float* grad, float* state1, float* state2, size_t count, float lr,
-                      float grad_scale, float weight_decay, const float hyper[5], mp_stream_t stream) {
-    if (!param || !grad || !hyper) return MP_ERR_NULL;
-    if (kind < 1 || kind > 4) return MP_ERR_UNSUPPORTED;
-    if (!state1 && !(kind == 2 && hyper[0] == 0.f)) return MP_ERR_NULL;
-    if (kind == 1 && !state2) return MP_ERR_NULL;
-    if (count == 0) return MP_OK;
-    size_t blocks = (count + 255) / 256;
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    const dim3 grid((unsigned)blocks), block(256);
-    hipStream_t s = as_stream(stream);
-    const float h0 = hyper[0], h1 = hyper[1], h2 = hyper[2], h3 = hyper[3], h4 = hyper[4];
-    switch (kind) {
-        case 1: hipLaunchKernelGGL(optimizer_kernel<1>, grid, block, 0, s, param, grad, state1, state2, count, lr, grad_scale, weight_decay, h0, h1, h2, h3, h4); break;
-        case 2: hipLaunchKernelGGL(optimizer_kernel<2>, grid, block, 0, s, param, grad, state1, state2, count, lr, grad_scale, weight_decay, h0, h1, h2, h3, h4); break;
-        case 3: hipLaunchKernelGGL(optimizer_kernel<3>, grid, block, 0, s, param, grad, state1, state2, count, lr, grad_scale, weight_decay, h0, h1, h2, h3, h4); break;
-        default: hipLaunchKernelGGL(optimizer_kernel<4>, grid, block, 0, s, param, grad, state1, state2, count, lr, grad_scale, weight_decay, h0, h1, h2, h3, h4); break;
-    }
-    return check_launch();
 }
 
 // The reducing forms of a validated record (bn16_fwd_fill / bn16_bwd_fill): every kernel argument comes from the record, none from the

@@ -42,7 +42,7 @@ class Trainer:
 
     def last_lr(self) -> float:
         """The learning rate of the last applied update (the base rate before any)."""
-        schedule = getattr(self.opt, "_schedule", None)
+        schedule = self.opt._schedule
         if schedule is None or self.opt.global_step == 0:
             return float(self.opt.lr)
         return float(schedule(self.opt.global_step - 1))
@@ -78,7 +78,7 @@ class Trainer:
                     extra["train_metrics"] = metric.compute()
                     metric.reset()
                 grad_norm = None
-                if getattr(self.opt, "clip_norm", None) is not None:  # the epoch's one read of the clip state, then a new period
+                if self.opt.clip_norm is not None:  # the epoch's one read of the clip state, then a new period
                     grad_norm = self.opt.grad_clip_stats()
                     self.opt.reset_grad_clip_stats()
                     _logger.info(f"epoch = {epoch}, gradient norm: mean = {grad_norm['mean_norm']:.6g}, max = {grad_norm['max_norm']:.6g}, "

@@ -12,8 +12,9 @@ for HRNet-W32).
 on the overflow check's one read of the arena (``mp_grad_finite_norm``), the coefficient is decided on the device and is one more
 factor of the gradient scale the update kernels apply while reading - no pass scales the gradients (include/mindpose_hip.h).
 """
+import ctypes
 import math
-from typing import Dict, Iterable, Optional, Tuple
+from typing import Dict, Iterable, Iterator, Optional, Tuple
 
 import numpy as np
 import torch
@@ -60,10 +61,15 @@ def clip_coefficient(norm: float, clip_norm: float) -> float:
 
 class _ArenaOptimizer:
     """Parameters, gradients and optimizer state as flat fp32 arenas ordered [decay | no-decay]; ``_update`` of a subclass
-    launches its streaming kernel once per group.  ``step`` = gradient mean over ranks (RCCL, overlapped with backward),
-    optional dynamic-loss-scale check, update."""
+    launches its streaming kernel on one group.  ``step`` = gradient mean over ranks (RCCL, overlapped with backward),
+    optional dynamic-loss-scale check, update.  The pieces of a step end are stated once here; ``step`` (the decision on the
+    host) and ``ResidentStepTail.launch`` (utils/step_tail.py, the decision on the device) put them together."""
 
     n_states = 2
+    kind = 0            # ``kind`` of mp_optimizer_step (0: AdamWeightDecay, which has entries of its own)
+    loss_scale = 1.0    # the static scale the MindSpore cells of ``_KernelOptimizer`` divide the gradient by
+    time_comm = False   # bench.py's DP leg sets it: ``finish_grads`` records a pair of events around the all-reduce wait
+    _schedule = None    # ``create_optimizer`` (utils/optim_factory.py) puts a scheduled learning rate here
 
     def __init__(self, net: torch.nn.Module, lr: float, weight_decay: float = 0.0, filter_bias_and_bn: bool = True,
                  bucket_mb: float = 32.0, process_group=None, overlap: bool = True, state_init: float = 0.0,
@@ -93,19 +99,13 @@ class _ArenaOptimizer:
         self._grad_flat = self.grads.arena
         self._overflow = torch.zeros(1, device=dev, dtype=torch.int32)  # device flag of the loss-scale overflow check
         self.global_step = 0
-        self.time_comm, self.comm_events = False, []
+        self.comm_events = []
         self.clip_coef = 1.0  # the last step's clip coefficient: the last factor of the gradient scale (exactly 1.0 = none)
         if self.clip_norm is not None:
             n_partials = _lib.load().mp_grad_norm_partials(self._grad_flat.numel())
             self._clip_partials = torch.zeros(n_partials, device=dev, dtype=torch.float64)  # one per workgroup of the fused pass
             self._clip_state = torch.zeros(CLIP_STATE_DTYPE.itemsize, device=dev, dtype=torch.uint8)
             self._clip_resolved = torch.zeros(CLIP_RESOLVED_DTYPE.itemsize, device=dev, dtype=torch.uint8)
-
-    def launch_finite_norm(self, lib, stream) -> None:
-        """Clipping on: the overflow check and the sum of squares in one read of the arena (flag zeroed first)."""
-        self._overflow.zero_()
-        _lib.check(lib.mp_grad_finite_norm(self._grad_flat.data_ptr(), self._grad_flat.numel(), self._overflow.data_ptr(),
-                                           self._clip_partials.data_ptr(), stream), "mp_grad_finite_norm")
 
     def grad_clip_stats(self) -> Dict[str, float]:
         """One download of the clip-state block (synchronises): the gradient norms of the steps since the last reset that were
@@ -128,19 +128,17 @@ class _ArenaOptimizer:
         """Release the gradient averager's hooks and communicator (call before ``destroy_process_group``)."""
         self.grads.close()
 
-    def step(self, loss_scale_manager=None) -> bool:
-        """All-reduce (mean) the gradients, then one streaming update per decay group.
+    # ---- the pieces of a step end ---------------------------------------------------------------------------------------------
 
-        With a ``DynamicLossScaleManager`` (amp O2, tools/train.py:170-181) the gradients are first divided by the loss
-        scale and checked: on overflow (inf / nan anywhere) the update is skipped and the scale halves, exactly one
-        host read-back per step; returns whether the parameters were updated.  With ``clip_norm`` the check also sums the
-        squares and a single-workgroup launch decides the clip coefficient: the read-back is its block instead of the flag."""
-        lib = _lib.load()
+    def finish_grads(self) -> None:
+        """The gradients are final: queued (grouped) weight gradients land in the arena before anything reads it, and the
+        bucket all-reduces have landed.  With ``time_comm`` (bench.py's DP leg) a pair of events brackets the device time from
+        "all gradients are in the arena" to "the all-reduces have landed" as the compute stream sees it (the native transport
+        runs them on its own stream; finish() makes this stream wait) - also in a resident step, which calls this too (today
+        nothing sets both ``time_comm`` and ``resident``)."""
         from ..models.train_ops import flush_wgrad_jobs
-        flush_wgrad_jobs()  # queued (grouped) weight gradients land in the arena before anything reads it
-        if getattr(self, "time_comm", False) and self.grads.active and self._grad_flat.is_cuda:
-            # bench.py's DP leg: device time from "all gradients are in the arena" to "the bucket all-reduces have landed" as the
-            # compute stream sees it (the native transport runs them on its own stream; finish() makes this stream wait for them)
+        flush_wgrad_jobs()
+        if self.time_comm and self.grads.active and self._grad_flat.is_cuda:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
             self.grads.finish()
@@ -148,42 +146,75 @@ class _ArenaOptimizer:
             self.comm_events.append((e0, e1))
         else:
             self.grads.finish()
-        # gradient scale the update kernels apply while reading the arena: 1 / loss_scale (amp O2) x 1 / world (gradient mean)
-        self.grad_scale = self.grads.mean_scale
-        self.clip_coef = 1.0
+
+    def launch_check(self, lib, scaling: bool, stream) -> Optional[int]:
+        """The step's one read of the gradient arena before the update (flag zeroed first): with clipping the overflow check and
+        the sum of squares as one pass, with loss scaling alone the check, else nothing.  Returns the flag's address for the
+        launch that decides the step, or None when nothing may skip it (no loss scaling: a clipping pass then runs for the norm
+        alone).  The sums are still scaled: inf / nan survive the scaling, so one read-only pass decides."""
+        if self.clip_norm is None and not scaling:
+            return None
+        self._overflow.zero_()
+        grad, flag = self._grad_flat, self._overflow.data_ptr()
         if self.clip_norm is not None:
-            # the fused pass instead of the check, and one single-workgroup launch that decides the coefficient with the device
-            # code of the resident tail; its block is downloaded where the flag would be: still one read-back per step
-            mgr = loss_scale_manager
-            if mgr is not None:
-                self.grad_scale /= mgr.loss_scale
-            self.launch_finite_norm(lib, _lib.stream())
-            _lib.check(lib.mp_grad_clip_resolve(
-                self._overflow.data_ptr() if mgr is not None else None, self._clip_partials.data_ptr(), self._clip_partials.numel(),
-                float(self.grads.mean_scale), float(mgr.loss_scale) if mgr is not None else 1.0, float(getattr(self, "loss_scale", 1.0)),
-                self.clip_norm, self._clip_state.data_ptr(), self._clip_resolved.data_ptr(), _lib.stream()), "mp_grad_clip_resolve")
-            resolved = self._clip_resolved.cpu().numpy().view(CLIP_RESOLVED_DTYPE)[0]
-            self.clip_coef = float(resolved["coef"])  # multiplies last, in ``_update``
-            if mgr is not None:
-                finite = int(resolved["flag"]) == 0
-                mgr.update_loss_scale(not finite)
-                if not finite:
-                    return False
-        elif loss_scale_manager is not None:
-            self.grad_scale /= loss_scale_manager.loss_scale
-            # overflow check on the (still scaled) sums: inf / nan survive the scaling, so one read-only pass decides
-            self._overflow.zero_()
-            _lib.check(lib.mp_grad_finite_check(self._grad_flat.data_ptr(), self._grad_flat.numel(), self._overflow.data_ptr(),
-                                                _lib.stream()), "mp_grad_finite_check")
-            finite = int(self._overflow.item()) == 0
-            loss_scale_manager.update_loss_scale(not finite)
-            if not finite:
-                return False
+            _lib.check(lib.mp_grad_finite_norm(grad.data_ptr(), grad.numel(), flag, self._clip_partials.data_ptr(), stream),
+                       "mp_grad_finite_norm")
+        else:
+            _lib.check(lib.mp_grad_finite_check(grad.data_ptr(), grad.numel(), flag, stream), "mp_grad_finite_check")
+        return flag if scaling else None
+
+    def groups(self) -> Iterator[Tuple[int, int, float]]:
+        """(start, count, weight decay) of the non-empty decay groups."""
         for start, count, wd in ((0, self.n_decay, self.weight_decay), (self.n_decay, self.flat.numel() - self.n_decay, 0.0)):
             if count:
-                self._update(lib, start, count, float(wd), _lib.stream())
+                yield start, count, float(wd)
+
+    def launch_updates(self, lib, stream, step_args: Optional[int] = None) -> None:
+        """One update launch per group - lr / gradient scale / skip from the host, or (``step_args``: the address of the device
+        step-arguments block of utils/step_tail.py) from the device.  The kernels write the master weights through raw pointers:
+        fp16 packings made before are stale."""
         from ..models.train_ops import invalidate_packs
-        invalidate_packs()  # the kernel wrote the master weights through raw pointers: fp16 packings made before are stale
+        for start, count, wd in self.groups():
+            self._update(lib, start, count, wd, stream, step_args)
+        invalidate_packs()
+
+    def _decide(self, lib, flag: Optional[int], mgr) -> bool:
+        """The host-driven decision, with the step's single read-back: the resolved block with clipping (a single-workgroup
+        launch decides the coefficient with the device code of the resident tail), else the flag, else nothing.  Sets
+        ``clip_coef``, advances the manager; returns whether the step applies."""
+        overflow = False
+        if self.clip_norm is not None:
+            _lib.check(lib.mp_grad_clip_resolve(
+                flag, self._clip_partials.data_ptr(), self._clip_partials.numel(), float(self.grads.mean_scale), float(mgr.loss_scale) if mgr is not None else 1.0,
+                float(self.loss_scale), self.clip_norm, self._clip_state.data_ptr(), self._clip_resolved.data_ptr(), _lib.stream()),
+                "mp_grad_clip_resolve")
+            resolved = self._clip_resolved.cpu().numpy().view(CLIP_RESOLVED_DTYPE)[0]
+            self.clip_coef = float(resolved["coef"])  # multiplies last, in ``_update``
+            overflow = int(resolved["flag"]) != 0
+        elif flag is not None:
+            overflow = int(self._overflow.item()) != 0
+        if mgr is not None:
+            mgr.update_loss_scale(overflow)
+        return not overflow
+
+    def step(self, loss_scale_manager=None) -> bool:
+        """All-reduce (mean) the gradients, then one streaming update per decay group.
+
+        With a ``DynamicLossScaleManager`` (amp O2, tools/train.py:170-181) the gradients are first divided by the loss
+        scale and checked: on overflow (inf / nan anywhere) the update is skipped and the scale halves, exactly one
+        host read-back per step; returns whether the parameters were updated.  With ``clip_norm`` the check also sums the
+        squares and a single-workgroup launch decides the clip coefficient: the read-back is its block instead of the flag."""
+        lib, mgr = _lib.load(), loss_scale_manager
+        self.finish_grads()
+        # gradient scale the update kernels apply while reading the arena: 1 / loss_scale (amp O2) x 1 / world (gradient mean)
+        self.grad_scale = self.grads.mean_scale
+        if mgr is not None:
+            self.grad_scale /= mgr.loss_scale
+        self.clip_coef = 1.0
+        flag = self.launch_check(lib, mgr is not None, _lib.stream())
+        if not self._decide(lib, flag, mgr):
+            return False
+        self.launch_updates(lib, _lib.stream())
         self.global_step += 1
         return True
 
@@ -197,25 +228,19 @@ class AdamWeightDecay(_ArenaOptimizer):
         self.beta1, self.beta2, self.eps = beta1, beta2, eps
         self.exp_avg, self.exp_avg_sq = self.states
 
-    def _update(self, lib, start, count, wd, stream):
-        _lib.check(lib.mp_adamw_step_scaled(self.flat[start:].data_ptr(), self._grad_flat[start:].data_ptr(),
-                                            self.exp_avg[start:].data_ptr(), self.exp_avg_sq[start:].data_ptr(), count,
-                                            float(self.lr), float(self.beta1), float(self.beta2), float(self.eps), wd,
-                                            float(self.grad_scale) * self.clip_coef, None, stream), "mp_adamw_step_scaled")
-
-    def _update_resident(self, lib, start, count, wd, step_args, stream):
-        """``_update`` with lr / gradient scale / skip read from the device step-arguments block (utils/step_tail.py)."""
-        _lib.check(lib.mp_adamw_step_resident(self.flat[start:].data_ptr(), self._grad_flat[start:].data_ptr(),
-                                              self.exp_avg[start:].data_ptr(), self.exp_avg_sq[start:].data_ptr(), count,
-                                              float(self.beta1), float(self.beta2), float(self.eps), wd, step_args, stream),
-                   "mp_adamw_step_resident")
+    def _update(self, lib, start, count, wd, stream, step_args=None):
+        arenas = [t[start:].data_ptr() for t in (self.flat, self._grad_flat, self.exp_avg, self.exp_avg_sq)]
+        betas = float(self.beta1), float(self.beta2), float(self.eps), wd
+        if step_args is not None:
+            _lib.check(lib.mp_adamw_step_resident(*arenas, count, *betas, step_args, stream), "mp_adamw_step_resident")
+        else:
+            _lib.check(lib.mp_adamw_step_scaled(*arenas, count, float(self.lr), *betas, float(self.grad_scale) * self.clip_coef, None,
+                                                stream), "mp_adamw_step_scaled")
 
 
 class _KernelOptimizer(_ArenaOptimizer):
     """The reference's other registered optimizers (optim_factory.py:9-14) through ``mp_optimizer_step``.  ``loss_scale`` is
     the static scale those MindSpore cells divide the gradient by; weight decay is their L2 term."""
-
-    kind = 0
 
     def __init__(self, net, lr, weight_decay=0.0, loss_scale: float = 1.0, **arena_kwargs) -> None:
         super().__init__(net, lr, weight_decay, **arena_kwargs)
@@ -224,23 +249,17 @@ class _KernelOptimizer(_ArenaOptimizer):
     def _hyper(self):
         raise NotImplementedError
 
-    def _update(self, lib, start, count, wd, stream):
-        import ctypes
-        hyper = (ctypes.c_float * 5)(*[float(v) for v in self._hyper()])
+    def _update(self, lib, start, count, wd, stream, step_args=None):
+        """With ``step_args`` the step-dependent entries of ``_hyper()`` - Adam's beta^t, SGD's first_step - are read from the
+        block too."""
+        hyper = ctypes.byref((ctypes.c_float * 5)(*[float(v) for v in self._hyper()]))
         st = [s_[start:].data_ptr() for s_ in self.states] + [None, None]
-        _lib.check(lib.mp_optimizer_step(self.kind, self.flat[start:].data_ptr(), self._grad_flat[start:].data_ptr(), st[0], st[1],
-                                         count, float(self.lr), float(self.grad_scale) / float(self.loss_scale) * self.clip_coef, wd,
-                                         ctypes.byref(hyper), stream),
-                   "mp_optimizer_step")
-
-    def _update_resident(self, lib, start, count, wd, step_args, stream):
-        """``_update`` with lr / gradient scale / skip - and the step-dependent entries of ``_hyper()``: Adam's beta^t, SGD's
-        first_step - read from the device step-arguments block (utils/step_tail.py)."""
-        import ctypes
-        hyper = (ctypes.c_float * 5)(*[float(v) for v in self._hyper()])
-        st = [s_[start:].data_ptr() for s_ in self.states] + [None, None]
-        _lib.check(lib.mp_optimizer_step_resident(self.kind, self.flat[start:].data_ptr(), self._grad_flat[start:].data_ptr(), st[0], st[1],
-                                                  count, wd, ctypes.byref(hyper), step_args, stream), "mp_optimizer_step_resident")
+        arenas = self.kind, self.flat[start:].data_ptr(), self._grad_flat[start:].data_ptr(), st[0], st[1], count
+        if step_args is not None:
+            _lib.check(lib.mp_optimizer_step_resident(*arenas, wd, hyper, step_args, stream), "mp_optimizer_step_resident")
+        else:
+            _lib.check(lib.mp_optimizer_step(*arenas, float(self.lr), float(self.grad_scale) / float(self.loss_scale) * self.clip_coef,
+                                             wd, hyper, stream), "mp_optimizer_step")
 
 
 class Adam(_KernelOptimizer):

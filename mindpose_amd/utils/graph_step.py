@@ -220,36 +220,29 @@ class GraphedTrainStep:
             del self.issue_ms[:2048]
 
     def __call__(self, *inputs: torch.Tensor) -> torch.Tensor:
-        """Copy the batch into the static buffers, replay the graph(s), run the optimizer; returns the (static) loss tensor."""
+        """Copy the batch into the static buffers, replay the graph(s), run the step end; returns the (static) loss tensor.
+
+        Host-driven: the optimizer's ``step`` decides, ``updated`` is its answer.  Resident (``self.tail``): ``scale_t`` already
+        holds the loss scale (the previous advance launch wrote it) and whether the update applies is the device's decision, so
+        ``updated`` is None and the recorded plans are dropped every step."""
         for dst, src in zip(self.static_in, inputs):
             if dst.data_ptr() != src.data_ptr():
                 dst.copy_(src)
-        if self.tail is not None:
-            return self._call_resident()
-        if self.mgr is not None:
+        if self.tail is None and self.mgr is not None:
             self.scale_t.fill_(self.mgr.loss_scale)
-        self.replay()  # under DP opt.step() waits for the bucket all-reduces (and launches those no segment boundary released)
-        self.updated = self.opt.step(loss_scale_manager=self.mgr)
-        if self.updated:
+        self.replay()  # under DP the step end waits for the bucket all-reduces (and launches those no segment boundary released)
+        if self.tail is not None:
+            self.opt.finish_grads()
+            self.tail.launch()
+            self.updated = None
+        else:
+            self.updated = self.opt.step(loss_scale_manager=self.mgr)
+        if self.tail is not None or self.updated:
             # a replay never passes through PlannedModule.forward, which is what drops recorded inference plans in training
             # mode: without this an evaluation between graphed steps would replay packed weights / folded BatchNorm of an
             # earlier parameter state
             for m in self._planned:
                 m._plans.clear()
-        return self.static_loss
-
-    def _call_resident(self) -> torch.Tensor:
-        """The step with the tail on the device: ``scale_t`` already holds the loss scale (the previous advance launch wrote it),
-        whether the update applies is the device's decision - so packs and recorded plans are dropped every step."""
-        from ..models.train_ops import flush_wgrad_jobs, invalidate_packs
-        self.replay()
-        flush_wgrad_jobs()  # as _ArenaOptimizer.step: queued weight gradients land before anything reads the arena
-        self.opt.grads.finish()
-        self.tail.launch()
-        invalidate_packs()
-        for m in self._planned:
-            m._plans.clear()
-        self.updated = None
         return self.static_loss
 
     def sync(self) -> None:

@@ -1,6 +1,6 @@
 """The step tail - overflow check, loss-scale update, skip decision, learning-rate lookup, parameter update - without a host
 read-back: what ``_ArenaOptimizer.step`` decides on the host from ``self._overflow.item()`` is decided on the device by one
-single-workgroup launch (``mp_train_tail_advance``, csrc/train_tail.hip), and the update launches read their step-dependent
+single-workgroup launch (``mp_train_tail_advance``, csrc/step_end.hip), and the update launches read their step-dependent
 arguments from the block it fills.  The host may therefore queue step t+1 before step t has run - the loop that
 ``mindspore.Model.train(..., dataset_sink_mode=True)`` runs on the device (tools/train.py:233).
 
@@ -44,13 +44,12 @@ class ResidentStepTail:
         the loss scale after every step.  The state starts from the manager's and the optimizer's current counters."""
         self.opt, self.mgr, self.scale_out = optimizer, loss_scale_manager, scale_out
         dev = optimizer.flat.device
-        schedule = getattr(optimizer, "_schedule", None)
-        self.lr_host = lr_table(schedule if schedule is not None else optimizer.lr, total_steps)
+        self.lr_host = lr_table(optimizer._schedule if optimizer._schedule is not None else optimizer.lr, total_steps)
         self.lr_dev = torch.from_numpy(self.lr_host).to(dev)
         self.aux_dev = None
-        if getattr(optimizer, "kind", 0) == 1:
+        if optimizer.kind == 1:
             self.aux_dev = torch.from_numpy(adam_aux_table(optimizer.beta1, optimizer.beta2, total_steps)).to(dev)
-        self.static_loss_scale = float(getattr(optimizer, "loss_scale", 1.0))
+        self.static_loss_scale = float(optimizer.loss_scale)
         self.state_dev = torch.zeros(STATE_DTYPE.itemsize, device=dev, dtype=torch.uint8)
         self.args_dev = torch.zeros(ARGS_DTYPE.itemsize, device=dev, dtype=torch.uint8)
         self.upload()
@@ -69,37 +68,22 @@ class ResidentStepTail:
             self.scale_out.fill_(mgr.loss_scale)
 
     def launch(self) -> None:
-        """Finite check (with a manager), advance, one update launch per non-empty decay group; no host read.  With the
-        optimizer's ``clip_norm`` the check also sums the squares and the advance launch decides the clip coefficient."""
+        """Check (with a manager or clipping), advance, one update launch per non-empty decay group; no host read.  With the
+        optimizer's ``clip_norm`` the check also sums the squares and the advance launch decides the clip coefficient; without a
+        manager that pass runs for the norm alone and its flag is not handed on (never skip)."""
         lib = _lib.load()
         opt, mgr, stream = self.opt, self.mgr, _lib.stream()
-
-        def tail_args(flag):
-            return (
-                flag, self.state_dev.data_ptr(), mgr.scale_factor if mgr is not None else 1.0, mgr.scale_window if mgr is not None else 1,
+        flag = opt.launch_check(lib, mgr is not None, stream)
+        args = (flag, self.state_dev.data_ptr(), mgr.scale_factor if mgr is not None else 1.0, mgr.scale_window if mgr is not None else 1,
                 float(opt.grads.mean_scale), self.static_loss_scale, self.lr_dev.data_ptr(), self.lr_dev.numel(),
                 self.aux_dev.data_ptr() if self.aux_dev is not None else None, self.aux_dev.shape[0] if self.aux_dev is not None else 0,
                 self.args_dev.data_ptr(), self.scale_out.data_ptr() if (self.scale_out is not None and mgr is not None) else None)
-
-        flag = None
-        if getattr(opt, "clip_norm", None) is not None:
-            # gradient clipping: the fused check + sum of squares and the tail that decides the coefficient, in place of the two
-            # launches below; without a manager the pass runs for the norm alone and its flag is not handed on (never skip)
-            opt.launch_finite_norm(lib, stream)
-            if mgr is not None:
-                flag = opt._overflow.data_ptr()
-            _lib.check(lib.mp_train_tail_advance_clip(*tail_args(flag), opt._clip_partials.data_ptr(), opt._clip_partials.numel(),
-                                                      opt.clip_norm, opt._clip_state.data_ptr(), stream), "mp_train_tail_advance_clip")
+        if opt.clip_norm is not None:
+            _lib.check(lib.mp_train_tail_advance_clip(*args, opt._clip_partials.data_ptr(), opt._clip_partials.numel(), opt.clip_norm,
+                                                      opt._clip_state.data_ptr(), stream), "mp_train_tail_advance_clip")
         else:
-            if mgr is not None:
-                opt._overflow.zero_()
-                _lib.check(lib.mp_grad_finite_check(opt._grad_flat.data_ptr(), opt._grad_flat.numel(), opt._overflow.data_ptr(), stream),
-                           "mp_grad_finite_check")
-                flag = opt._overflow.data_ptr()
-            _lib.check(lib.mp_train_tail_advance(*tail_args(flag), stream), "mp_train_tail_advance")
-        for start, count, wd in ((0, opt.n_decay, opt.weight_decay), (opt.n_decay, opt.flat.numel() - opt.n_decay, 0.0)):
-            if count:
-                opt._update_resident(lib, start, count, float(wd), self.args_dev.data_ptr(), stream)
+            _lib.check(lib.mp_train_tail_advance(*args, stream), "mp_train_tail_advance")
+        opt.launch_updates(lib, stream, self.args_dev.data_ptr())
 
     def read_state(self) -> np.ndarray:
         """One download of the state block (synchronises with the stream)."""

@@ -147,10 +147,10 @@ ENTRIES = {
                              lambda c: c[1] * c[2] * c[3] * c[4]),
     "mp_f16_gather_phase": Entry(16384 * 256, ("sb_train_ops.hip", "if (blocks > 16384) blocks = 16384;"), [c for c in GATHER_CASES if c[0]],
                                  lambda c: c[1] * c8_of(c[2]) * c[3] * c[4]),
-    "mp_adamw_step": Entry(OPT_CAP, ("train_ops.hip", "if (blocks > 256 * 16) blocks = 256 * 16;"), OPT_COUNTS, lambda c: c),
-    "mp_adamw_step_scaled": Entry(OPT_CAP, ("dp_ops.hip", "if (blocks > 256 * 16) blocks = 256 * 16;"), OPT_COUNTS, lambda c: c),
-    "mp_optimizer_step": Entry(OPT_CAP, ("train_ops.hip", "if (blocks > 256 * 16) blocks = 256 * 16;"), OPT_COUNTS, lambda c: c),
-    "mp_grad_finite_check": Entry(FINITE_CAP // 4, ("dp_ops.hip", "if (blocks > 256 * 8) blocks = 256 * 8;"), FINITE_COUNTS,
+    "mp_adamw_step": Entry(OPT_CAP, ("step_end.hip", "if (blocks > 256 * 16) blocks = 256 * 16;"), OPT_COUNTS, lambda c: c),
+    "mp_adamw_step_scaled": Entry(OPT_CAP, ("step_end.hip", "if (blocks > 256 * 16) blocks = 256 * 16;"), OPT_COUNTS, lambda c: c),
+    "mp_optimizer_step": Entry(OPT_CAP, ("step_end.hip", "if (blocks > 256 * 16) blocks = 256 * 16;"), OPT_COUNTS, lambda c: c),
+    "mp_grad_finite_check": Entry(FINITE_CAP // 4, ("step_end.hip", "if (blocks > 256 * 8) blocks = 256 * 8;"), FINITE_COUNTS,
                                   lambda c: c // 4, lambda c: c, vec=4),
 }
 
@@ -331,8 +331,8 @@ def _one_minus(v):
 
 
 def optimizer_ref(kind, p, g, s1, s2, lr, grad_scale, wd, hyper):
-    """The update rules written above adamw_kernel (kind 0: AdamWeightDecay, hyper = (b1, b2, eps); the gradient is g * grad_scale,
-    decoupled decay) and optimizer_kernel (kinds 1 ... 4; the gradient is g * grad_scale + wd * p) of csrc/train_ops.hip, in float64 on
+    """The update rules of csrc/optim_update.h, which step_update_kernel of csrc/step_end.hip runs (kind 0: AdamWeightDecay, hyper =
+    (b1, b2, eps); the gradient is g * grad_scale, decoupled decay; kinds 1 ... 4: the gradient is g * grad_scale + wd * p), in float64 on
     hyper-parameters first rounded to fp32.  Returns (p, s1, s2); states a rule does not have come back unchanged."""
     p, g = p.double(), g.double()
     s1 = None if s1 is None else s1.double()

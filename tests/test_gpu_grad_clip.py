@@ -1,4 +1,4 @@
-"""Gradient clipping by global norm decided on the device (csrc/grad_clip.hip, csrc/train_tail.hip, utils/adamw.py ``clip_norm``,
+"""Gradient clipping by global norm decided on the device (csrc/step_end.hip, utils/adamw.py ``clip_norm``,
 utils/step_tail.py): the fused overflow check + sum of squares against numpy in fp64 and against ``mp_grad_finite_check``, the tail
 with clipping against ``mp_train_tail_advance`` and a Python restatement of the definition in double, the five optimizers resident
 against host-driven, and the graphed step end to end.

@@ -1,4 +1,4 @@
-"""The device-resident step tail (csrc/train_tail.hip, utils/step_tail.py) against the host-driven one it restates
+"""The device-resident step tail (csrc/step_end.hip, utils/step_tail.py) against the host-driven one it restates
 (utils/loss_scale.py, utils/adamw.py).  Every comparison is bit for bit: the state machine is integer / double host arithmetic
 restated on the device, the update launches run the same fp32 body as the host-argument entries (csrc/optim_update.h)."""
 import ctypes

@@ -268,7 +268,7 @@ class _NoBatches:
 
 
 class _Optimizer:
-    lr, global_step = 1e-3, 0
+    lr, global_step, _schedule, clip_norm = 1e-3, 0, None, None  # (an arena optimizer always has the last two)
 
     def __init__(self):
         from types import SimpleNamespace

@@ -108,10 +108,11 @@ def _answer(name: str) -> int:
 
 
 class _FakeLib:
-    """Every export of the C ABI as a recording callable (argument kinds from `_lib._PROTOTYPES`)."""
+    """Every export of the C ABI as a recording callable (argument kinds from `_lib._PROTOTYPES`).  ``answers``: name -> a callable
+    that takes the call's arguments and gives its return value, for the exports whose constant answer does not fit a case."""
 
-    def __init__(self, trace):
-        self._trace = trace
+    def __init__(self, trace, answers=None):
+        self._trace, self._answers = trace, answers or {}
 
     def __getattr__(self, name):
         if name not in _lib._PROTOTYPES:
@@ -123,7 +124,7 @@ class _FakeLib:
                 raise TypeError(f"{name}: {len(args)} arguments for {len(argtypes)} parameters")
             c = _Call()
             self._trace.events.append([name] + [c.value(a, tp) for a, tp in zip(args, argtypes)])
-            return _answer(name)
+            return self._answers[name](*args) if name in self._answers else _answer(name)
 
         self.__dict__[name] = call
         return call
@@ -158,10 +159,10 @@ def _cold():
 
 
 @contextlib.contextmanager
-def recording(env=None):
+def recording(env=None, answers=None):
     """The patches under which the training path runs on host tensors; yields the trace being filled."""
     trace = _Trace()
-    fake = _FakeLib(trace)
+    fake = _FakeLib(trace, answers)
     _cold()
     settings = {k: None for k in _SWITCHES}
     settings.update({"MINDPOSE_AUTOTUNE": "0", "MINDPOSE_WGRAD_EARLY_FLUSH": "0"})
