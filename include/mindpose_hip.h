@@ -975,6 +975,12 @@ int mp_f16_conv_pre_supported(const mp_conv_desc* desc, int variant);
  * launch; host-only, no device work.  0 = the entry would answer MP_ERR_UNSUPPORTED (or a shape error).  The test matrix is
  * generated from this query, so a pair that stops being served shows up as a failing floor test instead of a skip. */
 int mp_f16_conv_supported(const mp_conv_desc* desc, int variant, int n_res, int stats_mode);
+/* The launch record that query builds, as numbers (host-only; tests pin the tile geometry with it): out[0] = the build's return
+ * code, out[1] = the dry dispatch's; after an accepted build: kernel size, stride, variant, LDS bytes, every scalar field of the
+ * kernel parameter block in declaration order (magic numbers unsigned), every pointer field as 0 / 1 (null / set), and the byte
+ * offset of the partial-sum pointer from partials_dev.  Returns the number of words written, MP_ERR_WORKSPACE when cap is too
+ * small (80 is enough). */
+int mp_f16_conv_launch_words(const mp_conv_desc* desc, int variant, int n_res, int stats_mode, int64_t* out, int cap);
 int mp_f16_conv2d_fwd_stats(const mp_conv_desc* desc, int variant, const void* x_c8_dev, const void* packed_w_dev,
                             const float* scale_dev, const float* shift_dev, const void* res1_c8_dev, void* out_c8_dev,
                             const mp_f16_conv_stats* stats, mp_stream_t stream);

@@ -5,6 +5,8 @@
 // LDS staging is plain 16-byte copies and every MFMA operand is ONE ds_read_b128 at any tap offset or stride.
 // Padding channels of the last block are kept zero by every producer.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 
 namespace mp {
@@ -61,33 +63,208 @@ struct ConvF16Launch {
     size_t lds_bytes;
 };
 
-// 0..4 tile shapes (cout tile x pixel tile), 5..9 their light builds, 10..14 / 15..19 the persistent multi-tile kernel
-// (weights resident in LDS, input tiles double-buffered) compiled for two / one workgroup per CU
+// ---- Tile geometry: the rules the four configure functions share (f16_configure / f16_configure_mt in conv_f16.hip,
+// f16_configure_wreg, f16_configure_ws).  Each family keeps what is its own: the LDS budget search over rows and chunk size (one
+// tile), the buffer count and tile runs (multi-tile), the shared zero column and the fast DMA form (weights in registers), the
+// fewest-tiles-per-workgroup row choice (weight-stationary).
+//
+// Fields whose meaning depends on the family that fills them in (the kernels read the same block):
+//
+//   field        | one-tile / multi-tile              | weights in registers                | weight-stationary
+//   -------------+------------------------------------+-------------------------------------+--------------------------------
+//   Wp           | columns the taps reach (widened to | W + halo: one shared zero column    | W + 1
+//                | the padded row when <= 2 wider)    |                                     |
+//   plane        | G img_plane, rounded (see          | G img_plane + halo, rounded; fast   | img_plane + 1, rounded up to 64
+//                | f16_geom_planes)                   | form: rounded up to 64              |
+//   ncols        | staged columns per row             | W                                   | W
+//   upc          | staging units per plane            | DMA pieces (64 elements) per plane, | DMA pieces per plane
+//                | (G Rin ncols)                      | 0 = the slow staging form           |
+//   magic_upc    | / upc                              | / plane                             | -
+//   magic_ncols  | / ncols                            | / Wp                                | / Wp
+//   magic_rin    | / Rin                              | / img_plane                         | 0
+//   magic_rwo    | / RWo                              | / RWo                               | 0
+//   magic_wo     | / Wo                               | / Wo                                | / W
+//   magic_rows   | one-tile: / (G Rin); multi-tile: - | -                                   | / tiles_y
+//   tiles_total  | multi-tile only                    | tiles_y tiles_n                     | tiles_y N
+//   nbuf         | chunk buffers (1 or 2) / input     | 1                                   | 2 (the DMA ring)
+//                | tile buffers (2, or 1)             |                                     |
+
+// tensor extents, padding, activation and the output mapping, straight from the desc
+inline void f16_geom_tensors(const mp_conv_desc& d, ConvF16Params& p) {
+    p.N = d.n; p.H = d.h; p.W = d.w; p.Cout = d.cout;
+    p.C8in = (d.cin + 7) / 8;
+    p.Cout_pad16 = round_up(d.cout, 16);
+    p.C8out = (d.cout + 7) / 8;
+    p.Ho = d.conv_h; p.Wo = d.conv_w; p.pad_t = d.pad_top; p.pad_l = d.pad_left;
+    p.relu = d.relu;
+    p.out_h = d.out_h; p.out_w = d.out_w; p.out_mul = d.out_mul; p.off_y = d.out_off_y; p.off_x = d.out_off_x;
+}
+// 32-bit byte offsets over the whole tensors (the output's are sums of masked parts: kInv in conv_f16_dev.h).  The one-tile kernel
+// rebases its input descriptor per tile and does not ask.
+inline bool f16_geom_offsets_fit(const mp_conv_desc& d, const ConvF16Params& p) {
+    return (long long)d.n * p.C8in * d.h * d.w * 16 < 0x7FFFFFF0LL && (long long)d.n * p.C8out * d.out_h * d.out_w * 16 < 0x60000000LL;
+}
+// a pixel tile of PT pixels holds R whole output rows of one image - or, when that is the whole image, G whole images
+inline void f16_geom_fit(ConvF16Params& p, int R, int PT) {
+    p.R = R;
+    p.G = 1;
+    if (R == p.Ho) {
+        p.G = PT / (p.Ho * p.Wo);
+        if (p.G > p.N) p.G = p.N;
+        if (p.G < 1) p.G = 1;
+    }
+    p.RWo = p.R * p.Wo;
+}
+// The staged tile: Rin input rows of pitch Wp per image, G images per 8-channel plane and `tail` elements behind them (the zero slot
+// of the DMA kernels).  Plane pitch in 16-byte elements: == 0 (mod 16) for stride 1, odd for stride 2 (the lanes of a wave then read
+// every other element) - either way every ds_read_b128 is conflict-free.
+inline void f16_geom_planes(ConvF16Params& p, int KS, int S, int Wp, int tail) {
+    p.Rin = (p.R - 1) * S + KS;
+    p.Wp = Wp;
+    p.img_plane = p.Rin * p.Wp;
+    p.plane = S == 1 ? round_up(p.G * p.img_plane + tail, 16) : ((p.G * p.img_plane + tail) | 1);
+}
+// the DMA kernels' staging by pieces: one image per tile, the plane pitch a whole number of 64-element pieces
+inline void f16_geom_dma_pieces(ConvF16Params& p, int tail) {
+    p.plane = round_up(p.img_plane + tail, 64);
+    p.upc = p.plane / 64;
+}
+// cout slices of CT, row bands per image (one when a tile holds whole images), image groups
+inline void f16_geom_tiles(ConvF16Params& p, int CT) {
+    p.n_ct = (p.Cout_pad16 + CT - 1) / CT;
+    p.tiles_y = (p.G > 1 || p.R >= p.Ho) ? 1 : (p.Ho + p.R - 1) / p.R;
+    p.tiles_n = (p.N + p.G - 1) / p.G;
+}
+// Persistent kernels: workgroups per cout slice - all resident at once, or what the test knob says (long tile runs on small
+// problems) - and the tile runs they walk.  False: a run of ONE tile amortises nothing, the one-tile kernels do that with less LDS.
+inline int f16_geom_groups(int occ, int n_ct, const char* knob_name) {
+    int groups = occ * 256 / n_ct;
+    if (const char* e = knob(knob_name)) {
+        const int v = atoi(e);
+        if (v >= 1) groups = v;
+    }
+    return groups;
+}
+inline bool f16_geom_runs(ConvF16Params& p, int groups) {
+    p.tiles_total = p.tiles_y * p.tiles_n;
+    p.tiles_per_wg = (p.tiles_total + groups - 1) / groups;
+    if (p.tiles_per_wg < 2) return false;
+    p.n_groups = (p.tiles_total + p.tiles_per_wg - 1) / p.tiles_per_wg;
+    p.total_blocks = p.n_ct * p.n_groups;
+    return true;
+}
+// lane -> (image, row, column) of its output pixel
+inline void f16_geom_pixel_magics(ConvF16Params& p) {
+    p.magic_rwo = magic_of(p.RWo);
+    p.magic_wo = magic_of(p.Wo);
+}
+
+// Tile variants.  The ids are ABI: the tuner's tables and persisted caches, tests/f16_matrix.py and
+// tests/golden/bench_plan_picks.json hold them.  What each id IS stands in kF16Variants below, and nowhere else.
 enum ConvF16Variant { F_CT32_PT192 = 0, F_CT64_PT192 = 1, F_CT48_PT192 = 2, F_CT64_PT96 = 3, F_CT32_PT96 = 4,
                       F_CT32_PT192_L = 5, F_CT64_PT192_L = 6, F_CT48_PT192_L = 7, F_CT64_PT96_L = 8, F_CT32_PT96_L = 9,
                       F_MT2_BASE = 10, F_MT1_BASE = 15,
-                      // 16-cout tiles (twice the workgroups: latency hiding for the large-K small-map layers)
-                      F_CT16_PT192 = 20, F_CT16_PT192_L = 21, F_CT16_PT192_MT2 = 22, F_CT16_PT192_MT1 = 23,
-                      // 384-pixel tiles for the small-K layers: a workgroup's fixed set-up (a third of its life at K = 288)
-                      // and its weight loads are spread over twice the MFMA work
-                      F_CT32_PT384 = 24,
-                      // "weights in registers" kernel (conv_f16_wreg.hip): P<pixel tiles of 16>C<cout tiles of 16 per wave, x 4 waves>
-                      // _W<n>: n waves split the pixel tiles (4 / n split the couts); no suffix = 1
+                      F_CT16_PT192 = 20, F_CT16_PT192_L = 21, F_CT16_PT192_MT2 = 22, F_CT16_PT192_MT1 = 23, F_CT32_PT384 = 24,
+                      // P<pixel tiles of 16>C<cout tiles of 16 per wave>_W<n>: n waves split the pixel tiles (4 / n split the couts)
                       F_WREG_P6C2 = 25, F_WREG_P3C2 = 26, F_WREG_P6C1 = 27, F_WREG_P6C3 = 28, F_WREG_P3C3 = 29, F_WREG_P3C4 = 30,
                       F_WREG_P6C2_W2 = 31, F_WREG_P6C3_W2 = 32, F_WREG_P3C2_W2 = 33, F_WREG_P6C2_W4 = 34, F_WREG_P6C3_W4 = 35,
                       F_WREG_P3C2_W4 = 36,
-                      // weight-stationary persistent kernel (conv_f16_ws.hip): shapes in kWsShapes
                       F_WS_BASE = 37, F_WS_COUNT = 8,
-                      // round 4, weights-in-registers shapes whose pixel tile makes W48's deep layers ONE round of 256 workgroups:
-                      // 112 px x 192 couts (192 -> 192 @24x18, N = 64: 6 rows of 18 = 4 tiles per image x 64) and 64 px x 192 couts
-                      // (384 -> 384 @12x9: 7 rows of 9 = 2 tiles per image x 64 x 2 cout slices); P5C4 = 80 px x 256 couts
                       F_WREG_P7C3 = 45, F_WREG_P4C3 = 46, F_WREG_P5C4 = 47, F_COUNT = 48 };
-inline bool f16_variant_wreg(int v) { return (v >= F_WREG_P6C2 && v <= F_WREG_P3C2_W4) || (v >= F_WREG_P7C3 && v <= F_WREG_P5C4); }
-inline int f16_wreg_index(int v) { return v <= F_WREG_P3C2_W4 ? v - F_WREG_P6C2 : 12 + v - F_WREG_P7C3; }
-inline bool f16_variant_ws(int v) { return v >= F_WS_BASE && v < F_WS_BASE + F_WS_COUNT; }
-inline bool f16_variant_mt(int v) { return (v >= F_MT2_BASE && v < F_CT16_PT192) || v == F_CT16_PT192_MT2 || v == F_CT16_PT192_MT1; }
-inline int f16_variant_mt_occ(int v) { return (v >= F_MT1_BASE && v < F_CT16_PT192) || v == F_CT16_PT192_MT1 ? 1 : 2; }
-bool f16_variant_light(int v);
+
+// kernel families: one tile per workgroup (conv_f16.hip), persistent multi-tile with the weights resident in LDS and the input tiles
+// double-buffered (conv_f16_mt.hip), weights in registers (conv_f16_wreg.hip), weight-stationary persistent (conv_f16_ws.hip)
+enum F16Family { kF16Tile, kF16Mt, kF16Wreg, kF16Ws };
+
+// One row per variant id.  A wave owns ps pixel tiles x cs cout tiles of 16; waves_p of the 4 waves split the pixels, 4 / waves_p the
+// couts: the workgroup's tile is 16 cs (4 / waves_p) couts x 16 ps waves_p pixels.  occ = workgroups per CU the build is compiled for.
+struct F16Variant {
+    F16Family family;
+    int ps, cs, waves_p, occ;
+    bool light;      // one-tile kernel: small chunks / few staging registers, three workgroups per CU (<= 52 KiB LDS)
+    bool one_chunk;  // one-tile kernel: the build without a chunk loop - launches with n_chunks == 1 only
+    bool k3s1_only;  // weights in registers: built for the 3x3 stride-1 branch convs only
+    int nq;          // weight-stationary: k-steps of 32 input channels, Cin in (32 (nq - 1), 32 nq]
+};
+constexpr F16Variant f16_tile_row(int ps, int cs, int waves_p, bool light = false, bool one_chunk = false) {
+    return {kF16Tile, ps, cs, waves_p, light ? 3 : 2, light, one_chunk, false, 0};
+}
+constexpr F16Variant f16_mt_row(int cs, int waves_p, int occ) { return {kF16Mt, 3, cs, waves_p, occ, false, false, false, 0}; }
+constexpr F16Variant f16_wreg_row(int ps, int cs, int waves_p, int occ, bool k3s1_only = false) {
+    return {kF16Wreg, ps, cs, waves_p, occ, false, false, k3s1_only, 0};
+}
+constexpr F16Variant f16_ws_row(int nq, int cs, int waves_p, int ps, int occ) { return {kF16Ws, ps, cs, waves_p, occ, false, false, false, nq}; }
+constexpr F16Variant kF16Variants[F_COUNT] = {
+    // 0..4: the five cout x pixel tiles of the one-tile kernel, 5..9 their light builds
+    f16_tile_row(3, 2, 4), f16_tile_row(3, 4, 4), f16_tile_row(3, 3, 4), f16_tile_row(3, 2, 2), f16_tile_row(3, 1, 2),
+    f16_tile_row(3, 2, 4, true), f16_tile_row(3, 4, 4, true), f16_tile_row(3, 3, 4, true), f16_tile_row(3, 2, 2, true), f16_tile_row(3, 1, 2, true),
+    // 10..14 / 15..19: the same tiles in the multi-tile kernel, compiled for two / one workgroup per CU
+    f16_mt_row(2, 4, 2), f16_mt_row(4, 4, 2), f16_mt_row(3, 4, 2), f16_mt_row(2, 2, 2), f16_mt_row(1, 2, 2),
+    f16_mt_row(2, 4, 1), f16_mt_row(4, 4, 1), f16_mt_row(3, 4, 1), f16_mt_row(2, 2, 1), f16_mt_row(1, 2, 1),
+    // 20..23: 16 couts x 192 px (twice the workgroups: latency hiding for the large-K small-map layers): one-tile, light, multi-tile
+    f16_tile_row(3, 1, 4), f16_tile_row(3, 1, 4, true), f16_mt_row(1, 4, 2), f16_mt_row(1, 4, 1),
+    // 24: 32 couts x 384 px for the small-K layers: a workgroup's fixed set-up (a third of its life at K = 288) and its
+    // weight loads are spread over twice the MFMA work
+    f16_tile_row(6, 2, 4, false, true),
+    // 25..36: weights in registers
+    f16_wreg_row(6, 2, 1, 1), f16_wreg_row(3, 2, 1, 2), f16_wreg_row(6, 1, 1, 2), f16_wreg_row(6, 3, 1, 1), f16_wreg_row(3, 3, 1, 1),
+    f16_wreg_row(3, 4, 1, 1), f16_wreg_row(6, 2, 2, 2), f16_wreg_row(6, 3, 2, 1), f16_wreg_row(3, 2, 2, 2), f16_wreg_row(6, 2, 4, 2),
+    f16_wreg_row(6, 3, 4, 1), f16_wreg_row(3, 2, 4, 2),
+    // 37..44: weight-stationary (the table that was conv_f16_ws.hip's kWsShapes)
+    f16_ws_row(1, 2, 4, 3, 2),  // 32 channels: 32 couts x 192 px (training convs of the 32-channel branch; inference runs them as fused blocks)
+    f16_ws_row(2, 3, 4, 5, 1),  // 48 (W48 branch 1): 48 couts x 320 px
+    f16_ws_row(2, 4, 4, 3, 1),  // 64: 64 couts x 192 px
+    f16_ws_row(2, 2, 4, 3, 1),  // 64: two cout slices of 32 x 192 px
+    f16_ws_row(3, 2, 4, 5, 1),  // 96 (W48 branch 2): three cout slices of 32 x 320 px
+    f16_ws_row(3, 3, 4, 3, 1),  // 96: two cout slices of 48 x 192 px
+    f16_ws_row(4, 2, 2, 3, 1),  // 128: two cout slices of 64 x 96 px
+    f16_ws_row(4, 2, 1, 6, 1),  // 128: 128 couts x 96 px
+    // 45..47: weights-in-registers shapes whose pixel tile makes W48's deep layers ONE round of 256 workgroups: 112 px x 192 couts
+    // (192 -> 192 @24x18, N = 64: 6 rows of 18 = 4 tiles per image x 64), 64 px x 192 couts (384 -> 384 @12x9: 7 rows of 9 = 2 tiles
+    // per image x 64 x 2 cout slices), 80 px x 256 couts
+    f16_wreg_row(7, 3, 1, 1, true), f16_wreg_row(4, 3, 1, 1, true), f16_wreg_row(5, 4, 1, 1, true),
+};
+constexpr const F16Variant& f16_variant(int v) { return kF16Variants[v]; }  // 0 <= v < F_COUNT (f16_build_launch refuses the rest)
+inline bool f16_variant_wreg(int v) { return f16_variant(v).family == kF16Wreg; }
+inline bool f16_variant_ws(int v) { return f16_variant(v).family == kF16Ws; }
+inline bool f16_variant_mt(int v) { return f16_variant(v).family == kF16Mt; }
+constexpr int f16_variant_ct(int v) { return 16 * f16_variant(v).cs * (4 / f16_variant(v).waves_p); }
+constexpr int f16_variant_pt(int v) { return 16 * f16_variant(v).ps * f16_variant(v).waves_p; }
+
+// Runs f(std::integral_constant<int, V>) for the id V == v of one family - the family's dispatch instantiates its kernels from the
+// table's rows, over its own ids only; MP_ERR_UNSUPPORTED for an id of another family
+template <F16Family FAM, int V = 0, class F>
+int f16_dispatch_variant(int v, F&& f) {
+    if constexpr (V == F_COUNT) {
+        return MP_ERR_UNSUPPORTED;
+    } else {
+        if constexpr (kF16Variants[V].family == FAM) {
+            if (v == V) return f(std::integral_constant<int, V>{});
+        }
+        return f16_dispatch_variant<FAM, V + 1>(v, f);
+    }
+}
+
+// The training builds (epilogue statistics, conv_f16_dev.h) of the one-tile and multi-tile kernels exist for the kernel sizes a
+// BatchNorm follows / a data gradient runs through - 1x1 and 3x3: forward sums at either stride, backward sums at stride 1 (data
+// gradients are stride-1 launches) - and for the 2x2 phase convs of a stride-2 data gradient: backward sums only.
+constexpr bool f16_has_stats_build(int ks, int s, int mode) {
+    if (mode == 0) return true;
+    if (ks == 1 || ks == 3) return mode == 1 || s == 1;
+    return ks == 2 && s == 1 && mode == 2;
+}
+// launch(std::integral_constant<int, STATS>) for the build that serves p.st_mode
+template <int KS, int S, class F>
+int f16_dispatch_stats(int st_mode, F&& launch) {
+    if (st_mode == 0) return launch(std::integral_constant<int, 0>{});
+    if constexpr (f16_has_stats_build(KS, S, 1)) {
+        if (st_mode == 1) return launch(std::integral_constant<int, 1>{});
+    }
+    if constexpr (f16_has_stats_build(KS, S, 2)) {
+        if (st_mode == 2) return launch(std::integral_constant<int, 2>{});
+    }
+    return MP_ERR_UNSUPPORTED;
+}
 
 // fused BasicBlock of the 32-channel branch (basicblock_f16.hip)
 struct BlockF16Params {
@@ -198,22 +375,17 @@ int f16_build_launch(const mp_conv_desc* desc, int variant, const void* x, const
 int f16_launch(const ConvF16Launch& L, hipStream_t s);
 // partial-sum slots (per channel) a launch with epilogue statistics writes: one per pixel-tile workgroup / persistent workgroup
 int f16_stats_parts(const ConvF16Launch& L);
-void f16_variant_dims(int v, int& ct, int& pt);
 int f16_mt_launch(const ConvF16Launch& L, hipStream_t s);
 bool f16_configure_wreg(const mp_conv_desc& d, int variant, ConvF16Launch& L);
 int f16_wreg_launch(const ConvF16Launch& L, hipStream_t s);
-void f16_wreg_dims(int v, int& ps, int& csw, int& waves_p);
 int f16_mt_ni(int occ);
 bool f16_configure_ws(const mp_conv_desc& d, int variant, ConvF16Launch& L);
 int f16_ws_launch(const ConvF16Launch& L, hipStream_t s);
-void f16_ws_dims(int v, int& ps, int& csw, int& waves_p);
 
 inline int run(const ConvF16Launch& L, hipStream_t s) { return f16_launch(L, s); }
 inline void describe(const ConvF16Launch& L, int64_t info[12]) {
-    int ct, pt;
-    f16_variant_dims(L.variant, ct, pt);
-    fill_info(info, {kConvF16, L.ks, L.stride, L.variant, L.p.total_blocks, (int64_t)L.lds_bytes, ct, pt, L.p.PK * 8, L.p.G, L.p.R,
-                     f16_variant_light(L.variant) ? 1 : 0});
+    fill_info(info, {kConvF16, L.ks, L.stride, L.variant, L.p.total_blocks, (int64_t)L.lds_bytes, f16_variant_ct(L.variant),
+                     f16_variant_pt(L.variant), L.p.PK * 8, L.p.G, L.p.R, f16_variant(L.variant).light ? 1 : 0});
 }
 
 }  // namespace mp

@@ -364,72 +364,59 @@ constexpr int f16_ni(int ks, bool light) { return light ? 5 : 10; }
 constexpr int f16_nw(int ks, bool light) { return light ? 5 : (ks == 3 ? 9 : 8); }  // ks 2 (deconv phases): 8
 constexpr int f16_occ(bool light) { return light ? 3 : 2; }
 
-// the training builds (epilogue statistics) exist for the kernel sizes a BatchNorm follows / a data gradient runs through: 1x1, 3x3
-constexpr bool f16_has_stats(int ks) { return ks == 1 || ks == 3; }
-
-template <int KS, int S, int PS, int CS, int WAVES_P, int WAVES_C, bool LIGHT, bool ONE_CHUNK, int STATS>
+// the kernel of variant V (a row of kF16Variants) for this kernel size, stride and statistics mode
+template <int KS, int S, int V, int STATS>
 int launch_f16_kernel(const ConvF16Params& p, size_t lds_bytes, hipStream_t s) {
     if (g_dry_launch) return MP_OK;  // mp_f16_conv_supported: the dispatch alone
-    constexpr auto kern = conv_f16_kernel<KS, S, PS, CS, WAVES_P, WAVES_C, f16_ni(KS, LIGHT), f16_nw(KS, LIGHT),
-                                          ONE_CHUNK ? 2 : f16_occ(LIGHT), ONE_CHUNK, STATS>;
+    constexpr F16Variant v = kF16Variants[V];
+    constexpr auto kern = conv_f16_kernel<KS, S, v.ps, v.cs, v.waves_p, 4 / v.waves_p, f16_ni(KS, v.light), f16_nw(KS, v.light),
+                                          v.one_chunk ? 2 : f16_occ(v.light), v.one_chunk, STATS>;
     return launch_lds<kern>(dim3(p.total_blocks, p.phases > 1 ? p.phases : 1), dim3(256), lds_bytes, s, p);
-}
-
-template <int KS, int S, int PS, int CS, int WAVES_P, int WAVES_C, bool LIGHT, bool ONE_CHUNK = false>
-int launch_f16_variant(const ConvF16Params& p, size_t lds_bytes, hipStream_t s) {
-    if (p.st_mode != 0) {
-        if constexpr (f16_has_stats(KS)) {
-            if (p.st_mode == 1) return launch_f16_kernel<KS, S, PS, CS, WAVES_P, WAVES_C, LIGHT, ONE_CHUNK, 1>(p, lds_bytes, s);
-            if constexpr (S == 1) return launch_f16_kernel<KS, S, PS, CS, WAVES_P, WAVES_C, LIGHT, ONE_CHUNK, 2>(p, lds_bytes, s);  // data gradients are stride-1 launches
-        }
-        if constexpr (KS == 2 && S == 1) {  // the phase convs of a stride-2 data gradient: backward sums only
-            if (p.st_mode == 2) return launch_f16_kernel<KS, S, PS, CS, WAVES_P, WAVES_C, LIGHT, ONE_CHUNK, 2>(p, lds_bytes, s);
-        }
-        return MP_ERR_UNSUPPORTED;
-    }
-    return launch_f16_kernel<KS, S, PS, CS, WAVES_P, WAVES_C, LIGHT, ONE_CHUNK, 0>(p, lds_bytes, s);
 }
 
 template <int KS, int S>
 int launch_f16_ks(const ConvF16Params& p, int variant, size_t lds_bytes, hipStream_t s) {
-    switch (variant) {
-        case F_CT32_PT192: return launch_f16_variant<KS, S, 3, 2, 4, 1, false>(p, lds_bytes, s);
-        case F_CT64_PT192: return launch_f16_variant<KS, S, 3, 4, 4, 1, false>(p, lds_bytes, s);
-        case F_CT48_PT192: return launch_f16_variant<KS, S, 3, 3, 4, 1, false>(p, lds_bytes, s);
-        case F_CT64_PT96: return launch_f16_variant<KS, S, 3, 2, 2, 2, false>(p, lds_bytes, s);
-        case F_CT32_PT96: return launch_f16_variant<KS, S, 3, 1, 2, 2, false>(p, lds_bytes, s);
-        case F_CT32_PT192_L: return launch_f16_variant<KS, S, 3, 2, 4, 1, true>(p, lds_bytes, s);
-        case F_CT64_PT192_L: return launch_f16_variant<KS, S, 3, 4, 4, 1, true>(p, lds_bytes, s);
-        case F_CT48_PT192_L: return launch_f16_variant<KS, S, 3, 3, 4, 1, true>(p, lds_bytes, s);
-        case F_CT64_PT96_L: return launch_f16_variant<KS, S, 3, 2, 2, 2, true>(p, lds_bytes, s);
-        case F_CT32_PT96_L: return launch_f16_variant<KS, S, 3, 1, 2, 2, true>(p, lds_bytes, s);
-        case F_CT16_PT192: return launch_f16_variant<KS, S, 3, 1, 4, 1, false>(p, lds_bytes, s);
-        case F_CT16_PT192_L: return launch_f16_variant<KS, S, 3, 1, 4, 1, true>(p, lds_bytes, s);
-        case F_CT32_PT384:
-            if (p.n_chunks != 1) return MP_ERR_UNSUPPORTED;
-            return launch_f16_variant<KS, S, 6, 2, 4, 1, false, true>(p, lds_bytes, s);
-        default: return MP_ERR_UNSUPPORTED;
-    }
+    return f16_dispatch_variant<kF16Tile>(variant, [&](auto v) {
+        if (kF16Variants[v].one_chunk && p.n_chunks != 1) return (int)MP_ERR_UNSUPPORTED;
+        return f16_dispatch_stats<KS, S>(p.st_mode, [&](auto stats) { return launch_f16_kernel<KS, S, v, stats>(p, lds_bytes, s); });
+    });
 }
 
 const int kLdsMax = 150 * 1024;
 const int kLdsBudget = 78 * 1024;  // two workgroups per CU
 
+// The LDS-operand kernels (one-tile, multi-tile) stage only the columns the taps reach - widened to the whole padded row when that
+// costs at most two columns - in units of 16 bytes: ncols per row, upc per plane.  False: no column of the input is reached.
+bool f16_geom_lds_tile(ConvF16Params& p, int KS, int S) {
+    int wp = (p.Wo - 1) * S + KS;
+    if (wp < p.pad_l + p.W && p.pad_l + p.W - wp <= 2) wp = p.pad_l + p.W;
+    f16_geom_planes(p, KS, S, wp, 0);
+    p.ncols = p.W < p.Wp - p.pad_l ? p.W : p.Wp - p.pad_l;
+    if (p.ncols < 1) return false;
+    p.upc = p.G * p.Rin * p.ncols;
+    return true;
+}
+// ... and what follows from the chosen tile: buffer sizes, tile counts, the staging and pixel magics, the staging slots in use
+void f16_geom_lds_finish(ConvF16Params& p, int T, int CT) {
+    p.in_buf = p.PK * p.plane;
+    p.w_buf = p.PK * T * CT;
+    f16_geom_tiles(p, CT);
+    p.magic_upc = magic_of(p.upc);
+    p.magic_ncols = magic_of(p.ncols);
+    p.magic_rin = magic_of(p.Rin);
+    f16_geom_pixel_magics(p);
+    p.ni_used = (p.PKs * p.upc + 255) / 256;
+}
+
 // persistent multi-tile geometry: whole K in one "chunk", weights resident, two input buffers
 bool f16_configure_mt(const mp_conv_desc& d, int variant, ConvF16Launch& L) {
-    int CT, PT;
-    f16_variant_dims(variant, CT, PT);
+    const int CT = f16_variant_ct(variant), PT = f16_variant_pt(variant);
     ConvF16Params& p = L.p;
     const int S = d.stride, KS = d.kh, T = KS * KS;
     if (!(KS == 3 || ((KS == 1 || KS == 2) && S == 1))) return false;
-    const int occ = f16_variant_mt_occ(variant);
-    p.N = d.n; p.H = d.h; p.W = d.w; p.Cout = d.cout;
-    p.C8in = (d.cin + 7) / 8;
-    p.Cout_pad16 = round_up(d.cout, 16);
-    p.C8out = (d.cout + 7) / 8;
-    p.Ho = d.conv_h; p.Wo = d.conv_w; p.pad_t = d.pad_top; p.pad_l = d.pad_left;
-    // 32-bit byte offsets over the whole tensors
-    if ((long long)d.n * p.C8in * d.h * d.w * 16 >= 0x7FFFFFF0LL || (long long)d.n * p.C8out * d.out_h * d.out_w * 16 >= 0x7FFFFFF0LL) return false;
+    const int occ = f16_variant(variant).occ;
+    f16_geom_tensors(d, p);
+    if (!f16_geom_offsets_fit(d, p)) return false;
     p.PK = round_up(d.cin, 32) / 8;
     p.PKs = p.C8in < p.PK ? p.C8in : p.PK;
     p.n_chunks = 1;
@@ -444,52 +431,18 @@ bool f16_configure_mt(const mp_conv_desc& d, int variant, ConvF16Launch& L) {
     for (int nbuf = 2; nbuf >= (occ == 1 ? 1 : 2) && !found; --nbuf)
     for (int R = rows_fit; R >= 1 && !found; --R) {
         p.nbuf = nbuf;
-        p.R = R;
-        p.G = 1;
-        if (R == p.Ho) {
-            p.G = PT / (p.Ho * p.Wo);
-            if (p.G > p.N) p.G = p.N;
-            if (p.G < 1) p.G = 1;
-        }
-        p.RWo = p.R * p.Wo;
-        p.Rin = (p.R - 1) * S + KS;
-        p.Wp = (p.Wo - 1) * S + KS;
-        if (p.Wp < p.pad_l + p.W && p.pad_l + p.W - p.Wp <= 2) p.Wp = p.pad_l + p.W;
-        p.img_plane = p.Rin * p.Wp;
-        p.plane = S == 1 ? round_up(p.G * p.img_plane, 16) : ((p.G * p.img_plane) | 1);
-        p.ncols = p.W < p.Wp - p.pad_l ? p.W : p.Wp - p.pad_l;
-        if (p.ncols < 1) return false;
-        p.upc = p.G * p.Rin * p.ncols;
+        f16_geom_fit(p, R, PT);
+        if (!f16_geom_lds_tile(p, KS, S)) return false;
         if ((long long)p.PKs * p.upc > (long long)ni * 256) continue;
         const long long bytes = ((long long)p.PK * T * CT + (long long)nbuf * p.PK * p.plane) * 16;
         if (bytes > budget) continue;
         found = true;
     }
     if (!found) return false;
-    p.in_buf = p.PK * p.plane;
-    p.w_buf = p.PK * T * CT;
-    p.n_ct = (p.Cout_pad16 + CT - 1) / CT;
-    p.tiles_y = (p.G > 1 || p.R >= p.Ho) ? 1 : (p.Ho + p.R - 1) / p.R;
-    p.tiles_n = (p.N + p.G - 1) / p.G;
-    p.tiles_total = p.tiles_y * p.tiles_n;
-    int max_groups = occ * 256 / p.n_ct;
-    if (const char* e = knob("MP_F16_MT_GROUPS")) {  // tests: force long tile runs on small problems
-        const int v = atoi(e);
-        if (v >= 1) max_groups = v;
-    }
+    f16_geom_lds_finish(p, T, CT);
+    int max_groups = f16_geom_groups(occ, p.n_ct, "MP_F16_MT_GROUPS");
     if (max_groups < 1) max_groups = 1;
-    p.tiles_per_wg = (p.tiles_total + max_groups - 1) / max_groups;
-    if (p.tiles_per_wg < 2) return false;  // nothing to amortise: the one-tile kernel does the same work with less LDS
-    p.n_groups = (p.tiles_total + p.tiles_per_wg - 1) / p.tiles_per_wg;
-    p.relu = d.relu;
-    p.out_h = d.out_h; p.out_w = d.out_w; p.out_mul = d.out_mul; p.off_y = d.out_off_y; p.off_x = d.out_off_x;
-    p.magic_upc = magic_of(p.upc);
-    p.magic_ncols = magic_of(p.ncols);
-    p.magic_rin = magic_of(p.Rin);
-    p.magic_rwo = magic_of(p.RWo);
-    p.magic_wo = magic_of(p.Wo);
-    p.total_blocks = p.n_ct * p.n_groups;
-    p.ni_used = (p.PKs * p.upc + 255) / 256;
+    if (!f16_geom_runs(p, max_groups)) return false;
     p.nw_used = 0;  // this kernel loads its weights once, outside the staging slots
     L.ks = KS; L.stride = S; L.variant = variant;
     L.lds_bytes = (size_t)(p.w_buf + p.nbuf * p.in_buf) * 16;
@@ -500,18 +453,13 @@ bool f16_configure(const mp_conv_desc& d, int variant, ConvF16Launch& L) {
     if (f16_variant_ws(variant)) return f16_configure_ws(d, variant, L);
     if (f16_variant_wreg(variant)) return f16_configure_wreg(d, variant, L);
     if (f16_variant_mt(variant)) return f16_configure_mt(d, variant, L);
-    int CT, PT;
-    f16_variant_dims(variant, CT, PT);
+    const int CT = f16_variant_ct(variant), PT = f16_variant_pt(variant);
     ConvF16Params& p = L.p;
     const int S = d.stride, KS = d.kh, T = KS * KS;
-    p.N = d.n; p.H = d.h; p.W = d.w; p.Cout = d.cout;
-    p.C8in = (d.cin + 7) / 8;
-    p.Cout_pad16 = round_up(d.cout, 16);
-    p.C8out = (d.cout + 7) / 8;
-    p.Ho = d.conv_h; p.Wo = d.conv_w; p.pad_t = d.pad_top; p.pad_l = d.pad_left;
+    f16_geom_tensors(d, p);
     const int planes_total = round_up(d.cin, 32) / 8;
     if (p.Wo > PT) return false;
-    const bool light = f16_variant_light(variant);
+    const bool light = f16_variant(variant).light;
     const int ni = f16_ni(KS, light), nw = f16_nw(KS, light);
     int rows_fit = PT / p.Wo;
     if (rows_fit > p.Ho) rows_fit = p.Ho;
@@ -520,22 +468,8 @@ bool f16_configure(const mp_conv_desc& d, int variant, ConvF16Launch& L) {
         const long long budget = pass == 0 ? (light ? 52 * 1024 : kLdsBudget) : kLdsMax;
         if (pass == 1 && light) break;  // a light build that cannot run three per CU has no point
         for (int R = rows_fit; R >= 1 && !found; --R) {
-            p.R = R;
-            p.G = 1;
-            if (R == p.Ho) {
-                p.G = PT / (p.Ho * p.Wo);
-                if (p.G > p.N) p.G = p.N;
-                if (p.G < 1) p.G = 1;
-            }
-            p.RWo = p.R * p.Wo;
-            p.Rin = (p.R - 1) * S + KS;
-            p.Wp = (p.Wo - 1) * S + KS;
-            if (p.Wp < p.pad_l + p.W && p.pad_l + p.W - p.Wp <= 2) p.Wp = p.pad_l + p.W;
-            p.img_plane = p.Rin * p.Wp;
-            p.plane = S == 1 ? round_up(p.G * p.img_plane, 16) : ((p.G * p.img_plane) | 1);
-            p.ncols = p.W < p.Wp - p.pad_l ? p.W : p.Wp - p.pad_l;
-            if (p.ncols < 1) return false;
-            p.upc = p.G * p.Rin * p.ncols;
+            f16_geom_fit(p, R, PT);
+            if (!f16_geom_lds_tile(p, KS, S)) return false;
             for (int pk = planes_total; pk >= 4; pk -= 4) {
                 if (planes_total % pk) continue;
                 const int n_chunks = planes_total / pk;
@@ -552,23 +486,11 @@ bool f16_configure(const mp_conv_desc& d, int variant, ConvF16Launch& L) {
         }
     }
     if (!found) return false;
-    if (variant == F_CT32_PT384 && p.n_chunks != 1) return false;  // single-chunk build
-    p.in_buf = p.PK * p.plane;
-    p.w_buf = p.PK * T * CT;
-    p.n_ct = (p.Cout_pad16 + CT - 1) / CT;
-    p.tiles_y = (p.G > 1 || p.R >= p.Ho) ? 1 : (p.Ho + p.R - 1) / p.R;
-    p.tiles_n = (p.N + p.G - 1) / p.G;
-    p.relu = d.relu;
-    p.out_h = d.out_h; p.out_w = d.out_w; p.out_mul = d.out_mul; p.off_y = d.out_off_y; p.off_x = d.out_off_x;
-    p.magic_upc = magic_of(p.upc);
-    p.magic_ncols = magic_of(p.ncols);
-    p.magic_rin = magic_of(p.Rin);
-    p.magic_rwo = magic_of(p.RWo);
-    p.magic_wo = magic_of(p.Wo);
+    if (f16_variant(variant).one_chunk && p.n_chunks != 1) return false;  // single-chunk build
+    f16_geom_lds_finish(p, T, CT);
     p.total_blocks = p.n_ct * p.tiles_y * p.tiles_n;
-    p.ni_used = (p.PKs * p.upc + 255) / 256;
     p.nw_used = (p.PK * T * CT + 255) / 256;
-    p.step_rows = 256 / p.ncols;
+    p.step_rows = 256 / p.ncols;  // slot-to-slot stepping of the staging table: 256 units = step_rows rows + step_cols columns
     p.step_cols = 256 % p.ncols;
     p.magic_rows = magic_of((unsigned)(p.G * p.Rin));
     L.ks = KS; L.stride = S; L.variant = variant;
@@ -823,24 +745,6 @@ int grid_for(size_t total) {
 
 }  // namespace
 
-void f16_variant_dims(int v, int& ct, int& pt) {
-    static const int cts[5] = {32, 64, 48, 64, 32};
-    static const int pts[5] = {192, 192, 192, 96, 96};
-    if (f16_variant_wreg(v) || f16_variant_ws(v)) {
-        int ps, csw, wp;
-        if (f16_variant_ws(v)) f16_ws_dims(v, ps, csw, wp);
-        else f16_wreg_dims(v, ps, csw, wp);
-        ct = 16 * csw * (4 / wp);
-        pt = 16 * ps * wp;
-        return;
-    }
-    if (v == F_CT32_PT384) { ct = 32; pt = 384; return; }
-    if (v >= F_CT16_PT192) { ct = 16; pt = 192; return; }
-    ct = cts[v % 5];
-    pt = pts[v % 5];
-}
-bool f16_variant_light(int v) { return (v >= F_CT32_PT192_L && v < F_MT2_BASE) || v == F_CT16_PT192_L; }
-
 int f16_build_launch(const mp_conv_desc* desc, int variant, const void* x, const void* w, const float* scale,
                      const float* shift, const void* res1, const void* res2, void* out, ConvF16Launch& L) {
     int rc = f16_validate(desc);
@@ -868,10 +772,8 @@ int f16_build_launch(const mp_conv_desc* desc, int variant, const void* x, const
         for (int i = 0; i < n; ++i) {
             ConvF16Launch c{};
             if (!f16_configure(*desc, order[i], c)) continue;
-            int CT, PT;
-            f16_variant_dims(order[i], CT, PT);
-            const double pix_eff = (double)(c.p.G * c.p.RWo) / PT;
-            const double co_eff = (double)desc->cout / (c.p.n_ct * CT);
+            const double pix_eff = (double)(c.p.G * c.p.RWo) / f16_variant_pt(order[i]);
+            const double co_eff = (double)desc->cout / (c.p.n_ct * f16_variant_ct(order[i]));
             const double waves = (double)c.p.total_blocks / 512.0;
             const double fill = waves >= 1.0 ? waves / (double)((long long)waves + ((waves - (long long)waves) > 1e-9 ? 1 : 0)) : waves;
             const double score = pix_eff * co_eff * fill;
@@ -1044,13 +946,12 @@ int mp_f16_conv2d_fwd_stats(const mp_conv_desc* desc, int variant, const void* x
     return f16_launch(L, as_stream(stream));
 }
 
-int mp_f16_conv_supported(const mp_conv_desc* desc, int variant, int n_res, int stats_mode) {
-    if (!desc || n_res < 0 || n_res > 2 || stats_mode < 0 || stats_mode > 2 || (stats_mode != 0 && n_res > 1)) return 0;
-    // the launch exactly as the entry points build it, on placeholder pointers (nothing is dereferenced on the host), then the
-    // family's own dispatch with the leaf launch switched off: whatever the entry would answer, by construction
-    const void* dummy = reinterpret_cast<const void*>(static_cast<uintptr_t>(16));
+// the launch exactly as the entry points build it, on placeholder pointers (nothing is dereferenced on the host), then the
+// family's own dispatch with the leaf launch switched off: whatever the entry would answer, by construction
+static const void* const kF16Dummy = reinterpret_cast<const void*>(static_cast<uintptr_t>(16));
+static int f16_dry_build(const mp_conv_desc* desc, int variant, int n_res, int stats_mode, ConvF16Launch& L, int& dry_rc) {
+    const void* dummy = kF16Dummy;
     const float* fdummy = reinterpret_cast<const float*>(dummy);
-    ConvF16Launch L{};
     int rc;
     if (stats_mode == 0) {
         rc = f16_build_launch(desc, variant, dummy, dummy, fdummy, fdummy, n_res >= 1 ? dummy : nullptr, n_res >= 2 ? dummy : nullptr,
@@ -1065,11 +966,53 @@ int mp_f16_conv_supported(const mp_conv_desc* desc, int variant, int n_res, int 
         st.y_dev = dummy;
         rc = f16_prepare_stats(desc, variant, dummy, dummy, fdummy, fdummy, n_res >= 1 ? dummy : nullptr, const_cast<void*>(dummy), &st, L);
     }
-    if (rc != MP_OK) return 0;
+    dry_rc = rc;
+    if (rc != MP_OK) return rc;
     g_dry_launch = true;
-    rc = f16_launch(L, nullptr);
+    dry_rc = f16_launch(L, nullptr);
     g_dry_launch = false;
-    return rc == MP_OK ? 1 : 0;
+    return rc;
+}
+
+static bool f16_query_args_ok(const mp_conv_desc* desc, int n_res, int stats_mode) {
+    return desc && n_res >= 0 && n_res <= 2 && stats_mode >= 0 && stats_mode <= 2 && !(stats_mode != 0 && n_res > 1);
+}
+
+int mp_f16_conv_supported(const mp_conv_desc* desc, int variant, int n_res, int stats_mode) {
+    if (!f16_query_args_ok(desc, n_res, stats_mode)) return 0;
+    ConvF16Launch L{};
+    int dry_rc;
+    return f16_dry_build(desc, variant, n_res, stats_mode, L, dry_rc) == MP_OK && dry_rc == MP_OK ? 1 : 0;
+}
+
+int mp_f16_conv_launch_words(const mp_conv_desc* desc, int variant, int n_res, int stats_mode, int64_t* out, int cap) {
+    if (!out) return MP_ERR_NULL;
+    if (!f16_query_args_ok(desc, n_res, stats_mode)) return MP_ERR_SHAPE;
+    ConvF16Launch L{};
+    int dry_rc;
+    const int rc = f16_dry_build(desc, variant, n_res, stats_mode, L, dry_rc);
+    const ConvF16Params& p = L.p;
+    const int64_t head[2] = {rc, dry_rc};
+    const int64_t body[] = {
+        L.ks, L.stride, L.variant, (int64_t)L.lds_bytes,
+        // scalar fields in declaration order
+        p.N, p.C8in, p.H, p.W, p.Cout, p.Cout_pad16, p.C8out, p.Ho, p.Wo, p.pad_t, p.pad_l, p.R, p.G, p.Rin, p.Wp, p.img_plane, p.plane,
+        p.PK, p.PKs, p.n_chunks, p.n_ct, p.tiles_y, p.tiles_n, p.ncols, p.upc, p.in_buf, p.w_buf, p.nbuf, p.relu, p.out_h, p.out_w,
+        p.out_mul, p.off_y, p.off_x, p.magic_upc, p.magic_ncols, p.magic_rin, p.magic_rwo, p.magic_wo, p.RWo, p.total_blocks, p.phases,
+        p.w_phase_bytes, p.tiles_total, p.tiles_per_wg, p.n_groups, p.ni_used, p.nw_used, p.magic_rows, p.step_rows, p.step_cols,
+        p.st_mode, p.st_nparts, p.st_relu, p.pre_relu,
+        // pointer fields: null / set
+        p.x != nullptr, p.wp != nullptr, p.scale != nullptr, p.shift != nullptr, p.res1 != nullptr, p.res2 != nullptr, p.out != nullptr,
+        p.st_part != nullptr, p.st_z != nullptr, p.st_y != nullptr, p.pre_scale != nullptr, p.pre_shift != nullptr, p.pre_out != nullptr,
+        // the partial-sum slot offset of a single-phase launch, in bytes
+        p.st_part ? (int64_t)(reinterpret_cast<const char*>(p.st_part) - reinterpret_cast<const char*>(kF16Dummy)) : 0};
+    // a refused build leaves the record half configured: only the two return codes are its answer
+    const int n_body = rc == MP_OK ? (int)(sizeof(body) / sizeof(body[0])) : 0;
+    if (cap < 2 + n_body) return MP_ERR_WORKSPACE;
+    out[0] = head[0];
+    out[1] = head[1];
+    for (int i = 0; i < n_body; ++i) out[2 + i] = body[i];
+    return 2 + n_body;
 }
 
 int mp_f16_fuse_upsample_sum(const void* base, const void* t1, int s1, const void* t2, int s2, const void* t3, int s3, void* out,

@@ -1,4 +1,7 @@
-// Device-side helpers shared by the fp16 convolution kernels (conv_f16.hip, conv_f16_mt.hip).
+// Device-side helpers shared by the fp16 convolution kernels - one-tile (conv_f16.hip), multi-tile (conv_f16_mt.hip), weights in
+// registers (conv_f16_wreg.hip), weight-stationary (conv_f16_ws.hip) - and by the other fp16 kernels built on the same accumulator
+// layout (fused BasicBlock, 1x1 chain, stem, weight gradient): vector types, the cout-tile pairing, the epilogue arithmetic of one
+// pixel and the BatchNorm statistics of the epilogue.
 #pragma once
 #include "common.h"
 

@@ -319,46 +319,20 @@ __global__ __launch_bounds__(256, OCC) void conv_f16_mt_kernel(const ConvF16Para
 
 constexpr int mt_ni(int occ) { return occ == 1 ? 12 : 8; }
 
-template <int KS, int S, int PS, int CS, int WAVES_P, int WAVES_C, int OCC, int STATS>
+// the kernel of variant V (a row of kF16Variants) for this kernel size, stride and statistics mode
+template <int KS, int S, int V, int STATS>
 int launch_mt_kernel(const ConvF16Params& p, size_t lds_bytes, hipStream_t s) {
     if (g_dry_launch) return MP_OK;  // mp_f16_conv_supported: the dispatch alone
-    constexpr auto kern = conv_f16_mt_kernel<KS, S, PS, CS, WAVES_P, WAVES_C, mt_ni(OCC), OCC, STATS>;
+    constexpr F16Variant v = kF16Variants[V];
+    constexpr auto kern = conv_f16_mt_kernel<KS, S, v.ps, v.cs, v.waves_p, 4 / v.waves_p, mt_ni(v.occ), v.occ, STATS>;
     return launch_lds<kern>(dim3(p.total_blocks, p.phases > 1 ? p.phases : 1), dim3(256), lds_bytes, s, p);
-}
-
-template <int KS, int S, int PS, int CS, int WAVES_P, int WAVES_C, int OCC>
-int launch_mt_variant(const ConvF16Params& p, size_t lds_bytes, hipStream_t s) {
-    if (p.st_mode != 0) {  // training builds with epilogue statistics: the kernel sizes a BatchNorm follows
-        if constexpr (KS == 1 || KS == 3) {
-            if (p.st_mode == 1) return launch_mt_kernel<KS, S, PS, CS, WAVES_P, WAVES_C, OCC, 1>(p, lds_bytes, s);
-            if constexpr (S == 1) return launch_mt_kernel<KS, S, PS, CS, WAVES_P, WAVES_C, OCC, 2>(p, lds_bytes, s);
-        }
-        if constexpr (KS == 2 && S == 1) {  // the phase convs of a stride-2 data gradient: backward sums only
-            if (p.st_mode == 2) return launch_mt_kernel<KS, S, PS, CS, WAVES_P, WAVES_C, OCC, 2>(p, lds_bytes, s);
-        }
-        return MP_ERR_UNSUPPORTED;
-    }
-    return launch_mt_kernel<KS, S, PS, CS, WAVES_P, WAVES_C, OCC, 0>(p, lds_bytes, s);
-}
-
-template <int KS, int S, int OCC>
-int launch_mt_shape(const ConvF16Params& p, int shape, size_t lds_bytes, hipStream_t s) {
-    switch (shape) {
-        case F_CT32_PT192: return launch_mt_variant<KS, S, 3, 2, 4, 1, OCC>(p, lds_bytes, s);
-        case F_CT64_PT192: return launch_mt_variant<KS, S, 3, 4, 4, 1, OCC>(p, lds_bytes, s);
-        case F_CT48_PT192: return launch_mt_variant<KS, S, 3, 3, 4, 1, OCC>(p, lds_bytes, s);
-        case F_CT64_PT96: return launch_mt_variant<KS, S, 3, 2, 2, 2, OCC>(p, lds_bytes, s);
-        case F_CT32_PT96: return launch_mt_variant<KS, S, 3, 1, 2, 2, OCC>(p, lds_bytes, s);
-        case 5: return launch_mt_variant<KS, S, 3, 1, 4, 1, OCC>(p, lds_bytes, s);  // 16 couts x 192 pixels
-        default: return MP_ERR_UNSUPPORTED;
-    }
 }
 
 template <int KS, int S>
 int launch_mt_ks(const ConvF16Params& p, int variant, size_t lds_bytes, hipStream_t s) {
-    const int shape = variant >= F_CT16_PT192_MT2 ? 5 : (variant - F_MT2_BASE) % 5;
-    return f16_variant_mt_occ(variant) == 1 ? launch_mt_shape<KS, S, 1>(p, shape, lds_bytes, s)
-                                            : launch_mt_shape<KS, S, 2>(p, shape, lds_bytes, s);
+    return f16_dispatch_variant<kF16Mt>(variant, [&](auto v) {
+        return f16_dispatch_stats<KS, S>(p.st_mode, [&](auto stats) { return launch_mt_kernel<KS, S, v, stats>(p, lds_bytes, s); });
+    });
 }
 
 }  // namespace

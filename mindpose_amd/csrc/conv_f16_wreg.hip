@@ -411,61 +411,28 @@ int launch_wreg(const ConvF16Params& p, size_t lds_bytes, hipStream_t s) {
 
 template <int KS, int S>
 int launch_wreg_ks(const ConvF16Params& p, int variant, size_t lds_bytes, hipStream_t s) {
-    switch (variant) {
-        case F_WREG_P6C2: return launch_wreg<KS, S, 6, 2, 1, 1>(p, lds_bytes, s);
-        case F_WREG_P3C2: return launch_wreg<KS, S, 3, 2, 1, 2>(p, lds_bytes, s);
-        case F_WREG_P6C1: return launch_wreg<KS, S, 6, 1, 1, 2>(p, lds_bytes, s);
-        case F_WREG_P6C3: return launch_wreg<KS, S, 6, 3, 1, 1>(p, lds_bytes, s);
-        case F_WREG_P3C3: return launch_wreg<KS, S, 3, 3, 1, 1>(p, lds_bytes, s);
-        case F_WREG_P3C4: return launch_wreg<KS, S, 3, 4, 1, 1>(p, lds_bytes, s);
-        case F_WREG_P6C2_W2: return launch_wreg<KS, S, 6, 2, 2, 2>(p, lds_bytes, s);
-        case F_WREG_P6C3_W2: return launch_wreg<KS, S, 6, 3, 2, 1>(p, lds_bytes, s);
-        case F_WREG_P3C2_W2: return launch_wreg<KS, S, 3, 2, 2, 2>(p, lds_bytes, s);
-        case F_WREG_P6C2_W4: return launch_wreg<KS, S, 6, 2, 4, 2>(p, lds_bytes, s);
-        case F_WREG_P6C3_W4: return launch_wreg<KS, S, 6, 3, 4, 1>(p, lds_bytes, s);
-        case F_WREG_P3C2_W4: return launch_wreg<KS, S, 3, 2, 4, 2>(p, lds_bytes, s);
-        case F_WREG_P7C3:
-            if constexpr (KS == 3 && S == 1) return launch_wreg<KS, S, 7, 3, 1, 1>(p, lds_bytes, s);
-            return MP_ERR_UNSUPPORTED;
-        case F_WREG_P4C3:
-            if constexpr (KS == 3 && S == 1) return launch_wreg<KS, S, 4, 3, 1, 1>(p, lds_bytes, s);
-            return MP_ERR_UNSUPPORTED;
-        case F_WREG_P5C4:
-            if constexpr (KS == 3 && S == 1) return launch_wreg<KS, S, 5, 4, 1, 1>(p, lds_bytes, s);
-            return MP_ERR_UNSUPPORTED;
-        default: return MP_ERR_UNSUPPORTED;
-    }
+    return f16_dispatch_variant<kF16Wreg>(variant, [&](auto id) {
+        constexpr F16Variant v = kF16Variants[id];
+        if constexpr (v.k3s1_only && !(KS == 3 && S == 1)) return (int)MP_ERR_UNSUPPORTED;
+        else return launch_wreg<KS, S, v.ps, v.cs, v.waves_p, v.occ>(p, lds_bytes, s);
+    });
 }
 
 }  // namespace
 
-void f16_wreg_dims(int v, int& ps, int& csw, int& waves_p) {
-    static const int pss[15] = {6, 3, 6, 6, 3, 3, 6, 6, 3, 6, 6, 3, 7, 4, 5};
-    static const int css[15] = {2, 2, 1, 3, 3, 4, 2, 3, 2, 2, 3, 2, 3, 3, 4};
-    static const int wps[15] = {1, 1, 1, 1, 1, 1, 2, 2, 2, 4, 4, 4, 1, 1, 1};
-    ps = pss[f16_wreg_index(v)];
-    csw = css[f16_wreg_index(v)];
-    waves_p = wps[f16_wreg_index(v)];
-}
-
 // geometry: 3x3 pad 1 (stride 1 or 2) and 1x1 pad 0 convolutions whose output rows tile the pixel tile
 bool f16_configure_wreg(const mp_conv_desc& d, int variant, ConvF16Launch& L) {
-    int PS, CSW, WP;
-    f16_wreg_dims(variant, PS, CSW, WP);
-    const int KS = d.kh, S = d.stride, halo = KS / 2, T = KS * KS;
+    const F16Variant& v = f16_variant(variant);
+    const int CSW = v.cs, WP = v.waves_p;
+    const int KS = d.kh, S = d.stride, halo = KS / 2;
     if (!((KS == 3 && (S == 1 || S == 2)) || (KS == 1 && S == 1))) return false;
-    if (variant >= F_WREG_P7C3 && !(KS == 3 && S == 1)) return false;  // the round-4 shapes are built for the 3x3 stride-1 branch convs
+    if (v.k3s1_only && !(KS == 3 && S == 1)) return false;
     if (d.pad_top != halo || d.pad_left != halo) return false;
     if (d.conv_h != (d.h + 2 * halo - KS) / S + 1 || d.conv_w != (d.w + 2 * halo - KS) / S + 1) return false;
     ConvF16Params& p = L.p;
-    const int WC = 4 / WP;
-    const int PT = 16 * PS * WP, CT = 16 * CSW * WC;
-    p.N = d.n; p.H = d.h; p.W = d.w; p.Cout = d.cout;
-    p.C8in = (d.cin + 7) / 8;
-    p.Cout_pad16 = round_up(d.cout, 16);
-    p.C8out = (d.cout + 7) / 8;
-    p.Ho = d.conv_h; p.Wo = d.conv_w; p.pad_t = halo; p.pad_l = halo;
-    if ((long long)d.n * p.C8in * d.h * d.w * 16 >= 0x7FFFFFF0LL || (long long)d.n * p.C8out * d.out_h * d.out_w * 16 >= 0x60000000LL) return false;
+    const int WC = 4 / WP, PT = f16_variant_pt(variant), CT = f16_variant_ct(variant);
+    f16_geom_tensors(d, p);
+    if (!f16_geom_offsets_fit(d, p)) return false;
     p.PK = round_up(d.cin, 32) / 8;
     p.PKs = p.C8in < p.PK ? p.C8in : p.PK;
     p.n_chunks = 1;
@@ -474,48 +441,26 @@ bool f16_configure_wreg(const mp_conv_desc& d, int variant, ConvF16Launch& L) {
     // weight stream (the small-K layers are HBM-bound: pixel-split shapes or the tile kernels)
     if ((p.Cout_pad16 / 16) % (WC * CSW) != 0) return false;
     if (WP == 1 && d.cin < 64) return false;
-    int R = PT / p.Wo;
-    if (R > p.Ho) R = p.Ho;
-    p.R = R;
-    p.G = 1;
-    if (R == p.Ho) {
-        p.G = PT / (p.Ho * p.Wo);
-        if (p.G > p.N) p.G = p.N;
-        if (p.G < 1) p.G = 1;
-    }
-    p.RWo = p.R * p.Wo;
+    f16_geom_fit(p, PT / p.Wo < p.Ho ? PT / p.Wo : p.Ho, PT);
     if (p.G * p.RWo * 10 < PT * 7) return false;  // more than 30 % padding lanes: another tile shape fits better
-    p.Rin = (p.R - 1) * S + KS;
-    p.Wp = p.W + halo;  // row pitch: one shared zero column
-    p.img_plane = p.Rin * p.Wp;
-    // plane stride: == 0 (mod 16) for stride 1, odd for stride 2 (lanes then read every other element): conflict-free ds_read_b128
-    p.plane = S == 1 ? round_up(p.G * p.img_plane + halo, 16) : ((p.G * p.img_plane + halo) | 1);
+    f16_geom_planes(p, KS, S, p.W + halo, halo);  // row pitch: one shared zero column
     p.ncols = p.W;
     p.upc = 0;
-    if (S == 1 && p.G == 1 && round_up(p.img_plane + halo, 64) / 64 <= 8 && !knob("MP_F16_WREG_SLOW_DMA")) {
-        // fast staging form: plane pitch a multiple of 64 elements, upc = DMA pieces per plane
-        p.plane = round_up(p.img_plane + halo, 64);
-        p.upc = p.plane / 64;
-    }
+    // fast staging form: at most kWregMaxPieces DMA pieces per plane, decoded once for all planes
+    if (S == 1 && p.G == 1 && round_up(p.img_plane + halo, 64) / 64 <= 8 && !knob("MP_F16_WREG_SLOW_DMA")) f16_geom_dma_pieces(p, halo);
     p.in_buf = p.PK * p.plane;
     p.w_buf = 0;
     p.nbuf = 1;
-    p.n_ct = (p.Cout_pad16 + CT - 1) / CT;
-    p.tiles_y = (p.G > 1 || p.R >= p.Ho) ? 1 : (p.Ho + p.R - 1) / p.R;
-    p.tiles_n = (p.N + p.G - 1) / p.G;
+    f16_geom_tiles(p, CT);
     p.tiles_total = p.tiles_y * p.tiles_n;
-    p.relu = d.relu;
-    p.out_h = d.out_h; p.out_w = d.out_w; p.out_mul = d.out_mul; p.off_y = d.out_off_y; p.off_x = d.out_off_x;
     p.magic_upc = magic_of(p.plane);       // slot -> plane
     p.magic_rin = magic_of(p.img_plane);   // slot -> image
     p.magic_ncols = magic_of(p.Wp);        // slot -> row
-    p.magic_rwo = magic_of(p.RWo);
-    p.magic_wo = magic_of(p.Wo);
+    f16_geom_pixel_magics(p);
     p.total_blocks = p.n_ct * p.tiles_y * p.tiles_n;
     p.ni_used = p.nw_used = 0;
     L.ks = KS; L.stride = S; L.variant = variant;
     L.lds_bytes = ((size_t)p.in_buf + 64) * 16;  // + one DMA piece of slack: the last piece may run past an odd-sized image
-    (void)T;
     return L.lds_bytes <= (size_t)150 * 1024;
 }
 

@@ -566,53 +566,24 @@ int launch_ws(const ConvF16Params& p, size_t lds_bytes, hipStream_t s) {
     return res ? launch_ws_kernel<NQ, CSW, WAVES_P, PS, OCC, 0, true>(p, lds_bytes, s) : launch_ws_kernel<NQ, CSW, WAVES_P, PS, OCC, 0, false>(p, lds_bytes, s);
 }
 
-struct WsShape { int nq, csw, waves_p, ps, occ; };
-// F_WS_BASE + i.  nq = k-steps of 32 input channels (Cin in (32 (nq - 1), 32 nq]); a workgroup = 16 csw (4 / waves_p) couts x
-// 16 ps waves_p pixels
-constexpr WsShape kWsShapes[F_WS_COUNT] = {
-    {1, 2, 4, 3, 2},  // 32 channels: 32 couts x 192 px (training convs of the 32-channel branch; inference runs them as fused blocks)
-    {2, 3, 4, 5, 1},  // 48 (W48 branch 1): 48 couts x 320 px
-    {2, 4, 4, 3, 1},  // 64: 64 couts x 192 px
-    {2, 2, 4, 3, 1},  // 64: two cout slices of 32 x 192 px
-    {3, 2, 4, 5, 1},  // 96 (W48 branch 2): three cout slices of 32 x 320 px
-    {3, 3, 4, 3, 1},  // 96: two cout slices of 48 x 192 px
-    {4, 2, 2, 3, 1},  // 128: two cout slices of 64 x 96 px
-    {4, 2, 1, 6, 1},  // 128: 128 couts x 96 px
-};
-
 }  // namespace
-
-void f16_ws_dims(int v, int& ps, int& csw, int& waves_p) {
-    const WsShape& s = kWsShapes[v - F_WS_BASE];
-    ps = s.ps; csw = s.csw; waves_p = s.waves_p;
-}
 
 // geometry: 3x3 stride-1 pad-1 convolutions with a plain output mapping whose rows tile the pixel tile
 bool f16_configure_ws(const mp_conv_desc& d, int variant, ConvF16Launch& L) {
-    const WsShape& sh = kWsShapes[variant - F_WS_BASE];
+    const F16Variant& sh = f16_variant(variant);
     if (d.kh != 3 || d.kw != 3 || d.stride != 1 || d.pad_top != 1 || d.pad_left != 1) return false;
     if (d.conv_h != d.h || d.conv_w != d.w || d.out_h != d.h || d.out_w != d.w || d.out_mul != 1 || d.out_off_y != 0 || d.out_off_x != 0) return false;
     if (d.cin <= 32 * (sh.nq - 1) || d.cin > 32 * sh.nq) return false;
     ConvF16Params& p = L.p;
-    const int WC = 4 / sh.waves_p;
-    const int PT = 16 * sh.ps * sh.waves_p, CT = 16 * sh.csw * WC;
-    p.N = d.n; p.H = d.h; p.W = d.w; p.Cout = d.cout;
-    p.C8in = (d.cin + 7) / 8;
-    p.Cout_pad16 = round_up(d.cout, 16);
-    p.C8out = (d.cout + 7) / 8;
-    p.Ho = d.h; p.Wo = d.w; p.pad_t = 1; p.pad_l = 1;
-    if ((long long)d.n * p.C8in * d.h * d.w * 16 >= 0x7FFFFFF0LL || (long long)d.n * p.C8out * d.h * d.w * 16 >= 0x60000000LL) return false;
+    const int PT = f16_variant_pt(variant), CT = f16_variant_ct(variant);
+    f16_geom_tensors(d, p);
+    if (!f16_geom_offsets_fit(d, p)) return false;
     if (p.Cout_pad16 % CT != 0) return false;  // every wave of every workgroup owns CSW real cout tiles
     p.PK = sh.nq * 4;
     p.PKs = p.C8in;
     p.n_chunks = 1;
     if (p.W > PT) return false;
-    p.n_ct = p.Cout_pad16 / CT;
-    int groups = sh.occ * 256 / p.n_ct;  // workgroups per cout slice, all resident at once
-    if (const char* e = knob("MP_F16_WS_GROUPS")) {  // tests: force long tile runs on small problems
-        const int v = atoi(e);
-        if (v >= 1) groups = v;
-    }
+    const int groups = f16_geom_groups(sh.occ, p.Cout_pad16 / CT, "MP_F16_WS_GROUPS");  // workgroups per cout slice
     if (groups < 1) return false;
     const int r_max = PT / p.W < p.H ? PT / p.W : p.H;
     // rows per tile: the fewest tiles per workgroup win (every tile costs the same MFMA time, padding lanes included), then the taller
@@ -627,28 +598,17 @@ bool f16_configure_ws(const mp_conv_desc& d, int variant, ConvF16Launch& L) {
         if (best_r == 0 || tpw < best_tpw) { best_r = R; best_tpw = tpw; }
     }
     if (best_r == 0) return false;
-    p.R = best_r;
+    p.R = best_r;  // one image per tile, whatever the tile would hold
     p.G = 1;
     p.RWo = p.R * p.W;
-    p.Rin = p.R + 2;
-    p.Wp = p.W + 1;
-    p.img_plane = p.Rin * p.Wp;
-    p.plane = round_up(p.img_plane + 1, 64);
-    p.upc = p.plane / 64;  // DMA pieces per plane
+    f16_geom_planes(p, 3, 1, p.W + 1, 1);
+    f16_geom_dma_pieces(p, 1);
     p.ncols = p.W;
     p.in_buf = p.PK * p.plane;
     p.w_buf = 0;
     p.nbuf = 2;
-    p.tiles_y = (p.H + p.R - 1) / p.R;
-    p.tiles_n = p.N;
-    p.tiles_total = p.tiles_y * p.N;
-    p.tiles_per_wg = (p.tiles_total + groups - 1) / groups;
-    // a run of ONE tile amortises nothing (the weight fragments would be fetched per tile, as the one-tile kernels do with less LDS)
-    if (p.tiles_per_wg < 2) return false;
-    p.n_groups = (p.tiles_total + p.tiles_per_wg - 1) / p.tiles_per_wg;
-    p.total_blocks = p.n_ct * p.n_groups;
-    p.relu = d.relu;
-    p.out_h = d.out_h; p.out_w = d.out_w; p.out_mul = 1; p.off_y = 0; p.off_x = 0;
+    f16_geom_tiles(p, CT);
+    if (!f16_geom_runs(p, groups)) return false;
     p.magic_ncols = magic_of((unsigned)p.Wp);      // slot -> row
     p.magic_wo = magic_of((unsigned)p.W);          // pixel -> row
     p.magic_rows = magic_of((unsigned)p.tiles_y);  // tile -> image
@@ -660,17 +620,10 @@ bool f16_configure_ws(const mp_conv_desc& d, int variant, ConvF16Launch& L) {
 }
 
 int f16_ws_launch(const ConvF16Launch& L, hipStream_t s) {
-    switch (L.variant - F_WS_BASE) {
-        case 0: return launch_ws<1, 2, 4, 3, 2>(L.p, L.lds_bytes, s);
-        case 1: return launch_ws<2, 3, 4, 5, 1>(L.p, L.lds_bytes, s);
-        case 2: return launch_ws<2, 4, 4, 3, 1>(L.p, L.lds_bytes, s);
-        case 3: return launch_ws<2, 2, 4, 3, 1>(L.p, L.lds_bytes, s);
-        case 4: return launch_ws<3, 2, 4, 5, 1>(L.p, L.lds_bytes, s);
-        case 5: return launch_ws<3, 3, 4, 3, 1>(L.p, L.lds_bytes, s);
-        case 6: return launch_ws<4, 2, 2, 3, 1>(L.p, L.lds_bytes, s);
-        case 7: return launch_ws<4, 2, 1, 6, 1>(L.p, L.lds_bytes, s);
-        default: return MP_ERR_UNSUPPORTED;
-    }
+    return f16_dispatch_variant<kF16Ws>(L.variant, [&](auto id) {
+        constexpr F16Variant v = kF16Variants[id];
+        return launch_ws<v.nq, v.cs, v.waves_p, v.ps, v.occ>(L.p, L.lds_bytes, s);
+    });
 }
 
 }  // namespace mp
