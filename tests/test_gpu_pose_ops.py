@@ -212,12 +212,16 @@ def test_dark_refine_intermediates_vs_oracle(case):
     of log(clip(blur(h))), the gradient and the Hessian entries of the kernel (mp_decode_topdown_debug: same kernel, extra output)
     against the oracle at 1e-5; the final 2x2 solve is checked as a solve (residual of (H + 1e-7 I) delta = g on the kernel's own
     terms), which holds however ill-conditioned H is - so a wrong tap, pad rule or clip bound cannot hide behind conditioning."""
-    import ctypes
     name, kind, shape, seed, kw = case
     hm, center, scale, score = decoder_inputs(kind, shape, seed)
-    n, k, h, w = shape
+    check_dark_intermediates(hm, center, scale, score, _dec(kw))
+
+
+def check_dark_intermediates(hm, center, scale, score, dec):
+    """The body of test_dark_refine_intermediates_vs_oracle for one batch of maps and a DARK decoder (tests/test_gpu_pose_edges.py runs
+    it on its designed maps too).  Returns the refined coordinates in heat-map pixels, [N,K,3] on the host."""
+    n, k, h, w = hm.shape
     lib = mp._lib.load()
-    dec = _dec(kw)
     thm, tc, ts, tsc = _cuda(hm, center, scale, score)
     preds = torch.empty(n, k, 3, device=DEV)
     boxes = torch.empty(n, 6, device=DEV)
@@ -261,6 +265,7 @@ def test_dark_refine_intermediates_vs_oracle(case):
                                         boxes.data_ptr(), idx.data_ptr(), n, k, h, w, mp._lib.MP_REFINE_DARK, int(dec.use_udp), 0,
                                         float(dec.pixel_std), blur.data_ptr(), int(dec.kernel_size), mp._lib.stream()), "decode")
     assert torch.equal(preds2.nan_to_num(123.0), preds.nan_to_num(123.0))
+    return preds.cpu().numpy()
 
 
 @pytest.mark.parametrize("shape", [(3, 3, 256, 192), (2, 3, 17, 13), (1, 5, 8, 4)])
