@@ -102,6 +102,7 @@ int mp_gaussian_target(const float* keypoints_dev, const float* patch_dev, int p
  *   L = mean_{n,k,h,w}( w[n,k] * (pred-target)^2 ) ; weight_dev NULL -> use_target_weight=False.
  * Deterministic two-stage fp32/fp64 reduction; workspace >= mp_joints_mse_workspace_bytes(n,k).
  * bwd: grad_pred = grad_out * 2 * w * (pred-target) / (N*K*H*W); grad_out_dev NULL means 1.0.
+ * 16-byte accesses when HW % 4 == 0 and every base the launch touches is 16-byte aligned, 4-byte ones otherwise (joints_loss.hip).
  * ------------------------------------------------------------------------------------------ */
 size_t mp_joints_mse_workspace_bytes(int n, int k);
 int mp_joints_mse_fwd(const float* pred_dev, const float* target_dev, const float* weight_dev, float* loss_dev,
@@ -110,7 +111,7 @@ int mp_joints_mse_bwd(const float* pred_dev, const float* target_dev, const floa
                       const float* grad_out_dev, float* grad_pred_dev, int n, int k, int hw, mp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
- * Loss: joint MSE with online hard keypoint mining (ohkm_loss.hip); the reference has no counterpart.
+ * Loss: joint MSE with online hard keypoint mining (joints_loss.hip); the reference has no counterpart.
  * pred, target: contiguous fp32 [N][K][HW]; weight_dev [N][K] or NULL (= 1); 1 <= topk <= K <= 1024.
  *   S[n,k]   = sum_i ((pred_i - target_i)^2 * w[n,k]), fp32, the arithmetic of mp_joints_mse_fwd's row pass: a function of the
  *              row's values and weight only (bit-identical rows give bit-identical sums).

@@ -87,7 +87,7 @@ _PROTOTYPES = {
     "mp_joints_mse_workspace_bytes": (c_size_t, [c_int, c_int]),
     "mp_joints_mse_fwd": (c_int, [c_f32p] * 5 + [c_size_t] + [c_int] * 3 + [ctypes.c_void_p]),
     "mp_joints_mse_bwd": (c_int, [c_f32p] * 5 + [c_int] * 3 + [ctypes.c_void_p]),
-    # joint MSE with online hard keypoint mining (ohkm_loss.hip): pred, target, weight, loss, row_sum, sel, workspace, bytes, n, k,
+    # joint MSE with online hard keypoint mining (joints_loss.hip): pred, target, weight, loss, row_sum, sel, workspace, bytes, n, k,
     # hw, topk, stream / pred, target, weight, sel, grad_out, grad_pred, n, k, hw, topk, stream
     "mp_joints_ohkm_workspace_bytes": (c_size_t, [c_int, c_int]),
     "mp_joints_ohkm_fwd": (c_int, [c_f32p] * 7 + [c_size_t] + [c_int] * 4 + [ctypes.c_void_p]),

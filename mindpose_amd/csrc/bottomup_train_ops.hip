@@ -3,30 +3,10 @@
 // mindpose/models/loss/ae.py:40-89 (AELoss), mindpose/data/transform/bottomup_transform.py:527-598 (BottomUpGenerateTarget).
 // Plain HIP C++: no inline assembly, no atomics; every reduction has a fixed order, so two runs are bit-identical.
 #include "common.h"
+#include "reduce.h"
 
 namespace mp {
 namespace {
-
-__device__ __forceinline__ float wave_sum_f(float v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// sum of one double per thread over a 256-thread block, the same value in every thread (fixed order)
-__device__ __forceinline__ double block_sum_d(double v, double* sm4) {
-    v = wave_sum_d(v);
-    __syncthreads();  // sm4 may still be read from an earlier call
-    if ((threadIdx.x & 63) == 0) sm4[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (sm4[0] + sm4[1]) + (sm4[2] + sm4[3]);
-}
 
 // ------------------------------------------------------------------------------------------
 // JointsMSELossWithMask: L = sum((pred - target)^2 * mask[n,h,w]) / (N K H W).  The operands are views (the first K channels of
@@ -82,11 +62,9 @@ __global__ __launch_bounds__(256) void mse_mask_fwd_kernel(MseMaskParams p) {
             acc += (d * d) * (float)mk[y * p.ms_r + x];
         }
     }
-    acc = wave_sum_f(acc);
     __shared__ float ws[4];
-    if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) p.out[row] = (ws[0] + ws[1]) + (ws[2] + ws[3]);
+    acc = block_sum_lane0(wave_sum(acc), ws);
+    if (threadIdx.x == 0) p.out[row] = acc;
 }
 
 __global__ __launch_bounds__(256) void mse_mask_final_kernel(const float* __restrict__ partial, float* __restrict__ loss, int rows,
@@ -94,7 +72,7 @@ __global__ __launch_bounds__(256) void mse_mask_final_kernel(const float* __rest
     double acc = 0.0;
     for (int i = threadIdx.x; i < rows; i += blockDim.x) acc += (double)partial[i];
     __shared__ double sm4[4];
-    acc = block_sum_d(acc, sm4);
+    acc = block_sum_all(acc, sm4);
     if (threadIdx.x == 0) loss[0] = (float)(acc * inv_count);
 }
 
@@ -164,8 +142,8 @@ __device__ void ae_person_stats(const float* __restrict__ tags, const int32_t* _
             if (f != 0.f) s += (double)tags[(size_t)j * hw + idx];
             kn += (double)f;
         }
-        s = wave_sum_d(s);
-        kn = wave_sum_d(kn);
+        s = wave_sum(s);
+        kn = wave_sum(kn);
         const double h = s / (kn + kAeEps);
         double d1 = 0.0, d2 = 0.0;
         for (int j = lane; j < k; j += 64) {
@@ -178,8 +156,8 @@ __device__ void ae_person_stats(const float* __restrict__ tags, const int32_t* _
                 d2 += d * d;
             }
         }
-        d1 = wave_sum_d(d1);
-        d2 = wave_sum_d(d2);
+        d1 = wave_sum(d1);
+        d2 = wave_sum(d2);
         if (lane == 0) {
             sh.h[p] = h;
             sh.kn[p] = kn;
@@ -208,9 +186,9 @@ __global__ __launch_bounds__(256) void ae_fwd_kernel(const float* __restrict__ t
             push += exp(-(d * d));
         }
     }
-    mc = block_sum_d(mc, sh.red);
-    pull = block_sum_d(pull, sh.red);
-    push = block_sum_d(push, sh.red);
+    mc = block_sum_all(mc, sh.red);
+    pull = block_sum_all(pull, sh.red);
+    push = block_sum_all(push, sh.red);
     if (threadIdx.x == 0) {
         partial[2 * n + 0] = 0.5 * (push - mc) / (mc * (mc - 1.0) + kAeEps);
         partial[2 * n + 1] = pull / (mc + kAeEps);
@@ -224,8 +202,8 @@ __global__ __launch_bounds__(256) void ae_final_kernel(const double* __restrict_
         push += partial[2 * i + 0];
         pull += partial[2 * i + 1];
     }
-    push = block_sum_d(push, red);
-    pull = block_sum_d(pull, red);
+    push = block_sum_all(push, red);
+    pull = block_sum_all(pull, red);
     if (threadIdx.x == 0) {
         out[0] = (float)(push / (double)n);
         out[1] = (float)(pull / (double)n);
@@ -258,7 +236,7 @@ __global__ __launch_bounds__(256) void ae_bwd_kernel(const float* __restrict__ t
     ae_person_stats(t_img, i_img, m, k, hw, sh);
     double mc = 0.0;
     for (int p = threadIdx.x; p < m; p += blockDim.x) mc += sh.kn[p] > 0.0 ? 1.0 : 0.0;
-    mc = block_sum_d(mc, sh.red);
+    mc = block_sum_all(mc, sh.red);
     const double inv_n = 1.0 / (double)n_img;
     const double c_push = (double)gout[0] * inv_n * 0.5 / (mc * (mc - 1.0) + kAeEps);
     const double c_pull = (double)gout[1] * inv_n / (mc + kAeEps);

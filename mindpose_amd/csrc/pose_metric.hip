@@ -12,6 +12,7 @@
 //
 // fp contraction is OFF in this file: the per-step mean and the running sums are compared bit for bit with a float64 restatement.
 #include "common.h"
+#include "reduce.h"
 
 #include <math.h>
 
@@ -25,14 +26,6 @@ constexpr int kPckGridCap = 256 * 16;    // launch 1's grid; more pairs than thi
 constexpr int kPckBatch = 4;             // 16-byte loads per map requested before the first is looked at
 constexpr int kPckUpdateThreads = 1024;  // launch 2: sixteen waves, one joint each at a time (17 joints: two dependent rounds of loads)
 constexpr int kPckJointChunk = 256;      // launch 2: joints reduced per pass
-
-// the idiom of pose_ops.hip: larger value wins, the smaller index among equals
-__device__ __forceinline__ void argmax_combine(float& best, int& bidx, float ov, int oi) {
-    if (ov > best || (ov == best && oi < bidx)) {
-        best = ov;
-        bidx = oi;
-    }
-}
 
 // per-thread running arg-max; the indices a thread sees ascend, so a strict comparison keeps the first of equal values
 struct ArgMax {
@@ -112,12 +105,7 @@ __global__ __launch_bounds__(kPckThreads) void pose_pck_flags_kernel(const float
         for (int m = 0; m < 2; ++m) {
             float best = am[m].best;
             int bidx = am[m].bidx;
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) {
-                const float ov = __shfl_xor(best, off, 64);
-                const int oi = __shfl_xor(bidx, off, 64);
-                argmax_combine(best, bidx, ov, oi);
-            }
+            wave_argmax(best, bidx);
             const int any_nan = __any(am[m].nan ? 1 : 0);
             if (lane == 0) {
                 s_best[m][wave] = best;
@@ -176,7 +164,7 @@ __global__ __launch_bounds__(kPckUpdateThreads) void pose_pck_update_kernel(cons
                 hsum += (f >> 1) & 1;
             }
 #pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) {
+            for (int off = 32; off >= 1; off >>= 1) {  // the two int sums advance together
                 hsum += __shfl_xor(hsum, off, 64);
                 vsum += __shfl_xor(vsum, off, 64);
             }

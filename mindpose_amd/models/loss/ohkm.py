@@ -13,7 +13,7 @@ Against the HRNet training code (``JointsOHKMMSELoss`` of lib/core/loss.py): tha
 target by the weight BEFORE squaring, this one has no 0.5 and multiplies the squared error by the weight, as ``JointsMSELoss`` here
 and in the reference does.  With 0 / 1 weights (COCO visibility) this loss is exactly twice the HRNet code's.
 
-The selection is made on the device (``mp_joints_ohkm_fwd``, csrc/ohkm_loss.hip: three launches, no read-back), the backward is one
+The selection is made on the device (``mp_joints_ohkm_fwd``, csrc/joints_loss.hip: three launches, no read-back), the backward is one
 launch that zero-fills the rows that were not selected without reading them; both capture into the training step's graph.
 """
 from typing import Optional, Tuple

@@ -130,7 +130,7 @@ class Entry:
 
 _planes16 = lambda case: case[0] * c8_of(case[1])  # noqa: E731
 ENTRIES = {
-    "mp_fuse_upsample_sum": Entry(256 * 32 * 256, ("pose_ops.hip", "if (blocks > 256 * 32) blocks = 256 * 32;"), FUSE32_CASES, fuse32_units,
+    "mp_fuse_upsample_sum": Entry(256 * 32 * 256, ("eltwise_f32.hip", "if (blocks > 256 * 32) blocks = 256 * 32;"), FUSE32_CASES, fuse32_units,
                                   lambda c: c[0] * c[1] * c[2] * c[3], vec=4),
     # one launch per output; the widest is dbase, one thread per element
     "mp_fuse_upsample_sum_bwd": Entry(256 * 32 * 256, ("train_ops.hip", "if (blocks > 256 * 32) blocks = 256 * 32;"), FUSE32_CASES,
@@ -139,7 +139,7 @@ ENTRIES = {
     "mp_f16_fuse_upsample_sum_bwd": Entry(8192 * 256, ("train_ops.hip", "if (blocks > 8192) blocks = 8192;"), fuse16_bwd_cases(),
                                           lambda c: _planes16(c) * c[2] * c[3]),
     "mp_sum_tensors": Entry(SUM_CAP, ("train_ops.hip", "if (blocks > 4096) blocks = 4096;"), SUM_CASES, lambda c: c[2]),
-    "mp_maxpool3x3s2_same": Entry(256 * 16 * 256, ("pose_ops.hip", "if (blocks > 256 * 16) blocks = 256 * 16;"), POOL_FWD_CASES,
+    "mp_maxpool3x3s2_same": Entry(256 * 16 * 256, ("eltwise_f32.hip", "if (blocks > 256 * 16) blocks = 256 * 16;"), POOL_FWD_CASES,
                                   lambda c: c[0] * c[1] * ceil_div(c[2], 2) * ceil_div(c[3], 2)),
     "mp_maxpool3x3s2_same_bwd": Entry(16384 * 256, ("sb_train_ops.hip", "if (blocks > 16384) blocks = 16384;"), POOL_BWD_CASES,
                                       lambda c: c[0] * c[1] * c[2] * c[3]),

@@ -1,5 +1,6 @@
 """The case lists, designed inputs and CPU references that force the top-down kernels of csrc/pose_ops.hip - decode_kernel<FLIP>,
-flip_aggregate_kernel, gaussian_target_kernel, mse_row_kernel / mse_final_kernel / mse_bwd_kernel - through every path and edge.
+flip_aggregate_kernel, gaussian_target_kernel - and the joint MSE kernels of csrc/joints_loss.hip - joints_sq_row_kernel /
+joints_mse_final_kernel / joints_bwd_kernel - through every path and edge.
 Importable without a GPU; tests/test_pose_matrix_cpu.py holds the floors of the lists and checks the builders on the CPU oracle alone,
 tests/test_gpu_pose_edges.py runs every case on the device.
 
@@ -22,23 +23,24 @@ F32 = np.float32
 U24 = 2.0 ** -24  # unit round-off of fp32
 Q6, Q12 = 2.0 ** -6, 2.0 ** -12
 
-# the lines of csrc/pose_ops.hip the predicates and the loop counts below restate
+# (file of csrc/, line) the predicates and the loop counts below restate
 SOURCE_LINES = {
-    "decode_path": "if ((hw & 3) == 0 && (!FLIP || (w & 3) == 0)) {",
-    "decode_round": "for (int q0 = lane; q0 < nq; q0 += 64 * B) {",
-    "decode_batch": "constexpr int B = 4;",
-    "decode_scalar": "for (int x = lane; x < w; x += 64) {",
-    "decode_empty": "if (bidx == 0x7fffffff) {",
-    "dark_path": "constexpr int kDarkFastKs = 17;",
-    "dark_fast": "const bool dark_fast = p.refine == MP_REFINE_DARK && p.ks <= kDarkFastKs;",
-    "dark_ks_range": "if (ks < 1 || (ks & 1) == 0 || ks > 63) return MP_ERR_UNSUPPORTED;",
-    "target_zero_path": "if ((w & 3) == 0) {",
-    "target_window_guard": "if (stamp && ix1 > ix0 && iy1 > iy0) {",
-    "target_oob": "const bool oob = (ulx >= w) || (uly >= h) || (brx < 0) || (bry < 0);",
-    "target_clamp": "fx = fmin(fmax(fx, -1.0e9), 1.0e9);",
-    "mse_path": "if ((hw & 3) == 0) {",
-    "mse_final_stride": "for (int i = threadIdx.x; i < rows; i += blockDim.x) acc += (double)partial[i];",
-    "mse_row_sum": "if (threadIdx.x == 0) partial[row] = (ws[0] + ws[1]) + (ws[2] + ws[3]);",
+    "decode_path": ("pose_ops.hip", "if ((hw & 3) == 0 && (!FLIP || (w & 3) == 0)) {"),
+    "decode_round": ("pose_ops.hip", "for (int q0 = lane; q0 < nq; q0 += 64 * B) {"),
+    "decode_batch": ("pose_ops.hip", "constexpr int B = 4;"),
+    "decode_scalar": ("pose_ops.hip", "for (int x = lane; x < w; x += 64) {"),
+    "decode_empty": ("pose_ops.hip", "if (bidx == 0x7fffffff) {"),
+    "dark_path": ("pose_ops.hip", "constexpr int kDarkFastKs = 17;"),
+    "dark_fast": ("pose_ops.hip", "const bool dark_fast = p.refine == MP_REFINE_DARK && p.ks <= kDarkFastKs;"),
+    "dark_ks_range": ("pose_ops.hip", "if (ks < 1 || (ks & 1) == 0 || ks > 63) return MP_ERR_UNSUPPORTED;"),
+    "target_zero_path": ("pose_ops.hip", "if ((w & 3) == 0) {"),
+    "target_window_guard": ("pose_ops.hip", "if (stamp && ix1 > ix0 && iy1 > iy0) {"),
+    "target_oob": ("pose_ops.hip", "const bool oob = (ulx >= w) || (uly >= h) || (brx < 0) || (bry < 0);"),
+    "target_clamp": ("pose_ops.hip", "fx = fmin(fmax(fx, -1.0e9), 1.0e9);"),
+    # the one host predicate of the four loss entries; the case lists below keep every base 16-byte aligned, where it is hw % 4 == 0
+    "mse_path": ("joints_loss.hip", "return (hw & 3) == 0 && (((uintptr_t)pred | (uintptr_t)target | (uintptr_t)grad) & 15u) == 0;"),
+    "mse_final_stride": ("joints_loss.hip", "for (int i = threadIdx.x; i < rows; i += blockDim.x) acc += (double)partial[i];"),
+    "mse_row_sum": ("reduce.h", "if (threadIdx.x == 0) v = (ws4[0] + ws4[1]) + (ws4[2] + ws4[3]);"),
 }
 
 DARK_FAST_KS = 17
@@ -64,7 +66,7 @@ def target_zero_path(w):
 
 
 def mse_path(hw):
-    """(hw & 3) == 0"""
+    """(hw & 3) == 0, on 16-byte aligned bases"""
     return "quad" if hw % 4 == 0 else "scalar"
 
 
@@ -345,7 +347,7 @@ def target_keypoints(case):
 
 MSE_HW_SCALAR = [1, 3, 63, 255, 257, 1023]
 MSE_HW_QUAD = [4, 252, 1028, 3072]
-# rows -> (n, k): mse_final_kernel strides 256 threads over the rows, so 257 and 600 take a second and a third ragged stride
+# rows -> (n, k): joints_mse_final_kernel strides 256 threads over the rows, so 257 and 600 take a second and a third ragged stride
 MSE_ROWS = {1: (1, 1), 5: (1, 5), 257: (257, 1), 600: (24, 25)}
 MSE_WEIGHTS = ("none", "ones", "mix")
 MSE_GRADS = (None, 0.375)  # grad_out NULL, or a one-element tensor
@@ -353,7 +355,7 @@ MSE_CASES = [(hw, rows, wk) for hw in MSE_HW_SCALAR + MSE_HW_QUAD for rows in MS
 
 
 def mse_additions(hw):
-    """the additions one thread of mse_row_kernel makes: one per element of its stride on the scalar path, four per float4"""
+    """the additions one thread of joints_sq_row_kernel makes: one per element of its stride on the scalar path, four per float4"""
     return ceil_div(hw, 256) if mse_path(hw) == "scalar" else 4 * ceil_div(hw, 1024)
 
 
@@ -373,6 +375,47 @@ def mse_inputs(hw, rows, weights):
     return pred, target, w
 
 
+def mse_rows_restated(pred, target, w, path):
+    """joints_sq_row_kernel in IEEE fp32, [rows] fp32: thread t of 256 adds (d * d) * w over its elements in ascending order - on the
+    scalar path elements t, t + 256, ..., on the quad path the four floats of quads t, t + 256, ... - then the xor butterfly 32 ... 1
+    inside each wave of 64 and (w0 + w1) + (w2 + w3).  No weights: w = 1 (the kernel multiplies by 1.f)."""
+    rows, hw = pred.shape
+    d = (pred - target).astype(F32)
+    wv = np.ones(rows, dtype=F32) if w is None else w.astype(F32)
+    terms = ((d * d).astype(F32) * wv[:, None]).astype(F32)
+    unit = 1 if path == "scalar" else 4
+    assert hw % unit == 0
+    trips = ceil_div(hw // unit, 256)
+    padded = np.zeros((rows, trips * 256 * unit), dtype=F32)  # + 0.0 leaves every partial sum as it is: they start at +0.0
+    padded[:, :hw] = terms
+    steps = padded.reshape(rows, trips, 256, unit)
+    acc = np.zeros((rows, 256), dtype=F32)
+    for t in range(trips):
+        for e in range(unit):
+            acc = (acc + steps[:, t, :, e]).astype(F32)
+    lanes = acc.reshape(rows, 4, 64)
+    for off in (32, 16, 8, 4, 2, 1):
+        lanes = (lanes + lanes[:, :, np.arange(64) ^ off]).astype(F32)
+    ws = lanes[:, :, 0]
+    return ((ws[:, 0] + ws[:, 1]).astype(F32) + (ws[:, 2] + ws[:, 3]).astype(F32)).astype(F32)
+
+
+def mse_fwd_restated(pred, target, w, path):
+    """mp_joints_mse_fwd in IEEE arithmetic, fp32 scalar: mse_rows_restated, then joints_mse_final_kernel - thread t of 256 adds rows
+    t, t + 256, ... in fp64, slot t takes slot t + s for s = 128 ... 1, the sum times 1.0 / (rows hw), rounded to fp32"""
+    part = mse_rows_restated(pred, target, w, path).astype(np.float64)
+    rows, hw = pred.shape
+    sm = np.zeros(256)
+    for t in range(min(rows, 256)):
+        for v in part[t::256]:
+            sm[t] += v
+    s = 128
+    while s >= 1:
+        sm[:s] = sm[:s] + sm[s:2 * s]
+        s >>= 1
+    return F32(sm[0] * (1.0 / (float(rows) * float(hw))))
+
+
 def mse_fwd_ref(pred, target, w):
     """float64 on the fp32 inputs: (sum(w d^2) / (rows hw), sum(|w| d^2) / (rows hw))"""
     d2 = (pred.astype(np.float64) - target.astype(np.float64)) ** 2
@@ -381,7 +424,7 @@ def mse_fwd_ref(pred, target, w):
 
 
 def mse_bwd_restated(pred, target, w, g):
-    """mse_bwd_kernel in IEEE fp32 (contraction is off in pose_ops.hip): (a - b) * (w * (g * float32(2 / (rows hw)))), g = 1 for a NULL
+    """joints_bwd_kernel in IEEE fp32 (contraction is off in joints_loss.hip): (a - b) * (w * (g * float32(2 / (rows hw)))), g = 1 for a NULL
     grad_out and no multiply by w without weights"""
     c = F32(1.0 if g is None else g) * F32(2.0 / pred.size)
     c = np.full(pred.shape[0], c, dtype=F32) if w is None else (w.astype(F32) * c).astype(F32)

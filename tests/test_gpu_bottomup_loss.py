@@ -242,7 +242,8 @@ def test_ae_one_person_and_no_visible_joint():
     assert float(out[0]) == 0.0 and float(out[1]) == 0.0 and not grad.any() and torch.isfinite(grad).all()
 
 
-def test_ae_random_cases():
+def ae_random_inputs():
+    """[(name, pred, tag_ind, weights, tag_per_joint)] of test_ae_random_cases (tests/pose_loss_bits.py digests the same inputs)"""
     rng = np.random.RandomState(3)
     g = torch.Generator().manual_seed(3)
     # persons with k_n = 0 among valid ones, flag-0 entries with index 0
@@ -250,14 +251,20 @@ def test_ae_random_cases():
     ind = make_tag_ind(rng, 3, 30, 17, 32 * 32, persons=[5, 1, 12], p_visible=0.6)
     ind[0, np.flatnonzero(ind[0, :, :, 1].sum(axis=1))[0]] = 0            # a listed person without any visible joint
     ind[2, np.flatnonzero(ind[2, :, :, 1].sum(axis=1) == 0)[0], 4] = (0, 1)  # a person whose only joint sits at index 0
-    check_ae("mixed", pred, ind, weights=(1.0, 2.0))
+    cases = [("mixed", pred, ind, (1.0, 2.0), True)]
     # not tag_per_joint: pred [N, H, W], tag_ind [N, M, 2]
     pred = torch.randn(3, 24, 20, generator=g)
     ind = make_tag_ind(rng, 3, 10, 1, 24 * 20, persons=[4, 0, 7], p_visible=0.9, tag_per_joint=False)
-    check_ae("not_per_joint", pred, ind, weights=(0.5, 3.0), tag_per_joint=False)
+    cases.append(("not_per_joint", pred, ind, (0.5, 3.0), False))
     # odd plane size: the scalar zero-fill
     pred = torch.randn(2, 5, 9, 7, generator=g)
-    check_ae("odd", pred, make_tag_ind(rng, 2, 6, 5, 63, persons=[3, 6]), weights=(2.0, 1.0))
+    cases.append(("odd", pred, make_tag_ind(rng, 2, 6, 5, 63, persons=[3, 6]), (2.0, 1.0), True))
+    return cases
+
+
+def test_ae_random_cases():
+    for name, pred, ind, weights, tag_per_joint in ae_random_inputs():
+        check_ae(name, pred, ind, weights=weights, tag_per_joint=tag_per_joint)
 
 
 def test_ae_shared_pixel_gradient_is_summed():

@@ -1,4 +1,4 @@
-"""The OHKM joint MSE on the GPU (csrc/ohkm_loss.hip, models/loss/ohkm.py) against the float64 restatement of
+"""The OHKM joint MSE on the GPU (csrc/joints_loss.hip, models/loss/ohkm.py) against the float64 restatement of
 tests/ohkm_restated.py: row sums, selection, loss and gradient on the smallest shapes at which a kernel can go wrong (one element,
 odd HW, one past a wave of joints, the LDS ranking up to K = 1024, more samples than the final reduction has threads), the tie and
 NaN rules of the order, the rows the backward must not read, known answers, the C ABI's refusals, the loss inside the graph-captured

@@ -1,9 +1,10 @@
 """tests/pose_matrix.py checked without a GPU: the lists keep the maps, row counts, refine / flip forms, peak positions, tie kinds,
 window classes and loss sizes that tests/test_gpu_pose_edges.py is written to reach (the floors below fail when a later edit thins a
-list), the quoted source lines exist in csrc/pose_ops.hip, and every builder does what it says ON THE ORACLE ALONE: the designed
+list), the quoted source lines exist in the files of csrc/ they name, and every builder does what it says ON THE ORACLE ALONE: the designed
 arg-max is the oracle's, a plateau does not move, every designed key point falls into its window class, the DARK blobs give a
 regular Hessian, and the float64 loss references agree with oracle.loss."""
 import os
+import re
 
 import numpy as np
 import pytest
@@ -100,12 +101,22 @@ def test_tie_kinds_sit_where_the_kernel_separates_them():
 
 def test_quoted_lines_exist_in_the_source():
     csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "mindpose_amd", "csrc")
-    with open(os.path.join(csrc, "pose_ops.hip")) as f:
-        text = f.read()
-    for name, line in pm.SOURCE_LINES.items():
-        assert line in text, (name, line)
-    assert text.count(pm.SOURCE_LINES["mse_path"]) == 2  # forward and backward
-    assert f"kDarkFastKs = {pm.DARK_FAST_KS};" in pm.SOURCE_LINES["dark_path"]
+    text = {}
+    for name, (source, line) in pm.SOURCE_LINES.items():
+        if source not in text:
+            with open(os.path.join(csrc, source)) as f:
+                text[source] = f.read()
+        assert line in text[source], (name, source, line)
+    # ONE host predicate picks the path of the joint MSE and the OHKM loss, forward and backward: one definition, and every launch
+    # of the row and backward kernels takes its `vec` from it
+    loss = text["joints_loss.hip"]
+    assert len(re.findall(r"\bint vec16\(", loss)) == 1 and pm.SOURCE_LINES["mse_path"][1] in loss
+    assert len(re.findall(r"& *3\b", loss)) == 1  # nothing else in the file decides a path by hw % 4
+    # the row kernel and the backward kernel are each launched from one place, with vec16's answer
+    for kernel in ("joints_sq_row_kernel", "joints_bwd_kernel"):
+        launches = re.findall(r"hipLaunchKernelGGL\(\s*" + kernel + r"\b[^;]*;", loss)
+        assert len(launches) == 1 and "vec16(" in launches[0], kernel
+    assert f"kDarkFastKs = {pm.DARK_FAST_KS};" in pm.SOURCE_LINES["dark_path"][1]
 
 
 def _bits(a):
@@ -303,3 +314,30 @@ def test_mse_references_agree_with_the_oracle(name):
     # a weight of -1 shows in the magnitude only
     ref, mag = pm.mse_fwd_ref(p2[:2], t2[:2], np.array([-1.0, 1.0], dtype=np.float32))
     assert mag > abs(ref)
+
+
+@pytest.mark.parametrize("hw", [1, 63, 257, 1023, 252, 1028, 3072])
+@pytest.mark.parametrize("weights", ["none", "mix"])
+def test_mse_restatement_of_the_row_pass(hw, weights):
+    """mse_rows_restated / mse_fwd_restated (the fp32 row pass, thread by thread) against float64 within the bound the GPU test allows,
+    on both paths where the size admits both.  The two paths associate differently: on the unweighted inputs some row differs in its
+    bits.  The value-only mutant of the four-wave sum, a dropped ws[2] + ws[3], is outside the bound wherever threads 128 ... 255 hold
+    elements."""
+    pred, target, w = pm.mse_inputs(hw, 5, weights)
+    ref, mag = pm.mse_fwd_ref(pred, target, w)
+    terms64 = (pred.astype(np.float64) - target.astype(np.float64)) ** 2 * (1.0 if w is None else w.astype(np.float64)[:, None])
+    rows64 = terms64.sum(axis=1)
+    got = {}
+    for path in ["scalar"] + (["quad"] if hw % 4 == 0 else []):
+        got[path] = pm.mse_rows_restated(pred, target, w, path)
+        assert got[path].dtype == np.float32
+        # the path's own additions: the scalar loop on a quad size makes ceil(hw / 256) of them
+        bound = ((pm.ceil_div(hw, 256) if path == "scalar" else pm.mse_additions(hw)) + 12) * pm.U24
+        assert np.all(np.abs(got[path] - rows64) <= bound * np.abs(rows64)), (path, got[path], rows64)
+        assert abs(float(pm.mse_fwd_restated(pred, target, w, path)) - ref) <= bound * mag
+        unit = 1 if path == "scalar" else 4
+        upper = (np.arange(hw) // unit) % 256 >= 128  # the elements of waves 2 and 3
+        if upper.any():
+            assert abs(terms64[:, ~upper].sum() / pred.size - ref) > bound * mag
+    if len(got) == 2 and weights == "none" and hw >= 252:
+        assert (got["scalar"].view(np.uint32) != got["quad"].view(np.uint32)).any()

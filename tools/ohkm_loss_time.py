@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Device times of the OHKM joint MSE (``joint_ohkm_mse``, csrc/ohkm_loss.hip) beside the joint MSE at the training shape
+"""Device times of the OHKM joint MSE (``joint_ohkm_mse``, csrc/joints_loss.hip) beside the joint MSE at the training shape
 (N = 128, K = 17, 64 x 48, topk = 8); prints ONE JSON line.
 
   python tools/ohkm_loss_time.py [--rounds 7] [--calls 100] [--step-rounds 5] [--step-steps 20] [--json out.json]

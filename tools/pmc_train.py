@@ -31,9 +31,9 @@ def collect(dirs):
 
 def step_totals(traffic, dur):
     """HBM bytes and summed kernel time of ONE training step: every forward + backward pass of the stats run (the eager warm-ups of
-    the capture and every replay) launches the loss gradient `mse_bwd_kernel` exactly once, so calls / that count = launches per
-    step (the tuner's trial launches were done by an earlier process: the profiled run replays its cache)."""
-    steps = dur.get("mse_bwd_kernel", (0, 0.0))[0]
+    the capture and every replay) launches the loss gradient `joints_bwd_kernel` (`mse_bwd_kernel` in traces recorded before the two losses shared it) exactly once,
+    so calls / that count = launches per step (the tuner's trial launches were done by an earlier process: the profiled run replays its cache)."""
+    steps = (dur.get("joints_bwd_kernel") or dur.get("mse_bwd_kernel") or (0, 0.0))[0]
     if not steps:
         return None
     tot_b = sum(traffic[k]["hbm_bytes_per_launch"] * dur[k][0] / steps for k in traffic if k in dur)
