@@ -135,6 +135,8 @@ def grad_clip_norm(args: Namespace) -> Optional[float]:
 def train(args: Namespace) -> None:
     metric = train_metric(args)  # refused before anything is opened
     clip_norm = grad_clip_norm(args)  # likewise
+    if getattr(args, "ema", False):  # (cli/eval takes the key; a run that silently kept no average would mislead)
+        raise ValueError("`ema`: keeping an exponential moving average of the weights while training is not built yet")
     torch.manual_seed(0)
     np.random.seed(0)
     random.seed(0)

@@ -169,15 +169,35 @@ def save_checkpoint(params: Dict[str, np.ndarray], ckpt_file_name: str) -> None:
 _STRIP = ("network.", "net.", "_backbone.")  # cells that wrap Net in the reference: NetWithLoss.net, TrainOneStepCell.network
 
 
-def load_param_into_net(net, parameter_dict: Dict[str, np.ndarray], strict_load: bool = False) -> List[str]:
+# a mindcv-style run with `ema: True` saves the averaged weights beside the live ones under this prefix: the names
+# `weights.clone(prefix="ema")` gives [MS-knowledge: recalled, no mindcv checkpoint at hand]
+EMA_PREFIX = "ema."
+
+
+def ema_parameters(parameter_dict: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
+    """The dictionary with every ``ema.<name>`` entry moved onto ``<name>`` (the averaged weights in place of the live ones;
+    everything without an averaged twin - BatchNorm statistics, which both sets share - stays).  A dictionary without any
+    ``ema.`` entry is refused."""
+    ema = {k[len(EMA_PREFIX):]: v for k, v in parameter_dict.items() if k.startswith(EMA_PREFIX)}
+    if not ema:
+        raise ValueError("the checkpoint holds no `ema.` entries: it was not written by a run that keeps an EMA of the weights")
+    out = {k: v for k, v in parameter_dict.items() if not k.startswith(EMA_PREFIX)}
+    out.update(ema)
+    return out
+
+
+def load_param_into_net(net, parameter_dict: Dict[str, np.ndarray], strict_load: bool = False, prefer_ema: bool = False) -> List[str]:
     """``mindspore.load_param_into_net(net, parameter_dict)``: copy matching parameters / BatchNorm statistics into a
     network of this package and return the names of the network's parameters that were NOT loaded.
 
     Wrapper prefixes of the reference's training cells (``net.``, ``network.``) are stripped; optimizer state
     (``moment1.*``, ``moment2.*``, ``global_step``, ``learning_rate`` ...) is ignored.  A shape mismatch raises
     ``RuntimeError`` like MindSpore; ``strict_load`` additionally requires equal dtypes (fp16 checkpoints are cast to
-    the network's fp32 otherwise)."""
+    the network's fp32 otherwise).  ``prefer_ema``: load the ``ema.<name>`` entries in place of ``<name>`` (``ema_parameters``;
+    a dictionary without any is refused); without it they are names the network does not know, and ignored."""
     import torch
+    if prefer_ema:
+        parameter_dict = ema_parameters(parameter_dict)
     own = dict(net.state_dict())
     lookup = {}
     for name, arr in parameter_dict.items():
