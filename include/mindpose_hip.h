@@ -1058,6 +1058,14 @@ int mp_f16_conv_wgrad(const mp_conv_desc* desc, const void* x_c8_dev, const void
 size_t mp_f16_conv_wgrad_grouped_workspace_bytes(const mp_conv_desc* desc, int n_jobs);
 int mp_f16_conv_wgrad_grouped(const mp_conv_desc* desc, const void* const* x_dev, const void* const* dz_dev, float* const* dw_dev,
                               int n_jobs, float scale, int accumulate, void* workspace_dev, size_t workspace_bytes, mp_stream_t stream);
+/* The launch a weight-gradient entry point builds, as numbers (host-only; tests pin the geometry and the dispatch with it).
+ * half = 0: mp_conv_wgrad (n_jobs 0 or 1); half = 1: mp_f16_conv_wgrad (n_jobs = 0) or mp_f16_conv_wgrad_grouped (n_jobs 1 .. 8).
+ * out[0] = the return code of the geometry; after MP_OK: every non-pointer field of the kernel parameter block in declaration
+ * order (magic numbers unsigned), the grid (x, y, z), the block, the LDS bytes, the kernel (half, form, kernel size, stride; form:
+ * fp32 0 = scalar-staged, 1 = pipelined; fp16 0 = LDS-DMA 32 x 32, 1 = wide, 2 = narrow, 3 = register-staged) and the slab reduce
+ * (threads per element or 0 for the plain kernel, workgroups, jobs).  Returns the number of words written, MP_ERR_WORKSPACE when
+ * cap is too small (64 is enough). */
+int mp_conv_wgrad_launch_words(const mp_conv_desc* desc, int half, int n_jobs, int64_t* out, int cap);
 
 /* ---- training kernels of the SimpleBaseline-ResNet family ---------------------------------------------------------------
  * mp_maxpool3x3s2_same_bwd: backward of nn.MaxPool2d(3, 2, pad_mode="same") (resnet.py:190), gradient to the first maximum of

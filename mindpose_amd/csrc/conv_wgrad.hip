@@ -5,13 +5,9 @@
 // Workgroup = 32 couts x 32 cins x all taps; wave w owns the 16x16 sub-tile (w&1, w>>1) for every tap
 // (T accumulators).  The pixel axis is split over blockIdx.y; every split writes its partial dW into its own
 // slab and a second kernel sums the slabs in a fixed order (deterministic, no atomics).
-#include <stdlib.h>
-
-#include "common.h"
+#include "wgrad_common.h"
 
 namespace mp {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 struct WgradParams {
     const float* x;    // [N,Cin,H,W]
@@ -28,11 +24,6 @@ struct WgradParams {
     int zq, xw4;       // 16-B units per cout row of the dz tile (R*Wo/4) / per input row (W/4)
 };
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-constexpr unsigned kOobW = 0x80000000u;
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t wg_rsrc(const void* base, size_t bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, (int)(bytes < 0x7FFFFFF0u ? bytes : 0x7FFFFFF0u), 0x00020000);
-}
 __device__ __forceinline__ f32x4 wg_load4(__amdgpu_buffer_rsrc_t r, unsigned off) {
     return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
 }
@@ -63,7 +54,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_pipe_kernel(const WgradPara
 #pragma unroll
     for (int i = 0; i < NZ; ++i) {
         const int u = tid + 256 * i;
-        zsrc[i] = kOobW;
+        zsrc[i] = kOob;
         zdst[i] = 0;
         if (u < 32 * p.zq) {
             const int c = u / p.zq, q4 = (u - c * p.zq) * 4;
@@ -76,7 +67,7 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_pipe_kernel(const WgradPara
 #pragma unroll
     for (int i = 0; i < NX; ++i) {
         const int u = tid + 256 * i;
-        xsrc[i] = kOobW;
+        xsrc[i] = kOob;
         xdst[i] = 0;
         if (u < 32 * xper) {
             const int c = u / xper, rem = u - c * xper;
@@ -100,20 +91,20 @@ __global__ __launch_bounds__(256, 2) void conv_wgrad_pipe_kernel(const WgradPara
     auto stage_load = [&](int tile) {
         int n, y0, npix, yin0;
         tile_geom(tile, n, y0, npix, yin0);
-        const __amdgpu_buffer_rsrc_t rz = wg_rsrc(p.dz + (size_t)n * p.Cout * HoWo, (size_t)p.Cout * HoWo * 4);
-        const __amdgpu_buffer_rsrc_t rx = wg_rsrc(p.x + (size_t)n * p.Cin * HW, (size_t)p.Cin * HW * 4);
+        const __amdgpu_buffer_rsrc_t rz = make_rsrc(p.dz + (size_t)n * p.Cout * HoWo, (size_t)p.Cout * HoWo * 4);
+        const __amdgpu_buffer_rsrc_t rx = make_rsrc(p.x + (size_t)n * p.Cin * HW, (size_t)p.Cin * HW * 4);
         unsigned oz = 0;
         asm volatile("" : "+v"(oz));  // keep the per-unit field arithmetic out of loop-invariant hoisting
 #pragma unroll
         for (int i = 0; i < NZ; ++i) {
-            const bool ok = zsrc[i] != kOobW && (int)((zdst[i] + oz) >> 16) < npix;
-            vz[i] = wg_load4(rz, ok ? (zsrc[i] + (unsigned)(y0 * p.Wo)) * 4u : kOobW);
+            const bool ok = zsrc[i] != kOob && (int)((zdst[i] + oz) >> 16) < npix;
+            vz[i] = wg_load4(rz, ok ? (zsrc[i] + (unsigned)(y0 * p.Wo)) * 4u : kOob);
         }
 #pragma unroll
         for (int i = 0; i < NX; ++i) {
             const int yin = yin0 + (int)((xdst[i] + oz) >> 16);
-            const bool ok = xsrc[i] != kOobW && (unsigned)yin < (unsigned)p.H;
-            vx[i] = wg_load4(rx, ok ? (unsigned)((int)xsrc[i] + yin0 * p.W) * 4u : kOobW);
+            const bool ok = xsrc[i] != kOob && (unsigned)yin < (unsigned)p.H;
+            vx[i] = wg_load4(rx, ok ? (unsigned)((int)xsrc[i] + yin0 * p.W) * 4u : kOob);
         }
     };
     auto stage_store = [&](int buf) {
@@ -263,10 +254,12 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(const WgradParams p) {
         }
 }
 
-// Sum the slabs in a FIXED order (deterministic): eight interleaved partial sums (slab k goes to partial k & 7) keep
-// eight loads in flight per thread, then the partials are combined left to right.
-__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ slabs, float* __restrict__ dw, size_t count,
-                                                           int splits, int accumulate) {
+// Sum the slabs of a job (blockIdx.y) in a FIXED order (deterministic): eight interleaved partial sums (slab k goes to partial
+// k & 7) keep eight loads in flight per thread, then the partials are combined left to right.  fp32 passes scale = 1 (exact).
+__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ slabs, WgradDst dst, size_t count, int splits,
+                                                           float scale, int accumulate) {
+    float* __restrict__ dw = dst.dw[blockIdx.y];
+    slabs += (size_t)blockIdx.y * splits * count;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (size_t)gridDim.x * blockDim.x) {
         float part[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         int k = 0;
@@ -275,16 +268,20 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restri
             for (int j = 0; j < 8; ++j) part[j] += slabs[(size_t)(k + j) * count + i];
         }
         for (int j = 0; k < splits; ++k, ++j) part[j] += slabs[(size_t)k * count + i];
-        const float s = ((part[0] + part[1]) + (part[2] + part[3])) + ((part[4] + part[5]) + (part[6] + part[7]));
-        dw[i] = accumulate ? dw[i] + s : s;
+        const float v = (((part[0] + part[1]) + (part[2] + part[3])) + ((part[4] + part[5]) + (part[6] + part[7]))) * scale;
+        dw[i] = accumulate ? dw[i] + v : v;
     }
 }
 
-// Small weights (the 32- / 64-channel layers): G threads per element share the walk over the slabs - see the fp16 twin in
-// wgrad_f16.hip; fixed-order combine through LDS, deterministic.
+// The same reduction for SMALL weights: with |dW| = 9 K floats (the 32-channel layers) the kernel above is 36 blocks of
+// threads that each walk 512 slabs serially - latency-bound at ~25 us.  Here a block serves 256 / G elements with G threads
+// per element, thread g summing slabs g, g + G, ... (four interleaved partial sums), then a fixed-order combine through LDS
+// (deterministic): G times the blocks, 1 / G of the serial depth.
 template <int G>
-__global__ __launch_bounds__(256) void wgrad_reduce_grouped_kernel(const float* __restrict__ slabs, float* __restrict__ dw,
-                                                                   size_t count, int splits, int accumulate) {
+__global__ __launch_bounds__(256) void wgrad_reduce_grouped_kernel(const float* __restrict__ slabs, WgradDst dst, size_t count,
+                                                                   int splits, float scale, int accumulate) {
+    float* __restrict__ dw = dst.dw[blockIdx.y];
+    slabs += (size_t)blockIdx.y * splits * count;
     constexpr int E = 256 / G;
     __shared__ float sm[G][E];
     const int e = threadIdx.x % E, g = threadIdx.x / E;
@@ -304,21 +301,41 @@ __global__ __launch_bounds__(256) void wgrad_reduce_grouped_kernel(const float* 
         float v = 0.f;
 #pragma unroll
         for (int q = 0; q < G; ++q) v += sm[q][e];
+        v *= scale;
         dw[i] = accumulate ? dw[i] + v : v;
     }
+}
+
+// The fp32 entry keeps the plain kernel in its single-destination form: through the kernel above its 128-channel 3x3 layer measured
+// 0.2 us slower per launch (7.0 against 6.8 us) - one thread per element there, nothing hides the longer prologue.
+__global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float* __restrict__ slabs, float* __restrict__ dw, size_t count,
+                                                           int splits, int accumulate) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (size_t)gridDim.x * blockDim.x) {
+        float part[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        int k = 0;
+        for (; k + 8 <= splits; k += 8) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) part[j] += slabs[(size_t)(k + j) * count + i];
+        }
+        for (int j = 0; k < splits; ++k, ++j) part[j] += slabs[(size_t)k * count + i];
+        const float s = ((part[0] + part[1]) + (part[2] + part[3])) + ((part[4] + part[5]) + (part[6] + part[7]));
+        dw[i] = accumulate ? dw[i] + s : s;
+    }
+}
+
+int wgrad_reduce_launch(const float* slabs, const WgradDst& dst, int jobs, size_t count, int splits, float scale, int accumulate,
+                        hipStream_t s) {
+    const WgradReduce r = wgrad_reduce_choice(count, splits);
+    void (*plain)(const float*, WgradDst, size_t, int, float, int) = wgrad_reduce_kernel;
+    const auto kern = r.G == 16 ? wgrad_reduce_grouped_kernel<16> : r.G == 4 ? wgrad_reduce_grouped_kernel<4> : plain;
+    hipLaunchKernelGGL(kern, dim3(r.blocks, jobs), dim3(256), 0, s, slabs, dst, count, splits, scale, accumulate ? 1 : 0);
+    return check_launch();
 }
 
 static int odd_up(int v) { return v | 1; }
 
 static int wgrad_geometry(const mp_conv_desc* d, WgradParams& p, size_t& lds_bytes) {
-    if (!d) return MP_ERR_NULL;
-    if (d->n <= 0 || d->cin <= 0 || d->cout <= 0 || d->h <= 0 || d->w <= 0 || d->conv_h <= 0 || d->conv_w <= 0) return MP_ERR_SHAPE;
-    // 1x1 / 3x3 with padding k/2, or the 4x4 stride-2 padding-1 form (the transposed convolution's weight gradient, roles of
-    // input and output gradient exchanged by the caller; simple kernel only)
-    if (d->kh != d->kw || !(d->kh == 1 || d->kh == 3 || d->kh == 4)) return MP_ERR_UNSUPPORTED;
-    if (!(d->stride == 1 || d->stride == 2)) return MP_ERR_UNSUPPORTED;
-    if (d->pad_top != d->pad_left) return MP_ERR_UNSUPPORTED;
-    if (d->kh == 4 ? (d->stride != 2 || d->pad_top != 1) : (d->pad_top != d->kh / 2)) return MP_ERR_UNSUPPORTED;
+    if (const int rc = wgrad_desc_ok(d)) return rc;  // (the 4x4 form: simple kernel only)
     p.N = d->n; p.Cin = d->cin; p.H = d->h; p.W = d->w; p.Cout = d->cout; p.Ho = d->conv_h; p.Wo = d->conv_w; p.pad = d->pad_top;
     const int S = d->stride, KS = d->kh;
     int R = 192 / p.Wo;
@@ -379,6 +396,37 @@ static int wgrad_geometry(const mp_conv_desc* d, WgradParams& p, size_t& lds_byt
     return MP_OK;
 }
 
+// The nine instantiations, keyed by (pipelined, kernel size, stride)
+struct WgradKernel {
+    int vec, ks, s;
+    int (*launch)(dim3, dim3, size_t, hipStream_t, const WgradParams&);
+};
+static const WgradKernel kWgradKernels[] = {
+    {1, 1, 1, launch_lds<conv_wgrad_pipe_kernel<1, 1, 6, 9>, WgradParams>}, {1, 1, 2, launch_lds<conv_wgrad_pipe_kernel<1, 2, 6, 9>, WgradParams>},
+    {1, 3, 1, launch_lds<conv_wgrad_pipe_kernel<3, 1, 6, 9>, WgradParams>}, {1, 3, 2, launch_lds<conv_wgrad_pipe_kernel<3, 2, 6, 9>, WgradParams>},
+    {0, 1, 1, launch_lds<conv_wgrad_kernel<1, 1>, WgradParams>},            {0, 1, 2, launch_lds<conv_wgrad_kernel<1, 2>, WgradParams>},
+    {0, 3, 1, launch_lds<conv_wgrad_kernel<3, 1>, WgradParams>},            {0, 3, 2, launch_lds<conv_wgrad_kernel<3, 2>, WgradParams>},
+    {0, 4, 2, launch_lds<conv_wgrad_kernel<4, 2>, WgradParams>},
+};
+
+// one launch, as the entry point, the workspace query and mp_conv_wgrad_launch_words build it
+struct WgradLaunch {
+    WgradParams p;
+    size_t lds, count;
+    dim3 grid;
+    const WgradKernel* kern;
+    size_t workspace_bytes() const { return (size_t)p.splits * count * sizeof(float); }
+};
+static int wgrad_prepare(const mp_conv_desc* d, WgradLaunch& L) {
+    const int rc = wgrad_geometry(d, L.p, L.lds);
+    if (rc != MP_OK) return rc;
+    L.count = wgrad_count(d);
+    L.grid = dim3(((L.p.Cout + 31) / 32) * L.p.ci_tiles, L.p.splits);
+    for (const WgradKernel& k : kWgradKernels)
+        if (k.vec == L.p.vec && k.ks == d->kh && k.s == d->stride) L.kern = &k;
+    return L.kern ? MP_OK : MP_ERR_UNSUPPORTED;
+}
+
 }  // namespace mp
 
 using namespace mp;
@@ -386,49 +434,43 @@ using namespace mp;
 extern "C" {
 
 size_t mp_conv_wgrad_workspace_bytes(const mp_conv_desc* desc) {
-    WgradParams p{};
-    size_t lds = 0;
-    if (wgrad_geometry(desc, p, lds) != MP_OK) return 0;
-    return (size_t)p.splits * p.Cout * p.Cin * desc->kh * desc->kw * sizeof(float);
+    WgradLaunch L{};
+    return wgrad_prepare(desc, L) == MP_OK ? L.workspace_bytes() : 0;
 }
 
 int mp_conv_wgrad(const mp_conv_desc* desc, const float* x, const float* dz, float* dw, int accumulate, void* workspace,
                   size_t workspace_bytes, mp_stream_t stream) {
     if (!x || !dz || !dw) return MP_ERR_NULL;
-    WgradParams p{};
-    size_t lds = 0;
-    int rc = wgrad_geometry(desc, p, lds);
+    WgradLaunch L{};
+    int rc = wgrad_prepare(desc, L);
     if (rc != MP_OK) return rc;
-    const size_t count = (size_t)p.Cout * p.Cin * desc->kh * desc->kw;
-    if (!workspace || workspace_bytes < (size_t)p.splits * count * sizeof(float)) return MP_ERR_WORKSPACE;
-    p.x = x; p.dz = dz; p.slabs = reinterpret_cast<float*>(workspace);
-    hipStream_t s = as_stream(stream);
-    dim3 grid(((p.Cout + 31) / 32) * p.ci_tiles, p.splits), block(256);
-    if (p.vec) {
-        if (desc->kh == 3 && desc->stride == 1) rc = launch_lds<conv_wgrad_pipe_kernel<3, 1, 6, 9>>(grid, block, lds, s, p);
-        else if (desc->kh == 3 && desc->stride == 2) rc = launch_lds<conv_wgrad_pipe_kernel<3, 2, 6, 9>>(grid, block, lds, s, p);
-        else if (desc->kh == 1 && desc->stride == 1) rc = launch_lds<conv_wgrad_pipe_kernel<1, 1, 6, 9>>(grid, block, lds, s, p);
-        else rc = launch_lds<conv_wgrad_pipe_kernel<1, 2, 6, 9>>(grid, block, lds, s, p);
-    } else {
-        if (desc->kh == 4) rc = launch_lds<conv_wgrad_kernel<4, 2>>(grid, block, lds, s, p);
-        else if (desc->kh == 3 && desc->stride == 1) rc = launch_lds<conv_wgrad_kernel<3, 1>>(grid, block, lds, s, p);
-        else if (desc->kh == 3 && desc->stride == 2) rc = launch_lds<conv_wgrad_kernel<3, 2>>(grid, block, lds, s, p);
-        else if (desc->kh == 1 && desc->stride == 1) rc = launch_lds<conv_wgrad_kernel<1, 1>>(grid, block, lds, s, p);
-        else rc = launch_lds<conv_wgrad_kernel<1, 2>>(grid, block, lds, s, p);
-    }
+    if (!workspace || workspace_bytes < L.workspace_bytes()) return MP_ERR_WORKSPACE;
+    L.p.x = x; L.p.dz = dz; L.p.slabs = reinterpret_cast<float*>(workspace);
+    rc = L.kern->launch(L.grid, dim3(256), L.lds, as_stream(stream), L.p);
     if (rc != MP_OK) return rc;
-    if (count <= 18432 && p.splits >= 64) {
-        hipLaunchKernelGGL(wgrad_reduce_grouped_kernel<16>, dim3((unsigned)((count + 15) / 16)), dim3(256), 0, s, p.slabs, dw, count,
-                           p.splits, accumulate ? 1 : 0);
-    } else if (count <= 73728 && p.splits >= 16) {
-        hipLaunchKernelGGL(wgrad_reduce_grouped_kernel<4>, dim3((unsigned)((count + 63) / 64)), dim3(256), 0, s, p.slabs, dw, count,
-                           p.splits, accumulate ? 1 : 0);
-    } else {
-        size_t blocks = (count + 255) / 256;
-        if (blocks > 4096) blocks = 4096;
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s, p.slabs, dw, count, p.splits, accumulate ? 1 : 0);
+    const WgradReduce red = wgrad_reduce_choice(L.count, L.p.splits);
+    if (red.G == 0) {
+        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3(red.blocks), dim3(256), 0, as_stream(stream), L.p.slabs, dw, L.count, L.p.splits,
+                           accumulate ? 1 : 0);
+        return check_launch();
     }
-    return check_launch();
+    WgradDst dst{};
+    dst.dw[0] = dw;
+    return wgrad_reduce_launch(L.p.slabs, dst, 1, L.count, L.p.splits, 1.0f, accumulate, as_stream(stream));
+}
+
+int mp_conv_wgrad_launch_words(const mp_conv_desc* desc, int half, int n_jobs, int64_t* out, int cap) {
+    if (!out) return MP_ERR_NULL;
+    if (half) return wgrad16_launch_words(desc, n_jobs, out, cap);
+    WgradLaunch L{};
+    const int rc = n_jobs < 0 || n_jobs > 1 ? MP_ERR_SHAPE : wgrad_prepare(desc, L);
+    if (rc != MP_OK) return wgrad_words_out(out, cap, rc, {});
+    const WgradParams& p = L.p;
+    const WgradReduce red = wgrad_reduce_choice(L.count, p.splits);
+    return wgrad_words_out(out, cap, rc,
+                           {p.N, p.Cin, p.H, p.W, p.Cout, p.Ho, p.Wo, p.pad, p.R, p.Rin, p.Wp, p.xplane, p.zpitch, p.tiles_y, p.n_tiles, p.splits,
+                            p.ci_tiles, p.vec, p.zq, p.xw4, L.grid.x, L.grid.y, L.grid.z, 256, (int64_t)L.lds, 0, L.kern->vec, L.kern->ks,
+                            L.kern->s, red.G, red.blocks, 1});
 }
 
 }  // extern "C"

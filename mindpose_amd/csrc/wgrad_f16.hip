@@ -17,6 +17,7 @@
 // next tile's 16-byte range-checked buffer loads in flight during the MFMA loop.
 #include "common.h"
 #include "conv_f16_dev.h"
+#include "wgrad_common.h"
 
 namespace mp {
 
@@ -47,13 +48,26 @@ struct Wgrad16Params {
     unsigned magic_px;
     unsigned magic_xs, magic_zs, magic_p;
     // grouped launch (mp_f16_conv_wgrad_grouped): blockIdx.z = job, up to kWgradJobs layers of ONE shape; the operand pointers
-    // travel by value in the kernel arguments (nothing to upload, hipGraph-capturable); n_jobs == 0: the single-layer launch
+    // travel by value in the kernel arguments (nothing to upload, hipGraph-capturable); n_jobs == 0: the single-layer launch, which
+    // reads x / dz (the z extent of a launch - workgroups, slabs, reduce - is Wgrad16Launch::jobs)
     int n_jobs;
-    const void* jx[8];
-    const void* jdz[8];
-    float* jdw[8];
+    const void* jx[kWgradJobs];
+    const void* jdz[kWgradJobs];
 };
-constexpr int kWgradJobs = 8;
+
+// The four forms: the tile a workgroup owns and the layers that take it.  A tile side is 8 channels per block wide:
+// 32 x 32 (cout x cin), 64 x 64 (wide), 64 x 16 (narrow, the 3-channel stem), and 32 x 32 again for the register-staged kernel.
+enum { kForm32 = 0, kFormWide = 1, kFormNarrow = 2, kFormReg = 3 };  // (the first three are Wgrad16Params::wide)
+struct WgradForm {
+    int tbx, tbz;  // 8-channel blocks per tile side (input, gradient)
+    int np;        // DMA pieces per wave and tile the kernels are built for (wide: 4 T accumulators per lane, the piece descriptors must stay small)
+    int ks_min, ks_max, cin_min, cin_max, cout_min;  // the layers the form is for ...
+    const char* knob;                                // ... unless this MP_* knob is 0 (A/B)
+};
+constexpr WgradForm kForms[4] = {{4, 4, 28, 1, 4, 1, 1 << 30, 1, nullptr},
+                                 {8, 8, 12, 1, 3, 33, 1 << 30, 33, "MP_WGRAD16_WIDE"},  // 1x1 / 3x3, more than 32 channels on both sides
+                                 {2, 8, 28, 3, 3, 1, 16, 17, "MP_WGRAD16_NARROW"},      // 3x3, at most 16 input channels, more than 16 couts
+                                 {4, 4, 0, 1, 4, 1, 1 << 30, 1, nullptr}};
 
 // The operand pointers of this workgroup's job (blockIdx.z).  Written as selects over CONSTANT indices: a dynamic index into the
 // by-value argument struct made the compiler copy the whole struct to scratch memory, and every later read of a launch parameter
@@ -374,9 +388,9 @@ struct WgradTaps2 {
 // MODE 0: 32 x 32 tile, wave = (16 couts, 16 cins) quarter.  1 (wide): 64 x 64 tile, wave = 32 x 32 quarter (see above).
 // 2 (narrow, layers with <= 16 input channels - the 3-channel stem): 64 couts x 16 cins, wave w = couts 16 w .. 16 w + 15: no wave
 //   multiplies all-zero channels, the input rows are copied once for all 64 couts and only two channel blocks of them.
-template <int KS, int S, int NP, int MODE = 0>
+template <int KS, int S, int MODE>
 __device__ __forceinline__ void wgrad_dma_body(const Wgrad16Params& p) {
-    constexpr int T = KS * KS;
+    constexpr int T = KS * KS, NP = kForms[MODE].np;
     extern __shared__ __attribute__((aligned(16))) u32x4 smem16[];
     // per buffer: [4][xslots] input image, padding up to a whole DMA piece, [4][zslots] gradient image, padding likewise
     const int buf_units = p.pieces * 64;
@@ -399,7 +413,7 @@ __device__ __forceinline__ void wgrad_dma_body(const Wgrad16Params& p) {
     // DMA piece descriptors, decoded once: piece = 64 consecutive slots of the buffer; slot -> (image kind, block, row, column)
     unsigned piece_rel[NP];  // byte offset relative to the tile origin of its tensor; kOob = padding slot
     int piece_row[NP];       // row within the tile, bit 30 set = gradient image
-    constexpr int TBX = MODE == 1 ? 8 : MODE == 2 ? 2 : 4, TBZ = MODE == 0 ? 4 : 8;  // 8-channel blocks per tile side (input, gradient)
+    constexpr int TBX = kForms[MODE].tbx, TBZ = kForms[MODE].tbz;
     const int x_units = TBX * p.xslots, z_units = TBZ * p.zslots;
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
@@ -480,10 +494,10 @@ __device__ __forceinline__ void wgrad_dma_body(const Wgrad16Params& p) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int cs = i >> 1, is = i & 1;
-            const int ci = ci_tile * 64 + ci_sub * 32 + is * 16 + (lane & 15);
+            const int ci = ci_tile * (8 * TBX) + ci_sub * 32 + is * 16 + (lane & 15);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const int co = co_tile * 64 + co_sub * 32 + cs * 16 + 4 * g + r;
+                const int co = co_tile * (8 * TBZ) + co_sub * 32 + cs * 16 + 4 * g + r;
                 if (co < p.Cout && ci < p.Cin) {
 #pragma unroll
                     for (int tp = 0; tp < T; ++tp) slab[((size_t)co * p.Cin + ci) * T + tp] = acc[tp][cs][is][r];
@@ -524,10 +538,10 @@ __device__ __forceinline__ void wgrad_dma_body(const Wgrad16Params& p) {
 
     // D: lane holds couts 4g .. 4g+3 (rows) of cin (lane & 15) (column) -> slab [Cout][Cin][T]
     float* slab = p.slabs + ((size_t)blockIdx.z * p.splits + blockIdx.y) * p.Cout * p.Cin * T;
-    const int ci = ci_tile * (MODE == 2 ? 16 : 32) + ci_sub * 16 + (lane & 15);
+    const int ci = ci_tile * (8 * TBX) + ci_sub * 16 + (lane & 15);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-        const int co = co_tile * (MODE == 2 ? 64 : 32) + co_sub * 16 + 4 * g + r;
+        const int co = co_tile * (8 * TBZ) + co_sub * 16 + 4 * g + r;
         if (co < p.Cout && ci < p.Cin) {
 #pragma unroll
             for (int tp = 0; tp < T; ++tp) slab[((size_t)co * p.Cin + ci) * T + tp] = acc[tp][r];
@@ -535,142 +549,114 @@ __device__ __forceinline__ void wgrad_dma_body(const Wgrad16Params& p) {
     }
 }
 
-struct WgradDst {  // destinations of a grouped reduce: blockIdx.y = job
-    float* dw[8];
+__global__ __launch_bounds__(256, 2) void conv_wgrad_f16_dma_k1s1(const Wgrad16Params p) { wgrad_dma_body<1, 1, kForm32>(p); }
+__global__ __launch_bounds__(256, 2) void conv_wgrad_f16_dma_k1s2(const Wgrad16Params p) { wgrad_dma_body<1, 2, kForm32>(p); }
+__global__ __launch_bounds__(256, 2) void conv_wgrad_f16_dma_k3s1(const Wgrad16Params p) { wgrad_dma_body<3, 1, kForm32>(p); }
+__global__ __launch_bounds__(256, 2) void conv_wgrad_f16_dma_k3s2(const Wgrad16Params p) { wgrad_dma_body<3, 2, kForm32>(p); }
+__global__ __launch_bounds__(256, 2) void conv_wgrad_f16_dma_k4s2(const Wgrad16Params p) { wgrad_dma_body<4, 2, kForm32>(p); }
+__global__ __launch_bounds__(256, 2) void conv_wgrad_f16_dmak_k1s1(const Wgrad16Params p) { wgrad_dma_body<1, 1, kFormWide>(p); }
+__global__ __launch_bounds__(256, 2) void conv_wgrad_f16_dmak_k1s2(const Wgrad16Params p) { wgrad_dma_body<1, 2, kFormWide>(p); }
+__global__ __launch_bounds__(256, 2) void conv_wgrad_f16_dmak_k3s1(const Wgrad16Params p) { wgrad_dma_body<3, 1, kFormWide>(p); }
+__global__ __launch_bounds__(256, 2) void conv_wgrad_f16_dmak_k3s2(const Wgrad16Params p) { wgrad_dma_body<3, 2, kFormWide>(p); }
+__global__ __launch_bounds__(256, 2) void conv_wgrad_f16_dman_k3s1(const Wgrad16Params p) { wgrad_dma_body<3, 1, kFormNarrow>(p); }
+__global__ __launch_bounds__(256, 2) void conv_wgrad_f16_dman_k3s2(const Wgrad16Params p) { wgrad_dma_body<3, 2, kFormNarrow>(p); }
+
+constexpr int kNZ = 4, kNX = 10;  // 16-byte staging units per thread of the register-staged kernel (gradient, input)
+
+// The sixteen kernels, keyed by (form, kernel size, stride)
+struct Wgrad16Kernel {
+    int form, ks, s;
+    int (*launch)(dim3, dim3, size_t, hipStream_t, const Wgrad16Params&);
+};
+const Wgrad16Kernel kWgrad16Kernels[] = {
+    {kForm32, 1, 1, launch_lds<conv_wgrad_f16_dma_k1s1, Wgrad16Params>},
+    {kForm32, 1, 2, launch_lds<conv_wgrad_f16_dma_k1s2, Wgrad16Params>},
+    {kForm32, 3, 1, launch_lds<conv_wgrad_f16_dma_k3s1, Wgrad16Params>},
+    {kForm32, 3, 2, launch_lds<conv_wgrad_f16_dma_k3s2, Wgrad16Params>},
+    {kForm32, 4, 2, launch_lds<conv_wgrad_f16_dma_k4s2, Wgrad16Params>},
+    {kFormWide, 1, 1, launch_lds<conv_wgrad_f16_dmak_k1s1, Wgrad16Params>},
+    {kFormWide, 1, 2, launch_lds<conv_wgrad_f16_dmak_k1s2, Wgrad16Params>},
+    {kFormWide, 3, 1, launch_lds<conv_wgrad_f16_dmak_k3s1, Wgrad16Params>},
+    {kFormWide, 3, 2, launch_lds<conv_wgrad_f16_dmak_k3s2, Wgrad16Params>},
+    {kFormNarrow, 3, 1, launch_lds<conv_wgrad_f16_dman_k3s1, Wgrad16Params>},
+    {kFormNarrow, 3, 2, launch_lds<conv_wgrad_f16_dman_k3s2, Wgrad16Params>},
+    {kFormReg, 1, 1, launch_lds<conv_wgrad_f16_kernel<1, 1, kNZ, kNX>, Wgrad16Params>},
+    {kFormReg, 1, 2, launch_lds<conv_wgrad_f16_kernel<1, 2, kNZ, kNX>, Wgrad16Params>},
+    {kFormReg, 3, 1, launch_lds<conv_wgrad_f16_kernel<3, 1, kNZ, kNX>, Wgrad16Params>},
+    {kFormReg, 3, 2, launch_lds<conv_wgrad_f16_kernel<3, 2, kNZ, kNX>, Wgrad16Params>},
+    {kFormReg, 4, 2, launch_lds<conv_wgrad_f16_kernel<4, 2, kNZ, kNX>, Wgrad16Params>},
 };
 
-__global__ __launch_bounds__(256) void wgrad16_reduce_kernel(const float* __restrict__ slabs, WgradDst dst, size_t count,
-                                                             int splits, float scale, int accumulate) {
-    float* __restrict__ dw = dst.dw[blockIdx.y];
-    slabs += (size_t)blockIdx.y * splits * count;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (size_t)gridDim.x * blockDim.x) {
-        float part[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        int k = 0;
-        for (; k + 8 <= splits; k += 8) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) part[j] += slabs[(size_t)(k + j) * count + i];
-        }
-        for (int j = 0; k < splits; ++k, ++j) part[j] += slabs[(size_t)k * count + i];
-        const float v = (((part[0] + part[1]) + (part[2] + part[3])) + ((part[4] + part[5]) + (part[6] + part[7]))) * scale;
-        dw[i] = accumulate ? dw[i] + v : v;
-    }
+bool form_takes(const WgradForm& f, int KS, int cin, int cout) {
+    if (KS < f.ks_min || KS > f.ks_max || cin < f.cin_min || cin > f.cin_max || cout < f.cout_min) return false;
+    const char* e = f.knob ? knob(f.knob) : nullptr;
+    return !e || atoi(e) != 0;
 }
 
-// The same reduction for SMALL weights: with |dW| = 9 K floats (the 32-channel layers) the kernel above is 36 blocks of
-// threads that each walk 512 slabs serially - latency-bound at ~25 us.  Here a block serves 256 / G elements with G threads
-// per element, thread g summing slabs g, g + G, ... (four interleaved partial sums), then a fixed-order combine through LDS
-// (deterministic): G times the blocks, 1 / G of the serial depth.
-template <int G>
-__global__ __launch_bounds__(256) void wgrad16_reduce_grouped_kernel(const float* __restrict__ slabs, WgradDst dst,
-                                                                     size_t count, int splits, float scale, int accumulate) {
-    float* __restrict__ dw = dst.dw[blockIdx.y];
-    slabs += (size_t)blockIdx.y * splits * count;
-    constexpr int E = 256 / G;
-    __shared__ float sm[G][E];
-    const int e = threadIdx.x % E, g = threadIdx.x / E;
-    const size_t i = (size_t)blockIdx.x * E + e;
-    float part[4] = {0.f, 0.f, 0.f, 0.f};
-    if (i < count) {
-        int k = g, j = 0;
-        for (; k + 3 * G < splits; k += 4 * G) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) part[u] += slabs[(size_t)(k + u * G) * count + i];
-        }
-        for (; k < splits; k += G, ++j) part[j] += slabs[(size_t)k * count + i];
+// The tallest tile (R <= 16 output rows) whose LDS image fits the budget.  R fixes the staged input rows Rin, the positions K of
+// the tile's k-steps (a multiple of 32) and the positions the input image must hold: the furthest one the last k-step's last tap
+// reads, and every staged row - with the rows split into two parity planes (geometry_dma) per plane, tap rows and staged rows
+// halved.  bytes(): the LDS bytes of the form for p as it stands, 0 = the form cannot take this R.
+template <typename Bytes>
+bool fit_rows(Wgrad16Params& p, int KS, int S, bool planes, size_t budget, size_t& lds_bytes, Bytes bytes) {
+    for (int R = p.Ho < 16 ? p.Ho : 16; R >= 1; --R) {
+        p.R = R;
+        p.Rin = (R - 1) * S + KS;
+        p.K = (R * p.P + 31) / 32 * 32;
+        const int tap_rows = planes ? (KS - 1) >> 1 : KS - 1, rows = planes ? (p.Rin + 1) >> 1 : p.Rin;
+        int need = S * (p.K - 1) + tap_rows * p.Px + (KS - 1) + 1;
+        if (need < rows * p.Px) need = rows * p.Px;
+        p.plane_slots = planes ? need : 0;
+        p.xrows = planes ? 2 * need : need;
+        lds_bytes = bytes();
+        if (lds_bytes != 0 && lds_bytes <= budget) return true;
     }
-    sm[g][e] = (part[0] + part[1]) + (part[2] + part[3]);
-    __syncthreads();
-    if (g == 0 && i < count) {
-        float v = 0.f;
-#pragma unroll
-        for (int q = 0; q < G; ++q) v += sm[q][e];
-        v *= scale;
-        dw[i] = accumulate ? dw[i] + v : v;
-    }
+    return false;
 }
 
-constexpr int kDmaPieces = 28;  // DMA pieces per wave and tile the LDS-DMA kernel is built for
-constexpr int kDmaPiecesK = 12;  // ... and its wide form (4 T accumulators per lane: the piece descriptors must stay small)
-__global__ __launch_bounds__(256, 2) void conv_wgrad_f16_dma_k1s1(const Wgrad16Params p) { wgrad_dma_body<1, 1, kDmaPieces>(p); }
-__global__ __launch_bounds__(256, 2) void conv_wgrad_f16_dma_k1s2(const Wgrad16Params p) { wgrad_dma_body<1, 2, kDmaPieces>(p); }
-__global__ __launch_bounds__(256, 2) void conv_wgrad_f16_dma_k3s1(const Wgrad16Params p) { wgrad_dma_body<3, 1, kDmaPieces>(p); }
-__global__ __launch_bounds__(256, 2) void conv_wgrad_f16_dma_k3s2(const Wgrad16Params p) { wgrad_dma_body<3, 2, kDmaPieces>(p); }
-__global__ __launch_bounds__(256, 2) void conv_wgrad_f16_dma_k4s2(const Wgrad16Params p) { wgrad_dma_body<4, 2, kDmaPieces>(p); }
-__global__ __launch_bounds__(256, 2) void conv_wgrad_f16_dmak_k1s1(const Wgrad16Params p) { wgrad_dma_body<1, 1, kDmaPiecesK, 1>(p); }
-__global__ __launch_bounds__(256, 2) void conv_wgrad_f16_dmak_k1s2(const Wgrad16Params p) { wgrad_dma_body<1, 2, kDmaPiecesK, 1>(p); }
-__global__ __launch_bounds__(256, 2) void conv_wgrad_f16_dmak_k3s1(const Wgrad16Params p) { wgrad_dma_body<3, 1, kDmaPiecesK, 1>(p); }
-__global__ __launch_bounds__(256, 2) void conv_wgrad_f16_dmak_k3s2(const Wgrad16Params p) { wgrad_dma_body<3, 2, kDmaPiecesK, 1>(p); }
-__global__ __launch_bounds__(256, 2) void conv_wgrad_f16_dman_k3s1(const Wgrad16Params p) { wgrad_dma_body<3, 1, kDmaPieces, 2>(p); }
-__global__ __launch_bounds__(256, 2) void conv_wgrad_f16_dman_k3s2(const Wgrad16Params p) { wgrad_dma_body<3, 2, kDmaPieces, 2>(p); }
-
-// LDS-DMA form of the same decomposition: two buffers of [4][xslots] + [4][zslots] elements; false = does not fit (the
-// register-staged kernel serves the shape).  MP_WGRAD16_DMA=0 switches it off (A/B).
+// LDS-DMA form of the same decomposition: two buffers of [tbx][xslots] + [tbz][zslots] elements; false = does not fit (the
+// register-staged kernel serves the shape, and p is as it was).  MP_WGRAD16_DMA=0 switches it off (A/B).
 bool geometry_dma(Wgrad16Params& p, int KS, int S, size_t& lds_bytes) {
     if (const char* e = knob("MP_WGRAD16_DMA"))
         if (atoi(e) == 0) return false;
-    // wide form (64 x 64 tile per workgroup): 1x1 / 3x3 layers with more than 32 channels on both sides
-    bool wide = KS <= 3 && p.Cin > 32 && p.Cout > 32;
-    if (const char* e = knob("MP_WGRAD16_WIDE")) wide = wide && atoi(e) != 0;
     // Stride 2: the position trick needs (input position) = 2 x (gradient position) + (tap offset), i.e. the gradient rows on the
     // pitch of the INPUT rows - with one linear input image that is 2 Wo + 2 positions per gradient row of Wo, half of every
     // k-step multiplying zeros.  With the tile's input rows split by parity into two planes (tile row i -> plane i & 1, row i >> 1;
     // tap row ky reads plane ky & 1 from row ky >> 1 on) the input pitch Px belongs to ONE plane and the gradient pitch is Px / 2.
     bool planes = S == 2;
     if (const char* e = knob("MP_WGRAD16_PLANES")) planes = planes && atoi(e) != 0;
-    const int P0 = p.P, Px0 = p.Px;
+    Wgrad16Params q = p;
     if (planes) {
-        p.P = (p.W + 2 * p.pad + 1) / 2 > p.Wo ? (p.W + 2 * p.pad + 1) / 2 : p.Wo;
-        p.Px = 2 * p.P;
+        q.P = (q.W + 2 * q.pad + 1) / 2 > q.Wo ? (q.W + 2 * q.pad + 1) / 2 : q.Wo;
+        q.Px = 2 * q.P;
     }
-    // narrow form (64 couts x 16 cins): 3x3 layers with at most 16 input channels
-    bool narrow = KS == 3 && p.Cin <= 16 && p.Cout > 16;
-    if (const char* e = knob("MP_WGRAD16_NARROW")) narrow = narrow && atoi(e) != 0;
-    for (int w = wide ? 1 : narrow ? 2 : 0; w >= 0; w = w == 2 ? 0 : w - 1) {
-        const int tbx = w == 1 ? 8 : w == 2 ? 2 : 4, tbz = w ? 8 : 4;  // 8-channel blocks per tile side (input, gradient)
-        const int np = w == 1 ? kDmaPiecesK : kDmaPieces;
-        for (int pass = 0; pass < 2; ++pass) {
-            const size_t budget = pass == 0 ? 78 * 1024 : 150 * 1024;
-            for (int R = p.Ho < 16 ? p.Ho : 16; R >= 1; --R) {
-                const int Rin = (R - 1) * S + KS;
-                const int K = (R * p.P + 31) / 32 * 32;
-                int xneed = S * (K - 1) + (KS - 1) * p.Px + (KS - 1) + 1;
-                if (xneed < Rin * p.Px) xneed = Rin * p.Px;
-                int plane_slots = 0;
-                if (planes) {  // per plane: the furthest position a k-step reads, and every row the plane holds
-                    plane_slots = S * (K - 1) + ((KS - 1) >> 1) * p.Px + (KS - 1) + 1;
-                    if (plane_slots < ((Rin + 1) >> 1) * p.Px) plane_slots = ((Rin + 1) >> 1) * p.Px;
-                    xneed = 2 * plane_slots;
-                }
+    // the wide or the narrow form where the layer takes one, then 32 x 32; per form two workgroups per CU, then whatever fits
+    const int first = form_takes(kForms[kFormWide], KS, q.Cin, q.Cout) ? kFormWide : form_takes(kForms[kFormNarrow], KS, q.Cin, q.Cout) ? kFormNarrow : kForm32;
+    for (int w = first;; w = kForm32) {
+        const WgradForm& f = kForms[w];
+        for (size_t budget : {78 * 1024, 150 * 1024}) {
+            const bool fits = fit_rows(q, KS, S, planes, budget, lds_bytes, [&]() -> size_t {
                 // == 4 (mod 16): the two channel blocks a 16-lane group reads are 64 B apart modulo the 256-byte bank row
-                const int xslots = (xneed + 11) / 16 * 16 + 4, zslots = K + 4 + ((K % 16) ? 16 - K % 16 : 0);
-                const int x_pieces = (tbx * xslots + 63) / 64, z_pieces = (tbz * zslots + 63) / 64;
-                const int pieces = x_pieces + z_pieces;
-                const size_t bytes = (size_t)2 * pieces * 64 * 16;
-                if (pieces > 4 * np || bytes > budget) continue;
-                p.R = R; p.Rin = Rin; p.K = K; p.xrows = xneed; p.nbuf = 2;
-                p.xslots = xslots; p.zslots = zslots; p.pieces = pieces; p.x_pieces = x_pieces; p.z_base = x_pieces * 64;
-                p.magic_xs = magic_of(xslots); p.magic_zs = magic_of(zslots); p.magic_p = magic_of(p.P); p.magic_px = magic_of(p.Px);
-                p.plane_slots = plane_slots;
-                p.wide = w;
-                lds_bytes = bytes;
-                return true;
-            }
+                q.xslots = (q.xrows + 11) / 16 * 16 + 4;
+                q.zslots = q.K + 4 + ((q.K % 16) ? 16 - q.K % 16 : 0);
+                q.x_pieces = (f.tbx * q.xslots + 63) / 64;
+                q.pieces = q.x_pieces + (f.tbz * q.zslots + 63) / 64;
+                return q.pieces > 4 * f.np ? 0 : (size_t)2 * q.pieces * 64 * 16;
+            });
+            if (!fits) continue;
+            q.nbuf = 2;
+            q.z_base = q.x_pieces * 64;
+            q.magic_xs = magic_of(q.xslots); q.magic_zs = magic_of(q.zslots); q.magic_p = magic_of(q.P); q.magic_px = magic_of(q.Px);
+            q.wide = w;
+            p = q;
+            return true;
         }
+        if (w == kForm32) return false;
     }
-    p.P = P0; p.Px = Px0;  // the register-staged kernel keeps the single linear image
-    return false;
 }
 
-constexpr int kNZ = 4, kNX = 10;
-
-int geometry(const mp_conv_desc* d, Wgrad16Params& p, size_t& lds_bytes, int n_jobs = 1) {
-    if (!d) return MP_ERR_NULL;
-    if (d->n <= 0 || d->cin <= 0 || d->cout <= 0 || d->h <= 0 || d->w <= 0 || d->conv_h <= 0 || d->conv_w <= 0) return MP_ERR_SHAPE;
-    // 1x1 / 3x3 with padding k/2, or the 4x4 stride-2 padding-1 form (the transposed convolution's weight gradient)
-    if (d->kh != d->kw || !(d->kh == 1 || d->kh == 3 || d->kh == 4)) return MP_ERR_UNSUPPORTED;
-    if (!(d->stride == 1 || d->stride == 2)) return MP_ERR_UNSUPPORTED;
-    if (d->pad_top != d->pad_left) return MP_ERR_UNSUPPORTED;
-    if (d->kh == 4 ? (d->stride != 2 || d->pad_top != 1) : (d->pad_top != d->kh / 2)) return MP_ERR_UNSUPPORTED;
+int geometry(const mp_conv_desc* d, Wgrad16Params& p, size_t& lds_bytes, int jobs) {
+    if (const int rc = wgrad_desc_ok(d)) return rc;
     const int S = d->stride, KS = d->kh;
     p.N = d->n; p.Cin = d->cin; p.C8in = (d->cin + 7) / 8; p.H = d->h; p.W = d->w;
     p.Cout = d->cout; p.C8out = (d->cout + 7) / 8; p.Ho = d->conv_h; p.Wo = d->conv_w; p.pad = d->pad_top;
@@ -679,30 +665,21 @@ int geometry(const mp_conv_desc* d, Wgrad16Params& p, size_t& lds_bytes, int n_j
     // common pitch: a row holds the Wo gradient columns and the W + 2*pad input columns
     p.P = p.W + 2 * p.pad > p.Wo ? p.W + 2 * p.pad : p.Wo;
     p.Px = p.P;
-    // pass 0: double-buffered, two workgroups per CU; pass 1: double-buffered, whatever fits; pass 2: single buffer
-    p.pieces = 0;
-    p.wide = 0;
-    p.plane_slots = 0;
     bool found = geometry_dma(p, KS, S, lds_bytes);  // the LDS-DMA form where its tiles fit (p.pieces > 0 marks it)
+    // register-staged: pass 0: double-buffered, two workgroups per CU; pass 1: double-buffered, whatever fits; pass 2: single buffer
     for (int pass = 0; pass < 3 && !found; ++pass) {
         p.nbuf = pass < 2 ? 2 : 1;
-        const size_t budget = pass == 0 ? 78 * 1024 : 150 * 1024;
-        for (int R = p.Ho < 16 ? p.Ho : 16; R >= 1; --R) {
-            p.R = R;
-            p.Rin = (R - 1) * S + KS;
-            p.K = (R * p.P + 31) / 32 * 32;
-            p.xrows = S * (p.K - 1) + (KS - 1) * p.Px + (KS - 1) + 1;
-            if (p.xrows < p.Rin * p.Px) p.xrows = p.Rin * p.Px;
-            lds_bytes = (size_t)p.nbuf * (p.K + p.xrows) * kRowHalfs * 2;
-            if (R * p.Wo * 4 <= kNZ * 256 && p.Rin * p.W * 4 <= kNX * 256 && lds_bytes <= budget) { found = true; break; }
-        }
+        found = fit_rows(p, KS, S, false, pass == 0 ? 78 * 1024 : 150 * 1024, lds_bytes, [&]() -> size_t {
+            const bool staged = p.R * p.Wo * 4 <= kNZ * 256 && p.Rin * p.W * 4 <= kNX * 256;
+            return staged ? (size_t)p.nbuf * (p.K + p.xrows) * kRowHalfs * 2 : 0;
+        });
     }
     if (!found) return MP_ERR_UNSUPPORTED;
     p.tiles_y = (p.Ho + p.R - 1) / p.R;
     p.tiles = p.N * p.tiles_y;
-    const int tw_o = p.wide ? 64 : 32, tw_i = p.wide == 1 ? 64 : p.wide == 2 ? 16 : 32;  // channels per tile side
-    p.ci_tiles = (p.Cin + tw_i - 1) / tw_i;
-    p.co_tiles = (p.Cout + tw_o - 1) / tw_o;
+    const WgradForm& f = kForms[p.pieces > 0 ? p.wide : kFormReg];
+    p.ci_tiles = (p.Cin + 8 * f.tbx - 1) / (8 * f.tbx);
+    p.co_tiles = (p.Cout + 8 * f.tbz - 1) / (8 * f.tbz);
     const int ct = p.co_tiles * p.ci_tiles;
     int target = 512;  // two workgroups per CU; the slab reduce reads splits x |dW| floats, so no finer than that
     if (const char* e = knob("MP_WGRAD16_WGS")) {  // experiments: total workgroups per launch
@@ -712,7 +689,7 @@ int geometry(const mp_conv_desc* d, Wgrad16Params& p, size_t& lds_bytes, int n_j
     // a grouped launch spreads ~768 workgroups over its layers: per layer fewer, longer pixel slabs - the slab traffic (written here,
     // re-read by the reduce) and the per-workgroup prologue / epilogue shrink by the group size
     // (a 64 x 64 tile's slab is four times the bytes: the wide form stays at ~512 workgroups)
-    int splits = n_jobs > 1 ? (p.wide == 1 ? target : target + target / 2) / (ct * n_jobs) : target / ct;
+    int splits = jobs > 1 ? (p.wide == kFormWide ? target : target + target / 2) / (ct * jobs) : target / ct;
     if (splits < 1) splits = 1;
     if (splits > p.tiles) splits = p.tiles;
     p.tiles_per_split = (p.tiles + splits - 1) / splits;
@@ -722,110 +699,93 @@ int geometry(const mp_conv_desc* d, Wgrad16Params& p, size_t& lds_bytes, int n_j
     return MP_OK;
 }
 
-template <int KS, int S>
-int launch_wgrad16_dma(const Wgrad16Params& p, size_t lds, hipStream_t s) {
-    const dim3 grid(p.co_tiles * p.ci_tiles, p.splits, p.n_jobs ? p.n_jobs : 1), block(256);
-    if constexpr (KS == 3) {  // 16-channel input side
-        constexpr auto kern_n = S == 1 ? conv_wgrad_f16_dman_k3s1 : conv_wgrad_f16_dman_k3s2;
-        if (p.wide == 2) return launch_lds<kern_n>(grid, block, lds, s, p);
-    }
-    if constexpr (KS <= 3) {  // 64 x 64 tile
-        constexpr auto kern_k = KS == 3 ? (S == 1 ? conv_wgrad_f16_dmak_k3s1 : conv_wgrad_f16_dmak_k3s2)
-                                        : (S == 1 ? conv_wgrad_f16_dmak_k1s1 : conv_wgrad_f16_dmak_k1s2);
-        if (p.wide == 1) return launch_lds<kern_k>(grid, block, lds, s, p);
-    }
-    constexpr auto kern = KS == 4 ? conv_wgrad_f16_dma_k4s2
-                                  : KS == 3 ? (S == 1 ? conv_wgrad_f16_dma_k3s1 : conv_wgrad_f16_dma_k3s2)
-                                            : (S == 1 ? conv_wgrad_f16_dma_k1s1 : conv_wgrad_f16_dma_k1s2);
-    return launch_lds<kern>(grid, block, lds, s, p);
-}
-
-template <int KS, int S>
-int launch_wgrad16(const Wgrad16Params& p, size_t lds, hipStream_t s) {
-    if (p.pieces > 0) return launch_wgrad16_dma<KS, S>(p, lds, s);
-    return launch_lds<conv_wgrad_f16_kernel<KS, S, kNZ, kNX>>(dim3(p.co_tiles * p.ci_tiles, p.splits, p.n_jobs ? p.n_jobs : 1), dim3(256), lds, s, p);
-}
-
-// launches + fixed-order slab reduction of 1 .. kWgradJobs layers of one shape
-int wgrad16_run(const mp_conv_desc* desc, Wgrad16Params& p, size_t lds, const WgradDst& dst, int jobs, float scale, int accumulate,
-                hipStream_t s) {
-    int rc;
-    if (desc->kh == 4) rc = launch_wgrad16<4, 2>(p, lds, s);
-    else if (desc->kh == 3) rc = desc->stride == 1 ? launch_wgrad16<3, 1>(p, lds, s) : launch_wgrad16<3, 2>(p, lds, s);
-    else rc = desc->stride == 1 ? launch_wgrad16<1, 1>(p, lds, s) : launch_wgrad16<1, 2>(p, lds, s);
+// One launch pair - kernel + fixed-order slab reduce - of 1 .. kWgradJobs layers of one shape, as the entry points, the workspace
+// queries and mp_conv_wgrad_launch_words build it.  n_jobs = 0 is the single-layer launch; either way `jobs` is the z extent.
+struct Wgrad16Launch {
+    Wgrad16Params p;
+    size_t lds, count;
+    int jobs;
+    dim3 grid;
+    const Wgrad16Kernel* kern;
+    size_t workspace_bytes() const { return (size_t)jobs * p.splits * count * sizeof(float); }
+};
+int wgrad16_prepare(const mp_conv_desc* d, int n_jobs, Wgrad16Launch& L) {
+    if (n_jobs < 0 || n_jobs > kWgradJobs) return MP_ERR_SHAPE;
+    L.jobs = n_jobs ? n_jobs : 1;
+    const int rc = geometry(d, L.p, L.lds, L.jobs);
     if (rc != MP_OK) return rc;
-    const size_t count = (size_t)p.Cout * p.Cin * desc->kh * desc->kw;
-    if (count * 16 <= 147456 * 2 && p.splits >= 64) {  // <= 18 K weights (32-channel 3x3): 16 threads per element
-        hipLaunchKernelGGL(wgrad16_reduce_grouped_kernel<16>, dim3((unsigned)((count + 15) / 16), jobs), dim3(256), 0, s, p.slabs, dst, count,
-                           p.splits, scale, accumulate ? 1 : 0);
-    } else if (count * 4 <= 147456 * 2 && p.splits >= 16) {  // <= 74 K weights (64-channel 3x3, the 1x1 convs): 4 per element
-        hipLaunchKernelGGL(wgrad16_reduce_grouped_kernel<4>, dim3((unsigned)((count + 63) / 64), jobs), dim3(256), 0, s, p.slabs, dst, count,
-                           p.splits, scale, accumulate ? 1 : 0);
-    } else {
-        size_t blocks = (count + 255) / 256;
-        if (blocks > 4096) blocks = 4096;
-        hipLaunchKernelGGL(wgrad16_reduce_kernel, dim3((unsigned)blocks, jobs), dim3(256), 0, s, p.slabs, dst, count, p.splits, scale,
-                           accumulate ? 1 : 0);
+    L.p.n_jobs = n_jobs;
+    L.count = wgrad_count(d);
+    L.grid = dim3(L.p.co_tiles * L.p.ci_tiles, L.p.splits, L.jobs);
+    const int form = L.p.pieces > 0 ? L.p.wide : kFormReg;
+    for (const Wgrad16Kernel& k : kWgrad16Kernels)
+        if (k.form == form && k.ks == d->kh && k.s == d->stride) L.kern = &k;
+    return L.kern ? MP_OK : MP_ERR_UNSUPPORTED;
+}
+
+// x / dz / dw: one pointer each for the single-layer launch (n_jobs = 0), n_jobs of them for a grouped one
+int wgrad16_entry(const mp_conv_desc* desc, const void* const* x, const void* const* dz, float* const* dw, int n_jobs, float scale,
+                  int accumulate, void* workspace, size_t workspace_bytes, mp_stream_t stream) {
+    Wgrad16Launch L{};
+    int rc = wgrad16_prepare(desc, n_jobs, L);
+    if (rc != MP_OK) return rc;
+    if (!workspace || workspace_bytes < L.workspace_bytes()) return MP_ERR_WORKSPACE;
+    WgradDst dst{};
+    for (int j = 0; j < L.jobs; ++j) {
+        if (!x[j] || !dz[j] || !dw[j]) return MP_ERR_NULL;
+        if (n_jobs) { L.p.jx[j] = x[j]; L.p.jdz[j] = dz[j]; }
+        else { L.p.x = x[j]; L.p.dz = dz[j]; }
+        dst.dw[j] = dw[j];
     }
-    return check_launch();
+    L.p.slabs = reinterpret_cast<float*>(workspace);
+    rc = L.kern->launch(L.grid, dim3(256), L.lds, as_stream(stream), L.p);
+    if (rc != MP_OK) return rc;
+    return wgrad_reduce_launch(L.p.slabs, dst, L.jobs, L.count, L.p.splits, scale, accumulate, as_stream(stream));
+}
+
+size_t wgrad16_workspace(const mp_conv_desc* desc, int n_jobs) {
+    Wgrad16Launch L{};
+    return wgrad16_prepare(desc, n_jobs, L) == MP_OK ? L.workspace_bytes() : 0;
 }
 
 }  // namespace
+
+int wgrad16_launch_words(const mp_conv_desc* desc, int n_jobs, int64_t* out, int cap) {
+    Wgrad16Launch L{};
+    const int rc = wgrad16_prepare(desc, n_jobs, L);
+    if (rc != MP_OK) return wgrad_words_out(out, cap, rc, {});
+    const Wgrad16Params& p = L.p;
+    const WgradReduce red = wgrad_reduce_choice(L.count, p.splits);
+    return wgrad_words_out(out, cap, rc,
+                           {p.N, p.Cin, p.C8in, p.H, p.W, p.Cout, p.C8out, p.Ho, p.Wo, p.pad, p.R, p.P, p.Px, p.Rin, p.K, p.xrows, p.tiles_y, p.tiles,
+                            p.splits, p.tiles_per_split, p.ci_tiles, p.nbuf, p.magic_wo, p.magic_w, p.xslots, p.zslots, p.pieces, p.x_pieces, p.z_base,
+                            p.wide, p.co_tiles, p.plane_slots, p.magic_px, p.magic_xs, p.magic_zs, p.magic_p, p.n_jobs, L.grid.x, L.grid.y,
+                            L.grid.z, 256, (int64_t)L.lds, 1, L.kern->form, L.kern->ks, L.kern->s, red.G, red.blocks, L.jobs});
+}
+
 }  // namespace mp
 
 using namespace mp;
 
 extern "C" {
 
-size_t mp_f16_conv_wgrad_workspace_bytes(const mp_conv_desc* desc) {
-    Wgrad16Params p{};
-    size_t lds = 0;
-    if (geometry(desc, p, lds) != MP_OK) return 0;
-    return (size_t)p.splits * p.Cout * p.Cin * desc->kh * desc->kw * sizeof(float);
-}
+size_t mp_f16_conv_wgrad_workspace_bytes(const mp_conv_desc* desc) { return wgrad16_workspace(desc, 0); }
 
 int mp_f16_conv_wgrad(const mp_conv_desc* desc, const void* x, const void* dz, float* dw, float scale, int accumulate,
                       void* workspace, size_t workspace_bytes, mp_stream_t stream) {
     if (!x || !dz || !dw) return MP_ERR_NULL;
-    Wgrad16Params p{};
-    size_t lds = 0;
-    int rc = geometry(desc, p, lds);
-    if (rc != MP_OK) return rc;
-    const size_t count = (size_t)p.Cout * p.Cin * desc->kh * desc->kw;
-    if (!workspace || workspace_bytes < (size_t)p.splits * count * sizeof(float)) return MP_ERR_WORKSPACE;
-    p.x = x; p.dz = dz; p.slabs = reinterpret_cast<float*>(workspace);
-    WgradDst dst{};
-    dst.dw[0] = dw;
-    return wgrad16_run(desc, p, lds, dst, 1, scale, accumulate, as_stream(stream));
+    return wgrad16_entry(desc, &x, &dz, &dw, 0, scale, accumulate, workspace, workspace_bytes, stream);
 }
 
 size_t mp_f16_conv_wgrad_grouped_workspace_bytes(const mp_conv_desc* desc, int n_jobs) {
-    if (n_jobs < 1 || n_jobs > kWgradJobs) return 0;
-    Wgrad16Params p{};
-    size_t lds = 0;
-    if (geometry(desc, p, lds, n_jobs) != MP_OK) return 0;
-    return (size_t)n_jobs * p.splits * p.Cout * p.Cin * desc->kh * desc->kw * sizeof(float);
+    return n_jobs < 1 ? 0 : wgrad16_workspace(desc, n_jobs);
 }
 
 int mp_f16_conv_wgrad_grouped(const mp_conv_desc* desc, const void* const* x, const void* const* dz, float* const* dw, int n_jobs,
                               float scale, int accumulate, void* workspace, size_t workspace_bytes, mp_stream_t stream) {
     if (!x || !dz || !dw) return MP_ERR_NULL;
-    if (n_jobs < 1 || n_jobs > kWgradJobs) return MP_ERR_SHAPE;
-    Wgrad16Params p{};
-    size_t lds = 0;
-    int rc = geometry(desc, p, lds, n_jobs);
-    if (rc != MP_OK) return rc;
-    const size_t count = (size_t)p.Cout * p.Cin * desc->kh * desc->kw;
-    if (!workspace || workspace_bytes < (size_t)n_jobs * p.splits * count * sizeof(float)) return MP_ERR_WORKSPACE;
-    WgradDst dst{};
-    for (int j = 0; j < n_jobs; ++j) {
-        if (!x[j] || !dz[j] || !dw[j]) return MP_ERR_NULL;
-        p.jx[j] = x[j]; p.jdz[j] = dz[j]; p.jdw[j] = dw[j];
-        dst.dw[j] = dw[j];
-    }
-    p.n_jobs = n_jobs;
-    p.slabs = reinterpret_cast<float*>(workspace);
-    return wgrad16_run(desc, p, lds, dst, n_jobs, scale, accumulate, as_stream(stream));
+    if (n_jobs < 1) return MP_ERR_SHAPE;
+    return wgrad16_entry(desc, x, dz, dw, n_jobs, scale, accumulate, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

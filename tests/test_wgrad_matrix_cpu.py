@@ -4,8 +4,6 @@ Every row names its properties - kernel or form, tiles per workgroup, short tile
 kernel and tail; they are recomputed here from the restated geometry, and the restatement is held against the library's own
 workspace queries (host-only: no GPU).  A geometry change that moves a row off its path fails here and names the row.
 """
-import random
-
 import pytest
 
 from tests import wgrad_matrix as wm
@@ -43,6 +41,7 @@ def _check_common(geo, want, per_wg, cin, cout):
 def test_fp32_row_reaches_its_path(case, knobs, want):
     geo = _geo32(case, knobs)
     assert geo.splits == wm.lib_splits32(case, **knobs)
+    wm.check_geometry_against_launch(geo, wm.launch_words(case, 0, **knobs), 0)
     per_wg = tuple(len(t) for t in geo.tile_lists)
     _check_common(geo, want, per_wg, case[1], case[2])
     if "kernel" in want:
@@ -59,6 +58,7 @@ def test_fp32_row_reaches_its_path(case, knobs, want):
 def test_fp16_row_reaches_its_path(case, knobs, want):
     geo = _geo16(case, knobs)
     assert geo.splits == wm.lib_splits16(case, **wm.env16(knobs))
+    wm.check_geometry_against_launch(geo, wm.launch_words(case, 1, **wm.env16(knobs)), 1)
     per_split = tuple(len(t) for t in geo.tile_lists)
     assert per_split == (geo.tiles_per_split,) * (geo.splits - 1) + (geo.last_split,)
     _check_common(geo, want, per_split, case[1], case[2])
@@ -78,6 +78,7 @@ def test_fp16_row_reaches_its_path(case, knobs, want):
 def test_fp16_grouped_row_reaches_its_path(case, knobs, jobs):
     geo = _geo16(case, knobs, jobs)
     assert geo.splits == wm.lib_splits16(case, jobs, **wm.env16(knobs))
+    wm.check_geometry_against_launch(geo, wm.launch_words(case, 1, jobs, **wm.env16(knobs)), 1)
     assert geo.tiles_per_split >= 3 and wm.stale_short_tile(geo)
 
 
@@ -118,25 +119,17 @@ def test_fp16_table_hits_every_targeted_condition():
 
 
 def test_restated_geometry_agrees_with_the_library_on_random_shapes():
-    """Split counts of both restatements against the workspace queries, every form switch and the grouped query included."""
-    rng = random.Random(20240607)
-    checked = 0
+    """Split counts of both restatements against the workspace queries, every form switch and the grouped query included; form,
+    tile rows, k-steps, pitch, buffers, planes, tiles per split, LDS bytes and reduce kernel against the launch words."""
     forms = set()
-    while checked < 600:
-        k, s = rng.choice([(1, 1), (1, 2), (3, 1), (3, 2), (4, 2)])
-        case = (rng.randint(1, 40), rng.choice([3, 16, 17, 32, 40, 48, 64, 72, 128, 256, 390, 512]),
-                rng.choice([16, 17, 24, 32, 64, 80, 136, 250, 256, 500, 512]), k, s, rng.randint(2, 70), rng.randint(2, 220))
-        if k == 4 and (case[5] % 2 or case[6] % 2):
-            continue
-        checked += 1
-        simple = rng.random() < 0.3
+    for case, simple, knobs, jobs in wm.random_draws(600):
+        env32 = {"MP_WGRAD_SIMPLE": "1"} if simple else {}
         geo = wm.geometry32(*case, simple=simple)
-        assert (geo.splits if geo else 0) == wm.lib_splits32(case, **({"MP_WGRAD_SIMPLE": "1"} if simple else {})), (case, simple)
-        knobs = {"WGS": rng.choice([1, 2, 3, 4, 8, 12, 16, 64])} if rng.random() < 0.7 else {}
-        knobs.update({key: 0 for key in ("DMA", "WIDE", "PLANES", "NARROW") if rng.random() < 0.25})
-        jobs = rng.choice([1, 1, 2, 3, 8])
+        assert (geo.splits if geo else 0) == wm.lib_splits32(case, **env32), (case, simple)
+        wm.check_geometry_against_launch(geo, wm.launch_words(case, 0, **env32), 0)
         geo = _geo16(case, knobs, jobs)
         assert (geo.splits if geo else 0) == wm.lib_splits16(case, jobs, **wm.env16(knobs)), (case, knobs, jobs)
+        wm.check_geometry_against_launch(geo, wm.launch_words(case, 1, 0 if jobs == 1 else jobs, **wm.env16(knobs)), 1)
         if geo:
             forms.add((geo.form, geo.planes, geo.nbuf))
     assert {f for f, _, _ in forms} == {"dma32", "wide", "narrow", "reg"} and ("reg", False, 1) in forms

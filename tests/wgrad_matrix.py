@@ -5,10 +5,12 @@ pixel tiles and stages tile t + 1 into the other LDS buffer while the matrix cor
 workgroup ONE tile; the tables here are shapes (and MP_* knobs) that give a workgroup three tiles or more on every kernel
 instantiation, form and reduce kernel.  `geometry32` / `geometry16` restate `wgrad_geometry` and `geometry` / `geometry_dma` in
 Python so that each row can say which path it reaches; tests/test_wgrad_matrix_cpu.py asserts those properties and checks the
-restatement against the library's workspace queries (host-only), tests/test_gpu_wgrad_tiles.py runs the rows.
+restatement against the library's workspace queries and against the launch it builds (`launch_words`, host-only),
+tests/test_gpu_wgrad_tiles.py runs the rows.
 """
 import ctypes
 import functools
+import random
 from types import SimpleNamespace
 
 from mindpose_amd import _lib
@@ -103,8 +105,8 @@ def desc(case):
 
 # ---- geometry restatement -------------------------------------------------------------------------------------------------------
 def _reduce(count, splits):
-    """(kernel, unrolled rounds, (fewest, most) slabs a thread takes in the tail loop) of the slab reduce - the same thresholds in
-    conv_wgrad.hip and wgrad_f16.hip."""
+    """(kernel, unrolled rounds, (fewest, most) slabs a thread takes in the tail loop) of the slab reduce - the thresholds of
+    `wgrad_reduce_choice` (csrc/wgrad_common.h), restated: the independent check of the one place they live."""
     if count <= 18432 and splits >= 64:
         name, g = "grouped16", 16
     elif count <= 73728 and splits >= 16:
@@ -278,6 +280,62 @@ def lib_splits16(case, n_jobs=1, **env):
         nb = (lib.mp_f16_conv_wgrad_workspace_bytes(ctypes.byref(d)) if n_jobs == 1
               else lib.mp_f16_conv_wgrad_grouped_workspace_bytes(ctypes.byref(d), n_jobs))
     return nb // (n_jobs * case[1] * case[2] * case[3] * case[3] * 4)
+
+
+# mp_conv_wgrad_launch_words (include/mindpose_hip.h, host-only): the return code, then - after an accepted geometry - the
+# non-pointer fields of the kernel parameter block in declaration order, grid, block, LDS bytes, kernel id and slab reduce
+_LAUNCH = ["grid_x", "grid_y", "grid_z", "block", "lds_bytes", "half", "form", "ks", "stride", "reduce_g", "reduce_blocks", "reduce_jobs"]
+WORDS32 = ["rc"] + ("N Cin H W Cout Ho Wo pad R Rin Wp xplane zpitch tiles_y n_tiles splits ci_tiles vec zq xw4").split() + _LAUNCH
+WORDS16 = ["rc"] + ("N Cin C8in H W Cout C8out Ho Wo pad R P Px Rin K xrows tiles_y tiles splits tiles_per_split ci_tiles nbuf magic_wo magic_w "
+                    "xslots zslots pieces x_pieces z_base wide co_tiles plane_slots magic_px magic_xs magic_zs magic_p n_jobs").split() + _LAUNCH
+FORMS16 = ("dma32", "wide", "narrow", "reg")
+
+
+def launch_words(case, half, n_jobs=0, **env):
+    """The launch of a case as the entry point builds it: [rc] after a refusal, else the words of WORDS32 / WORDS16.  n_jobs: 0 = the
+    single-layer entry, 1 .. 8 = mp_f16_conv_wgrad_grouped."""
+    cap = 64
+    buf = (ctypes.c_int64 * cap)()
+    with fm.knobs(**env):
+        n = _lib.load().mp_conv_wgrad_launch_words(ctypes.byref(desc(case)), int(half), int(n_jobs), buf, cap)
+    assert n == 1 or n == len(WORDS16 if half else WORDS32), f"mp_conv_wgrad_launch_words returned {n}"
+    return list(buf[:n])
+
+
+def check_geometry_against_launch(geo, words, half):
+    """The restated geometry (geometry32 / geometry16, None = refused) against the launch the library builds."""
+    if geo is None:
+        assert words[0] != 0 and len(words) == 1, words
+        return
+    w = SimpleNamespace(**dict(zip(WORDS16 if half else WORDS32, words)))
+    assert w.rc == 0 and w.half == half and (w.ks, w.stride) == (geo.k, geo.s)
+    reduce_g = {"plain": 0, "grouped4": 4, "grouped16": 16}[geo.reduce]
+    if half:
+        got = (FORMS16[w.form], w.R, w.K, w.P, w.nbuf, w.plane_slots > 0, w.tiles_per_split, w.tiles, w.splits, w.lds_bytes, w.reduce_g)
+        want = (geo.form, geo.R, geo.K, geo.P, geo.nbuf, geo.planes, geo.tiles_per_split, geo.tiles, geo.splits, geo.lds_bytes, reduce_g)
+        assert (w.grid_y, w.grid_z, w.reduce_jobs) == (geo.splits, geo.n_jobs, geo.n_jobs)
+    else:
+        got = (("simple", "pipe")[w.form], w.R, w.tiles_y, w.n_tiles, w.splits, w.lds_bytes, w.reduce_g)
+        want = (geo.kernel, geo.R, geo.tiles_y, geo.n_tiles, geo.splits, geo.lds_bytes, reduce_g)
+        assert (w.grid_y, w.grid_z, w.reduce_jobs) == (geo.splits, 1, 1)
+    assert got == want, (got, want)
+
+
+def random_draws(count=600, seed=20240607):
+    """`count` seeded random (case, fp32 forced simple, MP_WGRAD16_* knobs, jobs) draws over every kernel size, stride and form switch"""
+    rng = random.Random(seed)
+    out = []
+    while len(out) < count:
+        k, s = rng.choice([(1, 1), (1, 2), (3, 1), (3, 2), (4, 2)])
+        case = (rng.randint(1, 40), rng.choice([3, 16, 17, 32, 40, 48, 64, 72, 128, 256, 390, 512]),
+                rng.choice([16, 17, 24, 32, 64, 80, 136, 250, 256, 500, 512]), k, s, rng.randint(2, 70), rng.randint(2, 220))
+        if k == 4 and (case[5] % 2 or case[6] % 2):
+            continue
+        simple = rng.random() < 0.3
+        knobs = {"WGS": rng.choice([1, 2, 3, 4, 8, 12, 16, 64])} if rng.random() < 0.7 else {}
+        knobs.update({key: 0 for key in ("DMA", "WIDE", "PLANES", "NARROW") if rng.random() < 0.25})
+        out.append((case, simple, knobs, rng.choice([1, 1, 2, 3, 8])))
+    return out
 
 
 # ---- reference ------------------------------------------------------------------------------------------------------------------
